@@ -13,9 +13,13 @@ One "step" = one full optimisation step of the reference recipe (run_train.py:18
 sparsity mask -> trainable dual-stream U-Net forward -> sparse head -> log-L1 loss + scale regulariser -> backward
 (head, U-Net dgrad/wgrad) -> [N > 1: one RCCL all-reduce of the flat gradient] -> clip_grad_norm_(0.01) -> Adam.
 
-Timing: W warm-up steps, then `--repeats` blocks of EXACTLY K steps, each block bracketed by barrier +
-torch.cuda.synchronize() on both sides and reduced with MAX over ranks; `value` comes from the MEDIAN block (all block
-times are in `ms_per_step_blocks`).  Rank 0 prints ONE JSON line with
+Timing: W warm-up steps, then `--repeats` blocks of EXACTLY K steps (a plain run: ONE block, so K is the number of timed
+steps), each block bracketed by barrier + torch.cuda.synchronize() on both sides and reduced with MAX over ranks; `value`
+comes from the MEDIAN block (all block times are in `ms_per_step_blocks`).  The timed steps start from the state the model
+and optimiser had after set-up, with the same seed: the same arguments give the same inputs and the same outputs, whatever
+the pre-warm ran.  --dump-outputs DIR writes what the last timed step handed its caller as DIR/<name>.npy (float32).
+
+A plain run prints the headline line and nothing more.  --full (default --repeats 7) adds, on rank 0's line:
   roofline            the dominant single kernel (head backward), algorithmic flops (37,376 flop per
                       selected pixel) / live event-timed launch duration, plus the executed-MFMA view (the kernel
                       recomputes the forward: 56,064 flop per pixel are issued)
@@ -54,7 +58,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=7, help="timed blocks of --steps steps; the median block is reported")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed blocks of --steps steps; the median block is reported (default 1, with --full 7)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: roofline sections, cpu_baseline, the bf16 / h2d / soak extras, the N = 1 "
+                         "configuration legs (each can still be switched off with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, popcount, popdensemap, scale_map, parameters, "
+                         "gradients) as DIR/<name>.npy in float32")
     ap.add_argument("--batch", type=int, default=64, help="tiles per GPU per step (BASELINE config: 64)")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of HIP-graph replay")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -73,7 +84,10 @@ def parse():
                     help="untimed steps in front of the W warm-up steps until this much wall time has passed: the part's clocks settle "
                          "into their sustained state only after ~3 s of load (30-step blocks right after start-up read 1.81 ms, the same "
                          "blocks after 3 s 1.78 ms, a 1500-step block 1.77 ms); 0 = off")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 7 if args.full else 1
+    return args
 
 
 # ---- N > 1 without a launcher: become the launcher's parent (no GPU call has happened yet) ---------------------------
@@ -1215,6 +1229,18 @@ def extra_legs(torch, dist, args, world, rank, dev, B, batch, trainer, sample, s
     return out
 
 
+def dump_outputs(torch, trainer, outdir):
+    """--dump-outputs: what the last timed step handed its caller -- the loss pair {loss, regulariser} the step returns, the head's
+    outputs (trainer.last) and the parameters and gradients it left behind -- as float32 .npy files (~5 MB at B = 64)."""
+    import numpy as np
+    torch.cuda.synchronize()
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {"loss": trainer.loss_out, "popcount": trainer.last["popcount"], "popdensemap": trainer.last["popdensemap"],
+              "scale_map": trainer.last["scale_map"], "params": trainer.flat_p, "grads": trainer.flat_g}
+    for name, t in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -1282,6 +1308,8 @@ def main():
         return model, tr, smp, one_step, sd
 
     model, trainer, sample, step, sd_cpu = build(args.precision)
+    # the state the timed steps start from (the pre-warm runs a time-dependent number of steps)
+    init_state = (trainer.flat_p.clone(), trainer.m.clone(), trainer.v.clone(), trainer.step_count.clone())
 
     torch.manual_seed(1600 + rank)
     prewarm_steps = 0
@@ -1333,7 +1361,14 @@ def main():
             raise SystemExit(f"non-finite loss {loss_val}")
         return blocks, owns, loss_val
 
+    torch.cuda.synchronize()
+    for dst, src in zip((trainer.flat_p, trainer.m, trainer.v, trainer.step_count), init_state):
+        dst.copy_(src)
+    del init_state
+    torch.manual_seed(1600 + rank)                 # (the step's row / column selection is drawn on the CPU generator)
     blocks, owns, loss_val = run_blocks(step, args.steps, args.repeats)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, trainer, args.dump_outputs)
     dt = statistics.median(blocks)
     own_ms = statistics.median(owns) / args.steps * 1e3
     if world > 1:
@@ -1345,9 +1380,9 @@ def main():
         per_rank = [round(own_ms, 4)]
 
     extras = {}
-    if not args.no_extras and (world == 1 or args.extras_multi):
+    if args.full and not args.no_extras and (world == 1 or args.extras_multi):
         extras = extra_legs(torch, dist, args, world, rank, dev, B, batch, trainer, sample, step, build, run_blocks, timed_block)
-    elif not args.no_extras:
+    elif args.full and not args.no_extras:
         # N > 1 (round 6): the scaling run shows the one limit SURVEY 8e predicted -- N ranks fed through one host -- by default: ONE host-feed
         # leg with the narrowest feed (S2 as uint16 digital numbers + S1 fp32, 160 KB per tile: 8 ranks need 49 GB/s of pinned H2D against
         # 52.5 measured on the one-link test box; the fp32 6-band feed needs 73.6), reported next to the resident `value` as `value_fed`
@@ -1419,21 +1454,22 @@ def main():
             "step_tflops": round(value * FLOP_TRAIN_PER_TILE / 1e12, 3),
             "step_frac_of_fp32_mfma_peak": round(value * FLOP_TRAIN_PER_TILE / (FP32_MATRIX_PEAK * world), 4),
         }
-        from popcorn_amd import _lib as L
-        with L.precision(args.precision):
-            res["roofline_head"] = head_bwd_roofline(torch, trainer, sample)
-            # `roofline` = the kernel with the largest share of the step in the tracked rocprofv3 summary: the fused conv backward in the
-            # fp32 step; in bf16 mode (and with the split form switched off) the head backward, as before
-            res["roofline"] = fused_conv_bwd_roofline(torch, trainer, sample) or res["roofline_head"]
-            res["roofline_conv"] = conv_kernel_roofline(torch, B)
-        if world == 1 and not args.no_class_sweep:
-            res["roofline_conv_class"] = conv_class_sweep(torch, trainer, sample)
-        if world == 1 and not args.no_cpu_baseline:
-            res["cpu_baseline"] = cpu_baseline(torch, sd_cpu, args.cpu_seconds)
-        else:
-            res["cpu_baseline"] = None
+        if args.full:
+            from popcorn_amd import _lib as L
+            with L.precision(args.precision):
+                res["roofline_head"] = head_bwd_roofline(torch, trainer, sample)
+                # `roofline` = the kernel with the largest share of the step in the tracked rocprofv3 summary: the fused conv backward in the
+                # fp32 step; in bf16 mode (and with the split form switched off) the head backward, as before
+                res["roofline"] = fused_conv_bwd_roofline(torch, trainer, sample) or res["roofline_head"]
+                res["roofline_conv"] = conv_kernel_roofline(torch, B)
+            if world == 1 and not args.no_class_sweep:
+                res["roofline_conv_class"] = conv_class_sweep(torch, trainer, sample)
+            if world == 1 and not args.no_cpu_baseline:
+                res["cpu_baseline"] = cpu_baseline(torch, sd_cpu, args.cpu_seconds)
+            else:
+                res["cpu_baseline"] = None
         res.update(extras)
-        if world == 1 and not args.no_config_legs and args.precision == "fp32":
+        if args.full and world == 1 and not args.no_config_legs and args.precision == "fp32":
             # BASELINE's other configurations on the same line: forward parity of config[1] against the CPU oracle (the metric's
             # second half), config[2] at the reference's real region geometry, config[4]'s sliding windows
             res["fwd_parity"] = fwd_parity(torch, margs, sd_cpu, batch, dev)

@@ -92,9 +92,27 @@ def test_documents_quote_the_tracked_artefacts():
     assert out.returncode == 0, out.stderr
 
 
+def test_plain_run_times_one_block_and_full_keeps_seven():
+    """A plain `bench.py --steps K` times exactly K steps (one block); `--full` keeps the median of 7 blocks unless --repeats says otherwise."""
+    sys.path.insert(0, ROOT)
+    import bench
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "12", "--warmup", "3"]
+        a = bench.parse()
+        assert a.steps == 12 and a.warmup == 3 and a.repeats == 1 and a.full is False and a.dump_outputs is None
+        sys.argv = ["bench.py", "--full"]
+        assert bench.parse().repeats == 7
+        sys.argv = ["bench.py", "--full", "--repeats", "2", "--dump-outputs", "out"]
+        a = bench.parse()
+        assert a.repeats == 2 and a.full is True and a.dump_outputs == "out"
+    finally:
+        sys.argv = argv
+
+
 @pytest.mark.gpu
 def test_live_bench_prints_one_json_line_last():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--repeats", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--repeats", "2",
                           "--prewarm-seconds", "0", "--no-extras", "--no-cpu-baseline", "--no-class-sweep", "--no-config-legs"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -102,6 +120,34 @@ def test_live_bench_prints_one_json_line_last():
     d = json.loads(lines[-1])                            # the JSON line is the LAST line of stdout
     _check_line(d, extras=False)
     assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain run: the headline alone, ONE block of exactly --steps steps, and --dump-outputs writes the last step's outputs.  Two runs
+    with different pre-warm / warm-up lengths start their timed steps from the same state and seed: same loss, same outputs."""
+    dumps = []
+    for i, (prewarm, warmup) in enumerate((("0", "1"), ("0.5", "2"))):
+        dump = tmp_path / f"out{i}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", warmup,
+                              "--prewarm-seconds", prewarm, "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
+        assert REQUIRED <= set(d) and d["n_gpus"] == 1 and d["steps"] == 4 and d["dtype"] == "f32"
+        assert len(d["ms_per_step_blocks"]) == 1 and d["ms_per_step"] == d["ms_per_step_blocks"][0]
+        assert abs(d["value"] - 64 * 1e3 / d["ms_per_step"]) <= 2e-3 * d["value"]
+        assert not {"roofline", "roofline_head", "cpu_baseline", "bf16", "soak", "h2d", "fwd_parity", "config5"} & set(d)
+        dumps.append((d, dump))
+    import numpy as np
+    shapes = {"loss": (2,), "popcount": (64,), "popdensemap": (64, 100, 100), "scale_map": (64, 100, 100)}
+    a, b = ({f.stem: np.load(f) for f in dump.glob("*.npy")} for _, dump in dumps)
+    assert set(a) == set(shapes) | {"params", "grads"} and a["params"].shape == a["grads"].shape
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2 ** 20
+    for k, v in a.items():
+        assert v.dtype == np.float32 and np.isfinite(v).all(), k
+        assert k not in shapes or v.shape == shapes[k], (k, v.shape)
+        np.testing.assert_allclose(v, b[k], rtol=1e-4, atol=1e-6, err_msg=k)
+    assert abs(float(a["loss"][0]) - dumps[0][0]["final_loss"]) <= 1e-6 * max(1.0, abs(float(a["loss"][0])))
 
 
 def test_tracked_profiles_stamp_is_well_formed_and_reports_staleness():
@@ -132,7 +178,7 @@ def test_live_two_rank_bench_line_on_one_gpu_through_gloo():
     over ranks, the data-parallel fields) as a functional run on the one GPU of the test box (POPCORN_DIST_BACKEND=gloo: both ranks share
     the device, collectives through the host; the split-graph step).  Checks the contract of the N > 1 line, not its speed."""
     env = dict(os.environ, POPCORN_DIST_BACKEND="gloo")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--repeats", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--repeats", "2",
                           "--prewarm-seconds", "0"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]

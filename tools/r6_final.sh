@@ -9,7 +9,7 @@ for f in r6_fp32_graph_kernel_stats.csv r6_bf16_graph_kernel_stats.csv r6_stamp.
          r6_pmc_step_kernels_bf16.json r6_regions_2x230x220_kernel_stats.csv r6_regions_2x517x389_kernel_stats.csv r6_regions_2x700x640_kernel_stats.csv; do
   cp gpurun_out/$f profiles/$f
 done
-python3 bench.py > gpurun_out/r6_bench_final.json 2> gpurun_out/r6_bench_final.err
-python3 bench.py --precision bf16 > gpurun_out/r6_bench_final_bf16.json 2> gpurun_out/r6_bench_final_bf16.err
-wc -c gpurun_out/r6_bench_final.json gpurun_out/r6_bench_final_bf16.json
+python3 bench.py --full > profiles/r6_bench_final.json
+python3 bench.py --full --precision bf16 > profiles/r6_bench_final_bf16.json
+wc -c profiles/r6_bench_final.json profiles/r6_bench_final_bf16.json
 python3 -m pytest tests -m gpu -x -q 2>&1 | tail -4
