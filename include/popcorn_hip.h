@@ -667,6 +667,24 @@ int pc_stitch_count_windows(const int32_t* win, int nwin, int M, int16_t* count,
 int pc_stitch_finalize(float* out_sum, float* out_sq, float* scale_sum, float* scale_sq, const int16_t* count, int64_t n,
                        void* stream);
 
+/* ---- NaN fill of Sentinel inputs (data/PopulationDataset.py:526-551 interpolate_nan, scipy griddata "nearest") ----
+ * x: contiguous fp32 (B, C, H, W), filled in place.  Per sample b, over its extent rows [0, h_b) x columns [0, w_b) (hw: DEVICE int32
+ * [B][2] = {h_b, w_b}, NULL = the whole H x W; anchored top-left like the collate's zero padding; entries outside the extent are neither
+ * read as sources nor written):
+ *   - no NaN: untouched;
+ *   - NaNs and fewer than 4 known (non-NaN; +-Inf is known) entries: the whole extent is zeroed;
+ *   - otherwise every NaN at p = (c, i, j) takes the value of the known q minimising (|p - q|^2, q_c, q_i, q_j) lexicographically:
+ *     Euclidean distance in 3-D index space, compared exactly in integers; the value is copied bit for bit.
+ * counts: DEVICE int64 [B][2] receives {NaN entries, known entries} of each sample's extent (the 5 % orbit rule of
+ * PopulationDataset.py:426,486 needs no second pass).  flags: PC_NAN_FILL_COUNT_ONLY = count, do not fill.
+ * C <= PC_NAN_FILL_MAX_C, H, W <= PC_NAN_FILL_MAX_HW, B * C <= 65535.  ws: pc_nan_fill_ws_bytes(B, C, H, W) bytes of scratch.
+ * Every launch after the count reads the counts and returns at once for a sample without NaN. */
+#define PC_NAN_FILL_MAX_C 8
+#define PC_NAN_FILL_MAX_HW 16384
+#define PC_NAN_FILL_COUNT_ONLY 1
+int64_t pc_nan_fill_ws_bytes(int B, int C, int H, int W);
+int pc_nan_fill(float* x, const int32_t* hw, int64_t* counts, void* ws, int B, int C, int H, int W, int flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -103,6 +103,7 @@ PC_ABI_VERSION = 9
 PC_MAX_GROUP = 4
 PC_ADAM_MAX_SEG, PC_ADAM_GROUPS = 8, 4
 PC_EINVAL, PC_ENOGPU, PC_ENOMEM, PC_ENOTSUP = -1, -2, -3, -4
+PC_NAN_FILL_MAX_C, PC_NAN_FILL_MAX_HW, PC_NAN_FILL_COUNT_ONLY = 8, 16384, 1
 
 
 class PcAdamGroups(C.Structure):
@@ -178,9 +179,12 @@ def lib():
         _lib.pc_step_destroy.argtypes = [C.c_void_p]
         _lib.pc_train_step.argtypes = [C.c_void_p, C.POINTER(PcStepIo), C.c_int, C.c_void_p]
         for name in ("pc_conv3x3_wgrad_ws_bytes", "pc_convt2x2_wgrad_ws_bytes", "pc_head_ws_bytes",
-                     "pc_compact_ws_bytes", "pc_unet_ws_bytes", "pc_level2_bwd_ws_bytes", "pc_conv3x3_up_ws_bytes", "pc_conv3x3_up_bwd_ws_bytes"):
+                     "pc_compact_ws_bytes", "pc_unet_ws_bytes", "pc_level2_bwd_ws_bytes", "pc_conv3x3_up_ws_bytes", "pc_conv3x3_up_bwd_ws_bytes",
+                     "pc_nan_fill_ws_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_int64
+        _lib.pc_nan_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p]
     return _lib
 
 

@@ -83,6 +83,12 @@ def train_parser():
     p.add_argument("--test_overlap", type=int, default=32)
     p.add_argument("--precision", choices=["fp32", "bf16"], default="fp32",
                    help="bf16: mixed precision (bf16 MFMA operands + channels-last bf16 activations, fp32 master weights; DESIGN.md 7)")
+    p.add_argument("--nan_fill", action="store_true",
+                   help="nearest-value NaN fill of S2 / S1 on the device before augmentation and normalisation (on for real rasters: "
+                        "cloud masks, orbit gaps; data/PopulationDataset.py:419-441)")
+    p.add_argument("--nan_clouds", type=float, default=0.0,
+                   help="synthetic datasets: NaN cloud discs over about this fraction of S2, orbit gaps in S1 (pair with --nan_fill)")
+    p.add_argument("--ascfill", action="store_true", help="always take the ascending S1 where the descending one holds NaNs")
     return p
 
 
@@ -107,6 +113,11 @@ def eval_parser():
     p.add_argument("--overlap", type=int, default=128)
     p.add_argument("--ensemble", type=int, default=1, help="members to instantiate when no --resume checkpoints are given")
     p.add_argument("--precision", choices=["fp32", "bf16"], default="fp32", help="arithmetic mode of the kernels (DESIGN.md 7)")
+    p.add_argument("--raw_input", action="store_true",
+                   help="un-normalised S2 / S1 windows, NaN-filled on the device per window before normalisation (real rasters)")
+    p.add_argument("--nan_clouds", type=float, default=0.0, help="--raw_input: NaN cloud discs over about this fraction of S2")
+    p.add_argument("--s1_gap", type=float, default=0.0, help="--raw_input: orbit-gap rows over this fraction of the descending S1")
+    p.add_argument("--ascfill", action="store_true", help="always take the ascending S1 where the descending one holds NaNs")
     return p
 
 
@@ -135,11 +146,22 @@ def new_log(folder, args=None):
     return exp
 
 
-def normalize_sample(sample, device, transform=None):
+def fill_sample_(s2, s1, sample):
+    """--nan_fill: the nearest-value fill (data/PopulationDataset.py:526-551) of the batch's device S2 / S1 in place, each item over its
+    own extent (the collate's ``data_hw``): the zero padding of a smaller region is never a source."""
+    hw = sample.get("data_hw")
+    ops.nan_fill_(s2, hw)
+    ops.nan_fill_(s1, hw)
+
+
+def normalize_sample(sample, device, transform=None, nan_fill=False):
     """to_cuda_inplace + apply_transformations_and_normalize (utils/utils.py:22-43,130-214) on the device: S2 augmentations
     on the raw digital numbers, per-band normalisation + concat [S2, S1] (one HIP kernel), then the joint geometric
-    transform of input and admin_mask."""
+    transform of input and admin_mask.  nan_fill: ``fill_sample_`` first."""
     s2, s1 = sample["S2"].to(device, non_blocking=True).float(), sample["S1"].to(device, non_blocking=True).float()
+    if nan_fill:
+        s2, s1 = s2.contiguous(), s1.contiguous()
+        fill_sample_(s2, s1, sample)
     if transform is not None and "S2" in transform:
         s2 = transform["S2"](s2)
     raw = torch.cat([s2, s1], 1).contiguous()
@@ -153,12 +175,13 @@ def normalize_sample(sample, device, transform=None):
     return out
 
 
-def prepare_sample_fused(sample, transform=None):
+def prepare_sample_fused(sample, transform=None, nan_fill=False):
     """The fast form of ``normalize_sample`` for the fused step (round 6): ``sample`` holds DEVICE tensors (``data.feed.RegionFeed``); the
     augmentation parameters are drawn on the host with the reference's generator consumption (``draw_fused_params``), ONE launch
     (``ops.augment_raw``) applies them while it assembles the raw [S2 | S1] tile, and the normalisation happens inside the step's ingest
     (the executor's ``raw`` input form) -- no ``.float()`` / ``torch.cat`` / normalise / flip / rot90 launches, no synchronous copy.
-    Returns None when ``transform`` is not the reference trainer's set (the caller then takes ``normalize_sample``)."""
+    Returns None when ``transform`` is not the reference trainer's set (the caller then takes ``normalize_sample``).
+    nan_fill: ``fill_sample_`` on the staged tensors first."""
     from .utils.transform import draw_fused_params
     s2, s1, admin = sample["S2"], sample["S1"], sample["admin_mask"]
     if not (s2.is_cuda and s2.dtype == torch.float32 and s1.dtype == torch.float32 and s2.shape[1] == 4 and s1.shape[1] == 2):
@@ -166,6 +189,9 @@ def prepare_sample_fused(sample, transform=None):
     params = draw_fused_params(transform)
     if params is None:
         return None
+    if nan_fill:
+        s2, s1 = s2.contiguous(), s1.contiguous()
+        fill_sample_(s2, s1, sample)
     raw, adm = ops.augment_raw(s2.contiguous(), s1.contiguous(), admin.float().contiguous(), params)
     return {"raw": raw, "admin_mask": adm, "census_idx": sample["census_idx"].contiguous(), "y": sample["y"].float().contiguous()}
 
@@ -201,7 +227,7 @@ class Trainer:
                              "data-parallel runs use the fused step (drop the flag)")
         seed_all(args.seed)
         ds = SyntheticWeaksupDataset(args.synthetic_regions, min_hw=args.synthetic_hw_range[0], max_hw=args.synthetic_hw_range[1],
-                                     seed=args.seed, fixed_hw=args.fixed_hw)
+                                     seed=args.seed, fixed_hw=args.fixed_hw, nan_clouds=args.nan_clouds, ascfill=args.ascfill)
         self.sampler = None
         if self.world > 1:
             self.sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=self.world, rank=self.rank,
@@ -213,7 +239,7 @@ class Trainer:
         # weak validation set (run_train.py:410-414: a second Population_Dataset in weaksup mode, batch size -wvb)
         self.val_loader = torch.utils.data.DataLoader(
             SyntheticWeaksupDataset(args.synthetic_val_regions, min_hw=args.synthetic_hw_range[0], max_hw=args.synthetic_hw_range[1],
-                                    seed=args.seed + 77, fixed_hw=args.fixed_hw),
+                                    seed=args.seed + 77, fixed_hw=args.fixed_hw, nan_clouds=args.nan_clouds, ascfill=args.ascfill),
             batch_size=args.weak_val_batch_size, shuffle=False, collate_fn=Population_Dataset_collate_fn, drop_last=False)
         self._test_raster = None
         self.model = model_dict[args.model](**get_model_kwargs(args, args.model)).to(self.device)   # same seed: same init on every rank
@@ -303,9 +329,9 @@ class Trainer:
         s = None
         if self.fused is not None and torch.is_tensor(sample.get("S2")) and sample["S2"].is_cuda:
             # a batch staged by the feed: augmentation + assembly in one launch, normalisation inside the step (raw input form)
-            s = prepare_sample_fused(sample, self.data_transform)
+            s = prepare_sample_fused(sample, self.data_transform, nan_fill=a.nan_fill)
         if s is None:
-            s = normalize_sample(sample, self.device, self.data_transform)
+            s = normalize_sample(sample, self.device, self.data_transform, nan_fill=a.nan_fill)
         dk = "raw" if "raw" in s else "input"
         num_pix = s[dk].shape[0] * s[dk].shape[2] * s[dk].shape[3]
         if self.world > 1 and a.fixed_hw is None:
@@ -357,7 +383,7 @@ class Trainer:
         pred, gt = [], []
         with torch.no_grad():
             for sample in self.val_loader:
-                s = normalize_sample(sample, self.device, None)
+                s = normalize_sample(sample, self.device, None, nan_fill=self.args.nan_fill)
                 out = self.model(s, padding=False)
                 pred.append(out["popcount"])
                 gt.append(s["y"])
@@ -490,11 +516,12 @@ def run_eval(argv=None):
         if j < len(args.resume):
             m.load_state_dict(torch.load(args.resume[j], map_location="cpu", weights_only=False)["model"])   # run_eval.py:243-257
         models.append(m.eval().set_precision(args.precision))
-    data = SyntheticTestRaster(args.raster_hw[0], args.raster_hw[1], seasons=4 if args.fourseasons else 1, device=dev)
+    data = SyntheticTestRaster(args.raster_hw[0], args.raster_hw[1], seasons=4 if args.fourseasons else 1, device=dev,
+                               raw=args.raw_input, nan_clouds=args.nan_clouds, s1_gap=args.s1_gap)
     reducer = FlatReducer()
     t0 = time.time()
     out, out_std, scale, scale_std = E.evaluate_raster(models, data.raster, args.patchsize, args.overlap, args.fourseasons,
-                                                       reducer, rank)
+                                                       reducer, rank, raw=args.raw_input, ascfill=args.ascfill)
     res = {}
     cp, cg = E.convert_popmap_to_census(out, data.boundary, data.census_idx, data.census_pop)
     res.update({k: float(v) for k, v in get_test_metrics(cp, cg, tag="MainCensus_synthetic_fine").items()})

@@ -1,9 +1,21 @@
 """Batch assembly with the reference's semantics (Population_Dataset_collate_fn, data/PopulationDataset.py:885-958):
 variable-size census-region crops are zero-padded to the batch maximum (bottom/right), ``admin_mask`` is padded with
--1, ``census_idx`` concatenated.  Host-side glue (runs in DataLoader workers), plain torch."""
+-1, ``census_idx`` concatenated.  Host-side glue (runs in DataLoader workers), plain torch.
+
+Both collates also record each item's data extent as ``data_hw`` (int32 (n, 2) = (h, w), anchored top-left): the device NaN fill
+(``ops.nan_fill_``, Trainer ``--nan_fill``) must never take the zero padding of a smaller region as a source."""
 from __future__ import annotations
 
 import torch
+
+
+def _data_hw(batch, out):
+    for key in ("S2", "S1", "building_counts"):
+        if key in batch[0]:
+            for i, item in enumerate(batch):
+                out[i, 0], out[i, 1] = item[key].shape[1], item[key].shape[2]
+            return out
+    return out.zero_()
 
 
 def Population_Dataset_collate_fn(batch):
@@ -38,6 +50,7 @@ def Population_Dataset_collate_fn(batch):
         "valid_coords": [item["valid_coords"] for item in batch],
         "season": torch.tensor([item["season"] for item in batch]),
         "census_idx": torch.cat([item["census_idx"] for item in batch]),
+        "data_hw": _data_hw(batch, torch.empty(n, 2, dtype=torch.int32)),
     })
     return out
 
@@ -84,6 +97,7 @@ def collate_into(batch, alloc):
         "valid_coords": [item["valid_coords"] for item in batch],
         "season": torch.tensor([item["season"] for item in batch]),
         "census_idx": ci,
+        "data_hw": _data_hw(batch, alloc("data_hw", (n, 2), torch.int32)),
     })
     return out
 

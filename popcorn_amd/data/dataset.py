@@ -14,8 +14,43 @@ from torch.utils.data import Dataset
 from . import stats
 
 
+def cloud_mask(h, w, fraction, g):
+    """Seeded cloud discs (radii 4 - 40 px) over an h x w raster until about ``fraction`` of it is covered (a bool (h, w) mask)."""
+    m = torch.zeros(h, w, dtype=torch.bool)
+    if fraction <= 0:
+        return m
+    yy, xx = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
+    target = fraction * h * w
+    for _ in range(10000):
+        if m.sum() >= target:
+            break
+        cy, cx = torch.rand(2, generator=g) * torch.tensor([h, w])
+        r = 4 + torch.rand(1, generator=g).item() * min(36.0, max(h, w) / 4)
+        m |= (yy - cy) ** 2 + (xx - cx) ** 2 < r * r
+    return m
+
+
+def gap_rows(h, fraction, g):
+    """Seeded orbit-gap stripes: a bool (h,) mask of about ``fraction`` of the rows, in up to three bands."""
+    m = torch.zeros(h, dtype=torch.bool)
+    n = int(round(fraction * h))
+    if n <= 0:
+        return m
+    bands = min(3, n)
+    for k in range(bands):
+        ln = n // bands + (1 if k < n % bands else 0)
+        r0 = int(torch.randint(0, max(1, h - ln + 1), (1,), generator=g))
+        m[r0:r0 + ln] = True
+    return m
+
+
 class SyntheticWeaksupDataset(Dataset):
-    def __init__(self, n_regions=256, min_hw=64, max_hw=144, seed=1600, fixed_hw=None):
+    def __init__(self, n_regions=256, min_hw=64, max_hw=144, seed=1600, fixed_hw=None, nan_clouds=0.0, ascfill=False):
+        """nan_clouds > 0 (opt-in): real-raster NaNs -- cloud discs over about that fraction of every item's S2 (all bands), orbit-gap rows in
+        its descending S1 (every third item over 5 % of the rows) and a NaN-free ascending S1; the item carries the S1 of the orbit the
+        reference's rule picks (data.nanfill.select_s1_host; ``ascfill``: always the ascending one where the descending has a gap).  The
+        NaN-free data underneath is the same as with nan_clouds = 0.  The fill runs on the device (Trainer ``--nan_fill``)."""
+        self.nan_clouds, self.ascfill = float(nan_clouds), bool(ascfill)
         self.n = n_regions
         g = torch.Generator().manual_seed(seed)
         if fixed_hw is not None:
@@ -47,16 +82,49 @@ class SyntheticWeaksupDataset(Dataset):
         cid = i + 1
         admin = torch.where(inside, float(cid), float(cid + self.n))
         y = torch.rand(1, generator=g).item() * 500.0
+        if self.nan_clouds > 0:
+            s2, s1 = self._holes(i, s2, s1)
         return {"S2": s2, "S1": s1, "admin_mask": admin, "y": torch.tensor(y), "census_idx": torch.tensor([cid]),
                 "img_coords": (0, 0), "valid_coords": (0, 0), "season": i % 4}
 
 
-class SyntheticTestRaster:
-    """A normalised (seasons,6,H,W) raster with a blocky census map (ids 1..n, 0 = outside) and a census table."""
+    def _holes(self, i, s2, s1):
+        from .nanfill import select_s1_host
+        h, w = s2.shape[1:]
+        g = torch.Generator().manual_seed(self.seed * 104729 + i)       # a generator of its own: the data underneath does not change
+        s2 = s2.clone()
+        s2[:, cloud_mask(h, w, self.nan_clouds, g)] = float("nan")
+        desc = s1.clone()
+        desc[:, gap_rows(h, 0.08 if i % 3 == 0 else 0.02, g)] = float("nan")
+        asc = s1.flip(-1).contiguous()                                   # the other orbit: same statistics, other values
+        s1, _ = select_s1_host(desc, lambda: asc, self.ascfill)
+        return s2, s1
 
-    def __init__(self, h=2304, w=2560, seasons=1, n_regions=400, seed=1610, device="cpu"):
+
+class SyntheticTestRaster:
+    """A normalised (seasons,6,H,W) raster with a blocky census map (ids 1..n, 0 = outside) and a census table.
+
+    raw=True: the loader's un-normalised bands instead -- S2 (seasons, 4, H, W) digital numbers, S1 (seasons, 2, H, W) descending-orbit
+    backscatter and its ascending companion ``s1_asc`` -- with seeded NaNs: cloud discs over about ``nan_clouds`` of S2 (all bands) and
+    orbit-gap rows over ``s1_gap`` of the descending S1.  The object is then the raster callable of ``eval.evaluate_raster(raw=True)``:
+    ``self(x, y, season, ps)`` -> {"S2": (1,4,ps,ps), "S1": (1,2,ps,ps), "S1_asc": callable} (copies; ``self.raster`` is the object)."""
+
+    def __init__(self, h=2304, w=2560, seasons=1, n_regions=400, seed=1610, device="cpu", raw=False, nan_clouds=0.0, s1_gap=0.0):
         g = torch.Generator().manual_seed(seed)
-        self.raster = torch.randn(seasons, 6, h, w, generator=g).to(device)
+        self.raw = raw
+        if raw:
+            self.s2 = torch.randint(0, 10000, (seasons, 4, h, w), generator=g).float()
+            sd, mu = torch.tensor(stats.S1_STD).view(1, 2, 1, 1), torch.tensor(stats.S1_MEAN).view(1, 2, 1, 1)
+            self.s1 = torch.randn(seasons, 2, h, w, generator=g) * sd + mu
+            self.s1_asc = torch.randn(seasons, 2, h, w, generator=g) * sd + mu
+            gh = torch.Generator().manual_seed(seed + 1)
+            for s in range(seasons):
+                self.s2[s][:, cloud_mask(h, w, nan_clouds, gh)] = float("nan")
+                self.s1[s][:, gap_rows(h, s1_gap, gh)] = float("nan")
+            self.s2, self.s1, self.s1_asc = self.s2.to(device), self.s1.to(device), self.s1_asc.to(device)
+            self.raster = self
+        else:
+            self.raster = torch.randn(seasons, 6, h, w, generator=g).to(device)
         gy = int(n_regions ** 0.5)
         gx = (n_regions + gy - 1) // gy
         ys = torch.clamp((torch.arange(h) * gy) // h, max=gy - 1)
@@ -67,3 +135,8 @@ class SyntheticTestRaster:
         self.census_idx = torch.arange(1, n_regions + 1)
         self.census_pop = torch.rand(n_regions, generator=g) * 2000
         self.shape = (h, w)
+
+    def __call__(self, x, y, season, ps):
+        """One raw window (raw=True): copies of the bands, so that the fill can work in place."""
+        win = lambda t: t[season:season + 1, :, x:x + ps, y:y + ps].clone(memory_format=torch.contiguous_format)  # noqa: E731
+        return {"S2": win(self.s2), "S1": win(self.s1), "S1_asc": lambda: win(self.s1_asc)}

@@ -152,7 +152,7 @@ class RegionFeed:
     through.  Determinism: the FIRST batch is pulled on the caller's thread -- that is where a shuffling sampler draws its seed from the
     global generator -- so the producer never touches the generators the augmentation coins and selection grids come from."""
 
-    TENSOR_KEYS = ("S2", "S1", "admin_mask", "y", "census_idx", "building_counts")
+    TENSOR_KEYS = ("S2", "S1", "admin_mask", "y", "census_idx", "building_counts", "data_hw")
     DEPTH = 3                       # staged batches in flight (ring slots of pinned memory)
 
     def __init__(self, loader, device, copy_stream=None):

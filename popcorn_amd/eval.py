@@ -224,8 +224,23 @@ def adjust_map_to_census(pred, boundary, census_idx, census_pop):
     return pred
 
 
+def raw_window_input(win, ascfill=False):
+    """One raw window of ``evaluate_raster(raw=True)`` -> the normalised model input (1, 6, ps, ps): the window's S2 / S1 NaN-filled on
+    their own (data/PopulationDataset.py:479-500 via ``data.nanfill.fill_item_``; S1 may switch to ``win["S1_asc"]()``), THEN normalised
+    -- the fill copies values across channels, so it must see the loader's raw bands, not normalised ones.  Returns (input, orbit)."""
+    from .data import stats
+    from .data.nanfill import fill_item_
+    from . import ops
+    s2, s1 = win["S2"], win["S1"]
+    L.require_device(s2, s1)
+    raw = torch.cat([s2.float(), s1.float()], 1).contiguous()                # (1, 6, ps, ps); the two views below are contiguous
+    orbit = fill_item_(raw[:, :4], raw[:, 4:], win.get("S1_asc"), ascfill)
+    return ops.select_normalize(raw, tuple(range(6)), stats.MEAN6, stats.STD6), orbit
+
+
 def evaluate_raster(models, raster, patchsize=INFERENCE_PATCH_SIZE, overlap=OVERLAP, fourseasons=False,
-                    reducer: FlatReducer | None = None, rank=0, band_reduce=True, gather=True, return_stitcher=False):
+                    reducer: FlatReducer | None = None, rank=0, band_reduce=True, gather=True, return_stitcher=False, raw=False,
+                    ascfill=False):
     """Ensemble sliding-window inference over ``raster`` = callable (x, y, season, ps) -> normalised model input
     (1,6,ps,ps) on the device (the reference's Population_Dataset(mode="test") item, PopulationDataset.py:336-420), or a
     (S,6,h,w) device tensor of pre-normalised seasons.  Returns the finalised (mean map, std map, scale mean, scale std).
@@ -235,7 +250,10 @@ def evaluate_raster(models, raster, patchsize=INFERENCE_PATCH_SIZE, overlap=OVER
     bands are then all-gathered into full maps on every rank (True: the four maps are returned, as in the single-process
     case) or stay distributed (False: the ``Stitcher`` is returned; ``census_sums_sharded`` works on the band).
     ``band_reduce=False``: the round-2 form, an all-reduce of the full planes and of the count map.
-    ``return_stitcher``: also return the ``Stitcher`` (its visit-count map)."""
+    ``return_stitcher``: also return the ``Stitcher`` (its visit-count map).
+    ``raw``: real rasters -- the callable returns the loader's UN-normalised bands {"S2": (1,4,ps,ps), "S1": (1,2,ps,ps)} plus an optional
+    "S1_asc" callable (the ascending orbit); every window is NaN-filled on the device and then normalised (``raw_window_input``; one
+    host synchronisation per window for the 5 % orbit rule).  ``ascfill``: the reference's per-region switch to the ascending orbit."""
     reducer = reducer or FlatReducer()
     if torch.is_tensor(raster):
         h, w = raster.shape[-2:]
@@ -254,7 +272,10 @@ def evaluate_raster(models, raster, patchsize=INFERENCE_PATCH_SIZE, overlap=OVER
         x, y, season = (int(v) for v in idx[i])
         if i not in mine:
             continue
-        inp = raster(x, y, season, patchsize).contiguous()
+        if raw:
+            inp, _ = raw_window_input(raster(x, y, season, patchsize), ascfill)
+        else:
+            inp = raster(x, y, season, patchsize).contiguous()
         sample = {"input": inp}
         pds, scs = [], []
         with torch.no_grad(), L.padded_rows():      # (16-byte aligned rows for the levels whose width is not a multiple of 4)

@@ -652,6 +652,41 @@ def select_normalize(raw, band6, mean6, std6, out=None):
     return out
 
 
+def nan_fill_(x, hw=None, count_only=False):
+    """Nearest-value NaN fill in place (data/PopulationDataset.py:526-551 interpolate_nan, pc_nan_fill): x = contiguous fp32 device tensor
+    (B, C, H, W) or (C, H, W), each sample's (C, h, w) array filled on its own -- every NaN takes the value of the nearest known entry in
+    3-D index space (c, i, j), ties to the smallest channel, then row, then column; fewer than 4 known entries zero the array.
+    hw: per-sample extents (h_b, w_b) anchored top-left (the collate's ``data_hw``; entries outside are neither sources nor targets), a
+    (B, 2) integer tensor on the host or the device, or a list of pairs; None = the whole H x W.  count_only: count, do not fill.
+    Returns the per-sample (nan_count, known_count) as a device int64 tensor, (B, 2) -- or (2,) for a (C, H, W) input."""
+    L.require_device(x)
+    if x.dtype != torch.float32 or not x.is_contiguous() or x.dim() not in (3, 4):
+        raise ValueError(f"nan_fill_: a contiguous fp32 (B, C, H, W) or (C, H, W) tensor, got {x.dtype} {tuple(x.shape)}")
+    xb = x.unsqueeze(0) if x.dim() == 3 else x
+    B, Cc, H, W = xb.shape
+    if Cc > L.PC_NAN_FILL_MAX_C or H > L.PC_NAN_FILL_MAX_HW or W > L.PC_NAN_FILL_MAX_HW:
+        raise ValueError(f"nan_fill_: at most {L.PC_NAN_FILL_MAX_C} channels and {L.PC_NAN_FILL_MAX_HW} rows / columns, got {tuple(x.shape)}")
+    counts = torch.empty(B, 2, dtype=torch.int64, device=x.device)
+    if xb.numel() == 0:
+        counts.zero_()
+        return counts if x.dim() == 4 else counts[0]
+    hw_dev = None
+    if hw is not None:
+        if torch.is_tensor(hw) and hw.is_cuda:
+            if tuple(hw.shape) != (B, 2):
+                raise ValueError(f"nan_fill_: hw must be (B, 2), got {tuple(hw.shape)}")
+            hw_dev = hw.to(torch.int32).contiguous()
+        else:
+            hw_host = torch.as_tensor(hw, dtype=torch.int64).reshape(-1, 2)
+            if hw_host.shape[0] != B or bool((hw_host < 0).any()) or bool((hw_host[:, 0] > H).any()) or bool((hw_host[:, 1] > W).any()):
+                raise ValueError(f"nan_fill_: extents {hw_host.tolist()} do not fit a batch of {B} x {H} x {W}")
+            hw_dev = hw_host.to(torch.int32).to(x.device)
+    ws = _workspace(L.lib().pc_nan_fill_ws_bytes(B, Cc, H, W), x.device)
+    L.check(L.lib().pc_nan_fill(L.ptr(xb), L.ptr(hw_dev), L.ptr(counts), L.ptr(ws), B, Cc, H, W,
+                                L.PC_NAN_FILL_COUNT_ONLY if count_only else 0, L.stream_ptr()), "pc_nan_fill")
+    return counts if x.dim() == 4 else counts[0]
+
+
 def augment_raw(s2, s1, admin_mask, params, out=None, admin_out=None):
     """The trainer's augmentations (run_train.py:386-402) with parameters drawn on the host (utils/transform.py: draw_fused_params), applied
     while the raw 6-channel tile [S2 | S1] is assembled -- ONE launch (pc_augment_raw).  s2 (B, 4, H, W) digital numbers, s1 (B, 2, H, W),
