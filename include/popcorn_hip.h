@@ -458,6 +458,20 @@ int pc_head_bwd(const pc_src* feat, int py, int px, const float* const* hw, cons
                 const float* g_scale_const, float* const* dhw, int accumulate,
                 const pc_dst* g_feat, const pc_bn* feat_bn_sar, const pc_bn* feat_bn_opt,
                 int Hp, int Wp, void* ws, int B, int H, int W, int flags, void* stream);
+/* debug (tests/tie_adjudication.py, tests/test_gpu_convt_head.py): the ReLU decisions pc_head_bwd actually takes.  The kernel keeps
+ * the head's hidden activations in registers; while a device buffer is registered here (NULL = off), pc_head_bwd in fp32 mode launches
+ * an instantiation of its producer / consumer kernel -- in the multiplication form in force, pc_set_head_split -- that ALSO writes one
+ * record per SELECTED pixel of the B x H x W crop (mask == NULL: every pixel), record b * H * W + y * W + x, whatever the upstream
+ * gradients are; the records of unselected pixels are left untouched.  Everything else the call computes is unchanged bit for bit
+ * (the call drains its stream once before the launch; one exporting call at a time).  A record is PC_HEAD_DEC_BYTES = 4 little-endian 64-bit words, word k (0 - 3):
+ *   bit 16 l + 4 m + r  (l = 0, 1, 2; m, r = 0 - 3): the pre-activation of unit 16 m + 4 k + r of hidden layer l (head.0 / .2 / .4)
+ *                        is > 0, i.e. the unit passes gradient;
+ *   bit 48              : the output decision out[:, 0] > 0 of the final relu (the same in all four words);
+ *   bit 63              : set in every word the kernel wrote; all other bits are 0.
+ * pc_head_bwd returns PC_EINVAL, launching nothing, when a buffer is registered and it is smaller than B * H * W records or not 8-byte
+ * aligned, or the call would run a kernel without the export (bf16 mode, POPCORN_HEAD_BWD_SINGLE_ROLE=1). */
+#define PC_HEAD_DEC_BYTES 32
+void pc_debug_head_decisions(void* buf, int64_t bytes);
 
 /* ---- compaction of scale[mask] in row-major (b,y,x) order (the boolean-index gather of popcorn.py:173).
  * out must hold B*H*W floats; *n_out (device int32) receives Nsel. */

@@ -183,6 +183,8 @@ def lib():
                      "pc_nan_fill_ws_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_int64
+        _lib.pc_debug_head_decisions.restype = None
+        _lib.pc_debug_head_decisions.argtypes = [C.c_void_p, C.c_int64]
         _lib.pc_nan_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p]
     return _lib

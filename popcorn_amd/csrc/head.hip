@@ -1355,8 +1355,29 @@ __device__ __forceinline__ void hs_wgrad16(const f32x4 (&af)[4], const f32x4 (&b
     }
 }
 
+// The ReLU decisions of one lane (pixel li, lk) of the producer's forward chain as one 64-bit word (the record layout of
+// pc_debug_head_decisions, popcorn_hip.h): bit 16 l + 4 mb + r = hidden layer l (0, 1, 2), unit 16 mb + 4 lk + r is positive; bit 48 =
+// the output decision outv > 0; bit 63 = written.
+// (the buffer's address is a device global, written on the call's stream in front of the launch: as one more kernel argument it moves
+// the implicit arguments of EVERY instantiation, the product kernels' included)
+__device__ unsigned long long* g_head_dec_dev;
+__device__ __forceinline__ unsigned long long head_dec_word(const f32x4 (&h1)[4], const f32x4 (&h2)[4], const f32x4 (&h3)[4], float outv) {
+    unsigned long long w = 1ull << 63;
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            w |= (unsigned long long)(h1[mb][r] > 0.f) << (4 * mb + r);
+            w |= (unsigned long long)(h2[mb][r] > 0.f) << (16 + 4 * mb + r);
+            w |= (unsigned long long)(h3[mb][r] > 0.f) << (32 + 4 * mb + r);
+        }
+    w |= (unsigned long long)(outv > 0.f) << 48;
+    return w;
+}
+
 template <int DBG, bool SPL>   // SPL: the producer's chain on split bf16 operands (above).  DBG: ablation builds (tools/ablate_head.py): 1 consumer idle, 2 no hand-off; 0 = the product kernel (as run-time flags the
                           // two switches put a branch around every ring write of the producer: 14 extra basic blocks in its group loop)
+                          // 4: the producer also writes its ReLU decisions to g_head_dec_dev (pc_debug_head_decisions; the tests' tie adjudication)
 __global__ __launch_bounds__(512, 2) void head_bwd_pc_kernel(const HeadBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const HeadArgs& p = a.f;
@@ -1527,11 +1548,15 @@ __global__ __launch_bounds__(512, 2) void head_bwd_pc_kernel(const HeadBwdArgs a
         }
         const float b6v = lds[SPL ? LS_F32 / 4 + 256 : LB_W6 + 64];
         const LsLane LL = ls_lane(lane);
+        [[maybe_unused]] unsigned long long* dec_p = nullptr;
+        if constexpr ((DBG & 4) != 0) dec_p = g_head_dec_dev;
         int gg = blockIdx.x * 4 + wv;
         if (gg < a.total_groups) fetch(gg);
         for (; gg < a.total_groups; gg += gstep) {
             const bool valid = n_valid;
             const bool sel = valid && (!has_msk || n_msk != 0);
+            [[maybe_unused]] long long dpix = 0;          // (DBG & 4) this lane's pixel b * H * W + q: the prefetch below moves f_pb / f_qq on
+            if constexpr ((DBG & 4) != 0) dpix = (long long)f_pb + (long long)f_qq;
             float* const gp = a.g_feat.ptr + n_b * a.g_feat.bstride + n_go;       // this lane's pixel of the gradient map, channel 0
             float xv[4], fvv[4];
 #pragma unroll
@@ -1617,6 +1642,9 @@ __global__ __launch_bounds__(512, 2) void head_bwd_pc_kernel(const HeadBwdArgs a
                 s = pc_xor16_sum(s);
                 s = pc_xor32_sum(s);
                 const float outv = s + b6v;
+                if constexpr ((DBG & 4) != 0) {
+                    if (sel) dec_p[dpix * 4 + lk] = head_dec_word(h1, h2, h3, outv);
+                }
                 const float gout = (sel && outv > 0.f) ? gup : 0.f;
                 if (!__any(gout != 0.f)) { store_zero(); continue; }
                 f32x4 g3[4], g2[4], g1[4];
@@ -1746,6 +1774,9 @@ __global__ __launch_bounds__(512, 2) void head_bwd_pc_kernel(const HeadBwdArgs a
             s = pc_xor16_sum(s);
             s = pc_xor32_sum(s);
             const float outv = s + b6v;
+            if constexpr ((DBG & 4) != 0) {
+                if (sel) dec_p[dpix * 4 + lk] = head_dec_word(h1, h2, h3, outv);
+            }
             const float gout = (sel && outv > 0.f) ? gup : 0.f;
             if (!__any(gout != 0.f)) { store_zero(); continue; }
 
@@ -3338,6 +3369,14 @@ extern "C" int pc_head_bwd_partials(void* ws, int B, int H, int W, const float**
     return 0;
 }
 
+// debug: decision records of head_bwd_pc_kernel<4, *> (popcorn_hip.h)
+static unsigned long long* g_head_dec = nullptr;
+static int64_t g_head_dec_bytes = 0;
+extern "C" void pc_debug_head_decisions(void* buf, int64_t bytes) {
+    g_head_dec = reinterpret_cast<unsigned long long*>(buf);
+    g_head_dec_bytes = buf ? bytes : 0;
+}
+
 extern "C" int pc_head_bwd(const pc_src* feat, int py, int px, const float* const* hw, const uint8_t* mask,
                            const float* building, const float* admin_mask, const int64_t* census_idx,
                            const float* g_popcount, const float* g_popdense, const float* g_scale_map,
@@ -3353,6 +3392,12 @@ extern "C" int pc_head_bwd(const pc_src* feat, int py, int px, const float* cons
         use_pc = (ev && ev[0] == '1') ? 0 : 1;
     }
     const bool split = !bfmode && use_pc && head_split_on();     // fp32 mode: the producer waves' chain on split bf16 operands
+    if (g_head_dec) {
+        // only the producer / consumer kernel exports its decisions, and only into a buffer that holds every pixel's record
+        if (bfmode || !use_pc || B < 1 || H < 1 || W < 1 || g_head_dec_bytes < (int64_t)B * H * W * PC_HEAD_DEC_BYTES ||
+            (reinterpret_cast<uintptr_t>(g_head_dec) & 7) != 0)
+            return PC_EINVAL;
+    }
     if (bfmode) {
         if (!pc_cl_ok(*feat) || feat->xstride < 16 || !pc_cl_ok(*g_feat) || g_feat->xstride != 16 || g_feat->rstride != 16 * Wp ||
             g_feat->bstride != (int64_t)16 * Hp * Wp)
@@ -3390,18 +3435,24 @@ extern "C" int pc_head_bwd(const pc_src* feat, int py, int px, const float* cons
         const char* dv = getenv("POPCORN_HEAD_DBG");
         a.dbg = dv ? atoi(dv) : 0;
     }
+    const bool export_dec = g_head_dec != nullptr;
+    if (export_dec) {
+        hipError_t e1 = hipMemcpyToSymbolAsync(HIP_SYMBOL(g_head_dec_dev), &g_head_dec, sizeof(g_head_dec), 0, hipMemcpyHostToDevice, st);
+        if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);       // (debug path: the source is host memory the caller may clear right after this call)
+        if (e1 != hipSuccess) return (int)e1;
+    }
     static pc_once_per_device once;
     if (once.need()) {
         hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&head_bwd_kernel),
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LB_END * sizeof(float)));
         if (e2 != hipSuccess) return (int)e2;
         for (const void* f : {reinterpret_cast<const void*>(&head_bwd_pc_kernel<0, false>), reinterpret_cast<const void*>(&head_bwd_pc_kernel<1, false>),
-                              reinterpret_cast<const void*>(&head_bwd_pc_kernel<2, false>)}) {
+                              reinterpret_cast<const void*>(&head_bwd_pc_kernel<2, false>), reinterpret_cast<const void*>(&head_bwd_pc_kernel<4, false>)}) {
             e2 = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LP_END * sizeof(float)));
             if (e2 != hipSuccess) return (int)e2;
         }
         for (const void* f : {reinterpret_cast<const void*>(&head_bwd_pc_kernel<0, true>), reinterpret_cast<const void*>(&head_bwd_pc_kernel<1, true>),
-                              reinterpret_cast<const void*>(&head_bwd_pc_kernel<2, true>)}) {
+                              reinterpret_cast<const void*>(&head_bwd_pc_kernel<2, true>), reinterpret_cast<const void*>(&head_bwd_pc_kernel<4, true>)}) {
             e2 = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LPS_END * sizeof(float)));
             if (e2 != hipSuccess) return (int)e2;
         }
@@ -3445,7 +3496,8 @@ extern "C" int pc_head_bwd(const pc_src* feat, int py, int px, const float* cons
 #endif
     }
     else if (use_pc && split) {
-        if (a.dbg == 1) hipLaunchKernelGGL((head_bwd_pc_kernel<1, true>), dim3(nwg), dim3(512), LPS_END * sizeof(float), st, a);
+        if (export_dec) hipLaunchKernelGGL((head_bwd_pc_kernel<4, true>), dim3(nwg), dim3(512), LPS_END * sizeof(float), st, a);
+        else if (a.dbg == 1) hipLaunchKernelGGL((head_bwd_pc_kernel<1, true>), dim3(nwg), dim3(512), LPS_END * sizeof(float), st, a);
         else if (a.dbg == 2) hipLaunchKernelGGL((head_bwd_pc_kernel<2, true>), dim3(nwg), dim3(512), LPS_END * sizeof(float), st, a);
         else hipLaunchKernelGGL((head_bwd_pc_kernel<0, true>), dim3(nwg), dim3(512), LPS_END * sizeof(float), st, a);
 #ifdef POPCORN_HEAD_PROF
@@ -3464,7 +3516,8 @@ extern "C" int pc_head_bwd(const pc_src* feat, int py, int px, const float* cons
 #endif
     }
     else if (use_pc) {
-        if (a.dbg == 1) hipLaunchKernelGGL((head_bwd_pc_kernel<1, false>), dim3(nwg), dim3(512), LP_END * sizeof(float), st, a);
+        if (export_dec) hipLaunchKernelGGL((head_bwd_pc_kernel<4, false>), dim3(nwg), dim3(512), LP_END * sizeof(float), st, a);
+        else if (a.dbg == 1) hipLaunchKernelGGL((head_bwd_pc_kernel<1, false>), dim3(nwg), dim3(512), LP_END * sizeof(float), st, a);
         else if (a.dbg == 2) hipLaunchKernelGGL((head_bwd_pc_kernel<2, false>), dim3(nwg), dim3(512), LP_END * sizeof(float), st, a);
         else hipLaunchKernelGGL((head_bwd_pc_kernel<0, false>), dim3(nwg), dim3(512), LP_END * sizeof(float), st, a);
 #ifdef POPCORN_HEAD_PROF

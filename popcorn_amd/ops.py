@@ -601,11 +601,14 @@ def ingest_split(s2_u16, s1, band, mean, std, top, bottom, left, right, cl8=None
 
 def head_bwd(feat, py, px, H, W, head_tensors, building, mask=None, admin_mask=None, census_idx=None,
              g_popcount=None, g_popdense=None, g_scale_map=None, g_scale_const=None, grads=None, accumulate=False,
-             g_feat=None, feat_bn=None, packed=False, defer_reduce=False):
+             g_feat=None, feat_bn=None, packed=False, defer_reduce=False, decisions=None):
     """Backward of head_fwd.  Returns (list of 8 head grads, g_feat (B,16,Hp,Wp)).  pack_both (head_fwd) / packed (here): a training
     step's forward call assembles the backward's weight image too (same weights, same workspace): one launch less.  defer_reduce:
     the weight gradients stay per-workgroup partials; returns (HeadPartials, g_feat) instead -- hand the first to the
-    ``WgradBatch`` of the same backward pass (``head_reduce``), whose batched reduction writes ``grads``: one launch less."""
+    ``WgradBatch`` of the same backward pass (``head_reduce``), whose batched reduction writes ``grads``: one launch less.
+    decisions (debug, fp32 mode): a contiguous int64 device tensor of at least B * H * W * 4 words (``head_decision_buffer``) that
+    receives the ReLU decisions the kernel takes (pc_debug_head_decisions; decode with ``decode_head_decisions``); everything else the
+    call returns is bit-equal to the call without it."""
     L.require_device(feat, building, *head_tensors)
     B, _, Hp, Wp = feat.shape
     dev = feat.device
@@ -617,18 +620,59 @@ def head_bwd(feat, py, px, H, W, head_tensors, building, mask=None, admin_mask=N
     sf, d = L.src(feat), L.dst(g_feat)
     hw = _hw_array(head_tensors)
     dhw = (C.c_void_p * 8)(*[0 if t is None else t.data_ptr() for t in grads])
-    L.check(L.lib().pc_head_bwd(C.byref(sf), py, px, hw, L.ptr(mask), L.ptr(building), L.ptr(admin_mask),
-                                L.ptr(census_idx), L.ptr(g_popcount), L.ptr(g_popdense), L.ptr(g_scale_map),
-                                L.ptr(g_scale_const), dhw, int(accumulate), C.byref(d),
-                                C.byref(feat_bn[0]) if feat_bn else None, C.byref(feat_bn[1]) if feat_bn else None,
-                                Hp, Wp, L.ptr(ws), B, H, W,
-                                (PC_HEAD_BWD_PACKED if packed else 0) | (PC_HEAD_BWD_DEFER_REDUCE if defer_reduce else 0),
-                                L.stream_ptr()), "pc_head_bwd")
+    if decisions is not None:
+        L.require_device(decisions)
+        assert decisions.dtype == torch.int64 and decisions.is_contiguous()
+        L.lib().pc_debug_head_decisions(L.ptr(decisions), C.c_int64(decisions.numel() * 8))
+    try:
+        code = L.lib().pc_head_bwd(C.byref(sf), py, px, hw, L.ptr(mask), L.ptr(building), L.ptr(admin_mask),
+                                   L.ptr(census_idx), L.ptr(g_popcount), L.ptr(g_popdense), L.ptr(g_scale_map),
+                                   L.ptr(g_scale_const), dhw, int(accumulate), C.byref(d),
+                                   C.byref(feat_bn[0]) if feat_bn else None, C.byref(feat_bn[1]) if feat_bn else None,
+                                   Hp, Wp, L.ptr(ws), B, H, W,
+                                   (PC_HEAD_BWD_PACKED if packed else 0) | (PC_HEAD_BWD_DEFER_REDUCE if defer_reduce else 0),
+                                   L.stream_ptr())
+    finally:
+        if decisions is not None:
+            L.lib().pc_debug_head_decisions(None, C.c_int64(0))
+    L.check(code, "pc_head_bwd")
     if defer_reduce:
         pp, nwg = C.c_void_p(0), C.c_int(0)
         L.check(L.lib().pc_head_bwd_partials(L.ptr(ws), B, H, W, C.byref(pp), C.byref(nwg)), "pc_head_bwd_partials")
         return HeadPartials(pp.value, nwg.value, list(grads), bool(accumulate)), g_feat
     return grads, g_feat
+
+
+HEAD_DEC_WORDS = 4          # int64 words per pixel record (PC_HEAD_DEC_BYTES / 8)
+
+
+def head_decision_buffer(B, H, W, device):
+    """Zeroed record buffer for ``head_bwd(decisions=...)``: (B * H * W, 4) int64."""
+    return torch.zeros(B * H * W, HEAD_DEC_WORDS, device=device, dtype=torch.int64)
+
+
+def decode_head_decisions(buf, mask=None):
+    """The records of pc_debug_head_decisions (popcorn_hip.h: word k of a pixel's record, bit 16 l + 4 m + r = unit 16 m + 4 k + r of
+    hidden layer l is positive; bit 48 = the output decision; bit 63 = written) -> (hidden (3, 64, Nsel) bool, out (Nsel,) bool) on
+    the pixels ``mask`` (B, H, W) selects (None: all), in the order of the reference's sparse head: row-major over (b, h, w).  Raises
+    when a selected record was not written or its four words disagree on the output decision."""
+    w = buf.reshape(-1, HEAD_DEC_WORDS).cpu()
+    if mask is not None:
+        w = w[mask.reshape(-1).bool().cpu()]
+    if not bool((w < 0).all()):
+        raise ValueError("decision record of a selected pixel was not written")
+    hidden = torch.zeros(3, 64, w.shape[0], dtype=torch.bool)
+    for layer in range(3):
+        for k in range(HEAD_DEC_WORDS):
+            for m in range(4):
+                for r in range(4):
+                    hidden[layer, 16 * m + 4 * k + r] = ((w[:, k] >> (16 * layer + 4 * m + r)) & 1).bool()
+    out = ((w >> 48) & 1).bool()
+    if not bool((out == out[:, :1]).all()):
+        raise ValueError("the four words of a decision record disagree on the output decision")
+    if bool(((w & 0x7FFE000000000000) != 0).any()):
+        raise ValueError("reserved bits of a decision record are set")
+    return hidden, out[:, 0]
 
 
 class HeadPartials:

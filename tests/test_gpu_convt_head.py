@@ -312,6 +312,178 @@ def test_head_bwd_vs_oracle_autograd(sparse, shape, head_form):
             assert torch.all(tgt[6][1] == 0) and tgt[7][1].item() == 0.0
 
 
+# ---- the decisions the head backward kernel takes (pc_debug_head_decisions): what tests/tie_adjudication.py forces the fp64 oracle to ----
+DEC_SHAPES = [(3, 100, 100, 128, 128, 14, 14), (1, 37, 29, 64, 64, 13, 17)]       # (the second: a ragged last group of 16 pixels)
+
+
+def _dec_inputs(shape, sparse, seed):
+    B, H, W, Hp, Wp, py, px = shape
+    feat = _mk(B, 16, Hp, Wp, seed=seed)
+    gen = torch.Generator().manual_seed(seed + 1)
+    building = torch.rand(B, 1, H, W, generator=gen)
+    mask = (torch.rand(B, H, W, generator=gen) < 0.5) if sparse else torch.ones(B, H, W, dtype=torch.bool)
+    return feat, building, mask
+
+
+def _unit_pattern(seed):
+    """64 values of +1 / -1 / 0 with no symmetry under permutations of the kernel's unit indices (16 m + 4 k + r): a fixed random draw."""
+    gen = torch.Generator().manual_seed(seed)
+    return torch.randint(-1, 2, (64,), generator=gen).float()
+
+
+@pytest.mark.parametrize("head_form", [1, 0], indirect=True)
+@pytest.mark.parametrize("sparse", [True, False])
+@pytest.mark.parametrize("shape", DEC_SHAPES)
+def test_head_decision_export_known_answer(sparse, shape, head_form):
+    """Bit mapping of the exported records: with all head weights zero every pre-activation IS its bias, so every selected pixel must
+    export exactly the sign pattern of the biases -- a different irregular pattern of +1 / -1 / 0 per layer, b6 = +1, -1, 0 in turn; a
+    bias of exactly 0 exports 0 (the decision is the strict > 0).  Records of unselected pixels stay untouched."""
+    from popcorn_amd import ops
+    B, H, W, Hp, Wp, py, px = shape
+    feat, building, mask = _dec_inputs(shape, sparse, 61)
+    pats = [_unit_pattern(70 + i) for i in range(3)]
+    assert all(int((p == v).sum()) > 8 for p in pats for v in (-1.0, 0.0, 1.0)) and not any(torch.equal(pats[i], pats[j]) for i in range(3) for j in range(i))
+    for b6 in (1.0, -1.0, 0.0):
+        ht = [torch.zeros(64, 16, 1, 1), pats[0], torch.zeros(64, 64, 1, 1), pats[1], torch.zeros(64, 64, 1, 1), pats[2],
+              torch.zeros(2, 64, 1, 1), torch.tensor([b6, 0.5])]
+        ht = [t.cuda() for t in ht]
+        buf = ops.head_decision_buffer(B, H, W, "cuda")
+        ops.head_bwd(feat.cuda(), py, px, H, W, ht, building.cuda(), mask=mask.to(torch.uint8).cuda() if sparse else None,
+                     g_scale_const=torch.ones(1, device="cuda"), decisions=buf)
+        hidden, outd = ops.decode_head_decisions(buf, mask)
+        nsel = int(mask.sum())
+        assert hidden.shape == (3, 64, nsel) and outd.shape == (nsel,)
+        for layer in range(3):
+            want = (pats[layer] > 0).view(64, 1).expand(64, nsel)
+            assert torch.equal(hidden[layer], want), (layer, b6, int((hidden[layer] != want).sum()))
+        assert torch.equal(outd, torch.full((nsel,), b6 > 0)), b6
+        assert torch.all(buf.cpu()[~mask.reshape(-1)] == 0)
+
+
+def _feat_bn(seed):
+    from popcorn_amd import _lib as L
+    gen = torch.Generator().manual_seed(seed)
+    mk = lambda lo, hi: (lo + (hi - lo) * torch.rand(8, generator=gen)).cuda()  # noqa: E731
+    return tuple(L.bn(gamma=mk(0.5, 1.5), beta=mk(-0.2, 0.2), mean=mk(-0.2, 0.2), var=mk(0.5, 1.5)) for _ in range(2))
+
+
+@pytest.mark.parametrize("head_form", [1, 0], indirect=True)
+@pytest.mark.parametrize("sparse", [True, False])
+@pytest.mark.parametrize("shape", DEC_SHAPES)
+def test_head_decision_export_does_not_perturb_the_call(sparse, shape, head_form):
+    """The exporting instantiation computes what the product kernel computes: g_feat and the 8 weight gradients are torch.equal between
+    the two launches on the same inputs, with and without the fused feature-BN epilogue; with g_popcount all zero (every group leaves
+    through the kernel's early exit) the gradients are equal too AND the exported records are complete: the same as with gradient."""
+    from oracle import popcorn_oracle as O
+    from popcorn_amd import ops
+    B, H, W, Hp, Wp, py, px = shape
+    sd = O.load_golden_state(G)
+    feat, building, mask = _dec_inputs(shape, sparse, 81)
+    gen = torch.Generator().manual_seed(83)
+    admin = (torch.rand(B, H, W, generator=gen) < 0.6).float() * 5.0
+    census = torch.full((B,), 5, dtype=torch.int64)
+    g_pc = torch.randn(B, generator=gen)
+    ht = [sd[f"head.{i}.{n}"].cuda() for i in (0, 2, 4, 6) for n in ("weight", "bias")]
+    records = []
+    for bn in (None, _feat_bn(85)):
+        for gp in (g_pc, torch.zeros(B)):
+            kw = dict(mask=mask.to(torch.uint8).cuda() if sparse else None, admin_mask=admin.cuda(), census_idx=census.cuda(),
+                      g_popcount=gp.cuda(), feat_bn=bn)
+            grads0, gf0 = ops.head_bwd(feat.cuda(), py, px, H, W, ht, building.cuda(), **kw)
+            buf = ops.head_decision_buffer(B, H, W, "cuda")
+            grads1, gf1 = ops.head_bwd(feat.cuda(), py, px, H, W, ht, building.cuda(), decisions=buf, **kw)
+            assert torch.equal(gf0, gf1) and all(torch.equal(a, b) for a, b in zip(grads0, grads1)), (bn is not None, float(gp.abs().sum()))
+            if float(gp.abs().sum()) == 0.0:
+                assert not bool(gf0.any()) and not any(bool(g.any()) for g in grads0)
+            else:
+                assert bool(gf0.any())
+            records.append(buf.cpu())
+            # (the export is over: the next product launch is the product kernel again)
+            grads2, gf2 = ops.head_bwd(feat.cuda(), py, px, H, W, ht, building.cuda(), **kw)
+            assert torch.equal(gf0, gf2) and all(torch.equal(a, b) for a, b in zip(grads0, grads2))
+    assert all(torch.equal(records[0], r) for r in records[1:])
+    assert bool((records[0][mask.reshape(-1)] < 0).all())           # every selected record written (bit 63)
+    assert torch.all(records[0][~mask.reshape(-1)] == 0)
+
+
+@pytest.mark.parametrize("head_form", [1, 0], indirect=True)
+@pytest.mark.parametrize("sparse", [True, False])
+@pytest.mark.parametrize("shape", DEC_SHAPES)
+def test_head_decision_export_vs_float64(sparse, shape, head_form):
+    """The exported masks against a FLOAT64 head on the same random features (golden weights; head.6.bias[0] moved by the median of the
+    float64 output so that the output decision takes both signs): they may differ only at near-ties -- at most max(8, 2e-5 x sites)
+    sites, each with |float64 pre-activation| <= 1e-4 of its layer's mean magnitude (the bounds tests/tie_adjudication.py puts on the
+    sites it overrides).  Room under the cap: with generator seed 41 the float32 TORCH head on the CPU differs from the float64 one at
+    0 of 5,790,000 sites (3 x 100 x 100 dense) and 0 of 207,089 (1 x 37 x 29 dense) -- counted without a GPU; the sparse cases are
+    subsets of those pixels."""
+    from oracle import popcorn_oracle as O
+    from popcorn_amd import ops
+    B, H, W, Hp, Wp, py, px = shape
+    sd = O.load_golden_state(G)
+    feat, building, mask = _dec_inputs(shape, sparse, 41)
+    x = feat[:, :, py:py + H, px:px + W].double().permute(1, 0, 2, 3).reshape(16, -1, 1)
+
+    def pre64(b6):
+        h, pres = x, []
+        for i in (0, 2, 4):
+            h = F.conv2d(h, sd[f"head.{i}.weight"].double(), sd[f"head.{i}.bias"].double())
+            pres.append(h[:, :, 0])
+            h = F.relu(h)
+        pres.append(F.conv2d(h, sd["head.6.weight"].double(), b6.double())[0:1, :, 0])
+        return pres
+
+    b6 = sd["head.6.bias"].clone()
+    b6[0] -= pre64(b6)[3].median().float()
+    pres = [p[:, mask.reshape(-1)] for p in pre64(b6)]
+    assert 0.3 < float((pres[3] > 0).double().mean()) < 0.7
+    ht = [sd[f"head.{i}.{n}"] for i in (0, 2, 4) for n in ("weight", "bias")] + [sd["head.6.weight"], b6]
+    buf = ops.head_decision_buffer(B, H, W, "cuda")
+    ops.head_bwd(feat.cuda(), py, px, H, W, [t.cuda() for t in ht], building.cuda(), mask=mask.to(torch.uint8).cuda() if sparse else None,
+                 g_scale_const=torch.ones(1, device="cuda"), decisions=buf)
+    hidden, outd = ops.decode_head_decisions(buf, mask)
+    got = [hidden[0], hidden[1], hidden[2], outd.view(1, -1)]
+    sites = sum(p.numel() for p in pres)
+    ndiff, margin = 0, 0.0
+    for g, p in zip(got, pres):
+        d = g != (p > 0)
+        ndiff += int(d.sum())
+        if bool(d.any()):
+            margin = max(margin, float(p.abs()[d].max() / p.abs().mean()))
+    print(f"\n[head decisions vs float64] form {head_form}, sparse {sparse}, {shape[:3]}: {ndiff} of {sites} sites differ, worst margin {margin:.1e}")
+    assert ndiff <= max(8, 2e-5 * sites), (ndiff, sites)
+    assert margin <= 1e-4, margin
+
+
+@pytest.mark.parametrize("head_form", [1, 0], indirect=True)
+def test_head_decision_export_refusals_leave_the_buffer_untouched(head_form):
+    """PC_EINVAL, with nothing written: a buffer smaller than B x H x W records, and bf16 mode (its kernel has no export).  The
+    registration ends with the call either way: the next plain call runs."""
+    from oracle import popcorn_oracle as O
+    from popcorn_amd import ops, _lib as L
+    B, H, W, Hp, Wp, py, px = DEC_SHAPES[1]
+    sd = O.load_golden_state(G)
+    feat, building, mask = _dec_inputs(DEC_SHAPES[1], True, 91)
+    ht = [sd[f"head.{i}.{n}"].cuda() for i in (0, 2, 4, 6) for n in ("weight", "bias")]
+    kw = dict(mask=mask.to(torch.uint8).cuda(), g_scale_const=torch.ones(1, device="cuda"))
+    small = torch.full((B * H * W * 4 - 1,), 7, device="cuda", dtype=torch.int64)
+    with pytest.raises(L.PopcornHipError):
+        ops.head_bwd(feat.cuda(), py, px, H, W, ht, building.cuda(), decisions=small, **kw)
+    torch.cuda.synchronize()
+    assert torch.all(small == 7)
+    full = torch.full((B * H * W, 4), 7, device="cuda", dtype=torch.int64)
+    with L.precision("bf16"):
+        with pytest.raises(L.PopcornHipError):
+            ops.head_bwd(L.as_act(feat.cuda()), py, px, H, W, ht, building.cuda(), decisions=full, **kw)
+    torch.cuda.synchronize()
+    assert torch.all(full == 7)
+    # a sufficient buffer in fp32 mode: selected records written, the others still as they were
+    ops.head_bwd(feat.cuda(), py, px, H, W, ht, building.cuda(), decisions=full, **kw)
+    fc = full.cpu()
+    assert bool((fc[mask.reshape(-1)] < 0).all()) and torch.all(fc[~mask.reshape(-1)] == 7)
+    grads, _ = ops.head_bwd(feat.cuda(), py, px, H, W, ht, building.cuda(), **kw)
+    assert all(bool(torch.isfinite(g).all()) for g in grads)
+
+
 @pytest.mark.parametrize("case", ["regions", "empty_selection", "no_occupancy"])
 @pytest.mark.parametrize("C_", [16, 2])
 def test_building_score_mask_equals_the_two_separate_ops(case, C_):

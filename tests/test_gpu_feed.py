@@ -141,6 +141,40 @@ def test_augment_raw_equals_the_transform_classes_and_their_generator_consumptio
     assert seen == {True, False} or H == W
 
 
+def test_augment_raw_rotation_direction_known_answer():
+    """pc_augment_raw with rot = 1 / 3 (the transposed-tile kernel) against written-out answers on non-square tiles: rot = 1 is one
+    quarter turn COUNTER-clockwise (angle 90 of the reference, utils/transform.py:169), rot = 3 is clockwise -- for the four
+    Sentinel-2 bands, the two Sentinel-1 bands and admin_mask alike.  [[1,2,3],[4,5,6]] -> [[3,6],[2,5],[1,4]] / [[4,1],[5,2],[6,3]]; then
+    a 37 x 45 tile (a width that is no multiple of 32) element by element: out[i][j] = in[j][W-1-i] / in[H-1-j][i]."""
+    from popcorn_amd import ops
+    base = torch.tensor([[1., 2., 3.], [4., 5., 6.]])
+    want = {1: [[3., 6.], [2., 5.], [1., 4.]], 3: [[4., 1.], [5., 2.], [6., 3.]]}
+    s2 = torch.stack([base + 10 * c for c in range(4)]).unsqueeze(0)
+    s1 = torch.stack([-(base + 10 * c) for c in range(2)]).unsqueeze(0)
+    adm = (base + 100).unsqueeze(0)
+    for rot, w in want.items():
+        raw, ao = ops.augment_raw(s2.cuda(), s1.cuda(), adm.cuda(), {"rot": rot})
+        assert raw.shape == (1, 6, 3, 2) and ao.shape == (1, 3, 2)
+        wt = torch.tensor(w)
+        for c in range(4):
+            assert raw[0, c].cpu().tolist() == (wt + 10 * c).tolist(), (rot, c)
+        for c in range(2):
+            assert raw[0, 4 + c].cpu().tolist() == (-(wt + 10 * c)).tolist(), (rot, c)
+        assert ao[0].cpu().tolist() == (wt + 100).tolist(), rot
+    B, H, W = 2, 37, 45
+    g = torch.Generator().manual_seed(9)
+    s2 = torch.randint(0, 10000, (B, 4, H, W), generator=g).float()
+    s1 = torch.randn(B, 2, H, W, generator=g)
+    adm = torch.randint(0, 7, (B, H, W), generator=g).float()
+    src = torch.cat([s2, s1, adm.unsqueeze(1)], 1)
+    i, j = torch.meshgrid(torch.arange(W), torch.arange(H), indexing="ij")          # output coordinates (W rows, H columns)
+    for rot in (1, 3):
+        raw, ao = ops.augment_raw(s2.cuda(), s1.cuda(), adm.cuda(), {"rot": rot})
+        got = torch.cat([raw.cpu(), ao.cpu().unsqueeze(1)], 1)
+        exp = src[:, :, j, W - 1 - i] if rot == 1 else src[:, :, H - 1 - j, i]
+        assert got.shape == (B, 7, W, H) and torch.equal(got, exp), rot
+
+
 def test_trainer_fed_one_batch_ahead_takes_the_reference_order_steps(tmp_path):
     """Trainer.train() through RegionFeed (pinned loader, copy stream, one-launch augmentation, raw input form) against the same trainer
     stepped the reference's way (synchronous copy, per-op augmentation launches, normalised input): same seeds -> same batches, same

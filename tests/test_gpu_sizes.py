@@ -184,7 +184,12 @@ def test_config3_batch64_train_step_is_deterministic_and_graph_equals_eager():
 def test_config3_batch64_fused_step_gradients_vs_oracle():
     """BASELINE config[2] at its full size (B=64 tiles of 100x100, rwa recipe): loss, popcount and all 56 gradients of ONE
     fused step against the CPU oracle's autograd (~10 s of CPU), <= 2e-4 relative -- the same bar as the B=3 reference
-    fixture g5 (and the same adjudication of a mismatch above it: a proven decision flip + the shared-decision distance)."""
+    fixture g5 (and the same adjudication of a mismatch above it: a proven decision flip + the shared-decision distance).
+
+    On the adjudication path the sites that the fp64 oracle alone decides differently from the HIP side (ReLU masks + pooling arg-maxes
+    of the U-Net from the saved activations, head masks from the head backward kernel's export) must also be few IN TOTAL: <= 2e-5 of all
+    decision sites.  Room under that cap, from the references alone (no GPU): on this batch the fp32 and the fp64 CPU oracle decide 12
+    of 142,279,900 sites differently (8 ReLU, 0 pooling, 4 head) -- the cap is 2,845."""
     from popcorn_amd.data.synthetic import make_raw_batch
     batch = make_raw_batch(64, 100, 100, seed=1603, region="disc")
     x = O.select_normalize(batch["raw"])
@@ -209,6 +214,11 @@ def test_config3_batch64_fused_step_gradients_vs_oracle():
         assert_tie_flip(sd, cpu, x.cuda(), hip_g, {n: r.clone() for n, r in ref_grads.items()}, 5, worst)
         wf, wname, flips, _ = forced_decision_distance(sd, cpu, x.cuda(), hip_g, 5)
         assert wf < 1e-4, (wf, wname, flips)
+        from tests.tie_adjudication import SHARED
+        sites = sum(SHARED[-1]["sites"].values())
+        differing = flips["relu"] + flips["pool"] + len(flips["head"])
+        print(f"\n[B=64 shared decisions] {differing} of {sites} sites differ between the fp64 oracle and the HIP side: {flips}")
+        assert sites > 1e8 and differing <= 2e-5 * sites, (differing, sites, flips)
 
 
 def test_graph_replay_equals_eager_over_many_steps_with_static_buffers():

@@ -206,3 +206,122 @@ def test_force_decisions_with_the_oracles_own_decisions_changes_nothing_and_fore
     # where that unit fed gradient (first layer of its stream), and are finite everywhere
     changed = [n for n in grads if not torch.equal(grads[n], forced2[n])]
     assert changed and all(torch.isfinite(forced2[n]).all() for n in forced2)
+
+
+def _g5_sample():
+    g = np.load(os.path.join(G, "g5_train.npz"))
+    return {"input": torch.from_numpy(g["input"]), "admin_mask": torch.from_numpy(g["admin_mask"]),
+            "census_idx": torch.from_numpy(g["census_idx"]), "y": torch.from_numpy(g["y"])}
+
+
+def test_force_decisions_full_head_masks_own_masks_change_nothing(sd):
+    """ForceDecisions(head_masks=...): the head's three hidden ReLU masks and the output ReLU forced on the selected pixels (the GPU tests
+    hand in the masks the head backward kernel exports).  Forcing the oracle's OWN head masks, together with its own U-Net decisions,
+    reproduces the unforced gradients bit for bit with zero flips, and every head decision site is counted."""
+    sample = _g5_sample()
+    torch.manual_seed(1700)
+    with O.TieProbe() as probe:
+        _, out, grads, _ = O.train_step_grads(sd, dict(sample))
+    hidden, outd = probe.head_masks()
+    nsel = out["scale"].numel()
+    assert hidden.shape == (3, 64, nsel) and outd.shape == (nsel,) and nsel > 100
+    assert 0 < int(hidden.sum()) < hidden.numel()                   # both decisions occur
+    torch.manual_seed(1700)
+    with O.ForceDecisions(probe.acts, probe.pools, head_masks=(hidden, outd)) as f:
+        _, _, forced, _ = O.train_step_grads(sd, dict(sample))
+    assert f.flips == {"relu": 0, "pool": 0, "head": []} and f.margin["head"] == 0.0
+    assert f.sites["head"] == 3 * 64 * nsel + nsel
+    for n in grads:
+        assert torch.equal(grads[n], forced[n]), n
+
+
+def test_force_decisions_full_head_masks_a_wrong_mask_is_counted_and_far_from_a_tie(sd):
+    """A head mask with one FAR-from-tie hidden unit inverted (the unit with the largest |pre-activation| of the first layer) and one
+    output decision inverted (the column with the largest |out|): both are listed in flips["head"] -- the output as (6, 0, column) --
+    and margin["head"] is of order 1, four orders above the 1e-4 that tests/tie_adjudication.py: forced_decision_distance admits for
+    an overridden site: a kernel that exported (or used) such a mask is rejected there, not adopted."""
+    import torch.nn.functional as F
+    sample = _g5_sample()
+    torch.manual_seed(1700)
+    with O.TieProbe() as probe:
+        _, _, grads, _ = O.train_step_grads(sd, dict(sample))
+    hidden, outd = probe.head_masks()
+    torch.manual_seed(1700)
+    with torch.no_grad():
+        fo = O.popcorn_forward(sd, dict(sample), padding=False, sparse=True, return_features=True)
+    from popcorn_amd.model.popcorn import pad_geometry
+    H, W = sample["input"].shape[2:]
+    pt, _, pl, _ = pad_geometry(H, W, False)
+    x = fo["features"][:, :, pt:pt + H, pl:pl + W].permute(1, 0, 2, 3).reshape(16, -1, 1)[:, fo["mask"].reshape(-1)]
+    assert x.shape[1] == hidden.shape[2]
+    pre0 = F.conv2d(x, sd["head.0.weight"], sd["head.0.bias"])[:, :, 0]
+    assert torch.equal(pre0 > 0, hidden[0])
+    u, c = (pre0.abs() == pre0.abs().max()).nonzero()[0].tolist()
+    wrong = hidden.clone()
+    wrong[0, u, c] = ~wrong[0, u, c]
+    torch.manual_seed(1700)
+    with O.ForceDecisions(probe.acts, probe.pools, head_masks=(wrong, outd)) as f:
+        _, _, forced, _ = O.train_step_grads(sd, dict(sample))
+    # (with that unit off the column's later layers see other values: where their own decisions now differ from the forced ones they are
+    # listed too -- all in the same column)
+    assert f.flips["relu"] == 0 and f.flips["pool"] == 0 and f.flips["head"][0] == (0, u, c)
+    assert [s for s in f.flips["head"] if s[0] == 0] == [(0, u, c)] and all(s[2] == c for s in f.flips["head"])
+    assert f.margin["head"] > 1.0, f.margin                          # (the largest of a layer against the layer's mean magnitude)
+    assert any(not torch.equal(grads[n], forced[n]) for n in grads)
+    # the output decision
+    scale = fo["scale"]
+    co = int(scale.argmax())
+    wrong_out = outd.clone()
+    wrong_out[co] = ~wrong_out[co]
+    torch.manual_seed(1700)
+    with O.ForceDecisions(probe.acts, probe.pools, head_masks=(hidden, wrong_out)) as f2:
+        _, _, forced2, _ = O.train_step_grads(sd, dict(sample))
+    assert f2.flips["head"] == [(6, 0, co)] and f2.margin["head"] > 1e-2, (f2.flips, f2.margin)
+    assert any(not torch.equal(grads[n], forced2[n]) for n in grads)
+
+
+def test_head_decision_records_decode_round_trip():
+    """The record layout of pc_debug_head_decisions as include/popcorn_hip.h documents it, written here by hand: word k of pixel
+    b * H * W + y * W + x, bit 16 l + 4 m + r = unit 16 m + 4 k + r of hidden layer l, bit 48 = output decision, bit 63 = written.
+    ops.decode_head_decisions returns (3, 64, Nsel) / (Nsel,) in row-major (b, h, w) order of the selected pixels; 2 x 5 x 7 pixels: the
+    last 16-pixel group of a sample is ragged (35 = 2 x 16 + 3) and unselected records are unwritten."""
+    from popcorn_amd import ops
+    B, H, W = 2, 5, 7
+    gen = torch.Generator().manual_seed(5)
+    mask = torch.rand(B, H, W, generator=gen) < 0.6
+    mask[0, H - 1, W - 1] = True                        # a pixel of the ragged group
+    mask[1, 0, 0] = False
+    hidden = torch.rand(3, 64, B * H * W, generator=gen) < 0.5
+    outd = torch.rand(B * H * W, generator=gen) < 0.5
+    words = np.zeros((B * H * W, 4), dtype=np.uint64)
+    for p in range(B * H * W):
+        if not mask.reshape(-1)[p]:
+            continue
+        for k in range(4):
+            w = 1 << 63
+            for layer in range(3):
+                for m in range(4):
+                    for r in range(4):
+                        if hidden[layer, 16 * m + 4 * k + r, p]:
+                            w |= 1 << (16 * layer + 4 * m + r)
+            if outd[p]:
+                w |= 1 << 48
+            words[p, k] = w
+    buf = torch.from_numpy(words.view(np.int64))
+    got_h, got_o = ops.decode_head_decisions(buf, mask)
+    sel = mask.reshape(-1)
+    assert got_h.shape == (3, 64, int(sel.sum())) and got_h.dtype == torch.bool and got_o.shape == (int(sel.sum()),)
+    assert torch.equal(got_h, hidden[:, :, sel]) and torch.equal(got_o, outd[sel])
+    # one unit, one bit: unit 37 = 16 * 2 + 4 * 1 + 1 of layer 1 is bit 16 + 4 * 2 + 1 = 25 of word 1
+    one = torch.zeros(1, 4, dtype=torch.int64)
+    one[:] = -(1 << 63)
+    one[0, 1] |= 1 << 25
+    h1, o1 = ops.decode_head_decisions(one)
+    assert h1.nonzero().tolist() == [[1, 37, 0]] and not bool(o1[0])
+    # an unwritten selected record, and words that disagree on the output decision, are errors -- not decisions
+    with pytest.raises(ValueError):
+        ops.decode_head_decisions(buf, torch.ones(B, H, W, dtype=torch.bool))
+    bad = one.clone()
+    bad[0, 2] |= 1 << 48
+    with pytest.raises(ValueError):
+        ops.decode_head_decisions(bad)

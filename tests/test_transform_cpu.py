@@ -94,6 +94,17 @@ def test_rotation_is_ccw_quarter_turns_with_expand():
     assert y[0, 0, 0, 0] == x[0, 0, 0, 2]
 
 
+def test_rotation_direction_known_answer_on_a_non_square_tensor():
+    """Written-out answers, independent of torch.rot90: angle 90 is COUNTER-clockwise (TF.rotate(..., expand=True), reference
+    utils/transform.py:169), 270 is clockwise; input and mask move together."""
+    x = torch.tensor([[1., 2., 3.], [4., 5., 6.]])
+    want = {90: [[3., 6.], [2., 5.], [1., 4.]], 270: [[4., 1.], [5., 2.], [6., 3.]], 180: [[6., 5., 4.], [3., 2., 1.]]}
+    for angle, w in want.items():
+        y, ym = T.RandomRotationTransform([angle], p=1.1)((x.view(1, 1, 2, 3).clone(), (10 * x).view(1, 2, 3).clone()))
+        assert y[0, 0].tolist() == w, (angle, y)
+        assert ym[0].tolist() == [[10 * v for v in row] for row in w], (angle, ym)
+
+
 def test_apply_normalize_matches_constants():
     s = {"S2": torch.rand(2, 4, 3, 3) * 5000, "S1": torch.randn(2, 2, 3, 3) * 5 - 12}
     ref = {k: v.clone() for k, v in s.items()}

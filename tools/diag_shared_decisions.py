@@ -54,10 +54,28 @@ for i in (0, 2, 4):
 out = F.conv2d(xx, sd64["head.6.weight"], sd64["head.6.bias"])
 print("final: |out0| smallest %.3e (mean %.3e)" % (out[0].abs().min(), out[0].abs().mean()))
 
-from tests.tie_adjudication import head_near_ties
+
+
+def head_near_ties(sd, feats, mask, rel_eps=3e-6):
+    """Hidden units of the head whose pre-activation (fp64 head on the given cropped features, selected pixels) is within ``rel_eps`` of
+    zero relative to the layer's mean magnitude: [(layer 0 / 2 / 4, unit, column), ...] ordered by |pre-activation|."""
+    x = feats.double().permute(1, 0, 2, 3).reshape(feats.shape[1], -1, 1)[:, mask.reshape(-1)]
+    out = []
+    for i in (0, 2, 4):
+        pre = F.conv2d(x, sd[f"head.{i}.weight"].double(), sd[f"head.{i}.bias"].double())
+        a = pre.abs()[:, :, 0]
+        for u, c in (a < rel_eps * a.mean()).nonzero().tolist():
+            out.append((a[u, c].item() / a.mean().item(), i, u, c))
+        x = F.relu(pre)
+    return [(i, u, c) for _, i, u, c in sorted(out)]
+
+
+# the tests OBSERVE the head kernel's decisions (forced_decision_distance, observe_head=True); here the head is left to the oracle's own
+# decisions and single near-tie units are inverted by hand, to see which one a residual hangs on
 cands = head_near_ties(sd, feats, mask, 1e-5)[:8]
 print("head candidates (layer, unit, column):", cands)
-base = forced_decision_distance(sd, cpu, x, hip, 3)[0]
+print("observed head decisions: %.2e, differing head sites %s" % (lambda r: (r[0], r[2]["head"]))(forced_decision_distance(sd, cpu, x, hip, 3)))
+base = forced_decision_distance(sd, cpu, x, hip, 3, observe_head=False)[0]
 for c in cands:
-    wf = forced_decision_distance(sd, cpu, x, hip, 3, head_flips=[c])[0]
+    wf = forced_decision_distance(sd, cpu, x, hip, 3, observe_head=False, head_flips=[c])[0]
     print("  flip", c, "-> %.2e" % wf, "<-- explains it" if wf < 0.3 * base else "")
