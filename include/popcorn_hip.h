@@ -469,7 +469,7 @@ int pc_head_bwd(const pc_src* feat, int py, int px, const float* const* hw, cons
  *   bit 48              : the output decision out[:, 0] > 0 of the final relu (the same in all four words);
  *   bit 63              : set in every word the kernel wrote; all other bits are 0.
  * pc_head_bwd returns PC_EINVAL, launching nothing, when a buffer is registered and it is smaller than B * H * W records or not 8-byte
- * aligned, or the call would run a kernel without the export (bf16 mode, POPCORN_HEAD_BWD_SINGLE_ROLE=1). */
+ * aligned, or the call would run a kernel without the export (bf16 mode). */
 #define PC_HEAD_DEC_BYTES 32
 void pc_debug_head_decisions(void* buf, int64_t bytes);
 

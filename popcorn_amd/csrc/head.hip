@@ -1,12 +1,22 @@
-// head.hip -- POPCORN's sparse occupancy head on fp32 MFMA, plus the small per-pixel kernels around it.
+// head.hip -- POPCORN's sparse occupancy head: forward, backward, weight-image packing, popcount / loss reduction.
+// (The per-pixel kernels around the head live in mask.hip -- building score, sparsity mask, compaction -- and ingest.hip.)
 //
 // Replaces (reference model/popcorn.py):
 //   :80-85,161-164  head = Conv1x1(16,64) ReLU Conv1x1(64,64) ReLU Conv1x1(64,64) ReLU Conv1x1(64,2)[:,0]
 //   :195-228        sparse_module_forward (gather by mask -> head -> index_put)   -> masked in place, no gather
 //   :155,271-276    revert_padding (crop)                                          -> crop offsets in the loader
 //   :170-190        scale = relu(out); popdensemap = scale * building; popcount = masked sum over the census region
-//   :301,317-320    fusion_out_conv + sigmoid + crop (building score)
-//   :361-377        get_sparsity_mask
+//
+// Forms of the head in this file, and what each is for:
+//   form            kernels                                                 role
+//   split fp32      head_fwd_split_kernel<8>, head_bwd_pc_kernel<0, true>   product default: fp32 results from 3-way split bf16 operands
+//   bf16            head_fwd_bf16_kernel, head_bwd_bf16_coop4_kernel        product in PC_PREC_BF16 mode
+//   fp32 MFMA       head_fwd_kernel, head_bwd_pc_kernel<0, false>           test fixture behind pc_set_head_split(0): the strict flat-bar
+//                                                                           tests, and A/B runs against the split form
+//   DBG = 4         head_bwd_pc_kernel<4, .>                                decision export (pc_debug_head_decisions) for the tests' tie
+//                                                                           adjudication
+//   PROF / ABLATE   phase counters; head_bwd_pc_kernel<1 | 2, .>            macro builds only (-DPOPCORN_HEAD_PROF / -DPOPCORN_HEAD_ABLATE,
+//                                                                           tools/build_variant.sh): never in the product library
 //
 // MLP mapping: pixels ride on N (16 pixels per wave-step), hidden units on M, so the accumulator (D) layout of
 // layer l -- lane (n = pixel, lk): rows 16*mb + 4*lk + r -- is *already* the B-operand layout of layer l+1 when
@@ -85,43 +95,6 @@ __device__ __forceinline__ void head_stage_weights(float* lds, const HeadArgs& p
 // itself: 1024 workgroups doing that gather at once cost the bf16 forward kernel 10 of its 47 us
 __device__ __forceinline__ void head_copy_image(void* lds, const void* img, int nbytes) {
     for (int e = threadIdx.x; e < nbytes / 16; e += blockDim.x) reinterpret_cast<uint4*>(lds)[e] = reinterpret_cast<const uint4*>(img)[e];
-}
-
-// One 64-wide layer: acc[mb2] = bias + W * h  (h in D layout of the previous layer), ReLU applied by the caller.
-__device__ __forceinline__ void head_layer64(const float* lds, int a_off, int b_off, int lane, int lk,
-                                             const f32x4 (&h)[4], f32x4 (&acc)[4]) {
-#pragma unroll
-    for (int mb2 = 0; mb2 < 4; ++mb2) acc[mb2] = *reinterpret_cast<const f32x4*>(&lds[b_off + 16 * mb2 + 4 * lk]);
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb) {
-        f32x4 a4[4];
-#pragma unroll
-        for (int mb2 = 0; mb2 < 4; ++mb2) a4[mb2] = *reinterpret_cast<const f32x4*>(&lds[a_off + ((mb2 * 4 + mb) * 64 + lane) * 4]);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int mb2 = 0; mb2 < 4; ++mb2)
-                acc[mb2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[mb2][r], h[mb][r], acc[mb2], 0, 0, 0);
-    }
-}
-
-// first layer (16 -> 64): h[mb] = b0 + W0 * x
-__device__ __forceinline__ void head_layer1(const float* lds, int a_off, int b_off, int lane, int lk, const float (&xv)[4],
-                                            f32x4 (&h)[4]) {
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb) {
-        h[mb] = *reinterpret_cast<const f32x4*>(&lds[b_off + 16 * mb + 4 * lk]);
-        const f32x4 a4 = *reinterpret_cast<const f32x4*>(&lds[a_off + (mb * 64 + lane) * 4]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) h[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[j], xv[j], h[mb], 0, 0, 0);
-    }
-}
-
-__device__ __forceinline__ void relu4(f32x4 (&h)[4]) {
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) h[mb][r] = fmaxf(h[mb][r], 0.f);
 }
 
 // The same two contractions for the producer waves of head_bwd_pc_kernel, software-pipelined by hand: with ONE wave of that role
@@ -363,8 +336,8 @@ __global__ __launch_bounds__(256) void head_popcount_reduce_kernel(const float* 
 // layer at B=64), then walks back:  g3 = W6^T g_out . relu'   ->  g2 = W4^T g3 . relu'  ->  g1 = W2^T g2 . relu'
 // -> g_x = W0^T g1, with the transposed-weight A fragments staged in LDS.  Because hidden units stay on M and
 // pixels on N, every intermediate keeps the forward's register layout.  The weight gradients dW = g . h^T contract
-// over pixels, which needs (hidden x pixel) matrices as A and B operands: each wave transposes g and h through a
-// private LDS scratch (row stride 18 floats: conflict-free fragment reads) and accumulates dW in registers over a
+// over pixels, which needs (hidden x pixel) matrices as A and B operands: g and h go through LDS (the ring of
+// head_bwd_pc_kernel, the exchange area of head_bwd_bf16_coop4_kernel) and dW accumulates in registers over a
 // persistent loop of pixel groups.  One partial per workgroup, fixed-order second-stage reduction (deterministic).
 constexpr int LB_A1 = 0;                         // fwd fragments as in the forward kernel
 constexpr int LB_A2 = LB_A1 + 1024;
@@ -376,10 +349,7 @@ constexpr int LB_B0 = LB_T1 + 1024;
 constexpr int LB_B2 = LB_B0 + 64;
 constexpr int LB_B4 = LB_B2 + 64;
 constexpr int LB_W6 = LB_B4 + 64;
-constexpr int LB_SCR = LB_W6 + 64 + 4;           // per wave: Gm[64][18] + Hm[64][18]
-constexpr int SCR_LD = 20;    // multiple of 4 (ds_read_b128) and 5 x 16 B: the 16 rows of a fragment hit 16 distinct slots
-constexpr int SCR_WAVE = 2 * 64 * SCR_LD;
-constexpr int LB_END = LB_SCR + 4 * SCR_WAVE;
+constexpr int LB_SCR = LB_W6 + 64 + 4;           // end of the weight image; the kernel's own LDS (the ring) starts here
 // weight image of the fp32 backward kernels: forward fragments, transposed fragments, biases  (LB_A1 .. LB_W6; LB_SCR floats)
 __device__ __forceinline__ void head_stage_weights_bwd(float* lds, const HeadArgs& p, int tid, int nt) {
     head_stage_a(lds, p, tid, nt);                      // LB_A1..LB_A3 coincide with L_A1..L_A3
@@ -420,11 +390,13 @@ struct HeadBwdArgs {
     pc_dst g_feat;
     pc_bn fbn[2];                // BN of the layers that produced feat channels 0-7 / 8-15 (fuse_feat_bn)
     int fuse_feat_bn;            // 1: g_feat *= (feat > 0) * bn_scale  (ReLU + frozen-BN backward of those layers)
-    int dbg;                     // ablation (tools/ablate_head.py): 1 consumer idle, 2 no hand-off
     float* partial;              // [nwg][PE_TOTAL]
     int total_groups;
     int Hp, Wp;                  // extent of the padded feature / gradient maps
-    int zero_in_kernel;          // producer / consumer kernel: g_feat is zeroed by the kernel itself (border + skipped groups)
+    int zero_in_kernel;          // always 1: the kernels zero g_feat themselves (border + skipped groups).  Kept as a run-time constant
+                                 // because the kernels' instruction streams then stay what they were with the retired single-role
+                                 // backward around (which turned it off): without the uniform branch hipcc lays out
+                                 // head_bwd_bf16_coop4_kernel differently and it measured 0.4 us slower (88.6 -> 89.1 us, A/B on one MI355X)
 };
 
 __device__ __forceinline__ float lane_sum16(float v) {
@@ -433,264 +405,6 @@ __device__ __forceinline__ float lane_sum16(float v) {
     v += __shfl_xor(v, 4);
     v += __shfl_xor(v, 8);
     return v;
-}
-
-// dgrad through one 64x64 layer: out[mi] = sum_o W[o][16mi+i] * g[o]   (transposed fragments at t_off, float4-packed)
-__device__ __forceinline__ void head_dgrad64(const float* lds, int t_off, int lane, const f32x4 (&g)[4], f32x4 (&out)[4]) {
-#pragma unroll
-    for (int mi = 0; mi < 4; ++mi) out[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb) {
-        f32x4 a4[4];
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) a4[mi] = *reinterpret_cast<const f32x4*>(&lds[t_off + ((mi * 4 + mb) * 64 + lane) * 4]);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-                out[mi] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[mi][r], g[mb][r], out[mi], 0, 0, 0);
-    }
-}
-
-// scatter a D-layout (hidden x pixel) tile into the wave's LDS scratch as a [64][SCR_LD] matrix whose columns are
-// permuted so that the 4 K-steps (pixels 4*ks + k, ks = 0..3) of a lane are contiguous: column(px) = (px & 3)*4 + (px >> 2)
-__device__ __forceinline__ void head_store_mat(float* m, int li, int lk, const f32x4 (&v)[4]) {
-    const int c = (li & 3) * 4 + (li >> 2);
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) m[(16 * mb + 4 * lk + r) * SCR_LD + c] = v[mb][r];
-}
-
-// dW[o][i] += sum_px G[o][px] * Hm[i][px]   (64 x 64, 16 pixels = 4 k-steps; one ds_read_b128 per 16-row block)
-__device__ __forceinline__ void head_wgrad64(const float* gm, const float* hm, int li, int lk, f32x4 (&dw)[4][4]) {
-    f32x4 af[4], bf[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        af[q] = *reinterpret_cast<const f32x4*>(&gm[(16 * q + li) * SCR_LD + 4 * lk]);
-        bf[q] = *reinterpret_cast<const f32x4*>(&hm[(16 * q + li) * SCR_LD + 4 * lk]);
-    }
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb)
-                dw[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[mb][ks], bf[nb][ks], dw[mb][nb], 0, 0, 0);
-}
-
-__global__ __launch_bounds__(256, 1) void head_bwd_kernel(const HeadBwdArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const HeadArgs& p = a.f;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 15, lk = lane >> 4;
-    head_copy_image(lds, p.wimage, LB_SCR * (int)sizeof(float));     // forward + transposed fragments, biases (head_stage_weights_bwd)
-    __syncthreads();
-
-    float* gm = lds + LB_SCR + wave * SCR_WAVE;
-    float* hm = gm + 64 * SCR_LD;
-    const int HW = p.H * p.W;
-    const float gsc = a.g_scale_const ? *a.g_scale_const : 0.f;
-    float fscale[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        fscale[r] = 1.f;
-        if (a.fuse_feat_bn) {
-            const int c = 4 * lk + r;
-            float sh;
-            pc_bn_fold(a.fbn[c >> 3], c & 7, fscale[r], sh);
-        }
-    }
-
-    f32x4 dW4[4][4], dW2[4][4], dW0[4], dw6[4], db0[4], db2[4], db4[4];
-    float db6 = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        dW0[i] = dw6[i] = db0[i] = db2[i] = db4[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) dW4[i][j] = dW2[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-
-    for (int gg = blockIdx.x * 4 + wave; gg < a.total_groups; gg += gridDim.x * 4) {
-        const int b = (int)pc_div((uint32_t)gg, p.div_groups), g = gg - b * p.groups;
-        const int q = g * 16 + li;
-        const bool valid = q < HW;
-        const int64_t pix = (int64_t)b * HW + q;
-        const bool sel = valid && (p.mask ? p.mask[pix] != 0 : true);
-        if (!__any(sel)) continue;
-        const int y = valid ? (int)pc_div((uint32_t)q, p.div_w) : 0, x = valid ? q - y * p.W : 0;
-        const float* fp = p.feat.ptr + b * p.feat.bstride + (int64_t)(p.py + y) * p.feat.rstride + p.px + x;
-        float xv[4], fvv[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            xv[j] = valid ? fp[(4 * j + lk) * p.feat.cstride] : 0.f;
-            fvv[j] = (valid && a.fuse_feat_bn) ? fp[(4 * lk + j) * p.feat.cstride] : 1.f;   // issued with xv: not on the tail
-        }
-        // upstream gradient of relu(out) at this pixel
-        float gup = 0.f;
-        if (sel) {
-            const float bld = p.building[pix];
-            const bool region = p.admin ? (p.admin[pix] == (float)p.census[b]) : true;
-            gup = gsc;
-            if (a.g_popcount && region) gup += a.g_popcount[b] * bld;
-            if (a.g_popdense) gup += a.g_popdense[pix] * bld;
-            if (a.g_scale_map) gup += a.g_scale_map[pix];
-        }
-        // ---- forward recompute
-        f32x4 h1[4], h2[4], h3[4];
-        head_layer1(lds, LB_A1, LB_B0, lane, lk, xv, h1);
-        relu4(h1);
-        head_layer64(lds, LB_A2, LB_B2, lane, lk, h1, h2);
-        relu4(h2);
-        head_layer64(lds, LB_A3, LB_B4, lane, lk, h2, h3);
-        relu4(h3);
-        float s = 0.f;
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(&lds[LB_W6 + 16 * mb + 4 * lk]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s = fmaf(w[r], h3[mb][r], s);
-        }
-        s += __shfl_xor(s, 16);
-        s += __shfl_xor(s, 32);
-        const float outv = s + lds[LB_W6 + 64];
-        const float gout = (sel && outv > 0.f) ? gup : 0.f;
-        if (!__any(gout != 0.f)) continue;
-
-        // ---- layer 4 (64 -> 1)
-        f32x4 g3[4], g2[4], g1[4];
-        if (lk == 0) db6 += gout;
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) {
-            const f32x4 w = *reinterpret_cast<const f32x4*>(&lds[LB_W6 + 16 * mb + 4 * lk]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                dw6[mb][r] = fmaf(gout, h3[mb][r], dw6[mb][r]);
-                g3[mb][r] = h3[mb][r] > 0.f ? w[r] * gout : 0.f;
-                db4[mb][r] += g3[mb][r];
-            }
-        }
-        // ---- layer 3 (W4)
-        __builtin_amdgcn_wave_barrier();
-        head_store_mat(gm, li, lk, g3);
-        head_store_mat(hm, li, lk, h2);
-        __builtin_amdgcn_wave_barrier();
-        head_wgrad64(gm, hm, li, lk, dW4);
-        head_dgrad64(lds, LB_T3, lane, g3, g2);
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                g2[mb][r] = h2[mb][r] > 0.f ? g2[mb][r] : 0.f;
-                db2[mb][r] += g2[mb][r];
-            }
-        // ---- layer 2 (W2)
-        __builtin_amdgcn_wave_barrier();
-        head_store_mat(gm, li, lk, g2);
-        head_store_mat(hm, li, lk, h1);
-        __builtin_amdgcn_wave_barrier();
-        head_wgrad64(gm, hm, li, lk, dW2);
-        head_dgrad64(lds, LB_T2, lane, g2, g1);
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                g1[mb][r] = h1[mb][r] > 0.f ? g1[mb][r] : 0.f;
-                db0[mb][r] += g1[mb][r];
-            }
-        // ---- layer 1 (W0: 64 x 16)
-        __builtin_amdgcn_wave_barrier();
-        head_store_mat(gm, li, lk, g1);
-        {
-            const int c = (li & 3) * 4 + (li >> 2);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) hm[(4 * j + lk) * SCR_LD + c] = xv[j];
-        }
-        __builtin_amdgcn_wave_barrier();
-        {
-            const f32x4 bf = *reinterpret_cast<const f32x4*>(&hm[li * SCR_LD + 4 * lk]);
-            f32x4 af[4];
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb) af[mb] = *reinterpret_cast<const f32x4*>(&gm[(16 * mb + li) * SCR_LD + 4 * lk]);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-                for (int mb = 0; mb < 4; ++mb)
-                    dW0[mb] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[mb][ks], bf[ks], dW0[mb], 0, 0, 0);
-        }
-        f32x4 gx = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) {
-            const f32x4 t4 = *reinterpret_cast<const f32x4*>(&lds[LB_T1 + (mb * 64 + lane) * 4]);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) gx = __builtin_amdgcn_mfma_f32_16x16x4f32(t4[r], g1[mb][r], gx, 0, 0, 0);
-        }
-        if (valid) {
-            float* op = a.g_feat.ptr + b * a.g_feat.bstride + (int64_t)(p.py + y) * a.g_feat.rstride + p.px + x;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float o = gx[r];
-                // xv[r'] holds feat channel 4*j + lk; channel 4*lk + r is held by lane group lk' = r at j = lk
-                if (a.fuse_feat_bn) {
-                    const float fv = fvv[r];
-                    o = fv > 0.f ? o * fscale[r] : 0.f;
-                }
-                op[(4 * lk + r) * a.g_feat.cstride] = o;
-            }
-        }
-    }
-
-    // ---- per-lane vectors: reduce over the 16 pixel lanes
-#pragma unroll
-    for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            dw6[mb][r] = lane_sum16(dw6[mb][r]);
-            db0[mb][r] = lane_sum16(db0[mb][r]);
-            db2[mb][r] = lane_sum16(db2[mb][r]);
-            db4[mb][r] = lane_sum16(db4[mb][r]);
-        }
-    db6 = lane_sum16(db6);
-
-    // ---- cross-wave reduction (fixed order) -> one partial per workgroup
-    float* part = a.partial + (int64_t)blockIdx.x * PE_TOTAL;
-    __syncthreads();
-#pragma unroll
-    for (int stage = 0; stage < 2; ++stage) {
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb)
-                *reinterpret_cast<f32x4*>(&lds[wave * 4096 + ((mb * 4 + nb) * 64 + lane) * 4]) = stage == 0 ? dW4[mb][nb] : dW2[mb][nb];
-        __syncthreads();
-        for (int e = tid; e < 4096; e += 256)
-            part[(stage == 0 ? PE_W4 : PE_W2) + e] = ((lds[e] + lds[4096 + e]) + lds[8192 + e]) + lds[12288 + e];
-        __syncthreads();
-    }
-    // small stuff: per wave [dW0 1024][dw6 64][db0 64][db2 64][db4 64][db6 1] -> stride 1344
-    {
-        float* w = lds + wave * 1344;
-#pragma unroll
-        for (int mb = 0; mb < 4; ++mb) *reinterpret_cast<f32x4*>(&w[(mb * 64 + lane) * 4]) = dW0[mb];
-        if (li == 0) {
-#pragma unroll
-            for (int mb = 0; mb < 4; ++mb)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int h = 16 * mb + 4 * lk + r;
-                    w[1024 + h] = dw6[mb][r];
-                    w[1088 + h] = db0[mb][r];
-                    w[1152 + h] = db2[mb][r];
-                    w[1216 + h] = db4[mb][r];
-                }
-            if (lk == 0) w[1280] = db6;
-        }
-        __syncthreads();
-        for (int e = tid; e < 1281; e += 256) {
-            const float t = ((lds[e] + lds[1344 + e]) + lds[2688 + e]) + lds[4032 + e];
-            part[PE_W0 + e] = t;     // PE_W0.. contiguous: W0(1024) W6(64) B0 B2 B4 (64 each) B6(1)
-        }
-    }
 }
 
 // Phase profile of the producer waves (debug builds only: make CXXFLAGS+=-DPOPCORN_HEAD_PROF; tools/ablate_head.py prints it)
@@ -1171,10 +885,10 @@ __global__ __launch_bounds__(64 * NW) void head_fwd_split_kernel(const HeadArgs 
 }
 
 // ---- head backward, producer / consumer form ----------------------------------------------------------------------
-// The single-role kernel above needs 209 accumulator registers per wave for the three weight-gradient GEMMs, which
-// pins it at ONE wave per SIMD: every global-load, LDS round trip and VALU stretch of that wave idles the matrix pipe
-// (measured 0.50 of the fp32 MFMA peak).  Here a 512-thread workgroup runs two roles with <= 256 registers each, i.e.
-// two waves per SIMD:
+// One wave that does everything needs 209 accumulator registers for the three weight-gradient GEMMs, which pins it
+// at ONE wave per SIMD: every global-load, LDS round trip and VALU stretch of that wave idles the matrix pipe (such a
+// kernel measured 0.50 of the fp32 MFMA peak; DESIGN_HISTORY.md).  Here a 512-thread workgroup runs two roles with
+// <= 256 registers each, i.e. two waves per SIMD:
 //   producers (waves 0-3): per 16-pixel group, forward recompute + the data-gradient chain (288 MFMAs, ~130 registers);
 //       after each layer they hand the (G = pre-activation gradient, H = layer input) pair to their consumer through
 //       a 2-slot LDS ring as (hidden x pixel) matrices;
@@ -1189,7 +903,7 @@ constexpr int PC_MBS = 4 * PC_LKS;                        // per 16-row block
 constexpr int PC_MAT = 4 * PC_MBS;                        // one 64 x 16 matrix (1280 floats)
 constexpr int PC_SLOT = 2 * PC_MAT;                       // G + H
 constexpr int PC_NSLOT = 2;
-constexpr int LP_RING = LB_W6 + 64 + 4;                  // weights image is shared with the single-role kernel
+constexpr int LP_RING = LB_SCR;                           // behind the weight image
 constexpr int LP_FLAGS = LP_RING + 4 * PC_NSLOT * PC_SLOT;
 constexpr int LP_END = LP_FLAGS + 16;
 
@@ -1375,9 +1089,10 @@ __device__ __forceinline__ unsigned long long head_dec_word(const f32x4 (&h1)[4]
     return w;
 }
 
-template <int DBG, bool SPL>   // SPL: the producer's chain on split bf16 operands (above).  DBG: ablation builds (tools/ablate_head.py): 1 consumer idle, 2 no hand-off; 0 = the product kernel (as run-time flags the
-                          // two switches put a branch around every ring write of the producer: 14 extra basic blocks in its group loop)
-                          // 4: the producer also writes its ReLU decisions to g_head_dec_dev (pc_debug_head_decisions; the tests' tie adjudication)
+template <int DBG, bool SPL>   // SPL: the producer's chain on split bf16 operands (above).  DBG: 0 = the product kernel;
+                          // 4: the producer also writes its ReLU decisions to g_head_dec_dev (pc_debug_head_decisions; the tests' tie adjudication);
+                          // 1 consumer idle, 2 no hand-off: role ablations, instantiated in -DPOPCORN_HEAD_ABLATE builds only (tools/ablate_head.py;
+                          // as run-time flags the two switches put a branch around every ring write of the producer: 14 extra basic blocks in its group loop)
 __global__ __launch_bounds__(512, 2) void head_bwd_pc_kernel(const HeadBwdArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const HeadArgs& p = a.f;
@@ -2458,673 +2173,7 @@ __global__ __launch_bounds__(256) void head_bwd_reduce_kernel(const HeadReduceAr
     }
 }
 
-// ---- fusion_out_conv (1x1, 16->1) + sigmoid + crop ------------------------------------------------------------
-__global__ __launch_bounds__(256) void outconv_sigmoid_crop_kernel(pc_src feat, const float* w, const float* bias,
-                                                                   pc_dst out, int B, int H, int W, int py, int px, int bf) {
-    const int64_t n = (int64_t)B * H * W;
-    float wv[16];
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {      // C = 16 (fusion_out_conv) or 8 (sar/optical_out_conv); bf16 mode: operand rounding
-        const float t = c < feat.C ? w[c] : 0.f;
-        wv[c] = bf ? pc_bf16r(t) : t;
-    }
-    const float bv = bias[0];
-    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < (unsigned)n; i += gridDim.x * blockDim.x) {
-        const unsigned row = i / (unsigned)W;
-        const int x = (int)(i - row * (unsigned)W), y = (int)(row % (unsigned)H), b = (int)(row / (unsigned)H);
-        const int64_t fo = b * feat.bstride + (int64_t)(py + y) * feat.rstride + (int64_t)(px + x) * pc_xs(feat);
-        float s = bv;
-#pragma unroll
-        for (int c = 0; c < 16; ++c)
-            if (c < feat.C) s = fmaf(pc_src_at(feat, fo + c * feat.cstride), wv[c], s);
-        out.ptr[b * out.bstride + (int64_t)y * out.rstride + x] = 1.f / (1.f + expf(-s));
-    }
-}
-
-// ---- sparsity mask ----------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void sparsity_mask_kernel(const float* building, const float* admin, const int64_t* census,
-                                                            const uint8_t* rowsel, const uint8_t* colsel, int occ,
-                                                            uint8_t* mask, int32_t* counts, int B, int H, int W) {
-    const int64_t n = (int64_t)B * H * W;
-    int nsel = 0, nreg = 0;
-    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < (unsigned)n; i += gridDim.x * blockDim.x) {
-        const unsigned row = i / (unsigned)W;
-        const int x = (int)(i - row * (unsigned)W), y = (int)(row % (unsigned)H), b = (int)(row / (unsigned)H);
-        const bool region = admin[i] == (float)census[b];
-        // popcorn.py:365-372: ((building>0)*region | grid) & region  [occupancymodel]   /   region | grid) & region
-        const bool base = occ ? (building[i] > 0.f) : true;
-        const bool m = region && (base || (rowsel[y] && colsel[x]));
-        mask[i] = m ? 1 : 0;
-        nsel += m;
-        nreg += region;
-    }
-    // integer counts: order-independent, atomics are exact.  One atomic pair per BLOCK (a per-wave atomic on two words
-    // serialised 16 k atomics: 188 us for a 640 k-pixel batch, profiles/r1_v0).
-    __shared__ int red[2][4];
-    for (int off = 32; off > 0; off >>= 1) { nsel += __shfl_down(nsel, off); nreg += __shfl_down(nreg, off); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = nsel; red[1][threadIdx.x >> 6] = nreg; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int a = red[0][0] + red[0][1] + red[0][2] + red[0][3], b2 = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-        if (a) atomicAdd(&counts[0], a);
-        if (b2) atomicAdd(&counts[1], b2);
-    }
-}
-
-// popcorn.py:374-375: an empty selection falls back to the region mask
-__global__ __launch_bounds__(256) void sparsity_mask_fallback_kernel(const float* admin, const int64_t* census, uint8_t* mask,
-                                                                     int32_t* counts, int B, int H, int W) {
-    if (counts[0] != 0) return;
-    const int64_t n = (int64_t)B * H * W;
-    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < (unsigned)n; i += gridDim.x * blockDim.x) {
-        const int b = (int)(i / (unsigned)(W * H));
-        mask[i] = admin[i] == (float)census[b] ? 1 : 0;
-    }
-}
-
-__global__ void sparsity_mask_fix_count_kernel(int32_t* counts) {
-    if (counts[0] == 0) counts[0] = counts[1];
-}
-
-// ---- building score + sparsity mask in ONE launch -----------------------------------------------------------------
-// outconv_sigmoid_crop_kernel + sparsity_mask_kernel + the empty-selection fallback + the count fix-up (a memset and four
-// dependent launches, ~38 us between the U-Net forward and the head) as one kernel: every block accumulates {nsel, nregion}
-// into a scratch pair and takes a ticket; the block that draws the last ticket publishes the counts, applies the
-// fallback of popcorn.py:374-375 if the whole batch selected nothing (rare; done by that one block).  The accumulators live
-// in a library-owned scratch that a one-wave kernel zeroes in front of every launch.
-// Zero fills inside the train step are kernels, not hipMemsetAsync: memset nodes captured into the step's HIP graph were
-// not reliably re-executed / ordered on replay once the node sequence of the graph changed (a 16- or 32-byte one never
-// replayed; with it gone the 67 MB one of the head backward went wrong too: garbage gradients from the second replay on,
-// eager launches always correct).
-__global__ __launch_bounds__(256) void zero_fill_kernel(float* p, int64_t n4, int64_t rem) {
-    const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) reinterpret_cast<f32x4*>(p)[i] = z;
-    if (blockIdx.x == 0 && (int64_t)threadIdx.x < rem) p[4 * n4 + threadIdx.x] = 0.f;
-}
-
-__global__ void zero_words_kernel(uint32_t* p, int n) {
-    if ((int)threadIdx.x < n) p[threadIdx.x] = 0u;
-}
-
-struct ScoreMaskArgs {
-    pc_src feat; const float* w; const float* bias; pc_dst out;      // 1x1 conv + sigmoid + crop (as outconv_sigmoid_crop)
-    const float* admin; const int64_t* census; const uint8_t* rowsel; const uint8_t* colsel;
-    int occ; uint8_t* mask; int32_t* counts; unsigned* scratch;      // scratch: one packed 64-bit accumulator {nsel, nregion, ticket} (see the kernel), zero between launches
-    int B, H, W, py, px;
-    int bf;
-};
-
-constexpr int SM_THREADS = 1024;       // 16 waves per block, at most one block per CU: B = 64 tiles (160 k four-pixel items) in ONE round of loads
-__global__ __launch_bounds__(SM_THREADS) void score_mask_kernel(const ScoreMaskArgs a) {
-    const int64_t n = (int64_t)a.B * a.H * a.W;
-    float wv[16];
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-        const float t = c < a.feat.C ? a.w[c] : 0.f;
-        wv[c] = a.bf ? pc_bf16r(t) : t;
-    }
-    const float bv = a.bias[0];
-    int nsel = 0, nreg = 0;
-    const bool vec4 = a.feat.dtype == PC_F32 && pc_planar(a.feat) &&      // (a bf16 feature map -- the non-dot fallback of bf16 mode -- takes the scalar loop)
-                      (a.W & 3) == 0 && (a.out.rstride & 3) == 0 && (a.out.bstride & 3) == 0 &&
-                      ((reinterpret_cast<uintptr_t>(a.out.ptr) | reinterpret_cast<uintptr_t>(a.admin) |
-                        reinterpret_cast<uintptr_t>(a.mask)) & 15) == 0;
-    if (vec4) {
-        // four consecutive pixels of a row per thread: 16-byte accesses (the feature read is 4-byte aligned only: the crop
-        // offset px is arbitrary), a quarter of the dependent iterations of the scalar loop
-        const unsigned n4 = (unsigned)(n >> 2), w4 = (unsigned)a.W >> 2;
-        for (unsigned i4 = blockIdx.x * blockDim.x + threadIdx.x; i4 < n4; i4 += gridDim.x * blockDim.x) {
-            const unsigned row = i4 / w4;
-            const int x = (int)(i4 - row * w4) * 4, y = (int)(row % (unsigned)a.H), b = (int)(row / (unsigned)a.H);
-            const float* fp = a.feat.ptr + b * a.feat.bstride + (int64_t)(a.py + y) * a.feat.rstride + a.px + x;
-            f32x4 s = f32x4{bv, bv, bv, bv};
-#pragma unroll
-            for (int c = 0; c < 16; ++c)
-                if (c < a.feat.C) {
-                    const f32x4u f = *reinterpret_cast<const f32x4u*>(fp + c * a.feat.cstride);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) s[e] = fmaf(f[e], wv[c], s[e]);
-                }
-            const f32x4 adm = *reinterpret_cast<const f32x4*>(a.admin + 4 * (int64_t)i4);
-            const float cid = (float)a.census[b];
-            const bool rs = a.rowsel[y] != 0;
-            f32x4 bld;
-            unsigned mbits = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                bld[e] = 1.f / (1.f + expf(-s[e]));
-                const bool region = adm[e] == cid;
-                const bool base = a.occ ? (bld[e] > 0.f) : true;
-                const bool m = region && (base || (rs && a.colsel[x + e]));
-                mbits |= (m ? 1u : 0u) << (8 * e);
-                nsel += m;
-                nreg += region;
-            }
-            *reinterpret_cast<f32x4*>(a.out.ptr + b * a.out.bstride + (int64_t)y * a.out.rstride + x) = bld;
-            *reinterpret_cast<unsigned*>(a.mask + 4 * (int64_t)i4) = mbits;
-        }
-    } else
-    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < (unsigned)n; i += gridDim.x * blockDim.x) {
-        const unsigned row = i / (unsigned)a.W;
-        const int x = (int)(i - row * (unsigned)a.W), y = (int)(row % (unsigned)a.H), b = (int)(row / (unsigned)a.H);
-        const int64_t fo = b * a.feat.bstride + (int64_t)(a.py + y) * a.feat.rstride + (int64_t)(a.px + x) * pc_xs(a.feat);
-        float s = bv;
-#pragma unroll
-        for (int c = 0; c < 16; ++c)
-            if (c < a.feat.C) s = fmaf(pc_src_at(a.feat, fo + c * a.feat.cstride), wv[c], s);
-        const float building = 1.f / (1.f + expf(-s));
-        a.out.ptr[b * a.out.bstride + (int64_t)y * a.out.rstride + x] = building;
-        const bool region = a.admin[i] == (float)a.census[b];
-        const bool base = a.occ ? (building > 0.f) : true;
-        const bool m = region && (base || (a.rowsel[y] && a.colsel[x]));
-        a.mask[i] = m ? 1 : 0;
-        nsel += m;
-        nreg += region;
-    }
-    __shared__ int red[2][SM_THREADS / 64];
-    __shared__ unsigned last;
-    for (int off = 32; off > 0; off >>= 1) { nsel += __shfl_down(nsel, off); nreg += __shfl_down(nreg, off); }
-    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = nsel; red[1][threadIdx.x >> 6] = nreg; }
-    __syncthreads();
-    __shared__ unsigned long long tot_sh;
-    if (threadIdx.x == 0) {
-        int s0 = 0, s1 = 0;
-#pragma unroll
-        for (int w = 0; w < SM_THREADS / 64; ++w) { s0 += red[0][w]; s1 += red[1][w]; }
-        // integer counts: order-independent, exact.  ONE 64-bit atomic per block carries {nsel : 27 | nregion : 27 | ticket : 10}
-        // (device-scope atomics on one address retire at ~13 ns each, and every dependent one is a round trip to the memory side:
-        // counts, ticket and the last block's read of the totals were three of them); the block that draws the last ticket has the
-        // totals in the returned value
-        __threadfence();
-        const unsigned long long add = (unsigned long long)(unsigned)s0 | ((unsigned long long)(unsigned)s1 << 27) | (1ull << 54);
-        const unsigned long long old = atomicAdd(reinterpret_cast<unsigned long long*>(a.scratch), add);
-        last = (unsigned)(old >> 54) == gridDim.x - 1 ? 1u : 0u;
-        tot_sh = old + add;
-    }
-    __syncthreads();
-    if (!last) return;
-    __threadfence();
-    const unsigned tot_sel = (unsigned)(tot_sh & ((1ull << 27) - 1)), tot_reg = (unsigned)((tot_sh >> 27) & ((1ull << 27) - 1));
-    if (tot_sel == 0) {
-        // an empty selection falls back to the region mask (popcorn.py:374-375)
-        for (unsigned i = threadIdx.x; i < (unsigned)n; i += blockDim.x) {
-            const int b = (int)(i / (unsigned)(a.W * a.H));
-            a.mask[i] = a.admin[i] == (float)a.census[b] ? 1 : 0;
-        }
-    }
-    if (threadIdx.x == 0) {
-        a.counts[0] = (int32_t)(tot_sel ? tot_sel : tot_reg);
-        a.counts[1] = (int32_t)tot_reg;
-        // this block is the last one alive: leave the accumulator and the ticket at zero for the next call (which is ordered
-        // behind this kernel on the stream), instead of a zeroing launch in front of every call
-        a.scratch[0] = 0u; a.scratch[1] = 0u;
-        __threadfence();
-    }
-}
-
-// ---- ordered compaction: out[rank(i)] = src[i] for mask[i] != 0 (row-major order) --------------------------------
-constexpr int CBLK = 1024;   // elements per block
-
-__global__ __launch_bounds__(256) void compact_count_kernel(const uint8_t* mask, int32_t* block_counts, int64_t n) {
-    __shared__ int red[4];
-    const int64_t base = (int64_t)blockIdx.x * CBLK;
-    int c = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int64_t i = base + k * 256 + threadIdx.x;
-        c += (i < n && mask[i]) ? 1 : 0;
-    }
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
-
-// single block exclusive scan of block_counts (nblocks <= a few thousand)
-__global__ __launch_bounds__(1024) void compact_scan_kernel(int32_t* block_counts, int nblocks, int32_t* n_out) {
-    __shared__ int sh[1024];
-    __shared__ int carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nblocks; base += 1024) {
-        const int i = base + threadIdx.x;
-        const int v = i < nblocks ? block_counts[i] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const int t = threadIdx.x >= off ? sh[threadIdx.x - off] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < nblocks) block_counts[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += sh[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *n_out = carry;
-}
-
-__global__ __launch_bounds__(256) void compact_write_kernel(const float* src, const uint8_t* mask, const int32_t* block_off,
-                                                            float* out, int64_t n) {
-    __shared__ int wave_tot[4][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t base = (int64_t)blockIdx.x * CBLK;
-    // element order inside a block: k-major (k*256 + tid) keeps the global order row-major
-    bool m[4];
-    unsigned long long bal[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int64_t i = base + k * 256 + threadIdx.x;
-        m[k] = i < n && mask[i];
-        bal[k] = __ballot(m[k]);
-        if (lane == 0) wave_tot[k][wave] = __popcll(bal[k]);
-    }
-    __syncthreads();
-    int off = block_off[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        int pre = 0;
-        for (int w = 0; w < wave; ++w) pre += wave_tot[k][w];
-        if (m[k]) {
-            const int rank = __popcll(bal[k] & ((1ull << lane) - 1ull));
-            out[off + pre + rank] = src[base + k * 256 + threadIdx.x];
-        }
-        off += wave_tot[k][0] + wave_tot[k][1] + wave_tot[k][2] + wave_tot[k][3];
-    }
-}
-
-// inverse of compact_write_kernel: out[i] = mask[i] ? src[rank(i)] : 0  (autograd of the boolean-index gather, popcorn.py:173)
-__global__ __launch_bounds__(256) void scatter_masked_kernel(const float* src, const uint8_t* mask, const int32_t* block_off,
-                                                             float* out, int64_t n) {
-    __shared__ int wave_tot[4][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t base = (int64_t)blockIdx.x * CBLK;
-    bool m[4];
-    unsigned long long bal[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int64_t i = base + k * 256 + threadIdx.x;
-        m[k] = i < n && mask[i];
-        bal[k] = __ballot(m[k]);
-        if (lane == 0) wave_tot[k][wave] = __popcll(bal[k]);
-    }
-    __syncthreads();
-    int off = block_off[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        int pre = 0;
-        for (int w = 0; w < wave; ++w) pre += wave_tot[k][w];
-        const int64_t i = base + k * 256 + threadIdx.x;
-        if (i < n) out[i] = m[k] ? src[off + pre + __popcll(bal[k] & ((1ull << lane) - 1ull))] : 0.f;
-        off += wave_tot[k][0] + wave_tot[k][1] + wave_tot[k][2] + wave_tot[k][3];
-    }
-}
-
-// get_sparsity_mask(sparse_unet=True), popcorn.py:336-359: one workgroup per sample.
-//   bmask = building > thresh;  mask = (bmask | grid) & region;  ratio = #(region & ~bmask) / (#(grid & region & ~bmask) + 1e-5)
-__global__ __launch_bounds__(256) void sparsity_mask_unet_kernel(const float* building, const float* admin, const int64_t* census,
-                                                                 const uint8_t* rowsel, const uint8_t* colsel, float thresh,
-                                                                 uint8_t* mask, float* ratio, int H, int W) {
-    __shared__ int red[2][256];
-    const int b = blockIdx.x;
-    const float cid = (float)census[b];
-    const int64_t base = (int64_t)b * H * W;
-    int n_empty = 0, n_sub = 0;
-    for (int i = threadIdx.x; i < H * W; i += 256) {
-        const int y = i / W, x = i - y * W;
-        const bool region = admin[base + i] == cid;
-        const bool bm = building[base + i] > thresh;
-        const bool grid = rowsel[y] && colsel[x];
-        mask[base + i] = (uint8_t)((bm || grid) && region);
-        n_empty += (region && !bm) ? 1 : 0;
-        n_sub += (grid && region && !bm) ? 1 : 0;
-    }
-    red[0][threadIdx.x] = n_empty;
-    red[1][threadIdx.x] = n_sub;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) { red[0][threadIdx.x] += red[0][threadIdx.x + off]; red[1][threadIdx.x] += red[1][threadIdx.x + off]; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) ratio[b] = (float)red[0][0] / ((float)red[1][0] + 1e-5f);
-}
-
-// F.pad(x, (left, right, top, bottom), mode="reflect") for NCHW planes (add_padding, popcorn.py:231-258)
-__global__ __launch_bounds__(256) void reflect_pad_kernel(const float* in, float* out, int64_t planes, int H, int W, int Hp, int Wp,
-                                                          int top, int left) {
-    const int64_t n = planes * Hp * Wp;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int x = (int)(i % Wp), y = (int)((i / Wp) % Hp);
-        const int64_t pl = i / ((int64_t)Wp * Hp);
-        out[i] = in[(pl * H + pc_reflect(y - top, H)) * W + pc_reflect(x - left, W)];
-    }
-}
-
-// the same with a channel gather: out[b][j] = pad(in[b][sel[j]]); one thread = 4 consecutive x of one output row
-// NORM: also (x - mean[j]) / std[j] per output plane -- band selection + apply_normalize (utils/utils.py:105-127) + add_padding in
-// ONE pass over the raw tile (pc_select_normalize_pad); the division is the one pc_select_normalize performs (same bits)
-struct PadSel { int sel[8]; float mean[8]; float stdv[8]; };
-template <bool NORM>
-__global__ __launch_bounds__(256) void reflect_pad_select_kernel(const float* in, float* out, PadSel ps, int Cin, int nsel, int H, int W,
-                                                                 int Hp, int Wp, int top, int left, int nrows, int wq, int rows_per_block) {
-    // a block = rows_per_block output rows x wq 4-pixel pieces (wq * rows_per_block <= 256)
-    const int tr = threadIdx.x / wq, piece = threadIdx.x - tr * wq;
-    const int row = blockIdx.x * rows_per_block + tr;
-    if (tr >= rows_per_block || row >= nrows) return;
-    const int pl = row / Hp, y = row - pl * Hp;             // pl = b * nsel + j
-    const int b = pl / nsel, j = pl - b * nsel;
-    const float* src = in + ((int64_t)(b * Cin + ps.sel[j]) * H + pc_reflect(y - top, H)) * W;
-    float* dst = out + (int64_t)row * Wp + 4 * piece;
-    const int x0 = 4 * piece, xs = x0 - left;
-    f32x4 v;
-    if (xs >= 0 && xs + 3 < W) {
-        if (((xs | W) & 1) == 0) {
-            // even pad and even width (14 / 100 for the training tiles): the piece is 8-byte aligned -- two 8-byte loads (the
-            // 4-byte-aligned vector type below is split into four dword loads by the compiler)
-            typedef float f32x2a __attribute__((ext_vector_type(2)));
-            const f32x2a t0 = *reinterpret_cast<const f32x2a*>(src + xs), t1 = *reinterpret_cast<const f32x2a*>(src + xs + 2);
-            v = f32x4{t0[0], t0[1], t1[0], t1[1]};
-        } else {
-            const f32x4u t = *reinterpret_cast<const f32x4u*>(src + xs);   // interior: one (unaligned) 16-byte load
-            v = f32x4{t[0], t[1], t[2], t[3]};
-        }
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = x0 + e < Wp ? src[pc_reflect(xs + e, W)] : 0.f;
-    }
-    if (NORM) {
-        const float mu = ps.mean[j], sd = ps.stdv[j];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (v[e] - mu) / sd;
-    }
-    if ((Wp & 3) == 0) {
-        *reinterpret_cast<f32x4*>(dst) = v;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (x0 + e < Wp) dst[e] = v[e];
-    }
-}
-
-// PC_PREC_BF16 ingest (pc_ingest_cl8): one thread = one pixel of the padded domain = ONE aligned 16-byte channels-last slot:
-// band select + normalise + reflect padding + stream order + round to bf16; channel slots >= nsel are zero
-template <bool NORM>
-__global__ __launch_bounds__(256) void ingest_cl8_kernel(const float* __restrict__ in, uint4* __restrict__ out, PadSel ps, int Cin, int nsel,
-                                                         int H, int W, int Hp, int Wp, int top, int left, int npix) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= npix) return;
-    const int x = i % Wp, r = i / Wp;
-    const int y = r % Hp, b = r / Hp;
-    const int64_t o = (int64_t)pc_reflect(y - top, H) * W + pc_reflect(x - left, W);
-    const int64_t plane = (int64_t)H * W;
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        float t = 0.f;
-        if (j < nsel) {
-            t = in[((int64_t)b * Cin + ps.sel[j]) * plane + o];
-            if (NORM) t = (t - ps.mean[j]) / ps.stdv[j];
-        }
-        v[j] = t;
-    }
-    out[i] = make_uint4(pc_pack_bf16(v[0], v[1]), pc_pack_bf16(v[2], v[3]), pc_pack_bf16(v[4], v[5]), pc_pack_bf16(v[6], v[7]));
-}
-
-// the same ingest from the two tensors a loader ships (pc_ingest_split): S2 reflectances as UINT16 digital numbers (planar, C2 bands) and
-// S1 backscatter as fp32 (planar, C1 bands); channel index sel[j] < C2 -> s2, else s1[sel[j] - C2].  One thread = one pixel of the padded
-// domain, all nsel channels: the planar fp32 form writes nsel coalesced words, the channels-last bf16 form one 16-byte slot.
-template <bool CL8>
-__global__ __launch_bounds__(256) void ingest_split_kernel(const uint16_t* __restrict__ s2, const float* __restrict__ s1, void* __restrict__ out, PadSel ps,
-                                                           int C2, int C1, int nsel, int H, int W, int Hp, int Wp, int top, int left, int npix) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= npix) return;
-    const int x = i % Wp, r = i / Wp;
-    const int y = r % Hp, b = r / Hp;
-    const int64_t o = (int64_t)pc_reflect(y - top, H) * W + pc_reflect(x - left, W);
-    const int64_t plane = (int64_t)H * W;
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        float t = 0.f;
-        if (j < nsel) {
-            const int c = ps.sel[j];
-            t = c < C2 ? (float)s2[((int64_t)b * C2 + c) * plane + o] : s1[((int64_t)b * C1 + (c - C2)) * plane + o];
-            t = (t - ps.mean[j]) / ps.stdv[j];
-        }
-        v[j] = t;
-    }
-    if (CL8) {
-        reinterpret_cast<uint4*>(out)[i] = make_uint4(pc_pack_bf16(v[0], v[1]), pc_pack_bf16(v[2], v[3]), pc_pack_bf16(v[4], v[5]), pc_pack_bf16(v[6], v[7]));
-    } else {
-        float* op = reinterpret_cast<float*>(out) + (int64_t)b * nsel * Hp * Wp + (int64_t)y * Wp + x;
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-            if (j < nsel) op[(int64_t)j * Hp * Wp] = v[j];
-    }
-}
-
-
-// pc_ingest_pad_strided: the three ingests above for rows of ANY width and an output whose rows are `rs` >= Wp floats apart (the native
-// step executor's arena pads rows to 16 bytes): one thread = one 16-byte piece of an output row.  KIND 0: planar fp32 source (model input or
-// raw tile), 2: uint16 S2 + fp32 S1 (channel index sel < C2 -> s2).  Same arithmetic as the kernels above ((x - mean) / std), so the same bits.
-template <int KIND, bool NORM>
-__global__ __launch_bounds__(256) void ingest_pad_strided_kernel(const void* __restrict__ data, const void* __restrict__ data2, float* __restrict__ out, PadSel ps,
-                                                                 int Cin, int C2, int nsel, int H, int W, int Hp, int Wp, int rs, int top, int left,
-                                                                 int64_t npieces, int wq) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= npieces) return;
-    const int64_t row = i / wq;
-    const int piece = (int)(i - row * wq);
-    const int pl = (int)(row / Hp), y = (int)(row - (int64_t)pl * Hp);
-    const int b = pl / nsel, j = pl - b * nsel;
-    const int ys = pc_reflect(y - top, H);
-    const int x0 = 4 * piece, xs = x0 - left;
-    const int c = ps.sel[j];
-    f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (KIND == 2 && c < C2) {
-        const uint16_t* src = reinterpret_cast<const uint16_t*>(data) + ((int64_t)(b * C2 + c) * H + ys) * W;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (x0 + e < Wp) v[e] = (float)src[pc_reflect(xs + e, W)];
-    } else {
-        const float* src = KIND == 2 ? reinterpret_cast<const float*>(data2) + ((int64_t)(b * (Cin - C2) + (c - C2)) * H + ys) * W
-                                     : reinterpret_cast<const float*>(data) + ((int64_t)(b * Cin + c) * H + ys) * W;
-        if (xs >= 0 && xs + 3 < W) {
-            const f32x4u t = *reinterpret_cast<const f32x4u*>(src + xs);
-            v = f32x4{t[0], t[1], t[2], t[3]};
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                if (x0 + e < Wp) v[e] = src[pc_reflect(xs + e, W)];
-        }
-    }
-    if (NORM) {
-        const float mu = ps.mean[j], sd = ps.stdv[j];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = x0 + e < Wp ? (v[e] - mu) / sd : 0.f;
-    }
-    *reinterpret_cast<f32x4*>(out + ((int64_t)pl * Hp + y) * rs + x0) = v;      // (rs % 4 == 0: the pad columns of the row get zeros)
-}
-
 }  // namespace
-
-static int launch_pad_select(const float* in, float* out, int B, int Cin, int nsel, const int* sel, const float* mean, const float* stdv,
-                             int H, int W, int top, int bottom, int left, int right, void* stream) {
-    if (!in || !out || !sel || B < 1 || nsel < 1 || nsel > 8 || top >= H || bottom >= H || left >= W || right >= W || top < 0 ||
-        bottom < 0 || left < 0 || right < 0)
-        return PC_EINVAL;
-    PadSel ps{};
-    for (int j = 0; j < nsel; ++j) {
-        if (sel[j] < 0 || sel[j] >= Cin) return PC_EINVAL;
-        ps.sel[j] = sel[j];
-        ps.mean[j] = mean ? mean[j] : 0.f;
-        ps.stdv[j] = stdv ? stdv[j] : 1.f;
-    }
-    const int Hp = H + top + bottom, Wp = W + left + right;
-    const int64_t nrows = (int64_t)B * nsel * Hp;
-    const int wq = (Wp + 3) >> 2;
-    if (wq > 256 || nrows > 0x7fffffff) return PC_EINVAL;          // rows of up to 1024 pixels (the training tiles; windows are not padded)
-    const int rpb = 256 / wq;
-    const dim3 grid((unsigned)((nrows + rpb - 1) / rpb));
-    if (mean)
-        hipLaunchKernelGGL(reflect_pad_select_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, in, out, ps, Cin, nsel, H, W, Hp, Wp,
-                           top, left, (int)nrows, wq, rpb);
-    else
-        hipLaunchKernelGGL(reflect_pad_select_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, in, out, ps, Cin, nsel, H, W, Hp, Wp,
-                           top, left, (int)nrows, wq, rpb);
-    PC_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int pc_reflect_pad_select(const float* in, float* out, int B, int Cin, int nsel, const int* sel, int H, int W, int top,
-                                     int bottom, int left, int right, void* stream) {
-    return launch_pad_select(in, out, B, Cin, nsel, sel, nullptr, nullptr, H, W, top, bottom, left, right, stream);
-}
-
-extern "C" int pc_select_normalize_pad(const float* raw, float* out, int B, int Craw, int nsel, const int* band, const float* mean,
-                                       const float* stdv, int H, int W, int top, int bottom, int left, int right, void* stream) {
-    if (!mean || !stdv) return PC_EINVAL;
-    return launch_pad_select(raw, out, B, Craw, nsel, band, mean, stdv, H, W, top, bottom, left, right, stream);
-}
-
-extern "C" int pc_ingest_cl8(const float* raw, void* out, int B, int Craw, int nsel, const int* band, const float* mean, const float* stdv,
-                             int H, int W, int top, int bottom, int left, int right, void* stream) {
-    if (!raw || !out || !band || B < 1 || nsel < 1 || nsel > 8 || top >= H || bottom >= H || left >= W || right >= W || top < 0 ||
-        bottom < 0 || left < 0 || right < 0 || (mean == nullptr) != (stdv == nullptr) || (reinterpret_cast<uintptr_t>(out) & 15))
-        return PC_EINVAL;
-    PadSel ps{};
-    for (int j = 0; j < nsel; ++j) {
-        if (band[j] < 0 || band[j] >= Craw) return PC_EINVAL;
-        ps.sel[j] = band[j];
-        ps.mean[j] = mean ? mean[j] : 0.f;
-        ps.stdv[j] = stdv ? stdv[j] : 1.f;
-    }
-    const int Hp = H + top + bottom, Wp = W + left + right;
-    const int64_t npix = (int64_t)B * Hp * Wp;
-    if (npix > 0x7fffffff) return PC_EINVAL;
-    const dim3 grid((unsigned)((npix + 255) / 256));
-    if (mean)
-        hipLaunchKernelGGL(ingest_cl8_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, raw, reinterpret_cast<uint4*>(out), ps, Craw, nsel,
-                           H, W, Hp, Wp, top, left, (int)npix);
-    else
-        hipLaunchKernelGGL(ingest_cl8_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, raw, reinterpret_cast<uint4*>(out), ps, Craw, nsel,
-                           H, W, Hp, Wp, top, left, (int)npix);
-    PC_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int pc_ingest_split(const uint16_t* s2, int C2, const float* s1, int C1, void* out, int cl8, int B, int nsel, const int* band,
-                               const float* mean, const float* stdv, int H, int W, int top, int bottom, int left, int right, void* stream) {
-    if (!s2 || !s1 || !out || !band || !mean || !stdv || B < 1 || C2 < 1 || C1 < 1 || nsel < 1 || nsel > 8 || top >= H || bottom >= H ||
-        left >= W || right >= W || top < 0 || bottom < 0 || left < 0 || right < 0 || (reinterpret_cast<uintptr_t>(out) & 15))
-        return PC_EINVAL;
-    PadSel ps{};
-    for (int j = 0; j < nsel; ++j) {
-        if (band[j] < 0 || band[j] >= C2 + C1) return PC_EINVAL;
-        ps.sel[j] = band[j];
-        ps.mean[j] = mean[j];
-        ps.stdv[j] = stdv[j];
-    }
-    const int Hp = H + top + bottom, Wp = W + left + right;
-    const int64_t npix = (int64_t)B * Hp * Wp;
-    if (npix > 0x7fffffff) return PC_EINVAL;
-    const dim3 grid((unsigned)((npix + 255) / 256));
-    if (cl8)
-        hipLaunchKernelGGL(ingest_split_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, s2, s1, out, ps, C2, C1, nsel, H, W, Hp, Wp, top,
-                           left, (int)npix);
-    else
-        hipLaunchKernelGGL(ingest_split_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, s2, s1, out, ps, C2, C1, nsel, H, W, Hp, Wp, top,
-                           left, (int)npix);
-    PC_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int pc_ingest_pad_strided(int kind, const void* data, const void* data2, int Cin, float* out, int out_rstride, int B, int nsel,
-                                     const int* sel, const float* mean, const float* stdv, int H, int W, int top, int bottom, int left, int right,
-                                     void* stream) {
-    if (!data || !out || !sel || B < 1 || nsel < 1 || nsel > 8 || top >= H || bottom >= H || left >= W || right >= W || top < 0 || bottom < 0 ||
-        left < 0 || right < 0 || (mean == nullptr) != (stdv == nullptr) || (kind == PC_DATA_SPLIT && (!data2 || !mean)) ||
-        (kind != PC_DATA_INPUT && kind != PC_DATA_RAW && kind != PC_DATA_SPLIT))
-        return PC_EINVAL;
-    const int Hp = H + top + bottom, Wp = W + left + right;
-    if (out_rstride < Wp || (out_rstride & 3) || (reinterpret_cast<uintptr_t>(out) & 15)) return PC_EINVAL;
-    const int C2 = kind == PC_DATA_SPLIT ? 4 : 0;
-    const int Ctot = kind == PC_DATA_SPLIT ? 6 : Cin;
-    PadSel ps{};
-    for (int j = 0; j < nsel; ++j) {
-        if (sel[j] < 0 || sel[j] >= Ctot) return PC_EINVAL;
-        ps.sel[j] = sel[j];
-        ps.mean[j] = mean ? mean[j] : 0.f;
-        ps.stdv[j] = stdv ? stdv[j] : 1.f;
-    }
-    const int wq = (Wp + 3) >> 2;
-    const int64_t npieces = (int64_t)B * nsel * Hp * wq;
-    const int64_t nblk = (npieces + 255) / 256;
-    if (nblk > 0x7fffffff) return PC_EINVAL;
-    const dim3 grid((unsigned)nblk);
-    hipStream_t st = (hipStream_t)stream;
-    if (kind == PC_DATA_SPLIT)
-        hipLaunchKernelGGL((ingest_pad_strided_kernel<2, true>), grid, dim3(256), 0, st, data, data2, out, ps, 6, C2, nsel, H, W, Hp, Wp, out_rstride, top,
-                           left, npieces, wq);
-    else if (mean)
-        hipLaunchKernelGGL((ingest_pad_strided_kernel<0, true>), grid, dim3(256), 0, st, data, data2, out, ps, Cin, 0, nsel, H, W, Hp, Wp, out_rstride, top,
-                           left, npieces, wq);
-    else
-        hipLaunchKernelGGL((ingest_pad_strided_kernel<0, false>), grid, dim3(256), 0, st, data, data2, out, ps, Cin, 0, nsel, H, W, Hp, Wp, out_rstride, top,
-                           left, npieces, wq);
-    PC_CHECK_LAUNCH();
-    return 0;
-}
-
-// zero fill by a kernel (not a memset node: see zero_fill_kernel); p 16-byte aligned
-extern "C" int pc_zero_fill(float* p, int64_t n, void* stream) {
-    if (!p || n < 0 || (reinterpret_cast<uintptr_t>(p) & 15)) return PC_EINVAL;
-    if (n == 0) return 0;
-    const int64_t n4 = n / 4, rem = n - 4 * n4;
-    int grid = (int)((n4 + 255) / 256);
-    grid = grid < 1 ? 1 : (grid > 2048 ? 2048 : grid);
-    hipLaunchKernelGGL(zero_fill_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, p, n4, rem);
-    PC_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int pc_sparsity_mask_unet(const float* building, const float* admin_mask, const int64_t* census_idx,
-                                     const uint8_t* rowsel, const uint8_t* colsel, float threshold, uint8_t* mask, float* ratio,
-                                     int B, int H, int W, void* stream) {
-    if (!building || !admin_mask || !census_idx || !rowsel || !colsel || !mask || !ratio || B < 1) return PC_EINVAL;
-    hipLaunchKernelGGL(sparsity_mask_unet_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, building, admin_mask, census_idx,
-                       rowsel, colsel, threshold, mask, ratio, H, W);
-    PC_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int pc_reflect_pad(const float* in, float* out, int64_t planes, int H, int W, int top, int bottom, int left, int right,
-                              void* stream) {
-    if (!in || !out || top >= H || bottom >= H || left >= W || right >= W || top < 0 || bottom < 0 || left < 0 || right < 0) return PC_EINVAL;
-    const int Hp = H + top + bottom, Wp = W + left + right;
-    int64_t g = (planes * Hp * Wp + 255) / 256;
-    if (g > 8192) g = 8192;
-    if (g < 1) g = 1;
-    hipLaunchKernelGGL(reflect_pad_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, in, out, planes, H, W, Hp, Wp, top, left);
-    PC_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int pc_scatter_masked(const float* src, const uint8_t* mask, float* out, void* ws, int64_t n, void* stream) {
-    if (!src || !mask || !out || !ws) return PC_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const int nblocks = (int)((n + CBLK - 1) / CBLK);
-    if (nblocks == 0) return 0;
-    int32_t* bc = reinterpret_cast<int32_t*>(ws);
-    hipLaunchKernelGGL(compact_count_kernel, dim3(nblocks), dim3(256), 0, st, mask, bc, n);
-    PC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, st, bc, nblocks, bc + nblocks);
-    PC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(scatter_masked_kernel, dim3(nblocks), dim3(256), 0, st, src, mask, bc, out, n);
-    PC_CHECK_LAUNCH();
-    return 0;
-}
 
 extern "C" int64_t pc_head_ws_bytes(int B, int H, int W) {
     const int groups = (H * W + 15) / 16;
@@ -3141,8 +2190,7 @@ static int g_head_split = -1;
 static int head_split_on() {
     if (g_head_split < 0) {
         const char* ev = getenv("POPCORN_HEAD_SPLIT");
-        const char* sr = getenv("POPCORN_HEAD_BWD_SINGLE_ROLE");          // (the ablation's single-role backward is an fp32-MFMA kernel:
-        g_head_split = ((ev && ev[0] == '0') || (sr && sr[0] == '1')) ? 0 : 1;      // both head kernels then keep the fp32 images)
+        g_head_split = (ev && ev[0] == '0') ? 0 : 1;
     }
     return g_head_split;
 }
@@ -3179,6 +2227,18 @@ static int head_fwd_chunks(int B, int H, int W, bool split, int* groups_per_wave
     return 0;
 }
 
+// the arguments pc_head_fwd and pc_head_bwd share (the callers add their outputs, the launch geometry and the weight image)
+static void head_fill_args(HeadArgs& p, const pc_src* feat, int py, int px, const float* const* hw, const uint8_t* mask, const float* building,
+                           const float* admin_mask, const int64_t* census_idx, int B, int H, int W) {
+    p.feat = *feat; p.py = py; p.px = px;
+    p.w0 = hw[0]; p.b0 = hw[1]; p.w2 = hw[2]; p.b2 = hw[3]; p.w4 = hw[4]; p.b4 = hw[5]; p.w6 = hw[6]; p.b6 = hw[7];
+    p.mask = mask; p.building = building; p.admin = admin_mask; p.census = census_idx;
+    p.B = B; p.H = H; p.W = W; p.bf = g_pc_precision == PC_PREC_BF16;
+    p.groups = (H * W + 15) / 16;
+    p.div_w = pc_make_fastdiv(W);
+    p.div_groups = pc_make_fastdiv(p.groups);
+}
+
 extern "C" int pc_head_fwd(const pc_src* feat, int py, int px, const float* const* hw, const uint8_t* mask,
                            const float* building, const float* admin_mask, const int64_t* census_idx,
                            float* scale_map, float* popdensemap, float* popcount, double* stats,
@@ -3186,15 +2246,9 @@ extern "C" int pc_head_fwd(const pc_src* feat, int py, int px, const float* cons
     if (!feat || !hw || !building || !popdensemap || !popcount || !ws) return PC_EINVAL;
     if (admin_mask && !census_idx) return PC_EINVAL;
     HeadArgs p{};
-    p.feat = *feat; p.py = py; p.px = px;
-    p.w0 = hw[0]; p.b0 = hw[1]; p.w2 = hw[2]; p.b2 = hw[3]; p.w4 = hw[4]; p.b4 = hw[5]; p.w6 = hw[6]; p.b6 = hw[7];
-    p.mask = mask; p.building = building; p.admin = admin_mask; p.census = census_idx;
+    head_fill_args(p, feat, py, px, hw, mask, building, admin_mask, census_idx, B, H, W);
     p.scale_map = scale_map; p.popdense = popdensemap;
     p.partial = reinterpret_cast<float*>(ws);
-    p.B = B; p.H = H; p.W = W; p.bf = g_pc_precision == PC_PREC_BF16;
-    p.groups = (H * W + 15) / 16;
-    p.div_w = pc_make_fastdiv(W);
-    p.div_groups = pc_make_fastdiv(p.groups);
     const bool split = !p.bf && head_split_on();
     {
         const int rc = head_fwd_chunks(B, H, W, split, &p.groups_per_wave, &p.nchunk);
@@ -3262,93 +2316,6 @@ extern "C" int pc_head_popcount_loss(void* ws, int B, int H, int W, const int32_
     return 0;
 }
 
-extern "C" int pc_outconv_sigmoid_crop(const pc_src* feat, const float* w, const float* bias, const pc_dst* out,
-                                       int B, int H, int W, int py, int px, void* stream) {
-    if (!feat || !w || !bias || !out || feat->C < 1 || feat->C > 16) return PC_EINVAL;
-    const int64_t n = (int64_t)B * H * W;
-    int grid = (int)((n + 255) / 256);
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(outconv_sigmoid_crop_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, *feat, w, bias, *out,
-                       B, H, W, py, px, (int)(g_pc_precision == PC_PREC_BF16));
-    PC_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int pc_building_score_mask(const pc_src* feat, const float* w, const float* bias, const pc_dst* building_out,
-                                      const float* admin_mask, const int64_t* census_idx, const uint8_t* rowsel,
-                                      const uint8_t* colsel, int occupancymodel, uint8_t* mask, int32_t* counts,
-                                      int B, int H, int W, int py, int px, void* stream) {
-    if (!feat || !w || !bias || !building_out || !admin_mask || !census_idx || !rowsel || !colsel || !mask || !counts ||
-        feat->C < 1 || feat->C > 16)
-        return PC_EINVAL;
-    if ((int64_t)B * H * W >= ((int64_t)1 << 27)) return PC_EINVAL;      // the packed 64-bit accumulator holds two 27-bit counts
-    static unsigned* scratch = nullptr;     // one 64-bit word {nsel : 27 | nregion : 27 | ticket : 10}: device-scope atomics only; zero
-                                            // between calls (the kernel's last block resets it), zeroed once here
-    if (!scratch) {
-        hipError_t e = hipMalloc(&scratch, 4 * sizeof(unsigned));
-        if (e != hipSuccess) return (int)e;
-        e = hipMemset(scratch, 0, 4 * sizeof(unsigned));
-        if (e != hipSuccess) return (int)e;
-        e = hipDeviceSynchronize();            // the first kernel may run on a non-blocking stream
-        if (e != hipSuccess) return (int)e;
-    }
-    ScoreMaskArgs a{};
-    a.feat = *feat; a.w = w; a.bias = bias; a.out = *building_out; a.admin = admin_mask; a.census = census_idx;
-    a.rowsel = rowsel; a.colsel = colsel; a.occ = occupancymodel; a.mask = mask; a.counts = counts; a.scratch = scratch;
-    a.B = B; a.H = H; a.W = W; a.py = py; a.px = px; a.bf = g_pc_precision == PC_PREC_BF16;
-    const int64_t n = (int64_t)B * H * W;
-    int grid = (int)((n + SM_THREADS - 1) / SM_THREADS);
-    if (grid > 256) grid = 256;            // one block per CU: the per-block atomics are the serial part
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(score_mask_kernel, dim3(grid), dim3(SM_THREADS), 0, (hipStream_t)stream, a);
-    PC_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int pc_sparsity_mask(const float* building, const float* admin_mask, const int64_t* census_idx,
-                                const uint8_t* rowsel, const uint8_t* colsel, int occupancymodel,
-                                uint8_t* mask, int32_t* counts, int B, int H, int W, void* stream) {
-    if (!building || !admin_mask || !census_idx || !rowsel || !colsel || !mask || !counts) return PC_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<uint32_t*>(counts), 2);
-    PC_CHECK_LAUNCH();
-    const int64_t n = (int64_t)B * H * W;
-    int grid = (int)((n + 255) / 256);
-    if (grid > 512) grid = 512;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(sparsity_mask_kernel, dim3(grid), dim3(256), 0, st, building, admin_mask, census_idx, rowsel, colsel,
-                       occupancymodel, mask, counts, B, H, W);
-    PC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(sparsity_mask_fallback_kernel, dim3(grid), dim3(256), 0, st, admin_mask, census_idx, mask, counts, B, H, W);
-    PC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(sparsity_mask_fix_count_kernel, dim3(1), dim3(1), 0, st, counts);
-    PC_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int64_t pc_compact_ws_bytes(int64_t n) { return ((n + CBLK - 1) / CBLK + 1) * (int64_t)sizeof(int32_t); }
-
-extern "C" int pc_compact_masked(const float* src, const uint8_t* mask, float* out, int32_t* n_out, void* ws, int64_t n,
-                                 void* stream) {
-    if (!src || !mask || !out || !n_out || !ws) return PC_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    const int nblocks = (int)((n + CBLK - 1) / CBLK);
-    int32_t* bc = reinterpret_cast<int32_t*>(ws);
-    if (nblocks == 0) {           // (a kernel, not a memset node: see zero_fill_kernel)
-        hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<uint32_t*>(n_out), 1);
-        PC_CHECK_LAUNCH();
-        return 0;
-    }
-    hipLaunchKernelGGL(compact_count_kernel, dim3(nblocks), dim3(256), 0, st, mask, bc, n);
-    PC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(1024), 0, st, bc, nblocks, n_out);
-    PC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(compact_write_kernel, dim3(nblocks), dim3(256), 0, st, src, mask, bc, out, n);
-    PC_CHECK_LAUNCH();
-    return 0;
-}
-
 // workgroup partials of the backward call: behind the forward's partials in ws; one per workgroup of the kernel the mode launches
 // (fp32: one 8-wave workgroup per CU, 4 groups in flight each; bf16: two 4-wave workgroups per CU, 2 x 79 KB of LDS)
 static void head_bwd_partial_geometry(void* ws, int B, int H, int W, bool bf, float** partial, int* nwg) {
@@ -3377,6 +2344,49 @@ extern "C" void pc_debug_head_decisions(void* buf, int64_t bytes) {
     g_head_dec_bytes = buf ? bytes : 0;
 }
 
+// launches head_bwd_pc_kernel<DBG, SPL> with the LDS of its form (the first launch on a device raises the kernel's dynamic LDS limit)
+template <int DBG, bool SPL>
+static int head_bwd_pc_launch(const HeadBwdArgs& a, int nwg, hipStream_t st) {
+    constexpr size_t lds = (SPL ? LPS_END : LP_END) * sizeof(float);
+    static pc_once_per_device once;
+    if (once.need()) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&head_bwd_pc_kernel<DBG, SPL>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+        once.mark();
+    }
+    hipLaunchKernelGGL((head_bwd_pc_kernel<DBG, SPL>), dim3(nwg), dim3(512), lds, st, a);
+    return 0;
+}
+// the form of a call: the decision export when a buffer is registered, else the product kernel (an ablation build: POPCORN_HEAD_DBG = 1 / 2
+// picks a role ablation)
+template <bool SPL>
+static int head_bwd_pc_dispatch(const HeadBwdArgs& a, int nwg, bool export_dec, hipStream_t st) {
+    if (export_dec) return head_bwd_pc_launch<4, SPL>(a, nwg, st);
+#ifdef POPCORN_HEAD_ABLATE
+    const char* dv = getenv("POPCORN_HEAD_DBG");
+    const int dbg = dv ? atoi(dv) : 0;
+    if (dbg == 1) return head_bwd_pc_launch<1, SPL>(a, nwg, st);
+    if (dbg == 2) return head_bwd_pc_launch<2, SPL>(a, nwg, st);
+#endif
+    return head_bwd_pc_launch<0, SPL>(a, nwg, st);
+}
+
+#ifdef POPCORN_HEAD_PROF
+// phase line of a -DPOPCORN_HEAD_PROF build: the first n counters of the kernel's nrec records (g_head_prof), summed and divided by div
+static void head_prof_line(hipStream_t st, const char* label, int nrec, int n, double div) {
+    if (!getenv("POPCORN_HEAD_PROF")) return;
+    static long long hp[2048 * 16];
+    (void)hipStreamSynchronize(st);
+    (void)hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_head_prof), sizeof(hp));
+    double tot[16] = {0};
+    for (int w = 0; w < nrec && w < 2048; ++w) for (int k = 0; k < n; ++k) tot[k] += (double)hp[w * 16 + k];
+    fprintf(stderr, "%s:", label);
+    for (int k = 0; k < n; ++k) fprintf(stderr, " %.0f", tot[k] / div);
+    fprintf(stderr, "\n");
+}
+#endif
+
 extern "C" int pc_head_bwd(const pc_src* feat, int py, int px, const float* const* hw, const uint8_t* mask,
                            const float* building, const float* admin_mask, const int64_t* census_idx,
                            const float* g_popcount, const float* g_popdense, const float* g_scale_map,
@@ -3386,15 +2396,10 @@ extern "C" int pc_head_bwd(const pc_src* feat, int py, int px, const float* cons
     if (!feat || !hw || !building || !dhw || !g_feat || !ws) return PC_EINVAL;
     if (admin_mask && !census_idx) return PC_EINVAL;
     const bool bfmode = g_pc_precision == PC_PREC_BF16;          // bf16 mode: feat and g_feat are channels-last bf16 tensors
-    static int use_pc = -1;
-    if (use_pc < 0) {
-        const char* ev = getenv("POPCORN_HEAD_BWD_SINGLE_ROLE");
-        use_pc = (ev && ev[0] == '1') ? 0 : 1;
-    }
-    const bool split = !bfmode && use_pc && head_split_on();     // fp32 mode: the producer waves' chain on split bf16 operands
+    const bool split = !bfmode && head_split_on();               // fp32 mode: the producer waves' chain on split bf16 operands
     if (g_head_dec) {
         // only the producer / consumer kernel exports its decisions, and only into a buffer that holds every pixel's record
-        if (bfmode || !use_pc || B < 1 || H < 1 || W < 1 || g_head_dec_bytes < (int64_t)B * H * W * PC_HEAD_DEC_BYTES ||
+        if (bfmode || B < 1 || H < 1 || W < 1 || g_head_dec_bytes < (int64_t)B * H * W * PC_HEAD_DEC_BYTES ||
             (reinterpret_cast<uintptr_t>(g_head_dec) & 7) != 0)
             return PC_EINVAL;
     }
@@ -3408,55 +2413,21 @@ extern "C" int pc_head_bwd(const pc_src* feat, int py, int px, const float* cons
     }
     hipStream_t st = (hipStream_t)stream;
     if ((reinterpret_cast<uintptr_t>(g_feat->ptr) & 15) != 0) return PC_EINVAL;
-    const bool zero_launch = !bfmode && !use_pc;                  // (the single-role debug kernel only: the product kernels zero in-kernel)
-    if (zero_launch) {
-        // zero fill by a kernel, not a memset node (see zero_fill_kernel)
-        const int64_t n4 = (int64_t)B * 16 * Hp * Wp / 4, rem = (int64_t)B * 16 * Hp * Wp - 4 * n4;
-        hipLaunchKernelGGL(zero_fill_kernel, dim3(2048), dim3(256), 0, st, g_feat->ptr, n4, rem);
-        PC_CHECK_LAUNCH();
-    }
     HeadBwdArgs a{};
-    a.Hp = Hp; a.Wp = Wp; a.zero_in_kernel = zero_launch ? 0 : 1;
+    a.Hp = Hp; a.Wp = Wp; a.zero_in_kernel = 1;
     HeadArgs& p = a.f;
-    p.feat = *feat; p.py = py; p.px = px;
-    p.w0 = hw[0]; p.b0 = hw[1]; p.w2 = hw[2]; p.b2 = hw[3]; p.w4 = hw[4]; p.b4 = hw[5]; p.w6 = hw[6]; p.b6 = hw[7];
-    p.mask = mask; p.building = building; p.admin = admin_mask; p.census = census_idx;
-    p.B = B; p.H = H; p.W = W; p.bf = g_pc_precision == PC_PREC_BF16;
-    p.groups = (H * W + 15) / 16;
-    p.div_w = pc_make_fastdiv(W);
-    p.div_groups = pc_make_fastdiv(p.groups);
+    head_fill_args(p, feat, py, px, hw, mask, building, admin_mask, census_idx, B, H, W);
     a.g_popcount = g_popcount; a.g_popdense = g_popdense; a.g_scale_map = g_scale_map; a.g_scale_const = g_scale_const;
     a.g_feat = *g_feat;
     if (feat_bn_sar && feat_bn_opt) { a.fbn[0] = *feat_bn_sar; a.fbn[1] = *feat_bn_opt; a.fuse_feat_bn = 1; }
     a.total_groups = B * p.groups;
     int nwg;
     head_bwd_partial_geometry(ws, B, H, W, p.bf, &a.partial, &nwg);
-    {
-        const char* dv = getenv("POPCORN_HEAD_DBG");
-        a.dbg = dv ? atoi(dv) : 0;
-    }
     const bool export_dec = g_head_dec != nullptr;
     if (export_dec) {
         hipError_t e1 = hipMemcpyToSymbolAsync(HIP_SYMBOL(g_head_dec_dev), &g_head_dec, sizeof(g_head_dec), 0, hipMemcpyHostToDevice, st);
         if (e1 == hipSuccess) e1 = hipStreamSynchronize(st);       // (debug path: the source is host memory the caller may clear right after this call)
         if (e1 != hipSuccess) return (int)e1;
-    }
-    static pc_once_per_device once;
-    if (once.need()) {
-        hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(&head_bwd_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LB_END * sizeof(float)));
-        if (e2 != hipSuccess) return (int)e2;
-        for (const void* f : {reinterpret_cast<const void*>(&head_bwd_pc_kernel<0, false>), reinterpret_cast<const void*>(&head_bwd_pc_kernel<1, false>),
-                              reinterpret_cast<const void*>(&head_bwd_pc_kernel<2, false>), reinterpret_cast<const void*>(&head_bwd_pc_kernel<4, false>)}) {
-            e2 = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LP_END * sizeof(float)));
-            if (e2 != hipSuccess) return (int)e2;
-        }
-        for (const void* f : {reinterpret_cast<const void*>(&head_bwd_pc_kernel<0, true>), reinterpret_cast<const void*>(&head_bwd_pc_kernel<1, true>),
-                              reinterpret_cast<const void*>(&head_bwd_pc_kernel<2, true>), reinterpret_cast<const void*>(&head_bwd_pc_kernel<4, true>)}) {
-            e2 = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LPS_END * sizeof(float)));
-            if (e2 != hipSuccess) return (int)e2;
-        }
-        once.mark();
     }
     {
         void* img = head_image_slot(ws, B, H, W, 1);
@@ -3481,60 +2452,25 @@ extern "C" int pc_head_bwd(const pc_src* feat, int py, int px, const float* cons
         }
         hipLaunchKernelGGL(head_bwd_bf16_coop4_kernel, dim3(nwg), dim3(256), H4_END, st, a);
 #ifdef POPCORN_HEAD_PROF
-        if (getenv("POPCORN_HEAD_PROF")) {
-            static long long hp[2048 * 16];
-            (void)hipStreamSynchronize(st);
-            (void)hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_head_prof), sizeof(hp));
-            double tot[10] = {0};
-            const int nw = nwg * 4;
-            for (int w = 0; w < nw && w < 2048; ++w) for (int k = 0; k < 10; ++k) tot[k] += (double)hp[w * 16 + k];
-            const double nit = (double)((a.total_groups + nw - 1) / nw);
-            fprintf(stderr, "head_bwd_bf16_coop4 phases, cycles per iteration and wave (loop top, forward chain, backward chain + store, exchange writes, barrier 1, weight gradients, barrier 2; %d workgroups, %.0f iterations):", nwg, nit);
-            for (int k = 0; k < 7; ++k) fprintf(stderr, " %.0f", tot[k] / nw / nit);
-            fprintf(stderr, "\n");
-        }
+        const int nw = nwg * 4;
+        const double nit = (double)((a.total_groups + nw - 1) / nw);
+        char label[320];
+        snprintf(label, sizeof(label), "head_bwd_bf16_coop4 phases, cycles per iteration and wave (loop top, forward chain, backward chain + store, exchange writes, barrier 1, weight gradients, barrier 2; %d workgroups, %.0f iterations)", nwg, nit);
+        head_prof_line(st, label, nw, 7, nw * nit);
 #endif
-    }
-    else if (use_pc && split) {
-        if (export_dec) hipLaunchKernelGGL((head_bwd_pc_kernel<4, true>), dim3(nwg), dim3(512), LPS_END * sizeof(float), st, a);
-        else if (a.dbg == 1) hipLaunchKernelGGL((head_bwd_pc_kernel<1, true>), dim3(nwg), dim3(512), LPS_END * sizeof(float), st, a);
-        else if (a.dbg == 2) hipLaunchKernelGGL((head_bwd_pc_kernel<2, true>), dim3(nwg), dim3(512), LPS_END * sizeof(float), st, a);
-        else hipLaunchKernelGGL((head_bwd_pc_kernel<0, true>), dim3(nwg), dim3(512), LPS_END * sizeof(float), st, a);
+    } else {
+        const int rc = split ? head_bwd_pc_dispatch<true>(a, nwg, export_dec, st) : head_bwd_pc_dispatch<false>(a, nwg, export_dec, st);
+        if (rc) return rc;
 #ifdef POPCORN_HEAD_PROF
-        if (getenv("POPCORN_HEAD_PROF")) {
-            static long long hp[2048 * 16];
-            (void)hipStreamSynchronize(st);
-            (void)hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_head_prof), sizeof(hp));
-            double tot[12] = {0};
-            const int nw = nwg * 4;
-            for (int w = 0; w < nw && w < 2048; ++w) for (int k = 0; k < 12; ++k) tot[k] += (double)hp[w * 16 + k];
-            const double ngr = (double)a.total_groups / nw;
-            fprintf(stderr, "head_bwd_pc split producer phases, cycles per group (loop top, forward, out+g3, wait0, put0, dgrad3, wait1, put1, dgrad2, wait2, put2, gx+store):");
-            for (int k = 0; k < 12; ++k) fprintf(stderr, " %.0f", tot[k] / nw / ngr);
-            fprintf(stderr, "\n");
-        }
+        const double ngr = (double)a.total_groups / (nwg * 4);       // groups per producer wave
+        if (split)
+            head_prof_line(st, "head_bwd_pc split producer phases, cycles per group (loop top, forward, out+g3, wait0, put0, dgrad3, wait1, put1, dgrad2, wait2, put2, gx+store)",
+                           nwg * 4, 12, nwg * 4 * ngr);
+        else
+            head_prof_line(st, "head_bwd_pc producer phases, cycles per group (fwd, out+g3, slot0, dgrad3, slot1, dgrad2, slot2, gx+store, loop top; of which ring waits)",
+                           nwg, 10, nwg * ngr);
 #endif
     }
-    else if (use_pc) {
-        if (export_dec) hipLaunchKernelGGL((head_bwd_pc_kernel<4, false>), dim3(nwg), dim3(512), LP_END * sizeof(float), st, a);
-        else if (a.dbg == 1) hipLaunchKernelGGL((head_bwd_pc_kernel<1, false>), dim3(nwg), dim3(512), LP_END * sizeof(float), st, a);
-        else if (a.dbg == 2) hipLaunchKernelGGL((head_bwd_pc_kernel<2, false>), dim3(nwg), dim3(512), LP_END * sizeof(float), st, a);
-        else hipLaunchKernelGGL((head_bwd_pc_kernel<0, false>), dim3(nwg), dim3(512), LP_END * sizeof(float), st, a);
-#ifdef POPCORN_HEAD_PROF
-        if (getenv("POPCORN_HEAD_PROF")) {
-            static long long hp[256 * 16];
-            (void)hipStreamSynchronize(st);
-            (void)hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_head_prof), sizeof(hp));
-            double tot[10] = {0};
-            for (int w = 0; w < nwg; ++w) for (int k = 0; k < 10; ++k) tot[k] += (double)hp[w * 16 + k];
-            const double ngr = (double)a.total_groups / (nwg * 4);
-            fprintf(stderr, "head_bwd_pc producer phases, cycles per group (fwd, out+g3, slot0, dgrad3, slot1, dgrad2, slot2, gx+store, loop top; of which ring waits):");
-            for (int k = 0; k < 10; ++k) fprintf(stderr, " %.0f", tot[k] / nwg / ngr);
-            fprintf(stderr, "\n");
-        }
-#endif
-    }
-    else hipLaunchKernelGGL(head_bwd_kernel, dim3(nwg), dim3(256), LB_END * sizeof(float), st, a);
     PC_CHECK_LAUNCH();
     if (flags & PC_HEAD_BWD_DEFER_REDUCE) return 0;      // the caller's batched reduction finishes the partials (pc_head_bwd_partials)
     HeadReduceArgs r{};

@@ -1,5 +1,12 @@
-"""Ablation of the producer/consumer head-backward kernel (B=64, 100x100, all pixels selected).  GPU only.
-POPCORN_HEAD_DBG bits: 1 consumer idle, 2 no hand-off (producer never touches the ring)."""
+"""Time of one pc_head_bwd call of the producer/consumer head-backward kernel (B=64, 100x100, all pixels selected) and its role
+ablation.  GPU only.
+
+The product library holds the product kernel only: it prints the "pc full" row.  The role ablations (POPCORN_HEAD_DBG = 1 consumer idle,
+2 no hand-off: the producer never touches the ring) are instantiated in a -DPOPCORN_HEAD_ABLATE build, and their two rows are printed only
+when POPCORN_HIP_LIB points at one:
+
+    tools/build_variant.sh ablate -DPOPCORN_HEAD_ABLATE
+    POPCORN_HIP_LIB=ab/libpopcorn_ablate.so python tools/ablate_head.py"""
 import os, subprocess, sys
 code = r'''
 import sys, os
@@ -26,8 +33,19 @@ for _ in range(10): run()
 e1.record(); torch.cuda.synchronize()
 print("%.1f us" % (e0.elapsed_time(e1) * 100))
 '''
-for tag, env in [("pc full", {}), ("single-role", {"POPCORN_HEAD_BWD_SINGLE_ROLE": "1"}), ("consumer idle", {"POPCORN_HEAD_DBG": "1"}),
-                 ("no hand-off", {"POPCORN_HEAD_DBG": "2"})]:
+def ablation_build(lib):
+    # the ablation instantiations head_bwd_pc_kernel<1 | 2, .> are registered by (mangled) name: a product build has no such name
+    if not lib or not os.path.exists(lib):
+        return False
+    with open(lib, "rb") as fh:
+        return b"head_bwd_pc_kernelILi1E" in fh.read()
+
+rows = [("pc full", {})]
+if ablation_build(os.environ.get("POPCORN_HIP_LIB")):
+    rows += [("consumer idle", {"POPCORN_HEAD_DBG": "1"}), ("no hand-off", {"POPCORN_HEAD_DBG": "2"})]
+else:
+    print("product build: the role ablations need POPCORN_HIP_LIB = a -DPOPCORN_HEAD_ABLATE build (see the docstring)", file=sys.stderr)
+for tag, env in rows:
     e = dict(os.environ); e.update(env)
     out = subprocess.run([sys.executable, "-c", code], env=e, capture_output=True, text=True)
     if "--phases" in sys.argv:       # profiling build (tools/head_phases.sh): the last launch's producer phase cycles

@@ -1,7 +1,8 @@
 """Phase profile of the split-operand producer waves of head_bwd_pc_kernel<0, true> (fp32 mode, B = 64, 100 x 100, every pixel selected)
-and the role ablation of the kernel in both product forms.  Needs the profiling build:
+and the role ablation of the kernel in both product forms.  Needs the profiling build, with the role ablations in it (without
+-DPOPCORN_HEAD_ABLATE the "consumer idle" / "no hand-off" rows are absent: tools/ablate_head.py):
 
-    tools/build_variant.sh prof -DPOPCORN_HEAD_PROF                                             (here)
+    tools/build_variant.sh prof -DPOPCORN_HEAD_PROF -DPOPCORN_HEAD_ABLATE                       (here)
     gpurun -- 'python tools/head_phases_split.py --out gpurun_out/r5_head_bwd_split_phases.json'
 
 The stamps (s_memtime into scalar accumulators, HR_CLOSE in head.hip) wait for outstanding LDS operations, i.e. they serialise the phases:
@@ -36,12 +37,12 @@ def main():
         out = ablate(env)
         d = {}
         for line in out.splitlines():
-            m = re.match(r"(pc full|single-role|consumer idle|no hand-off)\s+([0-9.]+) us", line)
+            m = re.match(r"(pc full|consumer idle|no hand-off)\s+([0-9.]+) us", line)
             if m:
                 d[m.group(1).replace(" ", "_").replace("-", "_")] = float(m.group(2))
         res["call_us"][form] = d
     res["call_us"]["note"] = ("pack + kernel + reduce launches of one pc_head_bwd call, 10 back-to-back calls (tools/ablate_head.py); "
-                              "single-role = the fp32-MFMA one-role kernel in both rows")
+                              "consumer idle / no hand-off: only when POPCORN_HIP_LIB is a -DPOPCORN_HEAD_ABLATE build")
     if os.path.exists(a.lib):
         out = ablate({"POPCORN_HIP_LIB": a.lib, "POPCORN_HEAD_PROF": "1"})
         for line in out.splitlines():
@@ -54,7 +55,7 @@ def main():
         if full:
             res["sum_cycles_per_group"] = sum(full.values())
     else:
-        res["error_prof"] = f"{a.lib} missing: tools/build_variant.sh prof -DPOPCORN_HEAD_PROF"
+        res["error_prof"] = f"{a.lib} missing: tools/build_variant.sh prof -DPOPCORN_HEAD_PROF -DPOPCORN_HEAD_ABLATE"
     os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(res, fh, indent=1)
