@@ -237,6 +237,8 @@ int pc_conv3x3_up_chain_both(int n8, const pc_conv_up_bwd_desc* d8, int nwg8, in
  *   act != NULL, pool == 1     : MaxPool2d(2) backward fused: dgrad lives at the pooled resolution; it is routed to the
  *                                first arg-max of each 2x2 window of `act` (full resolution), times (act>0)*scale, and
  *                                ACCUMULATED into out (full resolution).
+ * Supported (Cg, Cn): {8, 16} x {8, 16} -- g is the output gradient of a conv layer.  g must be a PC_SRC_DIRECT source (a pooled or
+ * reflect-padded gradient does not exist).  Anything else returns PC_EINVAL before a launch.
  */
 int pc_conv3x3_dgrad(const pc_src* g, const float* w, int Cin_total, int c0, int Cn,
                      const pc_src* act, const pc_bn* act_bn, int pool, int accumulate,
@@ -269,11 +271,14 @@ int pc_conv3x3_bwd_group(int n, const pc_conv_bwd_desc* d, int Cin_total, int c0
  * writes, 2 no data-gradient matrix phase, 4 no weight-gradient matrix phase, 8 no prefetch loads, 16 no epilogue.  Honoured by builds with
  * -DPOPCORN_CONV_ABLATE only (tools/build_variant.sh): as run-time flags they cost the shipped kernel its wait placement */
 void pc_debug_conv_bwd(int dbg);
-/* ablation switches for tools/ablate_conv.py (0,0 = normal operation); the split-form forward kernel (tools/time_conv_fwd.py --ablate:
- * 1 no loads / LDS writes, 2 no matrix phase, 4 no epilogue, 32 no split + LDS writes, 64 no loads) honours them in -DPOPCORN_CONV_ABLATE
- * builds only */
+/* ablation switches of the forward / data-gradient conv kernels (0, 0 = normal operation).  dbg (tools/ablate_conv.py: 1 no loader, 2 no
+ * matrix phase, 4 no epilogue, 8 empty kernel; the split-form forward kernel, tools/time_conv_fwd.py --ablate: 1 no loads / LDS writes,
+ * 2 no matrix phase, 4 no epilogue, 32 no split + LDS writes, 64 no loads) is honoured by builds with -DPOPCORN_CONV_ABLATE only
+ * (tools/build_variant.sh): as run-time flags the switches cost the shipped kernels their wait placement.
+ * max_grid > 0 forces the persistent grid of these launches (host code: every build). */
 void pc_debug_conv(int dbg, int max_grid);
-/* debug: buffer of 8 x int64 per workgroup receiving wall-clock stamps of the conv kernels' phases (NULL = off; tools/conv_timeline.py) */
+/* debug: buffer of 8 x int64 per workgroup receiving wall-clock stamps of conv3x3_mfma_kernel's start and end (NULL = off;
+ * tools/conv_timeline.py).  Honoured by builds with -DPOPCORN_CONV_ABLATE only. */
 void pc_debug_conv_ts(void* buf);
 
 /* ---- conv3x3 weight/bias gradient.  x = forward input (a,b sources as in fwd), g as in dgrad.

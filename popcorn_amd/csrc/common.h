@@ -136,6 +136,46 @@ static inline int pc_resident_workgroups(int regs, size_t lds) {
     return per_cu * cus;
 }
 
+// The once-per-device prologue of a launcher, declared `static` next to the launch it serves.  First call on a device: PC_SETUP_LDS
+// raises the kernel's dynamic LDS limit to `lds` bytes; PC_SETUP_PROBE reads its register count (times `reg_scale` for workgroups of
+// more than 256 threads) into `resident` = the workgroups that fit on the chip at once with `lds` bytes of LDS each.  POPCORN_CONV_DBG
+// prints what was found under `who` (the launcher's __PRETTY_FUNCTION__: its template arguments name the instantiation).
+enum { PC_SETUP_LDS = 1, PC_SETUP_PROBE = 2 };
+struct pc_launch_setup {
+    pc_once_per_device once;
+    int resident = 0;
+    hipError_t operator()(const void* fn, size_t lds, int what, const char* who, int reg_scale = 1) {
+        if (!once.need()) return hipSuccess;
+        if (what & PC_SETUP_LDS) {
+            const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        int regs = 0;
+        if (what & PC_SETUP_PROBE) {
+            hipFuncAttributes fa;
+            const hipError_t e = hipFuncGetAttributes(&fa, fn);
+            if (e != hipSuccess) return e;
+            regs = fa.numRegs;
+            resident = pc_resident_workgroups(regs * reg_scale, lds);
+        }
+        once.mark();
+        if (getenv("POPCORN_CONV_DBG")) {
+            if (what & PC_SETUP_PROBE) fprintf(stderr, "%s: %d regs, %zu B LDS -> %d resident workgroups\n", who, regs, lds, resident);
+            else fprintf(stderr, "%s: %zu B LDS\n", who, lds);
+        }
+        return hipSuccess;
+    }
+};
+
+// Persistent grid over `ntiles` (>= 1) tiles with at most `cap` workgroups, shrunk to the smallest grid with the same number of rounds so
+// that the last round is as full as the others.
+static inline int pc_balanced_grid(int ntiles, int cap) {
+    int grid = cap < ntiles ? cap : ntiles;
+    if (grid < 1) grid = 1;
+    const int rounds = (ntiles + grid - 1) / grid;
+    return (ntiles + rounds - 1) / rounds;
+}
+
 // Division by a launch-invariant divisor without the ~40-instruction VALU sequence the compiler emits for a runtime
 // integer divide (there is no hardware integer divide; in the persistent tile loops those sequences were ~1000
 // instructions per stage per wave -- tools/ablate_conv.py).  q = umulhi(n, ceil(2^32 / d)) is exact for n * d < 2^32; pc_div

@@ -348,26 +348,11 @@ __global__ __launch_bounds__(256) void conv3x3_bwd_cl_kernel(const BwdArgs p) {
 template <int GC, int XC, bool POOL>
 int launch_bwd(BwdArgs& p, int n, int* nwg_out, hipStream_t stream) {
     using Cfg = BwdCfg<GC, XC>;
-    static int resident = 0;
-    static pc_once_per_device once;
-    if (once.need()) {
-        const void* fn = reinterpret_cast<const void*>(&conv3x3_bwd_cl_kernel<GC, XC, POOL>);
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_B);
-        if (e != hipSuccess) return (int)e;
-        hipFuncAttributes fa;
-        e = hipFuncGetAttributes(&fa, fn);
-        if (e != hipSuccess) return (int)e;
-        resident = pc_resident_workgroups(fa.numRegs, Cfg::LDS_B);
-        once.mark();
-        if (getenv("POPCORN_CONV_DBG"))
-            fprintf(stderr, "conv3x3_bwd<%d,%d,%d>: %d regs, %zu B LDS -> %d resident workgroups\n", GC, XC, (int)POOL, fa.numRegs, (size_t)Cfg::LDS_B, resident);
-    }
-    int nwg = resident / n;
-    if (nwg > 512) nwg = 512;                // partials per problem (the workspace slice holds more)
-    if (nwg > p.ntiles) nwg = p.ntiles;
-    if (nwg < 1) nwg = 1;
-    const int rounds = (p.ntiles + nwg - 1) / nwg;
-    nwg = (p.ntiles + rounds - 1) / rounds;
+    static pc_launch_setup setup;
+    const hipError_t e = setup(reinterpret_cast<const void*>(&conv3x3_bwd_cl_kernel<GC, XC, POOL>), Cfg::LDS_B, PC_SETUP_LDS | PC_SETUP_PROBE, __PRETTY_FUNCTION__);
+    if (e != hipSuccess) return (int)e;
+    const int cap = setup.resident / n;
+    const int nwg = pc_balanced_grid(p.ntiles, cap > 512 ? 512 : cap);       // 512 partials per problem (the workspace slice holds more)
     hipLaunchKernelGGL((conv3x3_bwd_cl_kernel<GC, XC, POOL>), dim3(nwg, n), dim3(256), Cfg::LDS_B, stream, p);
     PC_CHECK_LAUNCH();
     *nwg_out = nwg;
@@ -584,26 +569,11 @@ __global__ __launch_bounds__(256) void conv3x3_bwd_f32_kernel(const BwdArgs p) {
 }
 
 int launch_bwd_f32(BwdArgs& p, int n, int* nwg_out, hipStream_t stream) {
-    static int resident = 0;
-    static pc_once_per_device once;
-    if (once.need()) {
-        const void* fn = reinterpret_cast<const void*>(&conv3x3_bwd_f32_kernel);
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)F_LDS_B);
-        if (e != hipSuccess) return (int)e;
-        hipFuncAttributes fa;
-        e = hipFuncGetAttributes(&fa, fn);
-        if (e != hipSuccess) return (int)e;
-        resident = pc_resident_workgroups(fa.numRegs, F_LDS_B);
-        once.mark();
-        if (getenv("POPCORN_CONV_DBG"))
-            fprintf(stderr, "conv3x3_bwd_f32: %d regs, %zu B LDS -> %d resident workgroups\n", fa.numRegs, (size_t)F_LDS_B, resident);
-    }
-    int nwg = resident / n;
-    if (nwg > 512) nwg = 512;
-    if (nwg > p.ntiles) nwg = p.ntiles;
-    if (nwg < 1) nwg = 1;
-    const int rounds = (p.ntiles + nwg - 1) / nwg;
-    nwg = (p.ntiles + rounds - 1) / rounds;
+    static pc_launch_setup setup;
+    const hipError_t e = setup(reinterpret_cast<const void*>(&conv3x3_bwd_f32_kernel), F_LDS_B, PC_SETUP_LDS | PC_SETUP_PROBE, __PRETTY_FUNCTION__);
+    if (e != hipSuccess) return (int)e;
+    const int cap = setup.resident / n;
+    const int nwg = pc_balanced_grid(p.ntiles, cap > 512 ? 512 : cap);
     hipLaunchKernelGGL(conv3x3_bwd_f32_kernel, dim3(nwg, n), dim3(256), F_LDS_B, stream, p);
     PC_CHECK_LAUNCH();
     *nwg_out = nwg;
@@ -1105,26 +1075,11 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
 template <int GC, bool POOL>
 int launch_bwd_s3(BwdArgs& p, int n, int* nwg_out, hipStream_t stream) {
     using Cfg = S3Cfg<GC>;
-    static int resident = 0;
-    static pc_once_per_device once;
-    if (once.need()) {
-        const void* fn = reinterpret_cast<const void*>(&conv3x3_bwd_s3_kernel<GC, POOL>);
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_B);
-        if (e != hipSuccess) return (int)e;
-        hipFuncAttributes fa;
-        e = hipFuncGetAttributes(&fa, fn);
-        if (e != hipSuccess) return (int)e;
-        resident = pc_resident_workgroups(fa.numRegs, Cfg::LDS_B);
-        once.mark();
-        if (getenv("POPCORN_CONV_DBG"))
-            fprintf(stderr, "conv3x3_bwd_s3<%d,%d>: %d regs, %zu B LDS -> %d resident workgroups\n", GC, (int)POOL, fa.numRegs, (size_t)Cfg::LDS_B, resident);
-    }
-    int nwg = resident / n;
-    if (nwg > 512) nwg = 512;
-    if (nwg > p.ntiles) nwg = p.ntiles;
-    if (nwg < 1) nwg = 1;
-    const int rounds = (p.ntiles + nwg - 1) / nwg;
-    nwg = (p.ntiles + rounds - 1) / rounds;
+    static pc_launch_setup setup;
+    const hipError_t e = setup(reinterpret_cast<const void*>(&conv3x3_bwd_s3_kernel<GC, POOL>), Cfg::LDS_B, PC_SETUP_LDS | PC_SETUP_PROBE, __PRETTY_FUNCTION__);
+    if (e != hipSuccess) return (int)e;
+    const int cap = setup.resident / n;
+    const int nwg = pc_balanced_grid(p.ntiles, cap > 512 ? 512 : cap);
     hipLaunchKernelGGL((conv3x3_bwd_s3_kernel<GC, POOL>), dim3(nwg, n), dim3(256), Cfg::LDS_B, stream, p);
     PC_CHECK_LAUNCH();
     *nwg_out = nwg;

@@ -547,27 +547,12 @@ bool fwd_s3_ok(const ConvArgs& p, int nprob, int ZC) {
 template <int CI, int CO, int EPI, int ZC>
 int launch_fwd_s3(ConvArgs& p, int nprob, hipStream_t stream) {
     using Cfg = FS3Cfg<CI, CO, ZC>;
-    static int resident = 0;
-    static pc_once_per_device once;
-    if (once.need()) {
-        const void* fn = reinterpret_cast<const void*>(&conv3x3_fwd_s3_kernel<CI, CO, EPI, ZC>);
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)Cfg::LDS_B);
-        if (e != hipSuccess) return (int)e;
-        hipFuncAttributes fa;
-        e = hipFuncGetAttributes(&fa, fn);
-        if (e != hipSuccess) return (int)e;
-        resident = pc_resident_workgroups(fa.numRegs, Cfg::LDS_B);
-        once.mark();
-        if (getenv("POPCORN_CONV_DBG"))
-            fprintf(stderr, "conv3x3_fwd_s3<%d,%d,%d,z%d>: %d regs, %zu B LDS -> %d resident workgroups\n", CI, CO, EPI, ZC, fa.numRegs,
-                    (size_t)Cfg::LDS_B, resident);
-    }
-    int max_grid = g_conv_max_grid > 0 ? g_conv_max_grid : resident / nprob;
-    if (max_grid < 1) max_grid = 1;
-    int grid = p.ntiles < max_grid ? p.ntiles : max_grid;
-    const int rounds = (p.ntiles + grid - 1) / grid;
-    grid = (p.ntiles + rounds - 1) / rounds;
-    hipLaunchKernelGGL((conv3x3_fwd_s3_kernel<CI, CO, EPI, ZC>), dim3(grid, nprob), dim3(256), Cfg::LDS_B, stream, p);
+    static pc_launch_setup setup;
+    const hipError_t e = setup(reinterpret_cast<const void*>(&conv3x3_fwd_s3_kernel<CI, CO, EPI, ZC>), Cfg::LDS_B, PC_SETUP_LDS | PC_SETUP_PROBE,
+                               __PRETTY_FUNCTION__);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL((conv3x3_fwd_s3_kernel<CI, CO, EPI, ZC>), dim3(conv_grid(p, setup.resident, nprob), nprob), dim3(256), Cfg::LDS_B, stream,
+                       p);
     PC_CHECK_LAUNCH();
     return 0;
 }

@@ -788,25 +788,14 @@ int launch_wgrad_wave(const WgradGroup& g, int n, int kind, int& nwg, int nchunk
     size_t lw_f32 = (size_t)4 * CINC * WIN_CSW * sizeof(float);          // fp32 strips
     if (lw_f32 < lred) lw_f32 = lred;
     const size_t lw_bf = WgradClCfg<CINC, COUT>::LDS_B;                   // channels-last bf16 strips / reduction staging
-    static int resident[5] = {0, 0, 0, 0, 0};
-    static pc_once_per_device once[5];    // workgroups of the instantiation that fit on the chip at once
+    static pc_launch_setup setup[5];      // one per instantiation
     auto go = [&](auto kern, int slot) -> int {
         const size_t lw = slot >= 3 ? lw_bf : lw_f32;
-        if (once[slot].need()) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lw);
-            if (e != hipSuccess) return (int)e;
-            hipFuncAttributes fa;
-            e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern));
-            if (e != hipSuccess) return (int)e;
-            resident[slot] = pc_resident_workgroups(fa.numRegs, lw);
-            once[slot].mark();
-            if (getenv("POPCORN_CONV_DBG"))
-                fprintf(stderr, "wgrad<%d,%d,%d>: %d regs, %zu B LDS -> %d resident workgroups\n", CINC, COUT, slot, fa.numRegs, lw,
-                        resident[slot]);
-        }
+        const hipError_t e = setup[slot](reinterpret_cast<const void*>(kern), lw, PC_SETUP_LDS | PC_SETUP_PROBE, __PRETTY_FUNCTION__);
+        if (e != hipSuccess) return (int)e;
         // all workgroups of the launch resident at once (the 16-channel instantiations hold ONE workgroup per CU: a
         // fixed 2-per-CU grid ran them in two rounds), never more partial sums than the workspace holds
-        int cap = resident[slot] / (nchunk * n);
+        int cap = setup[slot].resident / (nchunk * n);
         if (cap < 1) cap = 1;
         if (nwg > cap) nwg = cap;
         hipLaunchKernelGGL(kern, dim3(nwg, nchunk, n), dim3(256), lw, stream, g);
@@ -858,13 +847,9 @@ int launch_wgrad(WgradArgs& p, int Cin, float* dw, float* db, int accumulate, vo
         if (rc) return rc;
     } else {
         const size_t ldsb = (size_t)Cfg::LDS_FLOATS * sizeof(float);
-        static pc_once_per_device once;
-        if (once.need()) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wgrad_kernel<CINC, COUT>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
-            if (e != hipSuccess) return (int)e;
-            once.mark();
-        }
+        static pc_launch_setup setup;
+        const hipError_t e = setup(reinterpret_cast<const void*>(&conv3x3_wgrad_kernel<CINC, COUT>), ldsb, PC_SETUP_LDS, __PRETTY_FUNCTION__);
+        if (e != hipSuccess) return (int)e;
         hipLaunchKernelGGL((conv3x3_wgrad_kernel<CINC, COUT>), dim3(nwg, nchunk), dim3(256), ldsb, stream, p);
         PC_CHECK_LAUNCH();
     }

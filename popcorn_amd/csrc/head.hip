@@ -2201,22 +2201,14 @@ extern "C" int pc_set_head_split(int on) {
     return prev;
 }
 static int head_fwd_chunks(int B, int H, int W, bool split, int* groups_per_wave, int* nchunk) {
-    static int resident[2] = {0, 0};
-    static pc_once_per_device once;
-    if (once.need()) {
-        hipFuncAttributes fa;
-        hipError_t e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&head_fwd_kernel));
-        if (e != hipSuccess) return (int)e;
-        resident[0] = pc_resident_workgroups(fa.numRegs, L_END * sizeof(float));
-        e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&head_fwd_split_kernel<HS_NW>));
-        if (e != hipSuccess) return (int)e;
-        // pc_resident_workgroups counts 256-thread workgroups: an HS_NW-wave workgroup takes HS_NW / 4 of those register slots
-        resident[1] = pc_resident_workgroups(fa.numRegs * (HS_NW / 4), HS_END);
-        once.mark();
-    }
+    static pc_launch_setup setup[2];      // (static LDS: nothing to raise)
+    // pc_resident_workgroups counts 256-thread workgroups: an HS_NW-wave workgroup takes HS_NW / 4 of those register slots
+    const hipError_t e = split ? setup[1](reinterpret_cast<const void*>(&head_fwd_split_kernel<HS_NW>), HS_END, PC_SETUP_PROBE, "head_fwd_split", HS_NW / 4)
+                               : setup[0](reinterpret_cast<const void*>(&head_fwd_kernel), L_END * sizeof(float), PC_SETUP_PROBE, "head_fwd");
+    if (e != hipSuccess) return (int)e;
     const int nw = split ? HS_NW : 4;
     const int groups = (H * W + 15) / 16;
-    int chunks = resident[split ? 1 : 0] / (B > 0 ? B : 1);       // chunks per image that fit in one round
+    int chunks = setup[split ? 1 : 0].resident / (B > 0 ? B : 1);       // chunks per image that fit in one round
     const int max_chunks = (groups + 8 * nw - 1) / (8 * nw);      // never fewer than 8 groups per wave (workspace bound)
     if (chunks > max_chunks) chunks = max_chunks;
     if (chunks < 1) chunks = 1;
@@ -2348,13 +2340,9 @@ extern "C" void pc_debug_head_decisions(void* buf, int64_t bytes) {
 template <int DBG, bool SPL>
 static int head_bwd_pc_launch(const HeadBwdArgs& a, int nwg, hipStream_t st) {
     constexpr size_t lds = (SPL ? LPS_END : LP_END) * sizeof(float);
-    static pc_once_per_device once;
-    if (once.need()) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&head_bwd_pc_kernel<DBG, SPL>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-        once.mark();
-    }
+    static pc_launch_setup setup;
+    const hipError_t e = setup(reinterpret_cast<const void*>(&head_bwd_pc_kernel<DBG, SPL>), lds, PC_SETUP_LDS, __PRETTY_FUNCTION__);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL((head_bwd_pc_kernel<DBG, SPL>), dim3(nwg), dim3(512), lds, st, a);
     return 0;
 }
@@ -2438,18 +2426,9 @@ extern "C" int pc_head_bwd(const pc_src* feat, int py, int px, const float* cons
         }
     }
     if (p.bf) {
-        static pc_once_per_device once4;
-        if (once4.need()) {
-            hipError_t e5 = hipFuncSetAttribute(reinterpret_cast<const void*>(&head_bwd_bf16_coop4_kernel),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, H4_END);
-            if (e5 != hipSuccess) return (int)e5;
-            if (getenv("POPCORN_CONV_DBG")) {
-                int nb = 0;
-                (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, head_bwd_bf16_coop4_kernel, 256, H4_END);
-                fprintf(stderr, "head_bwd_bf16_coop4: %d bytes of LDS -> %d workgroups per CU\n", H4_END, nb);
-            }
-            once4.mark();
-        }
+        static pc_launch_setup setup4;     // (the probe only feeds the POPCORN_CONV_DBG line: the grid is the partial geometry's)
+        const hipError_t e5 = setup4(reinterpret_cast<const void*>(&head_bwd_bf16_coop4_kernel), H4_END, PC_SETUP_LDS | PC_SETUP_PROBE, "head_bwd_bf16_coop4");
+        if (e5 != hipSuccess) return (int)e5;
         hipLaunchKernelGGL(head_bwd_bf16_coop4_kernel, dim3(nwg), dim3(256), H4_END, st, a);
 #ifdef POPCORN_HEAD_PROF
         const int nw = nwg * 4;

@@ -541,12 +541,9 @@ extern "C" int pc_level2_fwd_group(int n, const pc_level2_fwd_desc* d, int B, vo
         p.u2 = nullptr; p.u2_bs = p.u2_cs = 0; p.u2_rs = 0;
         if (s.u2) { p.u2 = s.u2->ptr; p.u2_bs = s.u2->bstride; p.u2_cs = s.u2->cstride; p.u2_rs = s.u2->rstride; }
     }
-    static pc_once_per_device once;
-    if (once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&level2_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L2_LDS);
-        if (e != hipSuccess) return (int)e;
-        once.mark();
-    }
+    static pc_launch_setup setup;
+    const hipError_t e = setup(reinterpret_cast<const void*>(&level2_fwd_kernel), L2_LDS, PC_SETUP_LDS, __PRETTY_FUNCTION__);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(level2_fwd_kernel, dim3(B, n), dim3(512), L2_LDS, (hipStream_t)stream, a);
     PC_CHECK_LAUNCH();
     return 0;
@@ -583,12 +580,9 @@ extern "C" int pc_level2_bwd_group(int n, const pc_level2_bwd_desc* d, int B, in
         p.out = s.out->ptr; p.o_bs = s.out->bstride; p.o_cs = s.out->cstride; p.o_rs = s.out->rstride;
         p.ws1 = (float*)s.ws1; p.ws2 = (float*)s.ws2;
     }
-    static pc_once_per_device once;
-    if (once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&level2_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)B2_LDS);
-        if (e != hipSuccess) return (int)e;
-        once.mark();
-    }
+    static pc_launch_setup setup;
+    const hipError_t e = setup(reinterpret_cast<const void*>(&level2_bwd_kernel), B2_LDS, PC_SETUP_LDS, __PRETTY_FUNCTION__);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(level2_bwd_kernel, dim3(2 * B, n), dim3(512), B2_LDS, (hipStream_t)stream, a);
     PC_CHECK_LAUNCH();
     *nwg_out = B2_PARTIALS * B;

@@ -532,12 +532,9 @@ int pc_level2_fwd_cl_launch(int n, const pc_level2_fwd_desc* d, int B, hipStream
         }
         if (s.u2) { p.u2 = reinterpret_cast<pc_bf16_t*>(s.u2->ptr); p.u2_bs = s.u2->bstride; p.u2_rs = s.u2->rstride; p.u2_xs = s.u2->xstride; }
     }
-    static pc_once_per_device once;
-    if (once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&level2_fwd_cl_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LC_LDS);
-        if (e != hipSuccess) return (int)e;
-        once.mark();
-    }
+    static pc_launch_setup setup;
+    const hipError_t e = setup(reinterpret_cast<const void*>(&level2_fwd_cl_kernel), LC_LDS, PC_SETUP_LDS, __PRETTY_FUNCTION__);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(level2_fwd_cl_kernel, dim3(B, n), dim3(512), LC_LDS, stream, a);
     PC_CHECK_LAUNCH();
     return 0;
@@ -568,12 +565,9 @@ int pc_level2_bwd_cl_launch(int n, const pc_level2_bwd_desc* d, int B, int* nwg_
         p.w1 = s.w1; p.w2 = s.w2; p.bn1 = *s.bn1; p.act_bn = *s.act_bn;
         p.ws1 = reinterpret_cast<float*>(s.ws1); p.ws2 = reinterpret_cast<float*>(s.ws2);
     }
-    static pc_once_per_device once;
-    if (once.need()) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&level2_bwd_cl_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LB_LDS);
-        if (e != hipSuccess) return (int)e;
-        once.mark();
-    }
+    static pc_launch_setup setup;
+    const hipError_t e = setup(reinterpret_cast<const void*>(&level2_bwd_cl_kernel), LB_LDS, PC_SETUP_LDS, __PRETTY_FUNCTION__);
+    if (e != hipSuccess) return (int)e;
     hipLaunchKernelGGL(level2_bwd_cl_kernel, dim3(B, n), dim3(512), LB_LDS, stream, a);
     PC_CHECK_LAUNCH();
     *nwg_out = B;                        // one partial per tile and layer (each ws holds pc_level2_bwd_ws_bytes(B) >= B * LB_EC floats)

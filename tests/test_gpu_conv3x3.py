@@ -151,6 +151,35 @@ def test_conv_dgrad_pool_scatter_matches_autograd(shape, cn):
     torch.testing.assert_close(out.cpu(), ref, rtol=1e-5, atol=2e-5)
 
 
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+@pytest.mark.parametrize("group", [False, True], ids=["single", "group"])
+@pytest.mark.parametrize("case", [2, 4, 32, "pool2"])
+def test_conv_dgrad_refuses_gradients_no_layer_produces(case, group, prec):
+    """The gradient of a data-gradient call is the output gradient of a conv layer: 8 or 16 channels, a plain DIRECT source.  Anything
+    else (2, 4 or 32 channels; a max-pool loader on the gradient) is PC_EINVAL before a launch: the output stays as it was."""
+    import ctypes as C
+    from popcorn_amd import _lib as L
+    with L.precision(prec):
+        cg = 8 if case == "pool2" else case
+        gs = 16 if case == "pool2" else 8
+        g = L.as_act(_mk(1, cg, gs, gs, seed=40).cuda())
+        w = _mk(cg, 8, 3, 3, seed=41, scale=0.2).cuda()
+        out = L.as_act(torch.full((1, 8, 8, 8), 7.0, device="cuda"))
+        sg = L.src(g, mode=L.PC_SRC_POOL2) if case == "pool2" else L.src(g)
+        d = L.dst(out)
+        if group:
+            descs = (L.PcConvDgradDesc * 1)()
+            descs[0].g, descs[0].w, descs[0].out = C.pointer(sg), w.data_ptr(), C.pointer(d)
+            code = L.lib().pc_conv3x3_dgrad_group(1, descs, 8, 0, 8, 0, 0, 1, 8, 8, cg, L.stream_ptr())
+        else:
+            code = L.lib().pc_conv3x3_dgrad(C.byref(sg), L.ptr(w), 8, 0, 8, None, None, 0, 0, C.byref(d), 1, 8, 8, cg, L.stream_ptr())
+        assert code == L.PC_EINVAL
+        with pytest.raises(L.PopcornHipError):
+            L.check(code, "pc_conv3x3_dgrad")
+        torch.cuda.synchronize()
+        assert bool((out.float() == 7.0).all())
+
+
 @pytest.mark.parametrize("cin,cout", [(2, 8), (4, 8), (8, 8), (16, 8), (32, 8), (8, 16), (16, 16)])
 @pytest.mark.parametrize("shape", [(3, 64, 64), (1, 37, 53), (40, 32, 32)])
 def test_conv_wgrad(cin, cout, shape):

@@ -2,12 +2,16 @@
 B=64, distinct buffers, rotated over NSETS buffer sets so that the 256 MiB Infinity Cache is cold.  GPU only.
 
     python3 tools/ablate_conv_group.py [cin cout hw]
+
+The phase switches need a -DPOPCORN_CONV_ABLATE build (tools/build_variant.sh ablate -DPOPCORN_CONV_ABLATE; POPCORN_HIP_LIB=ab/libpopcorn_ablate.so); a product build prints the unablated rows (full, forced grids) only.
 """
 import os
 import sys
 sys.path.insert(0, os.getcwd())
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
 from popcorn_amd import ops, _lib as L
+from conv_ablation import unablated_only
 
 lib = L.lib()
 PREC = os.environ.get("ABL_PREC", "fp32")          # bf16: the bf16-container instantiations (half the bytes)
@@ -23,8 +27,7 @@ variants = [(0, 0, "full"), (1, 0, "no loader"), (2, 0, "no mfma"), (4, 0, "no s
             (0, 256, "full 4 WG/CU"), (0, 384, "full 6 WG/CU")]
 if os.environ.get("ABL_ONE"):
     variants = [(int(os.environ["ABL_ONE"], 0), 0, "dbg=" + os.environ["ABL_ONE"])]
-elif os.environ.get("ABL_ONLY_FULL"):
-    variants = [(0, 0, "full"), (16, 0, "old grid"), (0, 0, "full"), (16, 0, "old grid")]
+variants = unablated_only(variants)
 for (cin, cout, hw) in cfgs:
     sets = []
     for s in range(NSETS):

@@ -1,10 +1,13 @@
 """Would decoupled roles overlap?  An MFMA-only conv launch (no loads, no stores) on one stream next to a
 loads+stores-only launch of the same kernel on another stream, both at half the resident grid, versus each alone and
-versus the normal kernel.  GPU only."""
+versus the normal kernel.  GPU only.
+The role variants need a -DPOPCORN_CONV_ABLATE build (tools/build_variant.sh ablate -DPOPCORN_CONV_ABLATE; POPCORN_HIP_LIB=ab/libpopcorn_ablate.so); a product build prints the full-kernel rows only."""
 import os, sys
 sys.path.insert(0, os.getcwd())
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch
 from popcorn_amd import ops, _lib as L
+from conv_ablation import unablated_only
 lib = L.lib()
 B, REPS = 64, 10
 cin, cout, hw = 8, 8, 128
@@ -45,12 +48,15 @@ def run(plan, tag):
     e0.record(); g.replay(); e1.record(); torch.cuda.synchronize()
     print(f"{tag:60s} {e0.elapsed_time(e1) * 1e3 / (REPS * 4):7.1f} us per step of the plan", flush=True)
 
-run([(0, 0, None), (0, 0, None)], "2 x full kernel, back to back")
-run([(5, 0, None), (5, 0, None)], "2 x MFMA-only, back to back (full grid)")
-run([(2, 0, None), (2, 0, None)], "2 x loads+stores-only, back to back (full grid)")
-run([(5, 128, None), (5, 128, None)], "2 x MFMA-only, back to back (half grid)")
-run([(2, 128, None), (2, 128, None)], "2 x loads+stores-only, back to back (half grid)")
-run([(5, 128, 0), (2, 128, 1)], "MFMA-only || loads+stores-only (two streams, half grids)")
-run([(5, 128, 0), (5, 128, 1)], "MFMA-only || MFMA-only (two streams, half grids)")
-run([(2, 128, 0), (2, 128, 1)], "loads+stores || loads+stores (two streams, half grids)")
-run([(0, 128, 0), (0, 128, 1)], "full || full (two streams, half grids)")
+# (dbg of the plan's first launch, plan, tag): a plan with a role variant in it runs in an ablation build only
+for _, plan, tag in unablated_only([
+        (0, [(0, 0, None), (0, 0, None)], "2 x full kernel, back to back"),
+        (5, [(5, 0, None), (5, 0, None)], "2 x MFMA-only, back to back (full grid)"),
+        (2, [(2, 0, None), (2, 0, None)], "2 x loads+stores-only, back to back (full grid)"),
+        (5, [(5, 128, None), (5, 128, None)], "2 x MFMA-only, back to back (half grid)"),
+        (2, [(2, 128, None), (2, 128, None)], "2 x loads+stores-only, back to back (half grid)"),
+        (5, [(5, 128, 0), (2, 128, 1)], "MFMA-only || loads+stores-only (two streams, half grids)"),
+        (5, [(5, 128, 0), (5, 128, 1)], "MFMA-only || MFMA-only (two streams, half grids)"),
+        (2, [(2, 128, 0), (2, 128, 1)], "loads+stores || loads+stores (two streams, half grids)"),
+        (0, [(0, 128, 0), (0, 128, 1)], "full || full (two streams, half grids)")]):
+    run(plan, tag)

@@ -1,9 +1,12 @@
-"""Per-workgroup timeline of one grouped conv3x3 launch (start / end wall clock, XCC / CU ids).  GPU only."""
+"""Per-workgroup timeline of one grouped conv3x3 launch (start / end wall clock, XCC / CU ids).  GPU only.
+The stamps (pc_debug_conv_ts) and ABL_DBG need a -DPOPCORN_CONV_ABLATE build (tools/build_variant.sh ablate -DPOPCORN_CONV_ABLATE; POPCORN_HIP_LIB=ab/libpopcorn_ablate.so); a product build prints the launch's event time only."""
 import os, sys, ctypes as C
 sys.path.insert(0, os.getcwd())
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np
 import torch
 from popcorn_amd import ops, _lib as L
+from conv_ablation import unablated_only
 lib = L.lib()
 B = 64
 cin, cout, hw = (int(v) for v in sys.argv[1:4]) if len(sys.argv) >= 4 else (8, 8, 128)
@@ -22,6 +25,7 @@ ts = torch.zeros(4096 * 8, dtype=torch.int64, device="cuda")
 for s in sets:
     ops.conv3x3_fwd_group(s)
 torch.cuda.synchronize()
+stamps = len(unablated_only([(1,)])) == 1
 lib.pc_debug_conv(int(os.environ.get('ABL_DBG', '0'), 0), 0)
 lib.pc_debug_conv_ts(C.c_void_p(ts.data_ptr()))
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -31,6 +35,10 @@ ops.conv3x3_fwd_group(sets[2])
 e1.record()
 torch.cuda.synchronize()
 lib.pc_debug_conv_ts(C.c_void_p(0))
+lib.pc_debug_conv(0, 0)
+if not stamps:
+    print(f"{cin}->{cout}@{hw}: event time {e0.elapsed_time(e1) * 1e3:.1f} us")
+    sys.exit(0)
 t = ts.cpu().numpy().reshape(-1, 8)
 t = t[t[:, 0] != 0]
 t0 = t[:, 0].min()
