@@ -686,6 +686,24 @@ int pc_stitch_count_windows(const int32_t* win, int nwin, int M, int16_t* count,
 int pc_stitch_finalize(float* out_sum, float* out_sq, float* scale_sum, float* scale_sq, const int16_t* count, int64_t n,
                        void* stream);
 
+/* ---- product grid: cell x cell block sums of the 10 m maps (cell = 10: the hectare grid the reference's README recommends) ----
+ * Cell grid anchored at raster pixel (0, 0): Hc = ceil(H / cell), Wc = ceil(W / cell); partial cells at the bottom / right edge sum what
+ * exists.  cell >= 1, any value (no power of two needed, may exceed a window interior).  No floating-point atomics anywhere: within a
+ * launch every coarse cell is written by exactly one lane in a fixed order, so equal inputs give equal bits.
+ *
+ * One sliding window of an M-member ensemble into the per-member planes cells[M][Hc][Wc]: for every member m and every interior pixel p
+ * of the window inside the raster (interior and origin (yl, xl) as for pc_stitch_accumulate)
+ *     cells[m][p.y / cell][p.x / cell] += popdense[m][p] / float(visits[p]).
+ * visits: [H][W] visit count of ONE member over the WHOLE window list (seasons included), complete before the first window is added
+ * (pc_stitch_count_windows with M = 1); it is not 0 anywhere inside an interior. */
+int pc_product_accumulate(const float* popdense, int M, int ps_y, int ps_x, int overlap, int yl, int xl, const int16_t* visits, int H,
+                          int W, int cell, float* cells, void* stream);
+/* Over the M member totals T_m of each of the n cells of cells[M][n]: mean[i] = sum_m T_m / M, stdv[i] = sqrt(sum_m (T_m - mean)^2 /
+ * (M - 1)), two passes in double (0 for M == 1). */
+int pc_product_finalize(const float* cells, int M, int64_t n, float* mean, float* stdv, void* stream);
+/* out[Hc][Wc] = the cell x cell sum pooling of map[H][W] (every cell of out is written). */
+int pc_block_sum(const float* map, int H, int W, int cell, float* out, void* stream);
+
 /* ---- NaN fill of Sentinel inputs (data/PopulationDataset.py:526-551 interpolate_nan, scipy griddata "nearest") ----
  * x: contiguous fp32 (B, C, H, W), filled in place.  Per sample b, over its extent rows [0, h_b) x columns [0, w_b) (hw: DEVICE int32
  * [B][2] = {h_b, w_b}, NULL = the whole H x W; anchored top-left like the collate's zero padding; entries outside the extent are neither

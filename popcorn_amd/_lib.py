@@ -187,6 +187,10 @@ def lib():
         _lib.pc_debug_head_decisions.argtypes = [C.c_void_p, C.c_int64]
         _lib.pc_nan_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_void_p]
+        _lib.pc_product_accumulate.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                               C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.pc_product_finalize.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.pc_block_sum.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     return _lib
 
 

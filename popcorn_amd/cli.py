@@ -118,6 +118,11 @@ def eval_parser():
     p.add_argument("--nan_clouds", type=float, default=0.0, help="--raw_input: NaN cloud discs over about this fraction of S2")
     p.add_argument("--s1_gap", type=float, default=0.0, help="--raw_input: orbit-gap rows over this fraction of the descending S1")
     p.add_argument("--ascfill", action="store_true", help="always take the ascending S1 where the descending one holds NaNs")
+    p.add_argument("--product_cell", type=int, default=0,
+                   help="side in pixels of the product grid the 10 m maps are aggregated to on the device (0 = off; 10 = the hectare grid "
+                        "the reference recommends for the final product and for evaluation)")
+    p.add_argument("--product_out", type=str, default=None,
+                   help="--product_cell: torch.save the product {mean, std, adjusted, cell} here (rank 0)")
     return p
 
 
@@ -519,15 +524,24 @@ def run_eval(argv=None):
     data = SyntheticTestRaster(args.raster_hw[0], args.raster_hw[1], seasons=4 if args.fourseasons else 1, device=dev,
                                raw=args.raw_input, nan_clouds=args.nan_clouds, s1_gap=args.s1_gap)
     reducer = FlatReducer()
+    product = E.ProductGrid(args.raster_hw[0], args.raster_hw[1], args.product_cell, n, dev) if args.product_cell > 0 else None
     t0 = time.time()
     out, out_std, scale, scale_std = E.evaluate_raster(models, data.raster, args.patchsize, args.overlap, args.fourseasons,
-                                                       reducer, rank, raw=args.raw_input, ascfill=args.ascfill)
+                                                       reducer, rank, raw=args.raw_input, ascfill=args.ascfill, product=product)
     res = {}
     cp, cg = E.convert_popmap_to_census(out, data.boundary, data.census_idx, data.census_pop)
     res.update({k: float(v) for k, v in get_test_metrics(cp, cg, tag="MainCensus_synthetic_fine").items()})
     adj = E.adjust_map_to_census(out.clone(), data.boundary, data.census_idx, data.census_pop)
     cp, cg = E.convert_popmap_to_census(adj, data.boundary, data.census_idx, data.census_pop)
     res.update({k: float(v) for k, v in get_test_metrics(cp, cg, tag="AdjCensus_synthetic_fine").items()})
+    if product is not None:
+        padj = ops.block_sum(adj, product.cell)
+        res.update({"product_cell": product.cell, "product_shape": list(product.mean.shape),
+                    "product_total": product.mean.double().sum().item(), "product_std_mean": product.std.double().mean().item(),
+                    "product_adj_total": padj.double().sum().item()})
+        if args.product_out and rank == 0:
+            torch.save({"mean": product.mean.cpu(), "std": product.std.cpu(), "adjusted": padj.cpu(), "cell": product.cell},
+                       args.product_out)
     torch.cuda.synchronize()
     if rank == 0:
         res["seconds"] = time.time() - t0

@@ -45,6 +45,25 @@ def create_mask(patchsize_x, patchsize_y, overlap):
     return m
 
 
+def count_windows(count, windows, M, ps, overlap=OVERLAP):
+    """count[r][c] += M for every window of ``windows`` (iterable of (row origin, column origin)) whose interior covers (r, c), in ONE
+    launch of ``census.hip`` (pc_stitch_count_windows).  count: (h, w) int16 device map, rows contiguous."""
+    h, w = count.shape
+    # clipped interiors {x0, x1, y0, y1} of all windows as ONE small device array; census.hip counts them into the map in one launch
+    rows = []
+    for x, y in windows:
+        x, y = int(x), int(y)
+        x0, x1 = min(x + overlap, h), min(x + ps - overlap, h)
+        y0, y1 = min(y + overlap, w), min(y + ps - overlap, w)
+        if x1 > x0 and y1 > y0:
+            rows.append((x0, x1, y0, y1))
+    if not rows:
+        return
+    win = torch.tensor(rows, dtype=torch.int32).to(count.device)
+    L.check(L.lib().pc_stitch_count_windows(L.ptr(win), len(rows), int(M), L.ptr(count), h, w, L.stream_ptr()),
+            "pc_stitch_count_windows")
+
+
 class Stitcher:
     """Device-resident accumulators of run_eval.py:84-90 and the write-back / averaging of :127-154.
 
@@ -89,23 +108,9 @@ class Stitcher:
     def add_counts_only(self, windows, M, ps, overlap=OVERLAP):
         """The visit counts of MANY windows other ranks computed, in ONE launch of ``census.hip`` (pc_stitch_count_windows) instead of one
         slice-add per window from the host loop.  windows: iterable of (row origin, column origin)."""
-        ws = [(int(x), int(y)) for x, y in windows]
-        if not ws:
-            return
-        # clipped interiors {x0, x1, y0, y1} of all windows as ONE small device array; census.hip counts them into the map in one launch
         # (round 6: the difference-array form did this bookkeeping with stock torch ops -- index_put_, two cumsum_, a banded int16
         # conversion -- and a transient int32 plane of the raster's size)
-        rows = []
-        for x, y in ws:
-            x0, x1 = min(x + overlap, self.h), min(x + ps - overlap, self.h)
-            y0, y1 = min(y + overlap, self.w), min(y + ps - overlap, self.w)
-            if x1 > x0 and y1 > y0:
-                rows.append((x0, x1, y0, y1))
-        if not rows:
-            return
-        win = torch.tensor(rows, dtype=torch.int32).to(self.count.device)
-        L.check(L.lib().pc_stitch_count_windows(L.ptr(win), len(rows), int(M), L.ptr(self.count), self.h, self.w, L.stream_ptr()),
-                "pc_stitch_count_windows")
+        count_windows(self.count, windows, M, ps, overlap)
 
     def all_reduce(self, reducer: FlatReducer):
         """Multi-GPU, simple form: sum the full accumulators on every rank (interiors of regular windows are disjoint, the
@@ -167,6 +172,68 @@ class Stitcher:
                     plane.copy_(torch.cat(parts, 0))
         self.band = None
         return self.out, self.out_sq, self.scale, self.scale_sq
+
+
+def product_shape(h, w, cell):
+    """(Hc, Wc) of the product grid: cells of ``cell`` x ``cell`` pixels anchored at pixel (0, 0), partial cells at the bottom / right."""
+    return -(-h // cell), -(-w // cell)
+
+
+class ProductGrid:
+    """The product the reference's README recommends for the final maps and for evaluation: the 10 m output aggregated to a grid of
+    ``cell`` x ``cell`` pixels (cell = 10: one hectare), stitched on the device (``csrc/product.hip``).
+
+    The product mean is the block sum of the 10 m mean map.  The product's ensemble spread is NOT a function of the 10 m std map: it is
+    the standard deviation over members of each member's own cell total, and a cell total is complete only once every window that
+    touches the cell has been added (cells are not aligned with window interiors; catch-up windows and seasons revisit pixels).  So the
+    grid keeps one small plane per member, ``cells`` (M, Hc, Wc), to which every window adds its interior pixels weighted by
+    1 / visit count; ``visits`` (h, w) int16 is that count for one member over the WHOLE window list and must be set (``set_windows``)
+    before the first ``add_window``.  ``finalize`` reduces the planes to ``mean`` / ``std`` (Hc, Wc).  No atomics: bit-reproducible.
+
+    Multi-GPU (windows sharded over ranks): every rank sets the complete window list, adds its own windows, and ``all_reduce`` sums the
+    small planes; the visit map depends on the window list alone and needs no collective."""
+
+    def __init__(self, h, w, cell, members, device):
+        if torch.device(device).type != "cuda":
+            raise L.PopcornHipError("ProductGrid accumulates on a HIP device only")
+        if int(cell) < 1 or int(members) < 1:
+            raise ValueError(f"ProductGrid: cell and members must be >= 1, got cell {cell}, members {members}")
+        self.h, self.w, self.cell, self.members = int(h), int(w), int(cell), int(members)
+        self.cells = torch.zeros(self.members, *product_shape(self.h, self.w, self.cell), dtype=torch.float32, device=device)
+        self.visits = torch.zeros(self.h, self.w, dtype=torch.int16, device=device)
+        self.mean = self.std = None
+
+    def set_windows(self, idx, patchsize=INFERENCE_PATCH_SIZE, overlap=OVERLAP):
+        """The complete window list of the evaluation (``get_patch_indices``: rows of (row origin, column origin[, season]); every
+        season's windows count) -> the visit map.  Starts a new accumulation: the planes are zeroed."""
+        self.cells.zero_()
+        self.visits.zero_()
+        self.mean = self.std = None
+        count_windows(self.visits, [(r[0], r[1]) for r in idx], 1, patchsize, overlap)
+
+    def add_window(self, xl, yl, popdense, overlap=OVERLAP):
+        """popdense: (M, ps, ps) member outputs of the window whose origin is row xl, column yl, as for ``Stitcher.add_window``."""
+        L.require_device(popdense)
+        M, psx, psy = popdense.shape
+        if M != self.members:
+            raise ValueError(f"ProductGrid of {self.members} members got a window of {M}")
+        popdense = popdense.contiguous().float()
+        L.check(L.lib().pc_product_accumulate(L.ptr(popdense), M, psx, psy, int(overlap), int(xl), int(yl), L.ptr(self.visits), self.h,
+                                              self.w, self.cell, L.ptr(self.cells), L.stream_ptr()), "pc_product_accumulate")
+
+    def all_reduce(self, reducer: FlatReducer):
+        """Multi-GPU: the sum of every rank's planes on every rank (M * Hc * Wc floats, one collective)."""
+        if reducer.active:
+            import torch.distributed as dist
+            dist.all_reduce(self.cells, group=reducer.group)
+
+    def finalize(self):
+        """(mean, std) over the members of every cell, (Hc, Wc) each; std is the n - 1 form, 0 for a single member."""
+        if self.mean is None:
+            self.mean, self.std = torch.empty_like(self.cells[0]), torch.empty_like(self.cells[0])
+        L.check(L.lib().pc_product_finalize(L.ptr(self.cells), self.members, self.mean.numel(), L.ptr(self.mean), L.ptr(self.std),
+                                            L.stream_ptr()), "pc_product_finalize")
+        return self.mean, self.std
 
 
 def census_sums(pred, boundary, num_ids, want_counts=False):
@@ -240,7 +307,7 @@ def raw_window_input(win, ascfill=False):
 
 def evaluate_raster(models, raster, patchsize=INFERENCE_PATCH_SIZE, overlap=OVERLAP, fourseasons=False,
                     reducer: FlatReducer | None = None, rank=0, band_reduce=True, gather=True, return_stitcher=False, raw=False,
-                    ascfill=False):
+                    ascfill=False, product: ProductGrid | None = None):
     """Ensemble sliding-window inference over ``raster`` = callable (x, y, season, ps) -> normalised model input
     (1,6,ps,ps) on the device (the reference's Population_Dataset(mode="test") item, PopulationDataset.py:336-420), or a
     (S,6,h,w) device tensor of pre-normalised seasons.  Returns the finalised (mean map, std map, scale mean, scale std).
@@ -253,7 +320,9 @@ def evaluate_raster(models, raster, patchsize=INFERENCE_PATCH_SIZE, overlap=OVER
     ``return_stitcher``: also return the ``Stitcher`` (its visit-count map).
     ``raw``: real rasters -- the callable returns the loader's UN-normalised bands {"S2": (1,4,ps,ps), "S1": (1,2,ps,ps)} plus an optional
     "S1_asc" callable (the ascending orbit); every window is NaN-filled on the device and then normalised (``raw_window_input``; one
-    host synchronisation per window for the 5 % orbit rule).  ``ascfill``: the reference's per-region switch to the ascending orbit."""
+    host synchronisation per window for the 5 % orbit rule).  ``ascfill``: the reference's per-region switch to the ascending orbit.
+    ``product``: a ``ProductGrid`` of this raster and ensemble; it is given the window list, fed every window this rank computes,
+    all-reduced and finalised on every rank (read ``product.mean`` / ``.std`` / ``.cells``); what is returned does not change."""
     reducer = reducer or FlatReducer()
     if torch.is_tensor(raster):
         h, w = raster.shape[-2:]
@@ -265,6 +334,11 @@ def evaluate_raster(models, raster, patchsize=INFERENCE_PATCH_SIZE, overlap=OVER
     st = Stitcher(h, w, dev, world=reducer.world)
     idx = get_patch_indices(h, w, patchsize, overlap, fourseasons)
     mine = set(shard_indices(idx.shape[0], rank, reducer.world))
+    if product is not None:
+        if (product.h, product.w, product.members) != (h, w, len(models)):
+            raise ValueError(f"product grid of {product.h} x {product.w} x {product.members} members for a raster of {h} x {w} and "
+                             f"{len(models)} models")
+        product.set_windows(idx, patchsize, overlap)
     if band_reduce and reducer.world > 1:
         # the visit count needs no collective: the windows of the OTHER ranks enter this rank's count map analytically, all at once
         st.add_counts_only([(int(idx[i][0]), int(idx[i][1])) for i in range(idx.shape[0]) if i not in mine], len(models), patchsize, overlap)
@@ -292,7 +366,13 @@ def evaluate_raster(models, raster, patchsize=INFERENCE_PATCH_SIZE, overlap=OVER
                 pds.append(o["popdensemap"][0])
                 if o.get("scale") is not None:
                     scs.append(o["scale"][0])
-        st.add_window(x, y, torch.stack(pds), torch.stack(scs) if scs else None, overlap)
+        pd = torch.stack(pds)
+        st.add_window(x, y, pd, torch.stack(scs) if scs else None, overlap)
+        if product is not None:
+            product.add_window(x, y, pd, overlap)
+    if product is not None:
+        product.all_reduce(reducer)
+        product.finalize()
     if band_reduce and reducer.world > 1:
         # one reduce-scatter by row band (half the bytes of an all-reduce, no count collective), every rank finalises its band
         st.reduce_scatter(reducer, rank)

@@ -696,6 +696,20 @@ def select_normalize(raw, band6, mean6, std6, out=None):
     return out
 
 
+def block_sum(map, cell):
+    """``cell`` x ``cell`` sum pooling of a (H, W) fp32 device map onto the product grid (csrc/product.hip: cells anchored at pixel (0, 0),
+    partial cells at the bottom / right sum what exists; no atomics, bit-reproducible).  Returns (ceil(H / cell), ceil(W / cell))."""
+    L.require_device(map)
+    if map.dim() != 2 or map.dtype != torch.float32 or int(cell) < 1 or map.numel() == 0:
+        raise ValueError(f"block_sum: a non-empty fp32 (H, W) map and cell >= 1, got {map.dtype} {tuple(map.shape)}, cell {cell}")
+    map = map.contiguous()
+    H, W = map.shape
+    cell = int(cell)
+    out = torch.empty(-(-H // cell), -(-W // cell), dtype=torch.float32, device=map.device)
+    L.check(L.lib().pc_block_sum(L.ptr(map), H, W, cell, L.ptr(out), L.stream_ptr()), "pc_block_sum")
+    return out
+
+
 def nan_fill_(x, hw=None, count_only=False):
     """Nearest-value NaN fill in place (data/PopulationDataset.py:526-551 interpolate_nan, pc_nan_fill): x = contiguous fp32 device tensor
     (B, C, H, W) or (C, H, W), each sample's (C, h, w) array filled on its own -- every NaN takes the value of the nearest known entry in
