@@ -7,8 +7,15 @@
 #include <atomic>
 #include "popcorn_hip.h"
 
+// ---- vector types: the register shapes of 8- / 16-byte memory accesses and of the MFMA operands (the one definition of each) -----------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte access at 4-byte alignment (global memory only)
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));             // one 16-byte slot = the 8 bf16 channels of a channels-last pixel
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));              // A / B operand of v_mfma_f32_16x16x32_bf16
+typedef short s16x4 __attribute__((ext_vector_type(4)));                // result of one transposing LDS read; operand of v_mfma_f32_16x16x16_bf16
+typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 // bf16 mixed precision (PC_PREC_BF16, popcorn_hip.h): round-to-nearest-even of an fp32 value to the nearest bf16, kept in an
 // fp32 register (what torch's `.to(torch.bfloat16).to(torch.float32)` gives; NaN payloads aside).
@@ -23,7 +30,7 @@ __device__ __forceinline__ unsigned pc_pack_bf16(float lo, float hi) {
 }
 extern int g_pc_precision;      // api.hip: pc_set_precision()
 
-// ---- fp32 results on the bf16 matrix pipe: exact 3-way operand splits (head.hip round 5, conv3x3_bwd.hip / conv3x3_s3.hip round 6) ----
+// ---- fp32 results on the bf16 matrix pipe: exact 3-way operand splits (head.hip, conv3x3_bwd.hip, conv3x3_fwd_s3.h) -------------------------
 // a = a1 + a2 + a3 exactly, with a1 = rn_bf16(a), a2 = rn_bf16(a - a1), a3 = a - a1 - a2 (8 + 8 + 8 mantissa bits, every difference exact
 // in fp32).  One PAIR of fp32 values -> the three packed bf16 pairs of its split (lo half = x0): 11 VALU instructions.
 __device__ __forceinline__ void pc_split_pair(float x0, float x1, unsigned& q1, unsigned& q2, unsigned& q3) {
@@ -33,25 +40,68 @@ __device__ __forceinline__ void pc_split_pair(float x0, float x1, unsigned& q1, 
     const float s0 = r0 - __uint_as_float(q2 << 16), s1 = r1 - __uint_as_float(q2 & 0xffff0000u);
     q3 = pc_pack_bf16(s0, s1);
 }
+// ... and ONE fp32 value -> its three bf16 halves (weight prologues).  a3 is itself a bf16 value for every |x| >= 2^-100, so the rounding
+// in its conversion never acts and every spelling of the third half gives the same bits.  Two sites keep a spelling of their own because
+// their instruction streams are pinned to it: head.hip's head_split3 (pack launch: third half through pc_bf16r(..) >> 16, other
+// instructions) and the weight prologue of conv3x3_bwd_s3_kernel (the split in front of the offset arithmetic, another schedule).
+__device__ __forceinline__ void pc_split3(float x, unsigned short& h1, unsigned short& h2, unsigned short& h3) {
+    const float a1 = pc_bf16r(x), r1 = x - a1, a2 = pc_bf16r(r1), a3 = r1 - a2;
+    h1 = (unsigned short)(__float_as_uint(a1) >> 16);
+    h2 = (unsigned short)(__float_as_uint(a2) >> 16);
+    h3 = (unsigned short)(pc_pack_bf16(a3, 0.f) & 0xffffu);     // (= pc_f2bf(a3), defined below)
+}
+// A product of two split operands is SIX bf16 x bf16 partial products: of the nine (weight plane pw, pixel plane pa) pairs the three with
+// pw + pa > 2 (together below 2^-23 of the product) are dropped, and the rest are accumulated in fp32 SMALLEST FIRST.  This table is the
+// one statement of that order; the rounding bars of tests/test_gpu_conv3x3.py and tests/test_gpu_conv_fwd_split.py rest on it.  Used as
+//     #pragma unroll
+//     for (int i = 0; i < PC_SPLIT_PRODUCTS; ++i) { const pc_split_product s = pc_split_product_at(i); ... s.pw ... s.pa ... }
+// by conv3x3_fwd_s3_kernel and the head's hs_wgrad16.  The same order written as the nest `for pw = 2..0, for pa = 2 - pw..0` stays in
+// conv3x3_bwd_s3_kernel and inside head_bwd_pc_kernel (the flat loop is unrolled in an earlier pass than the nest, and these two
+// register-bound kernels then come out of the scheduler in another order), and in the head's *_layer64 helpers, which read the
+// fragments of a weight plane between the two loops.
+struct pc_split_product { int pw, pa; };
+constexpr int PC_SPLIT_PRODUCTS = 6;
+__host__ __device__ constexpr pc_split_product pc_split_product_at(int i) {
+    constexpr pc_split_product order[PC_SPLIT_PRODUCTS] = {{2, 0}, {1, 1}, {1, 0}, {0, 2}, {0, 1}, {0, 0}};
+    return order[i];
+}
 // conv kernels' multiplication form in PC_PREC_FP32 (api.hip: pc_set_conv_split): 1 = split-operand kernels where they exist
 int pc_conv_split_on();
 
-// ---- wave-uniform descriptor fields pinned in scalar registers (round 6) --------------------------------------------------------------------
+// ---- wave-uniform values pinned in scalar registers ------------------------------------------------------------------------------------------
 // Kernel arguments are read with s_load from the kernarg segment.  hipcc treats those loads as free to REMATERIALISE: under SGPR pressure it
 // re-issues them wherever a field is used -- inside the strip loops that meant up to 34 scalar-memory round trips per iteration
 // (s_load + s_waitcnt lgkmcnt(0), which also drains the wave's LDS queue; tools/isa_scalar_loads.py lists them per kernel), 1,800 of
-// 10,000 cycles per strip in the first version of conv3x3_bwd_s3_kernel.  A value that went through an empty asm is opaque to that: it
-// stays in an SGPR (or is spilled to a VGPR lane, a v_readlane away).  Pointers come back GLOBAL (through an address_space(1) cast): a
-// pointer that lost its provenance would be dereferenced with flat_load, which counts on vmcnt AND lgkmcnt.
+// 10,000 cycles per strip in the first version of conv3x3_bwd_s3_kernel (profiles/r6_conv_bwd_s3_phases.json).  A value that went through
+// an empty asm is opaque to that: it stays in an SGPR (or is spilled to a VGPR lane, a v_readlane away).  pc_pin(v) pins in place,
+// pc_pinned(v) returns the pinned value.
 __device__ __forceinline__ void pc_pin(int& v) { asm volatile("" : "+s"(v)); }
 __device__ __forceinline__ void pc_pin(unsigned& v) { asm volatile("" : "+s"(v)); }
 __device__ __forceinline__ void pc_pin(int64_t& v) { asm volatile("" : "+s"(v)); }
 __device__ __forceinline__ void pc_pin(float& v) { asm volatile("" : "+s"(v)); }
 template <typename T>
+__device__ __forceinline__ T pc_pinned(T v) {
+    asm volatile("" : "+s"(v));
+    return v;
+}
+// Pointers come back GLOBAL (through an address_space(1) type): a pointer that went through the asm as a generic one is dereferenced with
+// flat_load / flat_store, which count on vmcnt AND lgkmcnt -- every LDS wait then drains the prefetch.  pc_pin_ptr keeps the pointee
+// type; pc_pin_global gives a byte pointer for kernels that address with one scalar base + a 32-bit byte offset per lane and access
+// through pc_gld4 / pc_gst4 / pc_gst2.
+template <typename T>
 __device__ __forceinline__ T* pc_pin_ptr(T* ptr) {
     uint64_t v = reinterpret_cast<uint64_t>(ptr);
     asm volatile("" : "+s"(v));
     return (T*)(__attribute__((address_space(1))) T*)v;
+}
+typedef __attribute__((address_space(1))) char* pc_gptr;
+typedef __attribute__((address_space(1))) const f32x4* pc_gld4;
+typedef __attribute__((address_space(1))) f32x4* pc_gst4;
+typedef __attribute__((address_space(1))) f32x2* pc_gst2;
+__device__ __forceinline__ pc_gptr pc_pin_global(const void* ptr) {
+    uint64_t v = reinterpret_cast<uint64_t>(ptr);
+    asm volatile("" : "+s"(v));
+    return (pc_gptr)v;
 }
 __device__ __forceinline__ void pc_pin(pc_src& s) {
     s.ptr = pc_pin_ptr(s.ptr);
@@ -209,6 +259,41 @@ __device__ __forceinline__ int pc_xcd_remap(int bid, int nwg) {
     const int base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return base + idx;
 }
+
+// Block-round index t (= blockIdx.x + round * gridDim.x of a persistent grid over ntiles tiles of TW x TH pixels, walked in the
+// XCD-aware order) -> image b and origin (y0, x0) of strip `strip` (4 rows) of the tile; the strip kernels give each wave one strip.
+// The geometry comes through POINTERS (kernel-argument fields or pinned locals): a field is then read where it is used.  By value the
+// scalar loads move in front of the arithmetic, and a reference is `dereferenceable` to the compiler, which then loads a divisor's
+// multiplier ahead of the d == 1 test -- either way every strip kernel came out with another instruction stream.
+template <int TW, int TH>
+__device__ __forceinline__ void pc_strip_coords(int t, const int* ntiles, const int* tiles_x, const int* tiles_y, const pc_fastdiv* div_tpi,
+                                                const pc_fastdiv* div_tx, int strip, int& b, int& y0, int& x0) {
+    const int tile = pc_xcd_remap(t, *ntiles);
+    b = (int)pc_div((uint32_t)tile, *div_tpi);
+    const int rem = tile - b * *tiles_x * *tiles_y;
+    const int ty = (int)pc_div((uint32_t)rem, *div_tx);
+    x0 = (rem - ty * *tiles_x) * TW;
+    y0 = ty * TH + 4 * strip;
+}
+
+// ---- LDS strip images of the channels-last / split-operand kernels --------------------------------------------------------------------------
+// gfx950's transposing LDS read (ds_read_b64_tr_b16): the 16 lanes of a group read a [4 rows][16 columns] block of 16-bit elements
+// (lane l supplies the address of row l >> 2, column quad l & 3) and lane l receives the 4 rows of column l.  With rows = 4 consecutive
+// pixels of a channels-last image this turns pixel-major storage into the pixel-contraction (K) operand of the weight gradient; two reads
+// (pixels + 0..3 and + 4..7) joined by pc_tr_pair are the 8 K-slots of a lane for v_mfma_f32_16x16x32_bf16.
+__device__ __forceinline__ s16x4 pc_lds_tr16(const unsigned char* p) {
+    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
+}
+__device__ __forceinline__ bf16x8 pc_tr_pair(s16x4 a, s16x4 b) {
+    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+// Physical slot of logical slot s inside a 34-slot strip row of the split-operand conv kernels (conv3x3_bwd_s3_kernel, the plain layers of
+// conv3x3_fwd_s3_kernel): an XOR swizzle of the low two bits with the 8-slot block index.  With the plain layout the 8 lanes of a
+// ds_write_b128 group (segments 4 slots apart) hit 2 of 8 bank groups (4-way conflict) and the two strip rows of a 16-lane ds_read_b128
+// group overlap (2-way): SQ_LDS_BANK_CONFLICT was 11.1 M of 18.0 M LDS-active cycles per launch, the LDS 70 % busy
+// (profiles/r6_pmc_conv_bwd_after.json).  A bank simulator over row strides, per-row rotations and XOR swizzles (tools/lds_bank_sim.py) puts
+// this one at 996 LDS cycles per strip against 1,368 (conflict-free: 504; that needs a 48-slot stride = one workgroup per CU).
+__device__ __forceinline__ int pc_strip_slot(int s) { return s ^ ((s >> 3) & 3); }
 
 // Per-channel folded BN: scale = gamma / sqrt(var + eps); shift = (bias - mean) * scale + beta.
 __device__ __forceinline__ void pc_bn_fold(const pc_bn& bn, int c, float& scale, float& shift) {

@@ -246,17 +246,11 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(const ConvArgs p) {
     // strips: tile-major so that the 4 waves of a workgroup take the 4 strips of one 32 x 16 tile (shared halo rows
     // hit in L1/L2); workgroups walk the tiles in the XCD-aware order.
     int gdim = (int)gridDim.x;                           // (pinned: read from the dispatch packet inside the loop it was one more scalar round trip per strip)
-    asm volatile("" : "+s"(gdim));
+    pc_pin(gdim);
     const int my_tiles = p.ntiles > (int)blockIdx.x ? (p.ntiles - 1 - (int)blockIdx.x) / gdim + 1 : 0;
     const int nstages = my_tiles * NST;
     auto strip_coords = [&](int stage, int& b, int& y0, int& x0) {
-        const int t = blockIdx.x + (stage / NST) * gdim;
-        const int tile = pc_xcd_remap(t, p.ntiles);
-        b = (int)pc_div((uint32_t)tile, p.div_tpi);
-        const int rem = tile - b * p.tiles_x * p.tiles_y;
-        const int ty = (int)pc_div((uint32_t)rem, p.div_tx);
-        x0 = (rem - ty * p.tiles_x) * TW;
-        y0 = ty * TH + 4 * wave;
+        pc_strip_coords<TW, TH>(blockIdx.x + (stage / NST) * gdim, &p.ntiles, &p.tiles_x, &p.tiles_y, &p.div_tpi, &p.div_tx, wave, b, y0, x0);
     };
 
     // The loads of the first strip are in flight while the weights are staged.

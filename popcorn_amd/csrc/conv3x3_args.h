@@ -1,10 +1,6 @@
 // conv3x3_args.h -- launch arguments and strip geometry shared by the conv kernels of conv3x3.hip (the planar fp32 kernel there,
 // conv3x3_fwd_s3.h, conv3x3_cl.h, conv3x3_up.h); included by conv3x3.hip inside its anonymous namespace.
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int TW = 32, TH = 16;          // output tile
 constexpr int RS = 48;                   // LDS row stride  (== 16 mod 32)
 constexpr int COL0 = 4;                  // LDS column of tile x0 (left halo at COL0-1): keeps float4 stores aligned

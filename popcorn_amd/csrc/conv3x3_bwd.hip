@@ -14,10 +14,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int TW = 32, TH = 16;
 constexpr int SROWS = 6, BSLOTS = 48, COL0 = 4, PX = 34, PIECES = SROWS * PX;
 constexpr int IMG_B = SROWS * BSLOTS * 16;              // bytes of one strip image
@@ -43,11 +39,6 @@ struct BwdArgs {
     int tiles_x, tiles_y, ntiles;
     pc_fastdiv div_tx, div_tpi;
 };
-
-__device__ __forceinline__ s16x4 bw_tr(const unsigned char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-__device__ __forceinline__ bf16x8 bw_pair(s16x4 a, s16x4 b) { return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7)); }
 
 // GC = channels of g (the layer's output channels), XC = channels of x (this block of the layer's input channels): 8 or 16
 template <int GC, int XC>
@@ -129,12 +120,7 @@ __global__ __launch_bounds__(256) void conv3x3_bwd_cl_kernel(const BwdArgs p) {
     };
     const int my_tiles = ntl > (int)blockIdx.x ? (ntl - 1 - (int)blockIdx.x) / gdim + 1 : 0;
     auto strip_coords = [&](int k, int& b, int& y0, int& x0) {
-        const int tile = pc_xcd_remap(blockIdx.x + k * gdim, ntl);
-        b = (int)pc_div((uint32_t)tile, dtpi);
-        const int rem = tile - b * tlx * tly;
-        const int ty = (int)pc_div((uint32_t)rem, dtx);
-        x0 = (rem - ty * tlx) * TW;
-        y0 = ty * TH + 4 * wave;
+        pc_strip_coords<TW, TH>(blockIdx.x + k * gdim, &ntl, &tlx, &tly, &dtpi, &dtx, wave, b, y0, x0);
     };
     int b = 0, y0 = 0, x0 = 0;
     if (my_tiles > 0) {
@@ -289,8 +275,8 @@ __global__ __launch_bounds__(256) void conv3x3_bwd_cl_kernel(const BwdArgs p) {
 #pragma unroll
             for (int mb = 0; mb < NG; ++mb) {
                 const unsigned char* ga = igb + mb * IMG_B + 2 * rpi * BSLOTS * 16 + a_off;
-                const s16x4 lo = bw_tr(ga), hi = bw_tr(ga + 4 * 16);
-                av[mb] = bw_pair(lo, hi);
+                const s16x4 lo = pc_lds_tr16(ga), hi = pc_lds_tr16(ga + 4 * 16);
+                av[mb] = pc_tr_pair(lo, hi);
                 bacc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[mb], ones8, bacc[mb], 0, 0, 0);
             }
 #pragma unroll
@@ -298,7 +284,7 @@ __global__ __launch_bounds__(256) void conv3x3_bwd_cl_kernel(const BwdArgs p) {
 #pragma unroll
                 for (int dx = 0; dx < 3; ++dx) {
                     const unsigned char* xb = ixb + (nb >> 1) * IMG_B + 2 * rpi * BSLOTS * 16 + b_off + dx * 16 + 8 * (nb & 1);
-                    const bf16x8 bv = bw_pair(bw_tr(xb), bw_tr(xb + 4 * 16));
+                    const bf16x8 bv = pc_tr_pair(pc_lds_tr16(xb), pc_lds_tr16(xb + 4 * 16));
 #pragma unroll
                     for (int mb = 0; mb < NG; ++mb)
                         wacc[mb][dx * NBP + nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[mb], bv, wacc[mb][dx * NBP + nb], 0, 0, 0);
@@ -413,12 +399,7 @@ __global__ __launch_bounds__(256) void conv3x3_bwd_f32_kernel(const BwdArgs p) {
     };
     const int my_tiles = p.ntiles > (int)blockIdx.x ? (p.ntiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
     auto strip_coords = [&](int k, int& b, int& y0, int& x0) {
-        const int tile = pc_xcd_remap(blockIdx.x + k * gridDim.x, p.ntiles);
-        b = (int)pc_div((uint32_t)tile, p.div_tpi);
-        const int rem = tile - b * p.tiles_x * p.tiles_y;
-        const int ty = (int)pc_div((uint32_t)rem, p.div_tx);
-        x0 = (rem - ty * p.tiles_x) * TW;
-        y0 = ty * TH + 4 * wave;
+        pc_strip_coords<TW, TH>(blockIdx.x + k * gridDim.x, &p.ntiles, &p.tiles_x, &p.tiles_y, &p.div_tpi, &p.div_tx, wave, b, y0, x0);
     };
     int b = 0, y0 = 0, x0 = 0;
     if (my_tiles > 0) {
@@ -620,7 +601,7 @@ __device__ long long g_bwd_prof[4096 * 8];
 template <int GC>
 struct S3Cfg {
     static constexpr int NG = GC / 8;
-    static constexpr int BSL = 34;                             // slots per strip row: logical slot s = pixel x0 - 1 + s, stored at s3_sl(s)
+    static constexpr int BSL = 34;                             // slots per strip row: logical slot s = pixel x0 - 1 + s, stored at pc_strip_slot(s)
     static constexpr int IMG = SROWS * BSL * 16;               // bytes of one 8-channel plane image
     static constexpr int PLANE = (NG + 1) * IMG;               // one split plane of a wave: NG images of g, one of x
     static constexpr int WAVE_B = 3 * PLANE;
@@ -633,32 +614,6 @@ struct S3Cfg {
     static_assert(3 * WPL <= 4 * WAVE_B, "the prologue's weight image overlays the strip images");
     static constexpr int WAVES_PER_SIMD = (size_t)2 * LDS_B <= 160 * 1024 ? 2 : 1;
 };
-
-// Physical slot of logical slot s inside a strip row: an XOR swizzle of the low two bits with the 8-slot block index.  With the plain
-// layout the 8 lanes of a ds_write_b128 group (segments 4 slots apart) hit 2 of 8 bank groups (4-way conflict) and the two strip rows of a
-// 16-lane ds_read_b128 group overlap (2-way): SQ_LDS_BANK_CONFLICT was 11.1 M of 18.0 M LDS-active cycles per launch, the LDS 70 % busy
-// (profiles/r6_pmc_conv_bwd_after.json).  A bank simulator over row strides, per-row rotations and XOR swizzles (tools/lds_bank_sim.py) puts
-// this one at 996 LDS cycles per strip against 1,368 (conflict-free: 504; that needs a 48-slot stride = one workgroup per CU).
-__device__ __forceinline__ int s3_sl(int s) { return s ^ ((s >> 3) & 3); }
-
-// a wave-uniform value the compiler must keep in a scalar register: without this hipcc re-loads kernel-argument fields (descriptor
-// pointers, strides, flags) with s_load + s_waitcnt at every use inside the strip loop -- four dependent scalar-memory round trips per
-// epilogue, 1,800 cycles per strip in the first version of this kernel (profiles/r6_conv_bwd_s3_phases.json)
-template <typename T>
-__device__ __forceinline__ T s3_pin(T v) {
-    asm volatile("" : "+s"(v));
-    return v;
-}
-// ... and a pinned base pointer that keeps the GLOBAL address space (a pointer that went through the asm as a generic one comes back as
-// flat_load / flat_store, which count on vmcnt AND lgkmcnt: every LDS wait then drains the prefetch)
-typedef __attribute__((address_space(1))) char* s3_gptr;
-typedef __attribute__((address_space(1))) const f32x4* s3_gld4;
-typedef __attribute__((address_space(1))) f32x4* s3_gst4;
-__device__ __forceinline__ s3_gptr s3_pin_global(const void* ptr) {
-    uint64_t v = reinterpret_cast<uint64_t>(ptr);
-    asm volatile("" : "+s"(v));
-    return (s3_gptr)v;
-}
 
 template <int GC, bool POOL>
 __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3_kernel(const BwdArgs p) {
@@ -673,24 +628,24 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
     const int s_row = li >> 3, col = li & 7;
     unsigned char* const wimg = ldsb + wave * Cfg::WAVE_B;                   // plane pl at wimg + pl * PLANE: g images, then the x image
 
-    // ---- wave-uniform descriptor fields, pinned in scalar registers for the whole kernel
-    const s3_gptr g_base = s3_pin_global(q.g.ptr), x_base = s3_pin_global(q.x.ptr), o_base = s3_pin_global(q.out.ptr);
-    const unsigned g_bs = s3_pin((unsigned)q.g.bstride), g_cs = s3_pin((unsigned)q.g.cstride * 4u), g_rs = s3_pin((unsigned)q.g.rstride);
-    const unsigned x_bs = s3_pin((unsigned)q.x.bstride), x_cs = s3_pin((unsigned)q.x.cstride * 4u), x_rs = s3_pin((unsigned)q.x.rstride);
-    const unsigned o_bs = s3_pin((unsigned)q.out.bstride), o_cs = s3_pin((unsigned)q.out.cstride), o_rs = s3_pin((unsigned)q.out.rstride);
-    const int H = s3_pin(p.H), W = s3_pin(p.W);
-    const int maskf = s3_pin(q.mask), accf = s3_pin(p.accumulate);
+    // ---- wave-uniform descriptor fields, pinned in scalar registers for the whole kernel (common.h: why)
+    const pc_gptr g_base = pc_pin_global(q.g.ptr), x_base = pc_pin_global(q.x.ptr), o_base = pc_pin_global(q.out.ptr);
+    const unsigned g_bs = pc_pinned((unsigned)q.g.bstride), g_cs = pc_pinned((unsigned)q.g.cstride * 4u), g_rs = pc_pinned((unsigned)q.g.rstride);
+    const unsigned x_bs = pc_pinned((unsigned)q.x.bstride), x_cs = pc_pinned((unsigned)q.x.cstride * 4u), x_rs = pc_pinned((unsigned)q.x.rstride);
+    const unsigned o_bs = pc_pinned((unsigned)q.out.bstride), o_cs = pc_pinned((unsigned)q.out.cstride), o_rs = pc_pinned((unsigned)q.out.rstride);
+    const int H = pc_pinned(p.H), W = pc_pinned(p.W);
+    const int maskf = pc_pinned(q.mask), accf = pc_pinned(p.accumulate);
     // ablation switches (pc_debug_conv_bwd; tools/time_conv_bwd.py --ablate) exist in -DPOPCORN_CONV_ABLATE builds only (tools/build_variant.sh):
     // as run-time flags they made commit() conditional, and a path that may skip it leaves its loads pending -- the compiler then waits
     // vmcnt(0) before it re-uses their registers for the next prefetch
 #ifdef POPCORN_CONV_ABLATE
-    const int dbg = s3_pin(p.dbg);
+    const int dbg = pc_pinned(p.dbg);
 #else
     constexpr int dbg = 0;
 #endif
-    const s3_gptr a_base = s3_pin_global(POOL ? q.pool_act.ptr : q.x.ptr);
-    const unsigned a_bs = s3_pin((unsigned)(POOL ? q.pool_act.bstride : 0)), a_cs = s3_pin((unsigned)(POOL ? q.pool_act.cstride : 0)),
-                   a_rs = s3_pin((unsigned)(POOL ? q.pool_act.rstride : 0));
+    const pc_gptr a_base = pc_pin_global(POOL ? q.pool_act.ptr : q.x.ptr);
+    const unsigned a_bs = pc_pinned((unsigned)(POOL ? q.pool_act.bstride : 0)), a_cs = pc_pinned((unsigned)(POOL ? q.pool_act.cstride : 0)),
+                   a_rs = pc_pinned((unsigned)(POOL ? q.pool_act.rstride : 0));
 
     // ---- loader: lane = (row of the 6-row strip, 16-byte segment of the 40-float row x0 - 4 ..), both tensors.  Byte offsets inside a
     //      tensor are 32-bit (the launcher checks the extents): one scalar base per channel + one vector offset per lane
@@ -702,7 +657,7 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const int sl = 4 * l_seg + e - 3;
-        c_sl[e] = s3_sl(sl < 0 ? 0 : (sl > 33 ? 33 : sl));
+        c_sl[e] = pc_strip_slot(sl < 0 ? 0 : (sl > 33 ? 33 : sl));
     }
     auto issue = [&](int b, int y0, int x0) {
         const int xg = x0 - 4 + 4 * l_seg, y = y0 - 1 + l_r;
@@ -711,9 +666,9 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
         const unsigned go = ok ? ((unsigned)b * g_bs + (unsigned)y * g_rs + (unsigned)xg) * 4u : 0u;
         const unsigned xo = ok ? ((unsigned)b * x_bs + (unsigned)y * x_rs + (unsigned)xg) * 4u : 0u;
 #pragma unroll
-        for (int it = 0; it < GC; ++it) RG[it] = *(s3_gld4)(g_base + (size_t)(it * g_cs) + go);
+        for (int it = 0; it < GC; ++it) RG[it] = *(pc_gld4)(g_base + (size_t)(it * g_cs) + go);
 #pragma unroll
-        for (int it = 0; it < 8; ++it) RX[it] = *(s3_gld4)(x_base + (size_t)(it * x_cs) + xo);
+        for (int it = 0; it < 8; ++it) RX[it] = *(pc_gld4)(x_base + (size_t)(it * x_cs) + xo);
     };
     // split + transpose while staging: pixel e of the lane's four = slot 4 * l_seg + e - 3 of row l_r (the outer three pixels of the first and
     // of the last segment are not part of the strip), its 8 channels = one 16-byte slot per plane
@@ -753,15 +708,10 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
                 }
             }
     };
-    const int gdim = s3_pin((int)gridDim.x), ntl = s3_pin(p.ntiles);
+    const int gdim = pc_pinned((int)gridDim.x), ntl = pc_pinned(p.ntiles);
     const int my_tiles = ntl > (int)blockIdx.x ? (ntl - 1 - (int)blockIdx.x) / gdim + 1 : 0;
     auto strip_coords = [&](int k, int& b, int& y0, int& x0) {
-        const int tile = pc_xcd_remap(blockIdx.x + k * gdim, ntl);
-        b = (int)pc_div((uint32_t)tile, p.div_tpi);
-        const int rem = tile - b * p.tiles_x * p.tiles_y;
-        const int ty = (int)pc_div((uint32_t)rem, p.div_tx);
-        x0 = (rem - ty * p.tiles_x) * TW;
-        y0 = ty * TH + 4 * wave;
+        pc_strip_coords<TW, TH>(blockIdx.x + k * gdim, &ntl, &p.tiles_x, &p.tiles_y, &p.div_tpi, &p.div_tx, wave, b, y0, x0);
     };
     int b = 0, y0 = 0, x0 = 0;
     if (my_tiles > 0) {
@@ -791,6 +741,7 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
         const int e = tid + k * 256;
         if (e < GC * 72) {
             const int tap = e % 9, gch = (e / 9) % GC, xch = e / (9 * GC);
+            // (pc_split3, spelled out: the kernel's instruction stream is pinned to the split in front of the offset arithmetic)
             const float a1 = pc_bf16r(wreg[k]), r1 = wreg[k] - a1, a2 = pc_bf16r(r1), a3 = r1 - a2;
             const int o = (tap / 3) * BW_DYS + xch * BW_CO + (gch / 8) * 24 + (tap % 3) * 8 + (gch % 8);
             w2h[o] = (unsigned short)(__float_as_uint(a1) >> 16);
@@ -820,15 +771,15 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
     int a_off[2], b_off[3][2];                                               // [.., hi]: the second transposing read sits 4 pixels on
 #pragma unroll
     for (int hi = 0; hi < 2; ++hi) {
-        a_off[hi] = ((1 + (t_q >> 1)) * BSL + s3_sl(SL0 + 8 * lk + t_j + 4 * hi)) * 16 + 8 * (t_q & 1);
+        a_off[hi] = ((1 + (t_q >> 1)) * BSL + pc_strip_slot(SL0 + 8 * lk + t_j + 4 * hi)) * 16 + 8 * (t_q & 1);
 #pragma unroll
-        for (int dx = 0; dx < 3; ++dx) b_off[dx][hi] = (t_q * BSL + s3_sl((SL0 - 1) + 8 * lk + t_j + dx + 4 * hi)) * 16;
+        for (int dx = 0; dx < 3; ++dx) b_off[dx][hi] = (t_q * BSL + pc_strip_slot((SL0 - 1) + 8 * lk + t_j + dx + 4 * hi)) * 16;
     }
     int dg_sl[3][2];                                                         // data gradient: the lane's pixel slot per (dx, half of the strip row)
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-        for (int h = 0; h < 2; ++h) dg_sl[dx][h] = s3_sl((SL0 - 1) + li + dx + 16 * h);
+        for (int h = 0; h < 2; ++h) dg_sl[dx][h] = pc_strip_slot((SL0 - 1) + li + dx + 16 * h);
     f32x4 wacc[NG][NBLK], bacc[NG];
     const bf16x8 ones8 = __builtin_bit_cast(bf16x8, u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u});
 #pragma unroll
@@ -844,7 +795,7 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
 #pragma unroll
     for (int h = 0; h < 2; ++h)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) m_sl[h][r] = s3_sl(SL0 + 16 * h + 4 * lk + r);
+        for (int r = 0; r < 4; ++r) m_sl[h][r] = pc_strip_slot(SL0 + 16 * h + 4 * lk + r);
 
     BQ_DECL;
     BQ_START;
@@ -887,7 +838,7 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
                     for (int u = 0; u < 4; ++u) av[pl][u] = __builtin_bit_cast(bf16x8, lrow[(u >> 1) * 2 * BSL + dg_sl[dx][u & 1]]);
                 }
 #pragma unroll
-                for (int pw = 2; pw >= 0; --pw)               // weight split index; pixel split indices 2 - pw .. 0: smallest products first
+                for (int pw = 2; pw >= 0; --pw)               // weight plane; pixel planes 2 - pw .. 0: pc_split_product_at's order (common.h), as a nest
 #pragma unroll
                     for (int pa = 2 - pw; pa >= 0; --pa)
 #pragma unroll
@@ -908,15 +859,15 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
                 const int y = y0 + 2 * (u >> 1) + s_row, x = x0 + (u & 1) * 16 + 4 * lk;
                 if (y < H && x < W) {
                     const f32x4 v = acc[u];
-                    const s3_gptr a0 = a_base + (size_t)(((unsigned)b * a_bs + (unsigned)col * a_cs + (unsigned)(2 * y) * a_rs + (unsigned)(2 * x)) * 4u);
-                    const s3_gptr o0 = o_base + (size_t)(((unsigned)b * o_bs + (unsigned)col * o_cs + (unsigned)(2 * y) * o_rs + (unsigned)(2 * x)) * 4u);
+                    const pc_gptr a0 = a_base + (size_t)(((unsigned)b * a_bs + (unsigned)col * a_cs + (unsigned)(2 * y) * a_rs + (unsigned)(2 * x)) * 4u);
+                    const pc_gptr o0 = o_base + (size_t)(((unsigned)b * o_bs + (unsigned)col * o_cs + (unsigned)(2 * y) * o_rs + (unsigned)(2 * x)) * 4u);
                     f32x4 A[2][2], O[2][2];
 #pragma unroll
                     for (int rr = 0; rr < 2; ++rr)
 #pragma unroll
                         for (int h = 0; h < 2; ++h) {
-                            A[rr][h] = *(s3_gld4)(a0 + (size_t)((rr * a_rs + 4 * h) * 4u));
-                            O[rr][h] = *(s3_gld4)(o0 + (size_t)((rr * o_rs + 4 * h) * 4u));
+                            A[rr][h] = *(pc_gld4)(a0 + (size_t)((rr * a_rs + 4 * h) * 4u));
+                            O[rr][h] = *(pc_gld4)(o0 + (size_t)((rr * o_rs + 4 * h) * 4u));
                         }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -936,7 +887,7 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
 #pragma unroll
                     for (int rr = 0; rr < 2; ++rr)
 #pragma unroll
-                        for (int h = 0; h < 2; ++h) *(s3_gst4)(o0 + (size_t)((rr * o_rs + 4 * h) * 4u)) = O[rr][h];
+                        for (int h = 0; h < 2; ++h) *(pc_gst4)(o0 + (size_t)((rr * o_rs + 4 * h) * 4u)) = O[rr][h];
                 }
             }
         } else {
@@ -953,33 +904,33 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
             const bool full = __builtin_amdgcn_readfirstlane((y0 + 4 <= H) && (x0 + TW <= W));
             if (full) {
                 // interior strip: no bounds checks, four 16-byte stores from one base address
-                s3_gptr op[4];
+                pc_gptr op[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) op[u] = o_base + (size_t)(ob + ((u >> 1) * 2 * o_rs + (u & 1) * 16) * 4u);
                 if (accf) {
                     f32x4 o4[4];
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) o4[u] = *(s3_gld4)op[u];
+                    for (int u = 0; u < 4; ++u) o4[u] = *(pc_gld4)op[u];
 #pragma unroll
                     for (int u = 0; u < 4; ++u)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) acc[u][r] += o4[u][r];
                 }
 #pragma unroll
-                for (int u = 0; u < 4; ++u) *(s3_gst4)op[u] = acc[u];
+                for (int u = 0; u < 4; ++u) *(pc_gst4)op[u] = acc[u];
             } else {
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int y = y0 + 2 * (u >> 1) + s_row, x = x0 + (u & 1) * 16 + 4 * lk;
                     if (y < H && x < W) {
-                        const s3_gptr op = o_base + (size_t)(ob + ((u >> 1) * 2 * o_rs + (u & 1) * 16) * 4u);
+                        const pc_gptr op = o_base + (size_t)(ob + ((u >> 1) * 2 * o_rs + (u & 1) * 16) * 4u);
                         f32x4 v = acc[u];
                         if (accf) {
-                            const f32x4 o4 = *(s3_gld4)op;
+                            const f32x4 o4 = *(pc_gld4)op;
 #pragma unroll
                             for (int r = 0; r < 4; ++r) v[r] += o4[r];
                         }
-                        *(s3_gst4)op = v;
+                        *(pc_gst4)op = v;
                     }
                 }
             }
@@ -996,7 +947,7 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl) {
                     const unsigned char* ga = wimg + pl * PLANE + mb * IMG + 2 * rpi * BSL * 16;
-                    av[mb][pl] = bw_pair(bw_tr(ga + a_off[0]), bw_tr(ga + a_off[1]));
+                    av[mb][pl] = pc_tr_pair(pc_lds_tr16(ga + a_off[0]), pc_lds_tr16(ga + a_off[1]));
                 }
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) {
@@ -1006,7 +957,7 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl) {
                         const unsigned char* xb = ixb + pl * PLANE + 2 * rpi * BSL * 16 + 8 * nb;
-                        bv[dx][pl] = bw_pair(bw_tr(xb + b_off[dx][0]), bw_tr(xb + b_off[dx][1]));
+                        bv[dx][pl] = pc_tr_pair(pc_lds_tr16(xb + b_off[dx][0]), pc_lds_tr16(xb + b_off[dx][1]));
                     }
                 if (nb == 0) {
 #pragma unroll
@@ -1015,7 +966,7 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
                         for (int mb = 0; mb < NG; ++mb) bacc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[mb][pl], ones8, bacc[mb], 0, 0, 0);
                 }
 #pragma unroll
-                for (int pg = 2; pg >= 0; --pg)
+                for (int pg = 2; pg >= 0; --pg)               // (plane of g, plane of x): the same order
 #pragma unroll
                     for (int px = 2 - pg; px >= 0; --px)
 #pragma unroll

@@ -149,13 +149,7 @@ __global__ __launch_bounds__(256) void conv3x3_cl_kernel(const ConvArgs p) {
     const int my_tiles = ntl > (int)blockIdx.x ? (ntl - 1 - (int)blockIdx.x) / gdim + 1 : 0;
     const int nstages = my_tiles * NCHUNK;
     auto strip_coords = [&](int stage, int& b, int& y0, int& x0) {
-        const int t = blockIdx.x + (stage / NCHUNK) * gdim;
-        const int tile = pc_xcd_remap(t, ntl);
-        b = (int)pc_div((uint32_t)tile, dtpi);
-        const int rem = tile - b * tlx * tly;
-        const int ty = (int)pc_div((uint32_t)rem, dtx);
-        x0 = (rem - ty * tlx) * TW;
-        y0 = ty * TH + 4 * wave;
+        pc_strip_coords<TW, TH>(blockIdx.x + (stage / NCHUNK) * gdim, &ntl, &tlx, &tly, &dtpi, &dtx, wave, b, y0, x0);
     };
     int b = 0, y0 = 0, x0 = 0;
     if (nstages > 0) {
@@ -212,8 +206,7 @@ __global__ __launch_bounds__(256) void conv3x3_cl_kernel(const ConvArgs p) {
     // fragment of v_mfma_f32_16x16x16_bf16 (N = pixel li, k-group lk = 4 channels): lanes lk = 0, 1 hold row s = 0 of the pair, lanes
     // lk = 2, 3 row s = 1 -- so the weights of row s sit in the k-groups 2 s, 2 s + 1 of A and the other two k-groups are zero
     // (M = (x parity b = li >> 3, output channel li & 7); one instruction per (row s, output-row parity a))
-    typedef short upt_s4 __attribute__((ext_vector_type(4)));
-    upt_s4 upt_aw[2][2];
+    s16x4 upt_aw[2][2];
     float upt_bias[4] = {0.f, 0.f, 0.f, 0.f};
     if constexpr (EPI == EPI_UPT) {
 #pragma unroll
@@ -288,7 +281,7 @@ __global__ __launch_bounds__(256) void conv3x3_cl_kernel(const ConvArgs p) {
                     if (ok && (EPI != EPI_UPT || outp)) pc_st4(outp + eb * o_bs + (int64_t)y * o_rs + (int64_t)x * o_xs + nb * 8 + c4, v);
                     if constexpr (EPI == EPI_UPT) {
                         // the transposed conv of this unit's two rows: D[(b, co)][pixel] -> up-sampled pixel (2 y_s + a, 2 x + b)
-                        upt_s4 bv;
+                        s16x4 bv;
                         {
                             const unsigned p0 = pc_pack_bf16(v[0], v[1]), p1 = pc_pack_bf16(v[2], v[3]);
                             bv[0] = (short)(p0 & 0xffffu); bv[1] = (short)(p0 >> 16); bv[2] = (short)(p1 & 0xffffu); bv[3] = (short)(p1 >> 16);

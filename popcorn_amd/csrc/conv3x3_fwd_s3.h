@@ -36,26 +36,10 @@ struct FS3Cfg {
     static constexpr int WAVES_PER_SIMD = (size_t)3 * LDS_B <= 160 * 1024 ? 3 : 2;   // (168 registers then; the 16 + 16z -> 8 layer keeps 2)
 };
 
-// physical slot of logical slot s inside a strip row.  Plain layers: conv3x3_bwd_s3_kernel's XOR swizzle (tools/lds_bank_sim.py); composed
-// layers: even pixels in slots 0..16, odd pixels in 17..33
-__device__ __forceinline__ int fs3_sl(int s) { return s ^ ((s >> 3) & 3); }
+// physical slot of logical slot s inside a strip row.  Plain layers: the XOR swizzle of conv3x3_bwd_s3_kernel (common.h: pc_strip_slot);
+// composed layers: even pixels in slots 0..16, odd pixels in 17..33
 __device__ __forceinline__ int fs3_sl_p2(int s) { return (s & 1) * 17 + (s >> 1); }
 
-template <typename T>
-__device__ __forceinline__ T fs3_pin(T v) {
-    asm volatile("" : "+s"(v));
-    return v;
-}
-typedef __attribute__((address_space(1))) char* fs3_gptr;
-typedef __attribute__((address_space(1))) const f32x4* fs3_gld4;
-typedef __attribute__((address_space(1))) f32x4* fs3_gst4;
-typedef float fs3_f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(1))) fs3_f32x2* fs3_gst2;
-__device__ __forceinline__ fs3_gptr fs3_pin_global(const void* ptr) {
-    uint64_t v = reinterpret_cast<uint64_t>(ptr);
-    asm volatile("" : "+s"(v));
-    return (fs3_gptr)v;
-}
 template <int N>
 using fs3_int = std::integral_constant<int, N>;
 
@@ -77,29 +61,29 @@ __global__ __launch_bounds__(256, (FS3Cfg<CI, CO, ZC>::WAVES_PER_SIMD)) void con
     unsigned short* const wzh = w2h + 3 * WPL;                                              // composed weights: plane pl at wzh + pl * ZPL
 
     // ---- wave-uniform descriptor fields, pinned in scalar registers for the whole kernel (common.h: why)
-    const fs3_gptr a_base = fs3_pin_global(q.a.ptr), o_base = fs3_pin_global(q.out.ptr);
-    const unsigned a_bs = fs3_pin((unsigned)q.a.bstride), a_cs = fs3_pin((unsigned)q.a.cstride * 4u), a_rs = fs3_pin((unsigned)q.a.rstride);
-    const unsigned o_bs = fs3_pin((unsigned)q.out.bstride), o_cs = fs3_pin((unsigned)q.out.cstride), o_rs = fs3_pin((unsigned)q.out.rstride);
-    const fs3_gptr z_base = fs3_pin_global(ZC > 0 ? (const void*)q.z : (const void*)q.a.ptr);
-    const unsigned z_bs = fs3_pin((unsigned)(ZC > 0 ? q.z_bs : 0)), z_cs = fs3_pin((unsigned)(ZC > 0 ? q.z_cs : 0) * 4u),
-                   z_rs = fs3_pin((unsigned)(ZC > 0 ? q.z_rs : 0));
+    const pc_gptr a_base = pc_pin_global(q.a.ptr), o_base = pc_pin_global(q.out.ptr);
+    const unsigned a_bs = pc_pinned((unsigned)q.a.bstride), a_cs = pc_pinned((unsigned)q.a.cstride * 4u), a_rs = pc_pinned((unsigned)q.a.rstride);
+    const unsigned o_bs = pc_pinned((unsigned)q.out.bstride), o_cs = pc_pinned((unsigned)q.out.cstride), o_rs = pc_pinned((unsigned)q.out.rstride);
+    const pc_gptr z_base = pc_pin_global(ZC > 0 ? (const void*)q.z : (const void*)q.a.ptr);
+    const unsigned z_bs = pc_pinned((unsigned)(ZC > 0 ? q.z_bs : 0)), z_cs = pc_pinned((unsigned)(ZC > 0 ? q.z_cs : 0) * 4u),
+                   z_rs = pc_pinned((unsigned)(ZC > 0 ? q.z_rs : 0));
     const bool has_po = EPI == EPI_POOL && q.pool_out.ptr != nullptr;
-    const fs3_gptr po_base = fs3_pin_global(has_po ? (const void*)q.pool_out.ptr : (const void*)q.out.ptr);
-    const unsigned po_bs = fs3_pin((unsigned)(has_po ? q.pool_out.bstride : 0)), po_cs = fs3_pin((unsigned)(has_po ? q.pool_out.cstride : 0)),
-                   po_rs = fs3_pin((unsigned)(has_po ? q.pool_out.rstride : 0));
-    const int H = fs3_pin(p.H), W = fs3_pin(p.W), relu = fs3_pin(p.relu);
+    const pc_gptr po_base = pc_pin_global(has_po ? (const void*)q.pool_out.ptr : (const void*)q.out.ptr);
+    const unsigned po_bs = pc_pinned((unsigned)(has_po ? q.pool_out.bstride : 0)), po_cs = pc_pinned((unsigned)(has_po ? q.pool_out.cstride : 0)),
+                   po_rs = pc_pinned((unsigned)(has_po ? q.pool_out.rstride : 0));
+    const int H = pc_pinned(p.H), W = pc_pinned(p.W), relu = pc_pinned(p.relu);
     // ablation switches (pc_debug_conv; tools/time_conv_fwd.py --ablate) exist in -DPOPCORN_CONV_ABLATE builds only (tools/build_variant.sh): as
     // run-time flags they made the commit conditional, and a path that may skip it leaves its loads pending -- the compiler then waits
     // vmcnt(0) before it re-uses their registers for the next prefetch, i.e. behind the epilogue's stores
 #ifdef POPCORN_CONV_ABLATE
-    const int dbg = fs3_pin(p.dbg);
+    const int dbg = pc_pinned(p.dbg);
 #else
     constexpr int dbg = 0;
 #endif
     // EPI_DOT: problems with dot_w write sum_co dot_w[co] * out[co] (the partial logit of the 1x1 out-conv that follows) instead of the map
     const bool has_dot = EPI == EPI_DOT && q.dot_w != nullptr;
-    const fs3_gptr d_base = fs3_pin_global(has_dot ? (const void*)q.dot_out.ptr : (const void*)q.out.ptr);
-    const unsigned d_bs = fs3_pin((unsigned)(has_dot ? q.dot_out.bstride : 0)), d_rs = fs3_pin((unsigned)(has_dot ? q.dot_out.rstride : 0));
+    const pc_gptr d_base = pc_pin_global(has_dot ? (const void*)q.dot_out.ptr : (const void*)q.out.ptr);
+    const unsigned d_bs = pc_pinned((unsigned)(has_dot ? q.dot_out.bstride : 0)), d_rs = pc_pinned((unsigned)(has_dot ? q.dot_out.rstride : 0));
     float dot_wl = 0.f;
     if constexpr (EPI == EPI_DOT) {
         if (has_dot) dot_wl = q.dot_w[col];
@@ -122,7 +106,7 @@ __global__ __launch_bounds__(256, (FS3Cfg<CI, CO, ZC>::WAVES_PER_SIMD)) void con
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const int sl = 4 * l_seg + e - 3;
-        c_sl[e] = (l_act && sl >= 0 && sl <= 33) ? l_r * BSL + (P2 ? fs3_sl_p2(sl) : fs3_sl(sl)) : Cfg::DUMMY;
+        c_sl[e] = (l_act && sl >= 0 && sl <= 33) ? l_r * BSL + (P2 ? fs3_sl_p2(sl) : pc_strip_slot(sl)) : Cfg::DUMMY;
         const int t = 4 * z_s + e - 3;
         cz_sl[e] = (z_act && t >= 0 && t <= 17) ? z_r * ZSL + t : Cfg::DUMMY;
     }
@@ -134,14 +118,14 @@ __global__ __launch_bounds__(256, (FS3Cfg<CI, CO, ZC>::WAVES_PER_SIMD)) void con
             rvalid = ok;
             const unsigned off = ok ? ((unsigned)b * a_bs + (unsigned)y * a_rs + (unsigned)xg) * 4u : 0u;
 #pragma unroll
-            for (int it = 0; it < 8; ++it) R[it] = *(fs3_gld4)(a_base + (size_t)((ch * 8 + it) * a_cs) + off);
+            for (int it = 0; it < 8; ++it) R[it] = *(pc_gld4)(a_base + (size_t)((ch * 8 + it) * a_cs) + off);
         } else {
             const int I = (y0 >> 1) - 1 + z_r, c = (x0 >> 1) - 4 + 4 * z_s;
             const bool ok = z_act && (unsigned)I < (unsigned)(H >> 1) && c >= 0 && c < (W >> 1);     // (W / 2) % 4 == 0: whole segments
             rvalid = ok;
             const unsigned off = ok ? ((unsigned)b * z_bs + (unsigned)I * z_rs + (unsigned)c) * 4u : 0u;
 #pragma unroll
-            for (int it = 0; it < 8; ++it) R[it] = *(fs3_gld4)(z_base + (size_t)(((ch - NCH) * 8 + it) * z_cs) + off);
+            for (int it = 0; it < 8; ++it) R[it] = *(pc_gld4)(z_base + (size_t)(((ch - NCH) * 8 + it) * z_cs) + off);
         }
     };
     // split + transpose while staging: the 8 channels of a pixel = one 16-byte slot per plane
@@ -171,15 +155,10 @@ __global__ __launch_bounds__(256, (FS3Cfg<CI, CO, ZC>::WAVES_PER_SIMD)) void con
             d[2 * (IMG / 16)] = q3;
         }
     };
-    const int gdim = fs3_pin((int)gridDim.x), ntl = fs3_pin(p.ntiles);
+    const int gdim = pc_pinned((int)gridDim.x), ntl = pc_pinned(p.ntiles);
     const int my_tiles = ntl > (int)blockIdx.x ? (ntl - 1 - (int)blockIdx.x) / gdim + 1 : 0;
     auto strip_coords = [&](int k, int& b, int& y0, int& x0) {
-        const int tile = pc_xcd_remap(blockIdx.x + k * gdim, ntl);
-        b = (int)pc_div((uint32_t)tile, p.div_tpi);
-        const int rem = tile - b * p.tiles_x * p.tiles_y;
-        const int ty = (int)pc_div((uint32_t)rem, p.div_tx);
-        x0 = (rem - ty * p.tiles_x) * TW;
-        y0 = ty * TH + 4 * wave;
+        pc_strip_coords<TW, TH>(blockIdx.x + k * gdim, &ntl, &p.tiles_x, &p.tiles_y, &p.div_tpi, &p.div_tx, wave, b, y0, x0);
     };
     int b = 0, y0 = 0, x0 = 0;
     if (my_tiles > 0) {
@@ -220,19 +199,13 @@ __global__ __launch_bounds__(256, (FS3Cfg<CI, CO, ZC>::WAVES_PER_SIMD)) void con
 #pragma unroll
         for (int k = 0; k < 9; ++k) zb[k] = q.tb[col * 9 + k];
     }
-    auto split3 = [](float w, unsigned short& h1, unsigned short& h2, unsigned short& h3) {
-        const float a1 = pc_bf16r(w), r1 = w - a1, a2 = pc_bf16r(r1), a3 = r1 - a2;
-        h1 = (unsigned short)(__float_as_uint(a1) >> 16);
-        h2 = (unsigned short)(__float_as_uint(a2) >> 16);
-        h3 = pc_f2bf(a3);
-    };
 #pragma unroll
     for (int k = 0; k < NWR; ++k) {
         const int e = tid + k * 256;
         if (e < CO * CI * 9) {
             const int tap = e % 9, ci = (e / 9) % CI, co = e / (9 * CI);
             const int o = (tap / 3) * BW_DYS + co * BW_CO + (ci / 8) * 24 + (tap % 3) * 8 + (ci % 8);
-            split3(wreg[k], w2h[o], w2h[WPL + o], w2h[2 * WPL + o]);
+            pc_split3(wreg[k], w2h[o], w2h[WPL + o], w2h[2 * WPL + o]);
         }
     }
     if constexpr (ZC > 0) {
@@ -242,7 +215,7 @@ __global__ __launch_bounds__(256, (FS3Cfg<CI, CO, ZC>::WAVES_PER_SIMD)) void con
             const int ln = r / 24, k24 = r - ln * 24, m = k24 >> 2, tjj = k24 & 3;
             const int qs = 4 * m + (ln >> 4), zci = qs / 3, v = qs - 3 * zci;
             const int o = (v * 16 + (ln & 15)) * ZW_N + zc * 32 + tjj * 8 + zci;
-            split3(wzreg[k], wzh[o], wzh[ZPL + o], wzh[2 * ZPL + o]);
+            pc_split3(wzreg[k], wzh[o], wzh[ZPL + o], wzh[2 * ZPL + o]);
         }
     }
     // folded BN (pc_bn_fold): scale = gamma / sqrt(var + eps); shift = (bias - mean) * scale + beta
@@ -297,7 +270,7 @@ __global__ __launch_bounds__(256, (FS3Cfg<CI, CO, ZC>::WAVES_PER_SIMD)) void con
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-        for (int h = 0; h < 2; ++h) dg_sl[dx][h] = fs3_sl(li + dx + 16 * h);
+        for (int h = 0; h < 2; ++h) dg_sl[dx][h] = pc_strip_slot(li + dx + 16 * h);
 #pragma unroll
     for (int t = 0; t < 4; ++t) p2_sl[t] = fs3_sl_p2(2 * li + t);
 
@@ -326,14 +299,14 @@ __global__ __launch_bounds__(256, (FS3Cfg<CI, CO, ZC>::WAVES_PER_SIMD)) void con
                         for (int u = 0; u < 4; ++u) av[pl][u] = __builtin_bit_cast(bf16x8, lrow[(u >> 1) * 2 * BSL + dg_sl[dx][u & 1]]);
                     }
 #pragma unroll
-                    for (int pw = 2; pw >= 0; --pw)           // weight split index; pixel split indices 2 - pw .. 0: smallest products first
+                    for (int i = 0; i < PC_SPLIT_PRODUCTS; ++i) {        // (weight plane, pixel plane), smallest products first
+                        const pc_split_product s = pc_split_product_at(i);
 #pragma unroll
-                        for (int pa = 2 - pw; pa >= 0; --pa)
+                        for (int u = 0; u < 4; ++u)
 #pragma unroll
-                            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                                for (int nb = 0; nb < NB; ++nb)
-                                    acc[u][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[pa][u], wq[pw][dx][nb], acc[u][nb], 0, 0, 0);
+                            for (int nb = 0; nb < NB; ++nb)
+                                acc[u][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[s.pa][u], wq[s.pw][dx][nb], acc[u][nb], 0, 0, 0);
+                    }
                 }
             } else {
 #pragma unroll
@@ -346,14 +319,14 @@ __global__ __launch_bounds__(256, (FS3Cfg<CI, CO, ZC>::WAVES_PER_SIMD)) void con
                         for (int t = 0; t < 4; ++t) av[pl][t] = __builtin_bit_cast(bf16x8, lrow[p2_sl[t]]);
                     }
 #pragma unroll
-                    for (int pw = 2; pw >= 0; --pw)
+                    for (int i = 0; i < PC_SPLIT_PRODUCTS; ++i) {
+                        const pc_split_product s = pc_split_product_at(i);
 #pragma unroll
-                        for (int pa = 2 - pw; pa >= 0; --pa)
+                        for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
-                            for (int dx = 0; dx < 3; ++dx)
-#pragma unroll
-                                for (int j = 0; j < 2; ++j)
-                                    acc[rp * 2 + j][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[pa][j + dx], wq[pw][dx][0], acc[rp * 2 + j][0], 0, 0, 0);
+                            for (int j = 0; j < 2; ++j)
+                                acc[rp * 2 + j][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[s.pa][j + dx], wq[s.pw][dx][0], acc[rp * 2 + j][0], 0, 0, 0);
+                    }
                 }
             }
         } else {
@@ -379,14 +352,14 @@ __global__ __launch_bounds__(256, (FS3Cfg<CI, CO, ZC>::WAVES_PER_SIMD)) void con
                     for (int t = 0; t < 3; ++t) zv[pl][t] = __builtin_bit_cast(bf16x8, lrow[t]);
                 }
 #pragma unroll
-                for (int pw = 2; pw >= 0; --pw)
+                for (int i = 0; i < PC_SPLIT_PRODUCTS; ++i) {
+                    const pc_split_product s = pc_split_product_at(i);
 #pragma unroll
-                    for (int pa = 2 - pw; pa >= 0; --pa)
+                    for (int tj = 0; tj < 2; ++tj)
 #pragma unroll
-                        for (int tj = 0; tj < 2; ++tj)
-#pragma unroll
-                            for (int j = 0; j < 2; ++j)
-                                acc[rp * 2 + j][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(zv[pa][tj + j], wz[pw][2 * tj + j], acc[rp * 2 + j][0], 0, 0, 0);
+                        for (int j = 0; j < 2; ++j)
+                            acc[rp * 2 + j][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(zv[s.pa][tj + j], wz[s.pw][2 * tj + j], acc[rp * 2 + j][0], 0, 0, 0);
+                }
             }
         }
     };
@@ -453,12 +426,12 @@ __global__ __launch_bounds__(256, (FS3Cfg<CI, CO, ZC>::WAVES_PER_SIMD)) void con
                         f32x4 t;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) t[r] = pc_sum8(__fmul_rn(v[r], dot_wl));      // (rounded product: no fma contraction into the first step)
-                        if (in && col == 0) *(fs3_gst4)(d_base + (size_t)(((unsigned)eb * d_bs + (unsigned)y * d_rs + (unsigned)x) * 4u)) = t;
+                        if (in && col == 0) *(pc_gst4)(d_base + (size_t)(((unsigned)eb * d_bs + (unsigned)y * d_rs + (unsigned)x) * 4u)) = t;
                         continue;
                     }
                 }
                 if (in)
-                    *(fs3_gst4)(o_base + (size_t)(((unsigned)eb * o_bs + (unsigned)(nb * 8 + col) * o_cs + (unsigned)y * o_rs + (unsigned)x) * 4u)) = v;
+                    *(pc_gst4)(o_base + (size_t)(((unsigned)eb * o_bs + (unsigned)(nb * 8 + col) * o_cs + (unsigned)y * o_rs + (unsigned)x) * 4u)) = v;
                 if constexpr (EPI == EPI_POOL) {
                     // MaxPool2d(2) (full strips only: pool_out_geometry_ok): the x pairs are in the lane, the row pair (s_row 0 / 1) sits 8 lanes apart
                     if (has_po) {
@@ -466,8 +439,8 @@ __global__ __launch_bounds__(256, (FS3Cfg<CI, CO, ZC>::WAVES_PER_SIMD)) void con
                         m0 = fmaxf(m0, pc_lane_xor8(m0));
                         m1 = fmaxf(m1, pc_lane_xor8(m1));
                         if (s_row == 0)
-                            *(fs3_gst2)(po_base + (size_t)(((unsigned)eb * po_bs + (unsigned)(nb * 8 + col) * po_cs + (unsigned)(y >> 1) * po_rs +
-                                                             (unsigned)(x >> 1)) * 4u)) = fs3_f32x2{m0, m1};
+                            *(pc_gst2)(po_base + (size_t)(((unsigned)eb * po_bs + (unsigned)(nb * 8 + col) * po_cs + (unsigned)(y >> 1) * po_rs +
+                                                             (unsigned)(x >> 1)) * 4u)) = f32x2{m0, m1};
                     }
                 }
             }

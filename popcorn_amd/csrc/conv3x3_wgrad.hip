@@ -19,9 +19,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
-
 constexpr int TW = 32, TH = 16;
 constexpr int IN_RS = 40;                    // == 8 mod 32: the 4 input rows v of a k-step land 8 banks apart
 constexpr int IN_CS = 18 * IN_RS + 20;       // 740 == 4 mod 32: the (at most) two channels of an N-block interleave
@@ -89,11 +86,8 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_kernel(const WgradArgs p) {
     }
 
     for (int t = blockIdx.x; t < p.ntiles; t += gridDim.x) {
-        const int tile = pc_xcd_remap(t, p.ntiles);
-        const int b = (int)pc_div((uint32_t)tile, p.div_tpi);
-        const int rem = tile - b * p.tiles_x * p.tiles_y;
-        const int ty = (int)pc_div((uint32_t)rem, p.div_tx);
-        const int x0 = (rem - ty * p.tiles_x) * TW, y0 = ty * TH;
+        int b, y0, x0;                                   // the whole tile: strip 0
+        pc_strip_coords<TW, TH>(t, &p.ntiles, &p.tiles_x, &p.tiles_y, &p.div_tpi, &p.div_tx, 0, b, y0, x0);
         __syncthreads();
         pc_load_halo_tile<CINC, IN_RS, IN_CS, IN_COL0, true>(lin, p.a, p.b, p.fast_a, p.fast_b, cbase, b, y0, x0, p.H, p.W, tid);
         // gradient tile: COUT x 16 rows x 32 cols, no halo; 8 lanes x float4 per row
@@ -315,12 +309,7 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_wave_kernel(const WgradGrou
 
     const int my_tiles = p.ntiles > (int)blockIdx.x ? (p.ntiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
     auto strip_coords = [&](int k, int& b, int& y0, int& x0) {
-        const int tile = pc_xcd_remap(blockIdx.x + k * gridDim.x, p.ntiles);
-        b = (int)pc_div((uint32_t)tile, p.div_tpi);
-        const int rem = tile - b * p.tiles_x * p.tiles_y;
-        const int ty = (int)pc_div((uint32_t)rem, p.div_tx);
-        x0 = (rem - ty * p.tiles_x) * TW;
-        y0 = ty * TH + 4 * wave;
+        pc_strip_coords<TW, TH>(blockIdx.x + k * gridDim.x, &p.ntiles, &p.tiles_x, &p.tiles_y, &p.div_tpi, &p.div_tx, wave, b, y0, x0);
     };
     int b = 0, y0 = 0, x0 = 0;
     if (my_tiles > 0) {
@@ -423,18 +412,9 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_wave_kernel(const WgradGrou
 // channels) use channel slots 0..3 of one block.
 constexpr int CLW_IN_RS = 52, CLW_G_RS = 36;        // slots per strip row
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ s16x4 clw_tr(const unsigned char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-__device__ __forceinline__ bf16x8 clw_pair(s16x4 a, s16x4 b) {
-    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-__device__ __forceinline__ u32x4w clw_swz(u32x4w v, bool sw) { return sw ? u32x4w{v[2], v[3], v[0], v[1]} : v; }
-__device__ __forceinline__ u32x4w clw_max8(u32x4w a, u32x4w b) {
-    u32x4w o;
+__device__ __forceinline__ u32x4 clw_swz(u32x4 v, bool sw) { return sw ? u32x4{v[2], v[3], v[0], v[1]} : v; }
+__device__ __forceinline__ u32x4 clw_max8(u32x4 a, u32x4 b) {
+    u32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         const float lo = fmaxf(__uint_as_float(a[e] << 16), __uint_as_float(b[e] << 16));
@@ -482,9 +462,9 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_cl_kernel(const WgradGroup 
         i_px[i] = id - i_r[i] * 34;
     }
     const int CA = p.a.C;
-    u32x4w R[NCH][LD == 2 ? 16 : 4];
+    u32x4 R[NCH][LD == 2 ? 16 : 4];
     f32x4 RF[LD == 3 ? NIT : 1];
-    u32x4w G[2 * MB];
+    u32x4 G[2 * MB];
     unsigned rvalid = 0, gvalid = 0;
     const int r_r = lane / 10, r_seg = lane - r_r * 10;
     const pc_bf16_t* const g_ptr = reinterpret_cast<const pc_bf16_t*>(p.g.ptr);
@@ -509,14 +489,14 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_cl_kernel(const WgradGroup 
                         const int ys = y - s.oy, xq = x - s.ox;
                         ok = ok && (unsigned)ys < (unsigned)s.H && (unsigned)xq < (unsigned)s.W;
                         const int64_t off = ok ? (int64_t)ys * s.rstride + (int64_t)xq * s.xstride : 0;
-                        R[c][i] = *reinterpret_cast<const u32x4w*>(base + off);
+                        R[c][i] = *reinterpret_cast<const u32x4*>(base + off);
                     } else {
                         const int64_t off = ok ? (int64_t)(2 * y) * s.rstride + (int64_t)(2 * x) * s.xstride : 0;
                         const int rs1 = ok ? s.rstride : 0, xs1 = ok ? s.xstride : 0;
-                        R[c][4 * i + 0] = *reinterpret_cast<const u32x4w*>(base + off);
-                        R[c][4 * i + 1] = *reinterpret_cast<const u32x4w*>(base + off + xs1);
-                        R[c][4 * i + 2] = *reinterpret_cast<const u32x4w*>(base + off + rs1);
-                        R[c][4 * i + 3] = *reinterpret_cast<const u32x4w*>(base + off + rs1 + xs1);
+                        R[c][4 * i + 0] = *reinterpret_cast<const u32x4*>(base + off);
+                        R[c][4 * i + 1] = *reinterpret_cast<const u32x4*>(base + off + xs1);
+                        R[c][4 * i + 2] = *reinterpret_cast<const u32x4*>(base + off + rs1);
+                        R[c][4 * i + 3] = *reinterpret_cast<const u32x4*>(base + off + rs1 + xs1);
                     }
                     vm |= (ok ? 1u : 0u) << (4 * c + i);
                 }
@@ -531,7 +511,7 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_cl_kernel(const WgradGroup 
             const int y = y0 + r, x = x0 + px;
             const bool ok = y < p.H && x < p.W;
             const int64_t off = ok ? b * p.g.bstride + (int64_t)y * p.g.rstride + (int64_t)x * p.g.xstride + 8 * mb : 0;
-            G[i] = *reinterpret_cast<const u32x4w*>(g_ptr + off);
+            G[i] = *reinterpret_cast<const u32x4*>(g_ptr + off);
             gm |= (ok ? 1u : 0u) << i;
         }
         gvalid = gm;
@@ -543,11 +523,11 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_cl_kernel(const WgradGroup 
                 for (int e = 0; e < 4; ++e) {
                     const int pi = 4 * r_seg - 3 + e;          // pixel x0 - 4 + 4 * seg + e  ->  strip pixel index (x0 - 1 = 0)
                     if (pi >= 0 && pi < 34) {
-                        u32x4w t = u32x4w{0u, 0u, 0u, 0u};
+                        u32x4 t = u32x4{0u, 0u, 0u, 0u};
 #pragma unroll
                         for (int h = 0; h < (NIT + 1) / 2; ++h)
                             t[h] = pc_pack_bf16(RF[2 * h][e], 2 * h + 1 < NIT ? RF[(2 * h + 1) % NIT][e] : 0.f);
-                        *reinterpret_cast<u32x4w*>(win + (r_r * CLW_IN_RS + pi) * 16) = clw_swz(t, (pi >> 3) & 1);
+                        *reinterpret_cast<u32x4*>(win + (r_r * CLW_IN_RS + pi) * 16) = clw_swz(t, (pi >> 3) & 1);
                     }
                 }
             }
@@ -557,11 +537,11 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_cl_kernel(const WgradGroup 
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     if (lane + 64 * i < 204) {
-                        u32x4w v;
+                        u32x4 v;
                         if constexpr (LD == 2) v = clw_max8(clw_max8(R[c][4 * i], R[c][4 * i + 1]), clw_max8(R[c][4 * i + 2], R[c][4 * i + 3]));
                         else v = R[c][i];
-                        if (!((rvalid >> (4 * c + i)) & 1u)) v = u32x4w{0u, 0u, 0u, 0u};
-                        *reinterpret_cast<u32x4w*>(win + c * Cl::IN_B + (i_r[i] * CLW_IN_RS + i_px[i]) * 16) = clw_swz(v, (i_px[i] >> 3) & 1);
+                        if (!((rvalid >> (4 * c + i)) & 1u)) v = u32x4{0u, 0u, 0u, 0u};
+                        *reinterpret_cast<u32x4*>(win + c * Cl::IN_B + (i_r[i] * CLW_IN_RS + i_px[i]) * 16) = clw_swz(v, (i_px[i] >> 3) & 1);
                     }
                 }
         }
@@ -569,8 +549,8 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_cl_kernel(const WgradGroup 
         for (int i = 0; i < 2 * MB; ++i) {
             const int id = lane + 64 * i;
             const int mb = id >> 7, r = (id >> 5) & 3, px = id & 31;
-            const u32x4w v = ((gvalid >> i) & 1u) ? G[i] : u32x4w{0u, 0u, 0u, 0u};
-            *reinterpret_cast<u32x4w*>(wg + mb * Cl::G_B + (r * CLW_G_RS + px) * 16) = clw_swz(v, (px >> 3) & 1);
+            const u32x4 v = ((gvalid >> i) & 1u) ? G[i] : u32x4{0u, 0u, 0u, 0u};
+            *reinterpret_cast<u32x4*>(wg + mb * Cl::G_B + (r * CLW_G_RS + px) * 16) = clw_swz(v, (px >> 3) & 1);
         }
     };
 
@@ -592,12 +572,7 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_cl_kernel(const WgradGroup 
 
     const int my_tiles = p.ntiles > (int)blockIdx.x ? (p.ntiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
     auto strip_coords = [&](int k, int& b, int& y0, int& x0) {
-        const int tile = pc_xcd_remap(blockIdx.x + k * gridDim.x, p.ntiles);
-        b = (int)pc_div((uint32_t)tile, p.div_tpi);
-        const int rem = tile - b * p.tiles_x * p.tiles_y;
-        const int ty = (int)pc_div((uint32_t)rem, p.div_tx);
-        x0 = (rem - ty * p.tiles_x) * TW;
-        y0 = ty * TH + 4 * wave;
+        pc_strip_coords<TW, TH>(blockIdx.x + k * gridDim.x, &p.ntiles, &p.tiles_x, &p.tiles_y, &p.div_tpi, &p.div_tx, wave, b, y0, x0);
     };
     int b = 0, y0 = 0, x0 = 0;
     if (my_tiles > 0) {
@@ -616,8 +591,8 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_cl_kernel(const WgradGroup 
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) {
                 const unsigned char* ga = wg + mb * Cl::G_B + 2 * rpi * CLW_G_RS * 16 + a_off;
-                const s16x4 lo = clw_tr(ga), hi = clw_tr(ga + 4 * 16);
-                av[mb] = clw_pair(lo, hi);
+                const s16x4 lo = pc_lds_tr16(ga), hi = pc_lds_tr16(ga + 4 * 16);
+                av[mb] = pc_tr_pair(lo, hi);
                 float t = 0.f;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) t += __uint_as_float((unsigned)(unsigned short)lo[e] << 16) + __uint_as_float((unsigned)(unsigned short)hi[e] << 16);
@@ -630,9 +605,9 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_cl_kernel(const WgradGroup 
                     // pixel index of read e: 8 * lk + 4 * e + j + dx  (the swizzle bit is bit 3 of THAT index)
                     const int p0 = 8 * lk + t_j + dx, p1 = p0 + 4;
                     const unsigned char* ib = win + (nb >> 1) * Cl::IN_B + (2 * rpi * CLW_IN_RS + b_row) * 16;
-                    const s16x4 lo = clw_tr(ib + p0 * 16 + 8 * ((nb & 1) ^ ((p0 >> 3) & 1)));
-                    const s16x4 hi = clw_tr(ib + p1 * 16 + 8 * ((nb & 1) ^ ((p1 >> 3) & 1)));
-                    const bf16x8 bv = clw_pair(lo, hi);
+                    const s16x4 lo = pc_lds_tr16(ib + p0 * 16 + 8 * ((nb & 1) ^ ((p0 >> 3) & 1)));
+                    const s16x4 hi = pc_lds_tr16(ib + p1 * 16 + 8 * ((nb & 1) ^ ((p1 >> 3) & 1)));
+                    const bf16x8 bv = pc_tr_pair(lo, hi);
 #pragma unroll
                     for (int mb = 0; mb < MB; ++mb)
                         acc[mb][dx * NBP + nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[mb], bv, acc[mb][dx * NBP + nb], 0, 0, 0);

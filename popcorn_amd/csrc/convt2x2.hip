@@ -192,11 +192,6 @@ struct CtWgradCfg {
 //           A = w[ci][co][a][b] (M = ci); v_mfma_f32_16x16x32_bf16 per 8 output channels
 //   wgrad : contraction over pixels -> both operands are transposed through the wave's LDS region with ds_read_b64_tr_b16
 //           (see conv3x3_wgrad.hip): group = 32 input pixels of a row and their 2 x 64 gradient pixels
-typedef short ct_s4 __attribute__((ext_vector_type(4)));
-typedef short ct_s8 __attribute__((ext_vector_type(8)));
-typedef __bf16 ct_bf8 __attribute__((ext_vector_type(8)));
-typedef unsigned ct_u4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ short ct_bf(float x) { return (short)pc_f2bf(x); }
 template <int C>
 __global__ __launch_bounds__(256) void convt2x2_fwd_cl_kernel(const CtGroup grp_) {
@@ -208,7 +203,7 @@ __global__ __launch_bounds__(256) void convt2x2_fwd_cl_kernel(const CtGroup grp_
     const int gwave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * blockDim.x) >> 6;
     // A fragments: lane (m = li, k-group lk): ci = 4*lk + e
-    ct_s4 aw[NT];
+    s16x4 aw[NT];
     float binit[NT][4];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
@@ -235,7 +230,7 @@ __global__ __launch_bounds__(256) void convt2x2_fwd_cl_kernel(const CtGroup grp_
         const bool ok = j < p.W;
         const bool kok = ok && 4 * lk < C;
         const uint2 xv = *reinterpret_cast<const uint2*>(xb + b * p.x.bstride + (int64_t)i * p.x.rstride + (kok ? (int64_t)j * p.x.xstride + 4 * lk : 0));
-        ct_s4 bv;
+        s16x4 bv;
         bv[0] = kok ? (short)(xv.x & 0xffffu) : (short)0; bv[1] = kok ? (short)(xv.x >> 16) : (short)0;
         bv[2] = kok ? (short)(xv.y & 0xffffu) : (short)0; bv[3] = kok ? (short)(xv.y >> 16) : (short)0;
 #pragma unroll
@@ -258,13 +253,13 @@ __global__ __launch_bounds__(256) void convt2x2_dgrad_cl_kernel(const CtGroup gr
     const int gwave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const int nwaves = (gridDim.x * blockDim.x) >> 6;
     // A fragments: lane (m = ci = li, k-group lk = (a, b)): slots e = co 8*h + e
-    ct_bf8 aw[NH];
+    bf16x8 aw[NH];
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
-        ct_s8 t;
+        s16x8 t;
 #pragma unroll
         for (int e = 0; e < 8; ++e) t[e] = li < C ? ct_bf(p.w[(li * C + 8 * h + e) * 4 + lk]) : (short)0;
-        aw[h] = __builtin_bit_cast(ct_bf8, t);
+        aw[h] = __builtin_bit_cast(bf16x8, t);
     }
     // D rows of this lane: ci = 4*lk + r
     float e_scale[4];
@@ -287,9 +282,9 @@ __global__ __launch_bounds__(256) void convt2x2_dgrad_cl_kernel(const CtGroup gr
         f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
-            ct_u4 gv = *reinterpret_cast<const ct_u4*>(gp + 8 * h);
-            if (!ok) gv = ct_u4{0u, 0u, 0u, 0u};
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aw[h], __builtin_bit_cast(ct_bf8, gv), acc, 0, 0, 0);
+            u32x4 gv = *reinterpret_cast<const u32x4*>(gp + 8 * h);
+            if (!ok) gv = u32x4{0u, 0u, 0u, 0u};
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aw[h], __builtin_bit_cast(bf16x8, gv), acc, 0, 0, 0);
         }
         if (ok && 4 * lk < C) {
             if (ab) {
@@ -300,10 +295,6 @@ __global__ __launch_bounds__(256) void convt2x2_dgrad_cl_kernel(const CtGroup gr
             pc_st4(ob + b * p.out.bstride + (int64_t)i * p.out.rstride + (int64_t)j * p.out.xstride + 4 * lk, acc);
         }
     }
-}
-
-__device__ __forceinline__ ct_s4 ct_tr(const unsigned char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) ct_s4*)(p));
 }
 
 // group = 32 consecutive input pixels of one row.  LDS per wave: x [32 px][C] and g [2 rows][64 px][C] (bf16), plain copies.
@@ -333,15 +324,15 @@ __global__ __launch_bounds__(256) void convt2x2_wgrad_cl_kernel(const CtGroup gr
 #pragma unroll
     for (int t = 0; t < NT; ++t) { acc[t] = f32x4{0.f, 0.f, 0.f, 0.f}; bsum[t] = 0.f; }
     constexpr int NH = C / 8;
-    ct_bf8 aw[DG ? NH : 1];
+    bf16x8 aw[DG ? NH : 1];
     float e_scale[4] = {1.f, 1.f, 1.f, 1.f};
     if constexpr (DG) {
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
-            ct_s8 t;
+            s16x8 t;
 #pragma unroll
             for (int e = 0; e < 8; ++e) t[e] = li < C ? ct_bf(p.w[(li * C + 8 * h + e) * 4 + lk]) : (short)0;
-            aw[h] = __builtin_bit_cast(ct_bf8, t);
+            aw[h] = __builtin_bit_cast(bf16x8, t);
         }
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -351,7 +342,7 @@ __global__ __launch_bounds__(256) void convt2x2_wgrad_cl_kernel(const CtGroup gr
     }
     constexpr int NXP = XB / 16 / 64 > 0 ? XB / 16 / 64 : 1;       // 16-byte pieces per lane: x (32 or 64 pieces), g (128 or 256)
     constexpr int NGP = GB / 16 / 64;
-    ct_u4 RX[NXP], RG[NGP];
+    u32x4 RX[NXP], RG[NGP];
     const pc_bf16_t* const xb = reinterpret_cast<const pc_bf16_t*>(p.x.ptr);
     const pc_bf16_t* const gb = reinterpret_cast<const pc_bf16_t*>(p.g.ptr);
     auto issue = [&](int grp) {
@@ -363,8 +354,8 @@ __global__ __launch_bounds__(256) void convt2x2_wgrad_cl_kernel(const CtGroup gr
             const int id = lane + 64 * k;                    // piece = (pixel, 8-channel half)
             const int px = id / (C / 8), hf = id % (C / 8);
             const bool ok = id < 32 * (C / 8) && j0 + px < p.W;
-            RX[k] = *reinterpret_cast<const ct_u4*>(xb + b * p.x.bstride + (int64_t)i * p.x.rstride + (ok ? (int64_t)(j0 + px) * p.x.xstride + 8 * hf : 0));
-            if (!ok) RX[k] = ct_u4{0u, 0u, 0u, 0u};
+            RX[k] = *reinterpret_cast<const u32x4*>(xb + b * p.x.bstride + (int64_t)i * p.x.rstride + (ok ? (int64_t)(j0 + px) * p.x.xstride + 8 * hf : 0));
+            if (!ok) RX[k] = u32x4{0u, 0u, 0u, 0u};
         }
 #pragma unroll
         for (int k = 0; k < NGP; ++k) {
@@ -372,16 +363,16 @@ __global__ __launch_bounds__(256) void convt2x2_wgrad_cl_kernel(const CtGroup gr
             const int a = id / (64 * (C / 8)), r2 = id % (64 * (C / 8));
             const int px = r2 / (C / 8), hf = r2 % (C / 8);
             const bool ok = 2 * j0 + px < 2 * p.W;
-            RG[k] = *reinterpret_cast<const ct_u4*>(gb + b * p.g.bstride + (int64_t)(2 * i + a) * p.g.rstride + (ok ? (int64_t)(2 * j0 + px) * p.g.xstride + 8 * hf : 0));
-            if (!ok) RG[k] = ct_u4{0u, 0u, 0u, 0u};
+            RG[k] = *reinterpret_cast<const u32x4*>(gb + b * p.g.bstride + (int64_t)(2 * i + a) * p.g.rstride + (ok ? (int64_t)(2 * j0 + px) * p.g.xstride + 8 * hf : 0));
+            if (!ok) RG[k] = u32x4{0u, 0u, 0u, 0u};
         }
     };
     auto commit = [&]() {
 #pragma unroll
         for (int k = 0; k < NXP; ++k)
-            if (lane + 64 * k < 32 * (C / 8)) *reinterpret_cast<ct_u4*>(wx + (lane + 64 * k) * 16) = RX[k];
+            if (lane + 64 * k < 32 * (C / 8)) *reinterpret_cast<u32x4*>(wx + (lane + 64 * k) * 16) = RX[k];
 #pragma unroll
-        for (int k = 0; k < NGP; ++k) *reinterpret_cast<ct_u4*>(wg + (lane + 64 * k) * 16) = RG[k];
+        for (int k = 0; k < NGP; ++k) *reinterpret_cast<u32x4*>(wg + (lane + 64 * k) * 16) = RG[k];
     };
     // transposing reads: lane supplies row jj = li >> 2 (pixel 8*lk + 4*e + jj) and column quad q = li & 3
     const int t_j = li >> 2, t_q = li & 3;
@@ -400,8 +391,8 @@ __global__ __launch_bounds__(256) void convt2x2_wgrad_cl_kernel(const CtGroup gr
                 f32x4 dacc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int h = 0; h < NH; ++h) {
-                    const ct_u4 gv = *reinterpret_cast<const ct_u4*>(wg + ((lk >> 1) * 64 + 2 * px + (lk & 1)) * PB + 16 * h);
-                    dacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aw[h], __builtin_bit_cast(ct_bf8, gv), dacc, 0, 0, 0);
+                    const u32x4 gv = *reinterpret_cast<const u32x4*>(wg + ((lk >> 1) * 64 + 2 * px + (lk & 1)) * PB + 16 * h);
+                    dacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aw[h], __builtin_bit_cast(bf16x8, gv), dacc, 0, 0, 0);
                 }
                 if (j0 + px < p.W && 4 * lk < C) {
                     if (p.act) {
@@ -416,20 +407,20 @@ __global__ __launch_bounds__(256) void convt2x2_wgrad_cl_kernel(const CtGroup gr
         }
         // A (M = ci): columns 4q .. 4q+3 of pixel j; for C = 8 the quads 2, 3 repeat 0, 1 (rows 8..15 of D are not used)
         const unsigned char* xa = wx + (8 * lk + t_j) * PB + 8 * (C == 8 ? (t_q & 1) : t_q);
-        const ct_s4 alo = ct_tr(xa), ahi = ct_tr(xa + 4 * PB);
-        const ct_bf8 av = __builtin_bit_cast(ct_bf8, __builtin_shufflevector(alo, ahi, 0, 1, 2, 3, 4, 5, 6, 7));
+        const s16x4 alo = pc_lds_tr16(xa), ahi = pc_lds_tr16(xa + 4 * PB);
+        const bf16x8 av = pc_tr_pair(alo, ahi);
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             // B (N tile t): C = 8: quad -> (b = q >> 1, channels 4*(q&1)..) of gradient row 2i + t; C = 16: (a, b) = t, channels 4q..
             const int a = C == 8 ? t : t >> 1;
             const int bq = C == 8 ? t_q >> 1 : t & 1, c4 = C == 8 ? 4 * (t_q & 1) : 4 * t_q;
             const unsigned char* gp = wg + (a * 64 + 2 * (8 * lk + t_j) + bq) * PB + 2 * c4;
-            const ct_s4 blo = ct_tr(gp), bhi = ct_tr(gp + 8 * PB);
+            const s16x4 blo = pc_lds_tr16(gp), bhi = pc_lds_tr16(gp + 8 * PB);
             float sb = 0.f;
 #pragma unroll
             for (int e = 0; e < 4; ++e) sb += __uint_as_float((unsigned)(unsigned short)blo[e] << 16) + __uint_as_float((unsigned)(unsigned short)bhi[e] << 16);
             bsum[t] += sb;
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(ct_bf8, __builtin_shufflevector(blo, bhi, 0, 1, 2, 3, 4, 5, 6, 7)), acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, pc_tr_pair(blo, bhi), acc[t], 0, 0, 0);
         }
     }
 

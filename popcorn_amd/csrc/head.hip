@@ -453,9 +453,6 @@ __device__ long long g_head_prof[2048 * 16];
 //       channels arrive packed, as the operand -- round 5; rounds 2-4 gathered channel 4*j + lk with four 2-byte loads and converted them
 //       to fp32 inside the prefetch, which made every prefetch wait for its own loads: profiles/r5_head_bwd_bf16_phases.json)
 //   32-pixel contraction (weight gradients):  slot (lk, j) -> pixel 8*lk + j of a pair of 16-pixel groups
-typedef __bf16 hbf16x8 __attribute__((ext_vector_type(8)));
-typedef short hs16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned hu32x4 __attribute__((ext_vector_type(4)));
 // LDS image (bytes): ready-made fragments, lane-linear
 constexpr int HB_A1 = 0;                          // [4 mb][64 lanes][4 bf16]   W0[16mb+i][4lk+j]
 constexpr int HB_A2 = HB_A1 + 4 * 64 * 8;         // [4 mb2][2 t][64][8 bf16]   W2[16mb2+i][unit(t,lk,j)]
@@ -500,13 +497,13 @@ __device__ __forceinline__ void head_stage_weights_bf16(unsigned char* lds, cons
     if (tid == 0) f[256] = p.b6[0];
 }
 
-__device__ __forceinline__ hbf16x8 hb_pack8(const f32x4& a, const f32x4& b) {
-    const hu32x4 q = {pc_pack_bf16(a[0], a[1]), pc_pack_bf16(a[2], a[3]), pc_pack_bf16(b[0], b[1]), pc_pack_bf16(b[2], b[3])};
-    return __builtin_bit_cast(hbf16x8, q);
+__device__ __forceinline__ bf16x8 hb_pack8(const f32x4& a, const f32x4& b) {
+    const u32x4 q = {pc_pack_bf16(a[0], a[1]), pc_pack_bf16(a[2], a[3]), pc_pack_bf16(b[0], b[1]), pc_pack_bf16(b[2], b[3])};
+    return __builtin_bit_cast(bf16x8, q);
 }
-__device__ __forceinline__ hs16x4 hb_pack4(float a, float b, float c, float d) {
+__device__ __forceinline__ s16x4 hb_pack4(float a, float b, float c, float d) {
     const uint2 q = make_uint2(pc_pack_bf16(a, b), pc_pack_bf16(c, d));
-    return __builtin_bit_cast(hs16x4, q);
+    return __builtin_bit_cast(s16x4, q);
 }
 // per 16-bit half: 0xffff where the bf16 is non-zero (packed min with 1, then 0 - x), and the AND of a packed vector with such a mask
 // (two VOP3P instructions per dword; written as asm because hipcc lowers the vector form to 16-bit compares + selects + perms)
@@ -516,26 +513,26 @@ __device__ __forceinline__ unsigned hb_nz32(unsigned x) {
     asm("v_pk_sub_u16 %0, 0, %1 op_sel_hi:[0,1]" : "=v"(r) : "v"(nz));
     return r;
 }
-__device__ __forceinline__ hu32x4 hb_nzmask(const hbf16x8& v) {
-    const hu32x4 q = __builtin_bit_cast(hu32x4, v);
-    return hu32x4{hb_nz32(q[0]), hb_nz32(q[1]), hb_nz32(q[2]), hb_nz32(q[3])};
+__device__ __forceinline__ u32x4 hb_nzmask(const bf16x8& v) {
+    const u32x4 q = __builtin_bit_cast(u32x4, v);
+    return u32x4{hb_nz32(q[0]), hb_nz32(q[1]), hb_nz32(q[2]), hb_nz32(q[3])};
 }
-__device__ __forceinline__ hbf16x8 hb_and(const hbf16x8& v, const hu32x4& m) {
-    return __builtin_bit_cast(hbf16x8, __builtin_bit_cast(hu32x4, v) & m);
+__device__ __forceinline__ bf16x8 hb_and(const bf16x8& v, const u32x4& m) {
+    return __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, v) & m);
 }
 // `lane` may carry an opaque zero (see the group loops): the fragment reads must stay INSIDE the loop -- hoisted, the 36 KB
 // of loop-invariant weight fragments would occupy ~150 registers per lane and spill the accumulators
-__device__ __forceinline__ hbf16x8 hb_frag8(const unsigned char* lds, int off, int blk, int t, int lane) {
-    return __builtin_bit_cast(hbf16x8, *reinterpret_cast<const hu32x4*>(lds + off + (blk * 2 + t) * 1024 + lane * 16));
+__device__ __forceinline__ bf16x8 hb_frag8(const unsigned char* lds, int off, int blk, int t, int lane) {
+    return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(lds + off + (blk * 2 + t) * 1024 + lane * 16));
 }
-__device__ __forceinline__ hs16x4 hb_frag4(const unsigned char* lds, int off, int blk, int lane) {
-    return __builtin_bit_cast(hs16x4, *reinterpret_cast<const uint2*>(lds + off + blk * 512 + lane * 8));
+__device__ __forceinline__ s16x4 hb_frag4(const unsigned char* lds, int off, int blk, int lane) {
+    return __builtin_bit_cast(s16x4, *reinterpret_cast<const uint2*>(lds + off + blk * 512 + lane * 8));
 }
 
 // one 64 -> 64 layer.  hb[t]: packed input (lane = pixel).  o1[mb2]: D = W . h (lane = pixel, regs = hidden 16*mb2 + 4*lk + r),
 // initialised with the bias.
 __device__ __forceinline__ void hb_layer64(const unsigned char* lds, int a_off, const float* bias, int lane, int lk,
-                                           const hbf16x8 (&hb)[2], f32x4 (&o1)[4]) {
+                                           const bf16x8 (&hb)[2], f32x4 (&o1)[4]) {
 #pragma unroll
     for (int mb2 = 0; mb2 < 4; ++mb2) {
         o1[mb2] = *reinterpret_cast<const f32x4*>(&bias[16 * mb2 + 4 * lk]);
@@ -618,7 +615,7 @@ __global__ __launch_bounds__(256) void head_fwd_bf16_kernel(const HeadArgs p) {
         const int64_t pix = (int64_t)b * HW + q;
         const bool sel = valid_n && (p.mask ? msk_n != 0 : true);
         const float bld = bld_n, adm = adm_n;
-        const hs16x4 xb = __builtin_bit_cast(hs16x4, valid_n ? xq_n : make_uint2(0u, 0u));
+        const s16x4 xb = __builtin_bit_cast(s16x4, valid_n ? xq_n : make_uint2(0u, 0u));
         fetch(g + 1, valid_n, xq_n);
         float outv = 0.f;
         if (__any(sel)) {
@@ -631,7 +628,7 @@ __global__ __launch_bounds__(256) void head_fwd_bf16_kernel(const HeadArgs p) {
                 h[mb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(hb_frag4(ldsb, HB_A1, mb, lane_o), xb, h[mb], 0, 0, 0);
             }
             hb_relu4(h);                                   // the pack rounds to bf16
-            hbf16x8 hb[2] = {hb_pack8(h[0], h[1]), hb_pack8(h[2], h[3])};
+            bf16x8 hb[2] = {hb_pack8(h[0], h[1]), hb_pack8(h[2], h[3])};
             hb_layer64(ldsb, HB_A2, lf + 64, lane_o, lk, hb, acc);
             hb_relu4(acc);
             hb[0] = hb_pack8(acc[0], acc[1]); hb[1] = hb_pack8(acc[2], acc[3]);
@@ -668,14 +665,6 @@ __global__ __launch_bounds__(256) void head_fwd_bf16_kernel(const HeadArgs p) {
 }
 
 
-// transposing LDS read ([4 rows][16 columns] of bf16 -> lane c receives column c) and the pairing of two of them into one operand
-__device__ __forceinline__ hs16x4 hc_tr(const unsigned char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) hs16x4*)(p));
-}
-__device__ __forceinline__ hbf16x8 hc_pair(hs16x4 a, hs16x4 b) {
-    return __builtin_bit_cast(hbf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
 // ---- fp32 results on the bf16 matrix pipe: 3-way operand splits (round 5) -----------------------------------------------------------
 // An fp32 number is EXACTLY the sum of three bf16 numbers (a1 = rn(a), a2 = rn(a - a1), a3 = rn(a - a1 - a2): 8 + 8 + 8 mantissa bits,
 // same exponent range; each difference is exact in fp32).  A product a * b is then the sum of nine bf16 x bf16 products, each exact in
@@ -692,7 +681,9 @@ constexpr int HS_PLANE = HB_T3;
 constexpr int HS_F32 = 3 * HS_PLANE;
 constexpr int HS_END = HS_F32 + (4 * 64 + 4) * 4;
 
-__device__ __forceinline__ void hs_split3(float x, unsigned short (&o)[3]) {
+// The pack launch's scalar split: pc_split3 (common.h) with the third half taken through pc_bf16r -- the same bits, other instructions
+// (head_pack_kernel's instruction stream is pinned to this spelling)
+__device__ __forceinline__ void head_split3(float x, unsigned short (&o)[3]) {
     const float a1 = pc_bf16r(x), r1 = x - a1, a2 = pc_bf16r(r1), r2 = r1 - a2, a3 = pc_bf16r(r2);
     o[0] = (unsigned short)(__float_as_uint(a1) >> 16);
     o[1] = (unsigned short)(__float_as_uint(a2) >> 16);
@@ -704,17 +695,17 @@ __device__ __forceinline__ void head_stage_weights_split(unsigned char* img, con
     unsigned short o[3];
     for (int e = tid; e < 4 * 64 * 4; e += nt) {
         const int j = e & 3, lane = (e >> 2) & 63, mb = e >> 8;
-        hs_split3(p.w0[(16 * mb + (lane & 15)) * 16 + 4 * (lane >> 4) + j], o);
+        head_split3(p.w0[(16 * mb + (lane & 15)) * 16 + 4 * (lane >> 4) + j], o);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) h[(pl * HS_PLANE + HB_A1) / 2 + e] = o[pl];
     }
     for (int e = tid; e < 8 * 64 * 8; e += nt) {
         const int j = e & 7, lane = (e >> 3) & 63, f = e >> 9, t = f & 1, mb2 = f >> 1;
         const int u = hb_unit(t, lane >> 4, j), i = lane & 15;
-        hs_split3(p.w2[(16 * mb2 + i) * HID + u], o);
+        head_split3(p.w2[(16 * mb2 + i) * HID + u], o);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) h[(pl * HS_PLANE + HB_A2) / 2 + e] = o[pl];
-        hs_split3(p.w4[(16 * mb2 + i) * HID + u], o);
+        head_split3(p.w4[(16 * mb2 + i) * HID + u], o);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) h[(pl * HS_PLANE + HB_A3) / 2 + e] = o[pl];
     }
@@ -728,41 +719,33 @@ __device__ __forceinline__ void head_stage_weights_split(unsigned char* img, con
     if (tid == 0) f[256] = p.b6[0];
 }
 
-// one pair of fp32 values -> the three packed bf16 pairs of its split
-__device__ __forceinline__ void hs_split_pair(float x0, float x1, unsigned& q1, unsigned& q2, unsigned& q3) {
-    q1 = pc_pack_bf16(x0, x1);
-    const float r0 = x0 - __uint_as_float(q1 << 16), r1 = x1 - __uint_as_float(q1 & 0xffff0000u);
-    q2 = pc_pack_bf16(r0, r1);
-    const float s0 = r0 - __uint_as_float(q2 << 16), s1 = r1 - __uint_as_float(q2 & 0xffff0000u);
-    q3 = pc_pack_bf16(s0, s1);
-}
 // the 16 values of a lane (D layout: h[mb][r] = hidden 16*mb + 4*lk + r) -> packed operands o[split][t] of the next 64-wide contraction
-__device__ __forceinline__ void hs_split_pack(const f32x4 (&h)[4], hbf16x8 (&o)[3][2]) {
+__device__ __forceinline__ void hs_split_pack(const f32x4 (&h)[4], bf16x8 (&o)[3][2]) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-        hu32x4 q[3];
+        u32x4 q[3];
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
             const f32x4& v = h[2 * t + (d >> 1)];
             unsigned q1, q2, q3;
-            hs_split_pair(v[2 * (d & 1)], v[2 * (d & 1) + 1], q1, q2, q3);
+            pc_split_pair(v[2 * (d & 1)], v[2 * (d & 1) + 1], q1, q2, q3);
             q[0][d] = q1; q[1][d] = q2; q[2][d] = q3;
         }
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) o[pl][t] = __builtin_bit_cast(hbf16x8, q[pl]);
+        for (int pl = 0; pl < 3; ++pl) o[pl][t] = __builtin_bit_cast(bf16x8, q[pl]);
     }
 }
 // 64 -> 64 layer on split operands: o1[mb2] = bias + W . h, six partial products per K-step, smallest first; the four accumulators
 // of the layer take turns (independent MFMA chains)
 __device__ __forceinline__ void hs_layer64(const unsigned char* lds, int a_off, const float* bias, int lane, int lk,
-                                           const hbf16x8 (&hb)[3][2], f32x4 (&o1)[4]) {
+                                           const bf16x8 (&hb)[3][2], f32x4 (&o1)[4]) {
 #pragma unroll
     for (int mb2 = 0; mb2 < 4; ++mb2) o1[mb2] = *reinterpret_cast<const f32x4*>(&bias[16 * mb2 + 4 * lk]);
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int pl = 2; pl >= 0; --pl) {                 // weight split index; activation split indices 0 .. 2 - pl
-            hbf16x8 fr[4];
+        for (int pl = 2; pl >= 0; --pl) {                 // weight split index; activation split indices 2 - pl .. 0 (common.h: pc_split_product_at's order)
+            bf16x8 fr[4];
 #pragma unroll
             for (int mb2 = 0; mb2 < 4; ++mb2) fr[mb2] = hb_frag8(lds, pl * HS_PLANE + a_off, mb2, t, lane);
 #pragma unroll
@@ -829,15 +812,15 @@ __global__ __launch_bounds__(64 * NW) void head_fwd_split_kernel(const HeadArgs 
             f32x4 h[4], acc[4];
             {
                 unsigned x1[2], x2[2], x3[2];
-                hs_split_pair(xv[0], xv[1], x1[0], x2[0], x3[0]);
-                hs_split_pair(xv[2], xv[3], x1[1], x2[1], x3[1]);
-                const hs16x4 xb[3] = {__builtin_bit_cast(hs16x4, make_uint2(x1[0], x1[1])), __builtin_bit_cast(hs16x4, make_uint2(x2[0], x2[1])),
-                                      __builtin_bit_cast(hs16x4, make_uint2(x3[0], x3[1]))};
+                pc_split_pair(xv[0], xv[1], x1[0], x2[0], x3[0]);
+                pc_split_pair(xv[2], xv[3], x1[1], x2[1], x3[1]);
+                const s16x4 xb[3] = {__builtin_bit_cast(s16x4, make_uint2(x1[0], x1[1])), __builtin_bit_cast(s16x4, make_uint2(x2[0], x2[1])),
+                                      __builtin_bit_cast(s16x4, make_uint2(x3[0], x3[1]))};
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb) h[mb] = *reinterpret_cast<const f32x4*>(&lf[16 * mb + 4 * lk]);
 #pragma unroll
                 for (int pl = 2; pl >= 0; --pl) {
-                    hs16x4 fr[4];
+                    s16x4 fr[4];
 #pragma unroll
                     for (int mb = 0; mb < 4; ++mb) fr[mb] = hb_frag4(ldsb, pl * HS_PLANE + HB_A1, mb, lane_o);
 #pragma unroll
@@ -847,7 +830,7 @@ __global__ __launch_bounds__(64 * NW) void head_fwd_split_kernel(const HeadArgs 
                 }
             }
             hb_relu4(h);
-            hbf16x8 hb[3][2];
+            bf16x8 hb[3][2];
             hs_split_pack(h, hb);
             hs_layer64(ldsb, HB_A2, lf + 64, lane_o, lk, hb, acc);
             hb_relu4(acc);
@@ -932,15 +915,15 @@ __device__ __forceinline__ void head_stage_weights_bsplit(unsigned char* img, co
         const int row = e >> 6, c = e & 63;
         const int pos = (c >> 5) * 32 + ((c >> 2) & 3) * 8 + ((c >> 4) & 1) * 4 + (c & 3);
         const int byte = row * 128 + (((pos >> 3) ^ ((row >> 1) & 7)) * 16) + (pos & 7) * 2;
-        hs_split3(p.w2[e], o);
+        head_split3(p.w2[e], o);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<unsigned short*>(img + pl * LS_PLANE + LS_W2 + byte) = o[pl];
-        hs_split3(p.w4[e], o);
+        head_split3(p.w4[e], o);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<unsigned short*>(img + pl * LS_PLANE + LS_W4 + byte) = o[pl];
     }
     for (int e = tid; e < 64 * 16; e += nt) {
-        hs_split3(p.w0[e], o);
+        head_split3(p.w0[e], o);
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) *reinterpret_cast<unsigned short*>(img + pl * LS_PLANE + LS_W0 + e * 2) = o[pl];
     }
@@ -972,21 +955,21 @@ __device__ __forceinline__ LsLane ls_lane(int lane) {
     L.t0 = (4 * lk + (li >> 2)) * 32 + (li & 3) * 8;
     return L;
 }
-__device__ __forceinline__ hbf16x8 ls_frag_a(const unsigned char* w, const LsLane& L, int mb2, int t) {
-    return __builtin_bit_cast(hbf16x8, *reinterpret_cast<const hu32x4*>(w + mb2 * 2048 + L.a[t]));
+__device__ __forceinline__ bf16x8 ls_frag_a(const unsigned char* w, const LsLane& L, int mb2, int t) {
+    return __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(w + mb2 * 2048 + L.a[t]));
 }
-__device__ __forceinline__ hbf16x8 ls_frag_t(const unsigned char* w, const LsLane& L, int mi, int t) {
+__device__ __forceinline__ bf16x8 ls_frag_t(const unsigned char* w, const LsLane& L, int mi, int t) {
     const unsigned char* q = w + L.t[mi >> 1] + (mi & 1) * 8;
-    return hc_pair(hc_tr(q + (2 * t) * 2048), hc_tr(q + (2 * t + 1) * 2048));
+    return pc_tr_pair(pc_lds_tr16(q + (2 * t) * 2048), pc_lds_tr16(q + (2 * t + 1) * 2048));
 }
 // o1[mb2] += W . h  (SPLIT forward fragments) or W^T . g (transposed fragments), six partial products per K-step, smallest first
 template <bool TR>
-__device__ __forceinline__ void ls_layer64(const unsigned char* planes, int w_off, const LsLane& L, const hbf16x8 (&hb)[3][2], f32x4 (&o1)[4]) {
+__device__ __forceinline__ void ls_layer64(const unsigned char* planes, int w_off, const LsLane& L, const bf16x8 (&hb)[3][2], f32x4 (&o1)[4]) {
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int pl = 2; pl >= 0; --pl) {
-            hbf16x8 fr[4];
+            bf16x8 fr[4];
 #pragma unroll
             for (int mo = 0; mo < 4; ++mo)
                 fr[mo] = TR ? ls_frag_t(planes + pl * LS_PLANE + w_off, L, mo, t) : ls_frag_a(planes + pl * LS_PLANE + w_off, L, mo, t);
@@ -1002,19 +985,19 @@ __device__ __forceinline__ void ls_layer64(const unsigned char* planes, int w_of
 // Six steps (K-step t, weight plane pl) of 4 / 8 / 12 instructions; fr: the fragments of step 0, loaded by the caller one phase earlier;
 // nxt(fr): issues the reads of the first fragments of whatever contraction FOLLOWS, in the shadow of this one's last step.
 template <bool TR>
-__device__ __forceinline__ void ls_load4(const unsigned char* planes, int w_off, const LsLane& L, int t, int pl, hbf16x8 (&fr)[4]) {
+__device__ __forceinline__ void ls_load4(const unsigned char* planes, int w_off, const LsLane& L, int t, int pl, bf16x8 (&fr)[4]) {
 #pragma unroll
     for (int mo = 0; mo < 4; ++mo) fr[mo] = TR ? ls_frag_t(planes + pl * LS_PLANE + w_off, L, mo, t) : ls_frag_a(planes + pl * LS_PLANE + w_off, L, mo, t);
 }
 template <bool TR, class Next>
-__device__ __forceinline__ void ls_layer64_pf(const unsigned char* planes, int w_off, const LsLane& L, const hbf16x8 (&hb)[3][2], f32x4 (&o1)[4],
-                                              hbf16x8 (&fr)[4], Next&& nxt) {
-    hbf16x8 fb[4];
+__device__ __forceinline__ void ls_layer64_pf(const unsigned char* planes, int w_off, const LsLane& L, const bf16x8 (&hb)[3][2], f32x4 (&o1)[4],
+                                              bf16x8 (&fr)[4], Next&& nxt) {
+    bf16x8 fb[4];
 #pragma unroll
     for (int st = 0; st < 6; ++st) {
         const int t = st / 3, pl = 2 - st % 3;
-        hbf16x8 (&cur)[4] = (st & 1) ? fb : fr;
-        hbf16x8 (&oth)[4] = (st & 1) ? fr : fb;
+        bf16x8 (&cur)[4] = (st & 1) ? fb : fr;
+        bf16x8 (&oth)[4] = (st & 1) ? fr : fb;
         if (st < 5) ls_load4<TR>(planes, w_off, L, (st + 1) / 3, 2 - (st + 1) % 3, oth);
         else nxt(oth);                                   // (step 5 is odd: `oth` is fr)
         __builtin_amdgcn_sched_barrier(0);
@@ -1027,45 +1010,44 @@ __device__ __forceinline__ void ls_layer64_pf(const unsigned char* planes, int w
 }
 // two blocks (one K-step's worth of the next contraction's operand) -> their three split planes
 template <int T>
-__device__ __forceinline__ void hs_split_t(const f32x4& a, const f32x4& b, hbf16x8 (&o)[3][2]) {
-    hu32x4 q[3];
+__device__ __forceinline__ void hs_split_t(const f32x4& a, const f32x4& b, bf16x8 (&o)[3][2]) {
+    u32x4 q[3];
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
         const f32x4& v = d < 2 ? a : b;
         unsigned q1, q2, q3;
-        hs_split_pair(v[2 * (d & 1)], v[2 * (d & 1) + 1], q1, q2, q3);
+        pc_split_pair(v[2 * (d & 1)], v[2 * (d & 1) + 1], q1, q2, q3);
         q[0][d] = q1; q[1][d] = q2; q[2][d] = q3;
     }
 #pragma unroll
-    for (int pl = 0; pl < 3; ++pl) o[pl][T] = __builtin_bit_cast(hbf16x8, q[pl]);
+    for (int pl = 0; pl < 3; ++pl) o[pl][T] = __builtin_bit_cast(bf16x8, q[pl]);
 }
 __device__ __forceinline__ void relu_block2(f32x4& a, f32x4& b) { relu_block(a); relu_block(b); }
 // four fp32 values (the four K-slots of a lane in v_mfma_f32_16x16x16_bf16) -> their three split planes
-__device__ __forceinline__ void hs_split4(const f32x4& v, hs16x4 (&o)[3]) {
+__device__ __forceinline__ void hs_split4(const f32x4& v, s16x4 (&o)[3]) {
     unsigned a1, a2, a3, b1, b2, b3;
-    hs_split_pair(v[0], v[1], a1, a2, a3);
-    hs_split_pair(v[2], v[3], b1, b2, b3);
-    o[0] = __builtin_bit_cast(hs16x4, make_uint2(a1, b1));
-    o[1] = __builtin_bit_cast(hs16x4, make_uint2(a2, b2));
-    o[2] = __builtin_bit_cast(hs16x4, make_uint2(a3, b3));
+    pc_split_pair(v[0], v[1], a1, a2, a3);
+    pc_split_pair(v[2], v[3], b1, b2, b3);
+    o[0] = __builtin_bit_cast(s16x4, make_uint2(a1, b1));
+    o[1] = __builtin_bit_cast(s16x4, make_uint2(a2, b2));
+    o[2] = __builtin_bit_cast(s16x4, make_uint2(a3, b3));
 }
 // consumer side of the split form: dW[mb][nb] += G block mb . (H block nb)^T over the slot's 16 pixels, six partial products
 template <int NB>
 __device__ __forceinline__ void hs_wgrad16(const f32x4 (&af)[4], const f32x4 (&bf)[4], f32x4 (&dW)[4][4]) {
-    hs16x4 as[4][3];
+    s16x4 as[4][3];
 #pragma unroll
     for (int mb = 0; mb < 4; ++mb) hs_split4(af[mb], as[mb]);
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
-        hs16x4 bs[3];
+        s16x4 bs[3];
         hs_split4(bf[nb], bs);
 #pragma unroll
-        for (int pl = 2; pl >= 0; --pl)
+        for (int i = 0; i < PC_SPLIT_PRODUCTS; ++i) {
+            const pc_split_product s = pc_split_product_at(i);
 #pragma unroll
-            for (int qq = 2 - pl; qq >= 0; --qq)
-#pragma unroll
-                for (int mb = 0; mb < 4; ++mb)
-                    dW[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(as[mb][pl], bs[qq], dW[mb][nb], 0, 0, 0);
+            for (int mb = 0; mb < 4; ++mb) dW[mb][nb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(as[mb][s.pw], bs[s.pa], dW[mb][nb], 0, 0, 0);
+        }
     }
 }
 
@@ -1303,20 +1285,20 @@ __global__ __launch_bounds__(512, 2) void head_bwd_pc_kernel(const HeadBwdArgs a
                 const unsigned char* const wpl = reinterpret_cast<const unsigned char*>(lds);
                 const float* const lf = reinterpret_cast<const float*>(wpl + LS_F32);
                 f32x4 h1[4], h2[4], h3[4];
-                hbf16x8 ob[3][2];
-                hbf16x8 fr[4];
+                bf16x8 ob[3][2];
+                bf16x8 fr[4];
                 {
                     unsigned x1[2], x2[2], x3[2];
-                    hs_split_pair(xv[0], xv[1], x1[0], x2[0], x3[0]);
-                    hs_split_pair(xv[2], xv[3], x1[1], x2[1], x3[1]);
-                    const hs16x4 xb[3] = {__builtin_bit_cast(hs16x4, make_uint2(x1[0], x1[1])), __builtin_bit_cast(hs16x4, make_uint2(x2[0], x2[1])),
-                                          __builtin_bit_cast(hs16x4, make_uint2(x3[0], x3[1]))};
-                    hs16x4 f1[3][4];
+                    pc_split_pair(xv[0], xv[1], x1[0], x2[0], x3[0]);
+                    pc_split_pair(xv[2], xv[3], x1[1], x2[1], x3[1]);
+                    const s16x4 xb[3] = {__builtin_bit_cast(s16x4, make_uint2(x1[0], x1[1])), __builtin_bit_cast(s16x4, make_uint2(x2[0], x2[1])),
+                                          __builtin_bit_cast(s16x4, make_uint2(x3[0], x3[1]))};
+                    s16x4 f1[3][4];
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
                         for (int mb = 0; mb < 4; ++mb)
-                            f1[pl][mb] = __builtin_bit_cast(hs16x4, *reinterpret_cast<const uint2*>(wpl + pl * LS_PLANE + LS_W0 + mb * 512 + LL.a0));
+                            f1[pl][mb] = __builtin_bit_cast(s16x4, *reinterpret_cast<const uint2*>(wpl + pl * LS_PLANE + LS_W0 + mb * 512 + LL.a0));
                     ls_load4<false>(wpl, LS_W2, LL, 0, 2, fr);                 // the second layer's first fragments
 #pragma unroll
                     for (int mb = 0; mb < 4; ++mb) h1[mb] = *reinterpret_cast<const f32x4*>(&lf[16 * mb + 4 * lk]);
@@ -1332,7 +1314,7 @@ __global__ __launch_bounds__(512, 2) void head_bwd_pc_kernel(const HeadBwdArgs a
                 }
                 hb_relu4(h1);
                 hs_split_pack(h1, ob);
-                ls_layer64_pf<false>(wpl, LS_W2, LL, ob, h2, fr, [&](hbf16x8 (&f)[4]) {
+                ls_layer64_pf<false>(wpl, LS_W2, LL, ob, h2, fr, [&](bf16x8 (&f)[4]) {
                     ls_load4<false>(wpl, LS_W4, LL, 0, 2, f);
 #pragma unroll
                     for (int mb = 0; mb < 4; ++mb) h3[mb] = *reinterpret_cast<const f32x4*>(&lf[128 + 16 * mb + 4 * lk]);
@@ -1341,7 +1323,7 @@ __global__ __launch_bounds__(512, 2) void head_bwd_pc_kernel(const HeadBwdArgs a
                 });
                 hb_relu4(h2);
                 hs_split_pack(h2, ob);
-                ls_layer64_pf<false>(wpl, LS_W4, LL, ob, h3, fr, [&](hbf16x8 (&f)[4]) {
+                ls_layer64_pf<false>(wpl, LS_W4, LL, ob, h3, fr, [&](bf16x8 (&f)[4]) {
                     ls_load4<true>(wpl, LS_W4, LL, 0, 2, f);
                     fetch_stage(3, gnx);
                     fetch_stage(4, gnx);
@@ -1384,7 +1366,7 @@ __global__ __launch_bounds__(512, 2) void head_bwd_pc_kernel(const HeadBwdArgs a
 #pragma unroll
                 for (int mi = 0; mi < 4; ++mi) g2[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
                 hs_split_pack(g3, ob);
-                ls_layer64_pf<true>(wpl, LS_W4, LL, ob, g2, fr, [&](hbf16x8 (&f)[4]) { ls_load4<true>(wpl, LS_W2, LL, 0, 2, f); });
+                ls_layer64_pf<true>(wpl, LS_W4, LL, ob, g2, fr, [&](bf16x8 (&f)[4]) { ls_load4<true>(wpl, LS_W2, LL, 0, 2, f); });
                 mask_block(g2[0], h2[0]);
                 mask_block(g2[1], h2[1]);
                 mask_block(g2[2], h2[2]);
@@ -1403,11 +1385,11 @@ __global__ __launch_bounds__(512, 2) void head_bwd_pc_kernel(const HeadBwdArgs a
                 for (int mi = 0; mi < 4; ++mi) g1[mi] = f32x4{0.f, 0.f, 0.f, 0.f};
                 hs_split_pack(g2, ob);
                 // (what follows is the 16-channel data gradient: its fragments of planes 2 and 1 -- [plane][K-step] -- come with the last step)
-                ls_layer64_pf<true>(wpl, LS_W2, LL, ob, g1, fr, [&](hbf16x8 (&f)[4]) {
+                ls_layer64_pf<true>(wpl, LS_W2, LL, ob, g1, fr, [&](bf16x8 (&f)[4]) {
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const unsigned char* q0 = wpl + (2 - (k >> 1)) * LS_PLANE + LS_W0 + LL.t0 + (k & 1) * 32 * 32;
-                        f[k] = hc_pair(hc_tr(q0), hc_tr(q0 + 16 * 32));
+                        f[k] = pc_tr_pair(pc_lds_tr16(q0), pc_lds_tr16(q0 + 16 * 32));
                     }
                 });
                 mask_block(g1[0], h1[0]);
@@ -1424,17 +1406,17 @@ __global__ __launch_bounds__(512, 2) void head_bwd_pc_kernel(const HeadBwdArgs a
                     release();
                 }
                 HR_CLOSE(10);
-                hbf16x8 fz[2];                            // plane 0 of the 16-channel data gradient's fragments
+                bf16x8 fz[2];                            // plane 0 of the 16-channel data gradient's fragments
                 {
                     const unsigned char* q0 = wpl + LS_W0 + LL.t0;
-                    fz[0] = hc_pair(hc_tr(q0), hc_tr(q0 + 16 * 32));
-                    fz[1] = hc_pair(hc_tr(q0 + 32 * 32), hc_tr(q0 + 48 * 32));
+                    fz[0] = pc_tr_pair(pc_lds_tr16(q0), pc_lds_tr16(q0 + 16 * 32));
+                    fz[1] = pc_tr_pair(pc_lds_tr16(q0 + 32 * 32), pc_lds_tr16(q0 + 48 * 32));
                 }
                 hs_split_pack(g1, ob);
                 f32x4 gx = f32x4{0.f, 0.f, 0.f, 0.f}, gx2 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                 for (int pl = 2; pl >= 0; --pl) {
-                    const hbf16x8 f0 = pl == 0 ? fz[0] : fr[2 * (2 - pl)], f1 = pl == 0 ? fz[1] : fr[2 * (2 - pl) + 1];
+                    const bf16x8 f0 = pl == 0 ? fz[0] : fr[2 * (2 - pl)], f1 = pl == 0 ? fz[1] : fr[2 * (2 - pl) + 1];
 #pragma unroll
                     for (int qq = 2 - pl; qq >= 0; --qq) {
                         gx = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f0, ob[qq][0], gx, 0, 0, 0);
@@ -1670,11 +1652,11 @@ __global__ __launch_bounds__(512, 2) void head_bwd_pc_kernel(const HeadBwdArgs a
 #pragma unroll
             for (int q = 0; q < 4; ++q) dbs[0][q] += (af[q][0] + af[q][1]) + (af[q][2] + af[q][3]);
             if constexpr (SPL) {
-                hs16x4 xs[3];
+                s16x4 xs[3];
                 hs_split4(bf[0], xs);
 #pragma unroll
                 for (int mb = 0; mb < 4; ++mb) {
-                    hs16x4 as[3];
+                    s16x4 as[3];
                     hs_split4(af[mb], as);
 #pragma unroll
                     for (int pl = 2; pl >= 0; --pl)
@@ -1829,7 +1811,7 @@ __global__ __launch_bounds__(256, 2) void head_bwd_bf16_coop4_kernel(const HeadB
     // bias gradients = row sums of G3 / G2 / G1 over the pixels: one more MFMA against an all-ones operand (every column of the block
     // then holds the row sums) instead of 7 VALU per transposed read -- the matrix pipe is 13 % busy, the VALU is the limiter
     f32x4 dB4 = f32x4{0.f, 0.f, 0.f, 0.f}, dB2 = dB4, dB0 = dB4;
-    const hbf16x8 ones8 = __builtin_bit_cast(hbf16x8, hu32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u});
+    const bf16x8 ones8 = __builtin_bit_cast(bf16x8, u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u});
     f32x4 dw6[4];
     float db6 = 0.f;
 #pragma unroll
@@ -1911,14 +1893,14 @@ __global__ __launch_bounds__(256, 2) void head_bwd_bf16_coop4_kernel(const HeadB
             bool active = __any(sel);
             int lane_o = lane;
             asm volatile("" : "+v"(lane_o));              // opaque: keeps the weight-fragment reads inside the loop
-            hbf16x8 hb1[2], hb2[2];
-            hu32x4 m1[2], m2[2];                          // 0xffff per bf16 half of hb1 / hb2 that is non-zero (= passed its ReLU)
+            bf16x8 hb1[2], hb2[2];
+            u32x4 m1[2], m2[2];                          // 0xffff per bf16 half of hb1 / hb2 that is non-zero (= passed its ReLU)
             f32x4 h3[4];
             float gout = 0.f;
             HQ_CLOSE(hq0);                            // phase 0: loop top (consume the prefetch, issue the next one)
             if (active) {
                 // ---- forward chain (lane = pixel, registers = hidden 16*mb + 4*lk + r)
-                const hs16x4 xb = __builtin_bit_cast(hs16x4, f4);
+                const s16x4 xb = __builtin_bit_cast(s16x4, f4);
                 {
                     f32x4 h1[4];
 #pragma unroll
@@ -1954,7 +1936,7 @@ __global__ __launch_bounds__(256, 2) void head_bwd_bf16_coop4_kernel(const HeadB
             if (active) {
                 if (lk == 0) db6 += gout;
                 // ---- backward chain: G3 = relu'(h3) . w6 . gout;  G2 = relu'(h2) . (W4^T G3);  G1 = relu'(h1) . (W2^T G2);  g_x = W0^T G1
-                hbf16x8 gb3[2], gb2[2], gb1[2];
+                bf16x8 gb3[2], gb2[2], gb1[2];
                 {
                     f32x4 g3[4];
 #pragma unroll
@@ -2008,12 +1990,12 @@ __global__ __launch_bounds__(256, 2) void head_bwd_bf16_coop4_kernel(const HeadB
                 // ---- operands of the weight gradients into this wave's slot: rows = pixels, 8-byte pieces of 4 channels
                 // (pack t holds hidden 16*(2t) + 4*lk .. +3 and 16*(2t+1) + 4*lk .. +3)
                 // piece p = lk + 4 * k of row li goes to physical piece p ^ li: low bits lk ^ (li & 3), block k ^ (li >> 2)
-                auto put = [&](int tensor, const hbf16x8 (&v)[2]) {
+                auto put = [&](int tensor, const bf16x8 (&v)[2]) {
                     unsigned char* d = my + tensor + li * H4_ROW + 8 * (lk ^ (li & 3));
                     const int bs = 32 * (li >> 2);
 #pragma unroll
                     for (int t = 0; t < 2; ++t) {
-                        const hu32x4 q4 = __builtin_bit_cast(hu32x4, v[t]);
+                        const u32x4 q4 = __builtin_bit_cast(u32x4, v[t]);
                         *reinterpret_cast<uint2*>(d + ((32 * (2 * t)) ^ bs)) = make_uint2(q4[0], q4[1]);
                         *reinterpret_cast<uint2*>(d + ((32 * (2 * t + 1)) ^ bs)) = make_uint2(q4[2], q4[3]);
                     }
@@ -2044,25 +2026,25 @@ __global__ __launch_bounds__(256, 2) void head_bwd_bf16_coop4_kernel(const HeadB
             const unsigned char* base = ex + 2 * ks * H4_SLOT + t_off;
             auto frag = [&](int tensor, int blk) {           // operand block `blk` (16 channels) of a tensor: two transposed reads
                 const int o = (32 * blk) ^ t_sel;
-                return hc_pair(hc_tr(base + tensor + o), hc_tr(base + tensor + 4 * H4_ROW + (o ^ 32)));
+                return pc_tr_pair(pc_lds_tr16(base + tensor + o), pc_lds_tr16(base + tensor + 4 * H4_ROW + (o ^ 32)));
             };
             {
-                const hbf16x8 av = frag(H4_G3, my_mb);
+                const bf16x8 av = frag(H4_G3, my_mb);
                 dB4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, ones8, dB4, 0, 0, 0);
 #pragma unroll
                 for (int nb = 0; nb < 4; ++nb) dW4[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, frag(H4_H2, nb), dW4[nb], 0, 0, 0);
             }
             {
-                const hbf16x8 av = frag(H4_G2, my_mb);
+                const bf16x8 av = frag(H4_G2, my_mb);
                 dB2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, ones8, dB2, 0, 0, 0);
 #pragma unroll
                 for (int nb = 0; nb < 4; ++nb) dW2[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, frag(H4_H1, nb), dW2[nb], 0, 0, 0);
             }
             {
-                const hbf16x8 av = frag(H4_G1, my_mb);
+                const bf16x8 av = frag(H4_G1, my_mb);
                 dB0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, ones8, dB0, 0, 0, 0);
                 const unsigned char* xb = ex + 2 * ks * H4_SLOT;
-                dW0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, hc_pair(hc_tr(xb + t_offx), hc_tr(xb + t_offx2)), dW0, 0, 0, 0);
+                dW0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, pc_tr_pair(pc_lds_tr16(xb + t_offx), pc_lds_tr16(xb + t_offx2)), dW0, 0, 0, 0);
             }
         }
         HQ_CLOSE(hq5);                                // phase 5: weight gradients (transposing reads + MFMAs)

@@ -39,8 +39,7 @@ __global__ __launch_bounds__(256) void reflect_pad_select_kernel(const float* in
         if (((xs | W) & 1) == 0) {
             // even pad and even width (14 / 100 for the training tiles): the piece is 8-byte aligned -- two 8-byte loads (the
             // 4-byte-aligned vector type below is split into four dword loads by the compiler)
-            typedef float f32x2a __attribute__((ext_vector_type(2)));
-            const f32x2a t0 = *reinterpret_cast<const f32x2a*>(src + xs), t1 = *reinterpret_cast<const f32x2a*>(src + xs + 2);
+            const f32x2 t0 = *reinterpret_cast<const f32x2*>(src + xs), t1 = *reinterpret_cast<const f32x2*>(src + xs + 2);
             v = f32x4{t0[0], t0[1], t1[0], t1[1]};
         } else {
             const f32x4u t = *reinterpret_cast<const f32x4u*>(src + xs);   // interior: one (unaligned) 16-byte load

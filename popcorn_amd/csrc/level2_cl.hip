@@ -16,10 +16,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int LC_SL = 48;                    // slots per image row (== 0 mod 16, as the strip rows of conv3x3_cl_kernel)
 constexpr int LC_ROWS = 34;
 constexpr int LC_COL0 = 4;                   // slot of x = 0 (left halo at slot 3, right halo at slot 36)
@@ -207,11 +203,6 @@ struct LbProb {
 };
 struct LbArgs { LbProb pr[PC_MAX_GROUP]; long long* ts; };
 
-__device__ __forceinline__ s16x4 lb_tr(const unsigned char* p) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-__device__ __forceinline__ bf16x8 lb_pair(s16x4 a, s16x4 b) { return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7)); }
-
 __global__ __launch_bounds__(512) void level2_bwd_cl_kernel(const LbArgs args) {
     extern __shared__ __attribute__((aligned(16))) u32x4 lds4[];
     const LbProb& q = args.pr[blockIdx.y];
@@ -329,7 +320,7 @@ __global__ __launch_bounds__(512) void level2_bwd_cl_kernel(const LbArgs args) {
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb) {
                 const unsigned char* ga = gb + mb * LC_CH * 16 + 2 * rpi * LC_SL * 16 + a_off;
-                av[mb] = lb_pair(lb_tr(ga), lb_tr(ga + 4 * 16));
+                av[mb] = pc_tr_pair(pc_lds_tr16(ga), pc_lds_tr16(ga + 4 * 16));
                 bacc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[mb], ones8, bacc[mb], 0, 0, 0);
             }
 #pragma unroll
@@ -337,7 +328,7 @@ __global__ __launch_bounds__(512) void level2_bwd_cl_kernel(const LbArgs args) {
 #pragma unroll
                 for (int dx = 0; dx < 3; ++dx) {
                     const unsigned char* xb = xb0 + (nb >> 1) * LC_CH * 16 + 2 * rpi * LC_SL * 16 + b_off + dx * 16 + 8 * (nb & 1);
-                    const bf16x8 bv = lb_pair(lb_tr(xb), lb_tr(xb + 4 * 16));
+                    const bf16x8 bv = pc_tr_pair(pc_lds_tr16(xb), pc_lds_tr16(xb + 4 * 16));
 #pragma unroll
                     for (int mb = 0; mb < 2; ++mb)
                         wacc[mb][dx * 4 + nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av[mb], bv, wacc[mb][dx * 4 + nb], 0, 0, 0);

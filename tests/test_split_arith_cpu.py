@@ -1,4 +1,4 @@
-"""The arithmetic behind the split form of the head kernels (popcorn_hip.h: pc_set_head_split; head.hip: hs_split3 / hs_split_pair),
+"""The arithmetic behind the split form of the head kernels (popcorn_hip.h: pc_set_head_split; common.h: pc_split3 / pc_split_pair),
 restated on the CPU: an fp32 number is EXACTLY the sum of three bf16 numbers, and the six partial products the kernels keep reproduce
 the fp32 product to within one fp32 rounding."""
 import torch
