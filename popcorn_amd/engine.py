@@ -17,7 +17,7 @@ All launches go to the current torch stream, so a whole step can be captured int
 """
 from __future__ import annotations
 
-import ctypes as C
+import collections
 import os
 
 import torch
@@ -133,11 +133,8 @@ class UNetEngine:
             raise L.PopcornHipError(f"popcorn_amd engine needs parameters on a HIP device, got {dev}; there is no CPU path")
         self.device = dev
 
-    # ------------------------------------------------------------------------------------------------ forward
-    def _conv(self, lay, a, out=None, **kw):
-        bn = lay.bn
-        return ops.conv3x3_raw(a, lay.w, bn, out=out, **kw)
 
+    # ------------------------------------------------------------------------------------------------ forward
     def forward(self, X, pad_top, pad_left, Hp, Wp, save=False, feats=None):
         """X: (B,6,H,W) in the dataset's channel order [R,G,B,NIR,VV,VH]; the conv domain is the reflect-padded
         (Hp,Wp) image.  Returns (features (B,16,Hp,Wp), saved activations or None)."""
@@ -151,29 +148,25 @@ class UNetEngine:
             f, _ = forward_multi([self], X, pad, pad, H + 2 * pad, W + 2 * pad, [False], logit_only=[True])
             return self.score_from_features(f[0], H, W, pad, pad)
         feats, _ = self.forward(X, pad, pad, H + 2 * pad, W + 2 * pad, save=False)
-        if self.single_out is not None:
-            f0 = self.streams[0][3]
-            return ops.outconv_sigmoid_crop(feats[:, f0:f0 + 8], self.single_out[0], self.single_out[1], H, W, pad, pad)
-        return ops.outconv_sigmoid_crop(feats, self.fusion_w, self.fusion_b, H, W, pad, pad)
+        f0 = self.streams[0][3]
+        return ops.outconv_sigmoid_crop(feats[:, f0:f0 + 8], self.single_out[0], self.single_out[1], H, W, pad, pad)
+
+    def _logit_weights(self, f):
+        """fusion_out_conv's weights for the 16-channel feature map, or ones for the (B,2,.,.) partial logits that
+        ``forward_multi(logit_only=...)`` returns (they only remain to be added)."""
+        if f.shape[1] != 2:
+            return self.fusion_w
+        if getattr(self, "_ones2", None) is None or self._ones2.device != f.device:
+            self._ones2 = torch.ones(2, device=f.device, dtype=torch.float32)
+        return self._ones2
 
     def score_from_features(self, f, H, W, py, px):
-        """fusion_out_conv + sigmoid + crop from either the 16-channel feature map or the (B,2,.,.) partial logits that
-        ``forward_multi(logit_only=...)`` returns."""
-        if f.shape[1] == 2:
-            if getattr(self, "_ones2", None) is None or self._ones2.device != f.device:
-                self._ones2 = torch.ones(2, device=f.device, dtype=torch.float32)
-            return ops.outconv_sigmoid_crop(f, self._ones2, self.fusion_b, H, W, py, px)
-        return ops.outconv_sigmoid_crop(f, self.fusion_w, self.fusion_b, H, W, py, px)
+        """fusion_out_conv + sigmoid + crop from either the 16-channel feature map or the partial logits."""
+        return ops.outconv_sigmoid_crop(f, self._logit_weights(f), self.fusion_b, H, W, py, px)
 
     def score_and_mask(self, f, H, W, py, px, admin_mask, census_idx, rowsel, colsel, occupancymodel=True):
         """score_from_features + get_sparsity_mask (popcorn.py:361-377) in one launch: (building, mask, counts)."""
-        if f.shape[1] == 2:
-            if getattr(self, "_ones2", None) is None or self._ones2.device != f.device:
-                self._ones2 = torch.ones(2, device=f.device, dtype=torch.float32)
-            w = self._ones2
-        else:
-            w = self.fusion_w
-        return ops.building_score_mask(f, w, self.fusion_b, H, W, py, px, admin_mask, census_idx, rowsel, colsel,
+        return ops.building_score_mask(f, self._logit_weights(f), self.fusion_b, H, W, py, px, admin_mask, census_idx, rowsel, colsel,
                                        occupancymodel)
 
     def feat_bn(self):
@@ -190,321 +183,302 @@ class UNetEngine:
         (= or += per ``accumulate``).  encoder_no_grad: networks.py:124-132 semantics.  head_reduce: the ``ops.HeadPartials`` of the
         pass's ``head_bwd(defer_reduce=True)`` -- finished by this pass's batched reduction launch.
         Data-gradient launches are grouped over the two streams (same shapes); weight-gradient launches are per
-        stream (each owns its partial-sum workspace)."""
-        X = saved["X"]                     # None when the forward pass was fed the padded input directly (Xp_all)
-        pad_top, pad_left, Hp, Wp = saved["geom"]
-        B = G.shape[0]
-        dev = G.device
+        stream (each owns its partial-sum workspace).  The network in reverse, one call per block (``_Backward`` below; the native
+        executor's counterpart, same calls in the same order: csrc/step.hip: backward)."""
+        p = _Backward(self, saved, G, grads, accumulate, encoder_no_grad, prefix, head_reduce)
+        _, _, Hp, Wp = saved["geom"]
         H1, W1 = Hp // 2, Wp // 2
         H2, W2 = H1 // 2, W1 // 2
-        E = lambda c, h, w: L.empty_act(B, c, h, w, dev)  # noqa: E731
-        S = [s for s, _, _, _ in self.streams]
-        A = {s: saved[s] for s in S}
-        ly = lambda s, t: self.layers[(s, t)]  # noqa: E731
-
-        # first stages now, ONE batched reduction at the end.  Everything stays on the caller's stream: running the weight-
-        # gradient branch on a second stream next to the data-gradient chain was measured three times and lost every time
-        # (DESIGN.md section 3: both branches are bound by the same memory pipe).
-        wb = ops.WgradBatch(dev, accumulate)
-        if head_reduce is not None:
-            wb.head_reduce(head_reduce)
-
-        def on_side(fn):
-            fn()
-
-        def wg(s, tag, a, g, **kw):
-            lay = ly(s, tag)
-            on_side(lambda: wb.conv3x3(a, g, lay.w.shape[0], grads[prefix + lay.wname], grads[prefix + lay.bname], **kw))
-
-        def wgs(tag, a_key, gs, b_key=None, off_key=None, **kw):
-            """weight gradients of layer `tag` for all streams in ONE launch (same shapes)"""
-            probs = []
-            for s in S:
-                lay = ly(s, tag)
-                pr = {"a": A[s][a_key], "g": gs[s], "dw": grads[prefix + lay.wname], "db": grads[prefix + lay.bname]}
-                if b_key is not None:
-                    pr["b"], pr["b_offset"] = A[s][b_key], A[s][off_key]
-                probs.append(pr)
-            on_side(lambda: wb.conv3x3_group(probs, ly(S[0], tag).w.shape[0], **kw))
-
-        def wgts(tag, xs, gs):
-            """transposed-conv weight gradients of layer `tag` for all streams in ONE launch"""
-            probs = [{"x": xs[s], "g": gs[s], "dw": grads[prefix + ly(s, tag).wname], "db": grads[prefix + ly(s, tag).bname]}
-                     for s in S]
-            on_side(lambda: wb.convt2x2_group(probs))
-
-        def finish():
-            wb.finish()
-
-        def dg(tag, gs, outs, c0, cn, acts=None, act_tag=None, pool=False, acc=False):
-            """grouped data-gradient of layer `tag` over both streams"""
-            probs = []
-            for s in S:
-                pr = {"g": gs[s], "w": ly(s, tag).w, "out": outs[s]}
-                if acts is not None:
-                    pr["act"] = acts[s]
-                    pr["act_bn"] = ly(s, act_tag).bn_nobias
-                probs.append(pr)
-            ops.conv3x3_dgrad_group(probs, c0, cn, pool=pool, accumulate=acc)
-            return outs
-
-        # bf16 mode: the data gradient and the weight gradient of a layer (or of one column block of a concat layer) read the
-        # same two tensors -- one launch for both (pc_conv3x3_bwd_group), the Down blocks' first layers included (pool_act)
-        bf = L.act_dtype() == torch.bfloat16
-        fuse = FUSED_CONV_BWD and bf
-
-        def fuse8(gs, x_key, off_key=None):
-            """8 -> 8 layers: also in fp32 mode, for planar tensors with 16-byte aligned rows and the input block placed at
-            (0, 0) with the extent of the gradient (anything else keeps the separate launches)"""
-            if not FUSED_CONV_BWD or bf:
-                return FUSED_CONV_BWD
-            for s in S:
-                g, x = gs[s], A[s][x_key]
-                if x.shape[2:] != g.shape[2:] or g.shape[3] % 4 or (off_key is not None and tuple(A[s][off_key]) != (0, 0)):
-                    return False
-                for t in (g, x):
-                    if t.stride(3) != 1 or t.stride(2) % 4 or t.stride(1) % 4 or t.stride(0) % 4 or t.data_ptr() % 16:
-                        return False
-            return True
-
-        def bwd_cat(tag, gs, skip_key, skip_act, up_key, off_key, C_, cin_total, h, w):
-            """both column blocks of a concat layer (networks.py:318: [skip | up]) in ONE launch: same g, the skip block masked by
-            its producer, the up-sampled block placed at its offset, unmasked and without a second bias gradient"""
-            g_skip, g_up = {s: E(C_, h, w) for s in S}, {s: E(C_, h, w) for s in S}
-            probs = []
-            for s in S:
-                lay = ly(s, tag)
-                probs.append({"g": gs[s], "x": A[s][skip_key], "w": lay.w, "out": g_skip[s], "dw": grads[prefix + lay.wname],
-                              "db": grads[prefix + lay.bname], "x_bn": ly(s, skip_act).bn_nobias})
-            for s in S:
-                lay = ly(s, tag)
-                probs.append({"g": gs[s], "x": A[s][up_key], "w": lay.w, "out": g_up[s], "dw": grads[prefix + lay.wname], "db": None,
-                              "x_offset": A[s][off_key], "c0_add": C_})
-            if len(probs) <= L.PC_MAX_GROUP:
-                wb.conv3x3_bwd_group(probs, cin_total, 0)
-            else:
-                wb.conv3x3_bwd_group(probs[:len(S)], cin_total, 0)
-                wb.conv3x3_bwd_group(probs[len(S):], cin_total, 0)
-            return g_skip, g_up
-
-        def bwd8(tag, gs, x_key, act_tag, outs, c0=0, cin_total=8, off_key=None, with_db=True, pool_key=None):
-            probs = []
-            for s in S:
-                lay = ly(s, tag)
-                pr = {"g": gs[s], "x": A[s][x_key], "w": lay.w, "out": outs[s], "dw": grads[prefix + lay.wname],
-                      "db": grads[prefix + lay.bname] if with_db else None}
-                if act_tag is not None:
-                    pr["x_bn"] = ly(s, act_tag).bn_nobias
-                if off_key is not None:
-                    pr["x_offset"] = A[s][off_key]
-                if pool_key is not None:               # Down block: x is the saved pooled map, outs the (accumulated) full-resolution gradient
-                    pr["pool_act"] = A[s][pool_key]
-                probs.append(pr)
-            wb.conv3x3_bwd_group(probs, cin_total, c0)
-            return outs
-
-        def ct_bwd(tag, x_key, act_tag, gviews, outs, probs):
-            """transposed conv `tag`: weight gradient + data gradient (masked by x's producer `act_tag`) -- one launch when the
-            fused form applies (bf16: always; fp32: aligned tensors, W % 16 == 0), else the two grouped launches"""
-            xs = {s: A[s][x_key] for s in S}
-            ok = FUSED_CONV_BWD
-            if ok and not bf:
-                for s in S:
-                    if xs[s].shape[3] % 16:
-                        ok = False
-                    for t in (xs[s], gviews[s], outs[s]):
-                        if t.stride(3) != 1 or t.stride(2) % 4 or t.stride(1) % 4 or t.stride(0) % 4 or t.data_ptr() % 16:
-                            ok = False
-            if ok:
-                wb.convt2x2_bwd_group([{"x": xs[s], "g": gviews[s], "w": ly(s, tag).w, "out": outs[s], "x_bn": ly(s, act_tag).bn_nobias,
-                                        "dw": grads[prefix + ly(s, tag).wname], "db": grads[prefix + ly(s, tag).bname]} for s in S])
-            else:
-                wgts(tag, xs, gviews)
-                ops.convt2x2_dgrad_group(probs)
-
-        def up_bwd(ttag, tag, gs, z_key, z_act, ws_key, gz):
-            """composed Up block (the forward never made the up-sampled tensor): gradient of the conv's up-sampled weight half, of the
-            transposed conv's weight / bias, and (gz) of the low-resolution map, from one pass over gs"""
-            wb.up_bwd_group([{"g": gs[s], "z": A[s][z_key], "z_bn": ly(s, z_act).bn_nobias, "gz": None if gz is None else gz[s],
-                              "w": ly(s, tag).w, "wt": ly(s, ttag).w, "bt": ly(s, ttag).b, "fwd_ws": A[s][ws_key],
-                              "dw": grads[prefix + ly(s, tag).wname], "dwt": grads[prefix + ly(s, ttag).wname],
-                              "dbt": grads[prefix + ly(s, ttag).bname]} for s in S])
-
-        composed1 = all(A[s].get("ws_up1") is not None for s in S)
-        composed2 = all(A[s].get("ws_up2") is not None for s in S)
         G_f2 = {s: G[:, f0:f0 + 8] for s, _, _, f0 in self.streams}
-        if fuse8(G_f2, "f1"):
-            G_f1 = bwd8("up1b", G_f2, "f1", "up1a", {s: E(8, Hp, Wp) for s in S})
-        else:
-            wgs("up1b", "f1", G_f2)
-            G_f1 = dg("up1b", G_f2, {s: E(8, Hp, Wp) for s in S}, 0, 8, {s: A[s]["f1"] for s in S}, "up1a")
-        G_e2 = {s: E(8, H1, W1) for s in S}
-        if composed1:
-            # skip column block: data + weight gradient (and the bias gradient) in one launch; up-sampled block: up_bwd
-            G_a2 = bwd8("up1a", G_f1, "a2", "inc2", {s: E(8, Hp, Wp) for s in S}, c0=0, cin_total=16)
-            up_bwd("up1t", "up1a", G_f1, "e2", "up2b", "ws_up1", G_e2)
-        else:
-            if not encoder_no_grad and fuse8(G_f1, "a2") and fuse8(G_f1, "u1", "o1"):
-                G_a2, g_u1 = bwd_cat("up1a", G_f1, "a2", "inc2", "u1", "o1", 8, 16, Hp, Wp)
-            else:
-                wgs("up1a", "a2", G_f1, b_key="u1", off_key="o1")
-                if not encoder_no_grad:
-                    G_a2 = dg("up1a", G_f1, {s: E(8, Hp, Wp) for s in S}, 0, 8, {s: A[s]["a2"] for s in S}, "inc2")
-                g_u1 = dg("up1a", G_f1, {s: E(8, Hp, Wp) for s in S}, 8, 8)
-            probs = []
-            g_u1vs = {}
-            for s in S:
-                oy, ox = A[s]["o1"]
-                g_u1v = g_u1vs[s] = g_u1[s][:, :, oy:oy + 2 * H1, ox:ox + 2 * W1]
-                probs.append({"g": g_u1v, "w": ly(s, "up1t").w, "out": G_e2[s], "act": A[s]["e2"], "act_bn": ly(s, "up2b").bn_nobias})
-            ct_bwd("up1t", "e2", "up2b", g_u1vs, G_e2, probs)
-        if fuse8(G_e2, "e1"):
-            G_e1 = bwd8("up2b", G_e2, "e1", "up2a", {s: E(8, H1, W1) for s in S})
-        else:
-            wgs("up2b", "e1", G_e2)
-            G_e1 = dg("up2b", G_e2, {s: E(8, H1, W1) for s in S}, 0, 8, {s: A[s]["e1"] for s in S}, "up2a")
-        G_c2 = {}
-        if composed2:
-            # skip column block (16 channels @ H1 x W1): weight gradient into the first 16 input columns, data gradient masked by d1b
-            def f32_ok(g, x):
-                if x.shape[2:] != g.shape[2:] or g.shape[3] % 4:
-                    return False
-                return all(t.stride(3) == 1 and t.stride(2) % 4 == 0 and t.stride(1) % 4 == 0 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
-                           for t in (g, x))
-            if FUSED_CONV_BWD and not bf and not encoder_no_grad and 2 * len(S) <= L.PC_MAX_GROUP and \
-                    all(f32_ok(G_e1[s], A[s]["b2"]) for s in S):
-                # ... as ONE launch of the fused 8 <-> 8 backward kernel (round 4): the two 8-channel halves of the 16-channel skip tensor
-                # are two problems per stream over the same gradient (it comes out of L2 once), each writing its half of the data
-                # gradient and its column block of the weight gradient -- instead of a 16 -> 8 weight-gradient launch + an 8 -> 16
-                # data-gradient launch over the same two tensors
-                G_b2 = {s: E(16, H1, W1) for s in S}
-                probs = []
-                for s in S:
-                    lay = ly(s, "up2a")
-                    for i in (0, 1):
-                        probs.append({"g": G_e1[s], "x": A[s]["b2"][:, 8 * i:8 * i + 8], "w": lay.w, "out": G_b2[s][:, 8 * i:8 * i + 8],
-                                      "dw": grads[prefix + lay.wname], "db": grads[prefix + lay.bname] if i == 0 else None,
-                                      "x_bn": ly(s, "d1b").bn_slice(8 * i, 8), "c0_add": 8 * i})
-                wb.conv3x3_bwd_group(probs, 32, 0)
-                G_c2 = {s: E(16, H2, W2) for s in S}
-            else:
-                wb.conv3x3_group([{"a": A[s]["b2"], "g": G_e1[s], "dw": grads[prefix + ly(s, "up2a").wname],
-                                   "db": grads[prefix + ly(s, "up2a").bname]} for s in S], ly(S[0], "up2a").w.shape[0], cin_total=32)
-                if not encoder_no_grad:
-                    G_b2 = dg("up2a", G_e1, {s: E(16, H1, W1) for s in S}, 0, 16, {s: A[s]["b2"] for s in S}, "d1b")
-                    G_c2 = {s: E(16, H2, W2) for s in S}
-            up_bwd("up2t", "up2a", G_e1, "c2", "d2b", "ws_up2", None if encoder_no_grad else G_c2)
-        else:
-            if fuse and not encoder_no_grad:
-                G_b2, g_u2 = bwd_cat("up2a", G_e1, "b2", "d1b", "u2", "o2", 16, 32, H1, W1)
-            else:
-                wgs("up2a", "b2", G_e1, b_key="u2", off_key="o2")
-                if not encoder_no_grad and 2 * len(S) <= L.PC_MAX_GROUP:
-                    # both column blocks in one launch: the four problems read the same gradient
-                    G_b2, g_u2 = {s: E(16, H1, W1) for s in S}, {s: E(16, H1, W1) for s in S}
-                    ops.conv3x3_dgrad_group(
-                        [{"g": G_e1[s], "w": ly(s, "up2a").w, "out": G_b2[s], "act": A[s]["b2"], "act_bn": ly(s, "d1b").bn_nobias} for s in S] +
-                        [{"g": G_e1[s], "w": ly(s, "up2a").w, "out": g_u2[s], "c0_add": 16} for s in S], 0, 16)
-                else:
-                    if not encoder_no_grad:
-                        G_b2 = dg("up2a", G_e1, {s: E(16, H1, W1) for s in S}, 0, 16, {s: A[s]["b2"] for s in S}, "d1b")
-                    g_u2 = dg("up2a", G_e1, {s: E(16, H1, W1) for s in S}, 16, 16)
-            probs = []
-            g_u2vs = {}
-            for s in S:
-                oy, ox = A[s]["o2"]
-                g_u2v = g_u2vs[s] = g_u2[s][:, :, oy:oy + 2 * H2, ox:ox + 2 * W2]
-                if not encoder_no_grad:
-                    G_c2[s] = E(16, H2, W2)
-                    probs.append({"g": g_u2v, "w": ly(s, "up2t").w, "out": G_c2[s], "act": A[s]["c2"], "act_bn": ly(s, "d2b").bn_nobias})
-            if probs:
-                ct_bwd("up2t", "c2", "d2b", g_u2vs, G_c2, probs)
-            else:
-                wgts("up2t", {s: A[s]["c2"] for s in S}, g_u2vs)
+        G_f1 = p.conv8("up1b", G_f2, "f1", "up1a", Hp, Wp)
+        G_a2, G_e2 = p.up(UP1, G_f1, Hp, Wp, H1, W1, want_gz=True)
+        G_e1 = p.conv8("up2b", G_e2, "e1", "up2a", H1, W1)
+        G_b2, G_c2 = p.up(UP2, G_e1, H1, W1, H2, W2, want_gz=not encoder_no_grad)
         if encoder_no_grad:
-            finish()
+            p.wb.finish()
             return
-        # encoder
-        if FUSED_LEVEL2 and FUSED_LEVEL2_BWD and all(A[s].get("pb2") is not None and
-                                            ops.level2_bwd_ok(G_c2[s], A[s]["c1"], A[s]["pb2"], A[s]["b2"], G_b2[s]) for s in S):
-            # the 32 x 32 level: both weight gradients, the data gradient chain d2b -> d2a and the pooling scatter in one launch
-            # (both arithmetic modes: level2.hip / level2_cl.hip)
-            wb.level2_bwd_group([{"g2": G_c2[s], "c1": A[s]["c1"], "x": A[s]["pb2"], "w1": ly(s, "d2a").w, "w2": ly(s, "d2b").w,
-                                  "bn1": ly(s, "d2a").bn_nobias, "act": A[s]["b2"], "act_bn": ly(s, "d1b").bn_nobias, "out": G_b2[s],
-                                  "dw1": grads[prefix + ly(s, "d2a").wname], "db1": grads[prefix + ly(s, "d2a").bname],
-                                  "dw2": grads[prefix + ly(s, "d2b").wname], "db2": grads[prefix + ly(s, "d2b").bname]} for s in S])
-        else:
-            if fuse:
-                G_c1 = bwd8("d2b", G_c2, "c1", "d2a", {s: E(16, H2, W2) for s in S}, cin_total=16)
+        if not p.level2(G_c2, G_b2):
+            p.down(DOWN2, G_c2, G_b2, H2, W2)
+        p.down(DOWN1, G_b2, G_a2, H1, W1)
+        G_a1 = p.conv8("inc2", G_a2, "a1", "inc1", Hp, Wp)
+        p.first_layer(G_a1)
+        p.wb.finish()
+
+
+def _rows16(t):
+    """planar fp32 tensor with unit column stride and every row on a 16-byte boundary"""
+    return t.stride(3) == 1 and t.stride(2) % 4 == 0 and t.stride(1) % 4 == 0 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0
+
+
+# The blocks of the network as the backward pass walks them: layer tags and saved-activation keys.
+# Up: first conv (over cat[skip | up-sampled z]) and transposed conv; c = channels of the skip tensor = of z = of the up-sampled block
+_Up = collections.namedtuple("_Up", "conv convt skip skip_act up off z z_act ws c")
+UP1 = _Up("up1a", "up1t", "a2", "inc2", "u1", "o1", "e2", "up2b", "ws_up1", 8)
+UP2 = _Up("up2a", "up2t", "b2", "d1b", "u2", "o2", "c2", "d2b", "ws_up2", 16)
+# Down: the DoubleConv behind a MaxPool2d(2); cin = channels of the pooled map (`pooled`: its saved copy, `full`: what it was pooled from)
+_Down = collections.namedtuple("_Down", "conv1 conv2 mid pooled full full_act cin")
+DOWN1 = _Down("d1a", "d1b", "b1", "pa2", "a2", "inc2", 8)
+DOWN2 = _Down("d2a", "d2b", "c1", "pb2", "b2", "d1b", 16)
+
+
+class _Backward:
+    """One backward pass of a UNetEngine: its context, the launch helpers (``wgrad`` ... ``up_bwd``: one ops / WgradBatch call each, both
+    streams grouped) and one function per block of the network (``conv8``, ``up``, ``level2``, ``down``, ``first_layer``), each of which
+    decides its launch form where it stands.  Everything stays on the caller's stream: running the weight-gradient branch on a second
+    stream next to the data-gradient chain was measured three times and lost every time (both branches are bound
+    by the same memory pipe); the first stages are enqueued as the pass goes, ONE batched reduction ends it (``wb.finish``).
+
+    Which launch a conv layer gets -- two notions, never mixed:
+      ``fuse_bf16``  this run is bf16 with FUSED_CONV_BWD on: data + weight gradient of ANY layer (or column block of a concat layer, or
+                     Down block's first layer with its pooling scatter) read the same two tensors -- one launch (conv3x3_bwd_group)
+      ``f32_ok()``   fp32: the launcher's own predicate (pc_conv3x3_bwd_ok) takes these problems -- 8-channel input blocks, planar
+                     16-byte aligned rows, the input placed at (0, 0) with the gradient's extent"""
+
+    def __init__(self, eng, saved, G, grads, accumulate, encoder_no_grad, prefix, head_reduce):
+        self.eng, self.saved, self.grads, self.prefix, self.enc_ng = eng, saved, grads, prefix, encoder_no_grad
+        self.S = [s for s, _, _, _ in eng.streams]
+        assert len(self.S) <= 2             # at most two problems per stream in a launch: a group takes four
+        self.A = {s: saved[s] for s in self.S}
+        self.B, self.dev = G.shape[0], G.device
+        self.bf = L.act_dtype() == torch.bfloat16
+        self.fuse_bf16 = FUSED_CONV_BWD and self.bf
+        self.wb = ops.WgradBatch(self.dev, accumulate)
+        if head_reduce is not None:
+            self.wb.head_reduce(head_reduce)
+
+    def new(self, c, h, w):
+        return {s: L.empty_act(self.B, c, h, w, self.dev) for s in self.S}
+
+    def ly(self, s, tag):
+        return self.eng.layers[(s, tag)]
+
+    def dw(self, s, tag):
+        return self.grads[self.prefix + self.ly(s, tag).wname]
+
+    def db(self, s, tag):
+        return self.grads[self.prefix + self.ly(s, tag).bname]
+
+    def f32_ok(self, gs, xs, outs, pool_acts=None):
+        return FUSED_CONV_BWD and not self.bf and all(
+            ops.conv3x3_bwd_ok(gs[s], xs[s], outs[s], None if pool_acts is None else pool_acts[s]) for s in self.S)
+
+    # ---- launch helpers
+    def wgrad(self, tag, a_key, gs, b_key=None, off_key=None, **kw):
+        """weight gradient of layer `tag` (b_key / off_key: the second source of a concat layer and its offset)"""
+        probs = []
+        for s in self.S:
+            pr = {"a": self.A[s][a_key], "g": gs[s], "dw": self.dw(s, tag), "db": self.db(s, tag)}
+            if b_key is not None:
+                pr["b"], pr["b_offset"] = self.A[s][b_key], self.A[s][off_key]
+            probs.append(pr)
+        self.wb.conv3x3_group(probs, self.ly(self.S[0], tag).w.shape[0], **kw)
+
+    def dgrad(self, tag, gs, outs, c0, cn, acts=None, act_tag=None, pool=False, acc=False):
+        """data gradient of layer `tag` w.r.t. its input channels [c0, c0 + cn), masked by the producer `act_tag` of `acts`"""
+        probs = []
+        for s in self.S:
+            pr = {"g": gs[s], "w": self.ly(s, tag).w, "out": outs[s]}
+            if acts is not None:
+                pr["act"] = acts[s]
+                pr["act_bn"] = self.ly(s, act_tag).bn_nobias
+            probs.append(pr)
+        ops.conv3x3_dgrad_group(probs, c0, cn, pool=pool, accumulate=acc)
+        return outs
+
+    def bwd8(self, tag, gs, x_key, act_tag, outs, cin_total=8, pool_key=None, accumulate=False):
+        """data + weight gradient of layer `tag` in one launch.  pool_key: a Down block's first layer -- x is the saved pooled map,
+        outs the (accumulated) gradient of the full-resolution map it was pooled from"""
+        probs = []
+        for s in self.S:
+            pr = {"g": gs[s], "x": self.A[s][x_key], "w": self.ly(s, tag).w, "out": outs[s], "dw": self.dw(s, tag), "db": self.db(s, tag),
+                  "x_bn": self.ly(s, act_tag).bn_nobias}
+            if pool_key is not None:
+                pr["pool_act"] = self.A[s][pool_key]
+            probs.append(pr)
+        self.wb.conv3x3_bwd_group(probs, cin_total, 0, accumulate=accumulate)
+        return outs
+
+    def halves(self, gs, x_key, outs):
+        """fp32: the two 8-channel halves of a layer's 16-channel input and of its gradient, per stream: [(x half, out half)] * 2 -- or
+        None where the fused backward does not take them as problems (asked of the second half: the first is aligned wherever it is)"""
+        hv = {s: [(self.A[s][x_key][:, c:c + 8], outs[s][:, c:c + 8]) for c in (0, 8)] for s in self.S}
+        return hv if self.f32_ok(gs, {s: hv[s][1][0] for s in self.S}, {s: hv[s][1][1] for s in self.S}) else None
+
+    def bwd_halves(self, tag, gs, hv, act_tag, cin_total):
+        """fp32: a layer with a 16-channel input as ONE launch of the fused 8-channel backward (round 4) -- the two halves are two
+        problems per stream over the same gradient (it comes out of L2 once), each writing its half of the data gradient and its
+        column block of the weight gradient"""
+        probs = []
+        for s in self.S:
+            for i, (x, out) in enumerate(hv[s]):
+                probs.append({"g": gs[s], "x": x, "w": self.ly(s, tag).w, "out": out, "dw": self.dw(s, tag),
+                              "db": self.db(s, tag) if i == 0 else None, "x_bn": self.ly(s, act_tag).bn_slice(8 * i, 8), "c0_add": 8 * i})
+        self.wb.conv3x3_bwd_group(probs, cin_total, 0)
+
+    def bwd_cat(self, lv, gs, g_skip, g_up):
+        """both column blocks of a concat layer (networks.py:318: [skip | up]) in ONE launch: same g, the skip block masked by
+        its producer, the up-sampled block placed at its offset, unmasked and without a second bias gradient"""
+        probs = []
+        for s in self.S:
+            probs.append({"g": gs[s], "x": self.A[s][lv.skip], "w": self.ly(s, lv.conv).w, "out": g_skip[s], "dw": self.dw(s, lv.conv),
+                          "db": self.db(s, lv.conv), "x_bn": self.ly(s, lv.skip_act).bn_nobias})
+        for s in self.S:
+            probs.append({"g": gs[s], "x": self.A[s][lv.up], "w": self.ly(s, lv.conv).w, "out": g_up[s], "dw": self.dw(s, lv.conv),
+                          "db": None, "x_offset": self.A[s][lv.off], "c0_add": lv.c})
+        self.wb.conv3x3_bwd_group(probs, 2 * lv.c, 0)
+
+    def convt_bwd(self, tag, x_key, act_tag, gs, outs):
+        """transposed conv `tag`: weight gradient + (outs not None) data gradient masked by x's producer `act_tag` -- one launch when the
+        fused form applies (bf16: always; fp32: aligned tensors, W % 16 == 0), else the two grouped launches"""
+        S, ly = self.S, self.ly
+        xs = {s: self.A[s][x_key] for s in S}
+        if outs is not None and FUSED_CONV_BWD and (self.bf or all(
+                xs[s].shape[3] % 16 == 0 and _rows16(xs[s]) and _rows16(gs[s]) and _rows16(outs[s]) for s in S)):
+            self.wb.convt2x2_bwd_group([{"x": xs[s], "g": gs[s], "w": ly(s, tag).w, "out": outs[s], "x_bn": ly(s, act_tag).bn_nobias,
+                                         "dw": self.dw(s, tag), "db": self.db(s, tag)} for s in S])
+            return
+        self.wb.convt2x2_group([{"x": xs[s], "g": gs[s], "dw": self.dw(s, tag), "db": self.db(s, tag)} for s in S])
+        if outs is not None:
+            ops.convt2x2_dgrad_group([{"g": gs[s], "w": ly(s, tag).w, "out": outs[s], "act": xs[s], "act_bn": ly(s, act_tag).bn_nobias}
+                                      for s in S])
+
+    def up_bwd(self, lv, gs, gz):
+        """composed Up block (the forward never made the up-sampled tensor): gradient of the conv's up-sampled weight half, of the
+        transposed conv's weight / bias, and (gz) of the low-resolution map, from one pass over gs"""
+        ly = self.ly
+        self.wb.up_bwd_group([{"g": gs[s], "z": self.A[s][lv.z], "z_bn": ly(s, lv.z_act).bn_nobias, "gz": None if gz is None else gz[s],
+                               "w": ly(s, lv.conv).w, "wt": ly(s, lv.convt).w, "bt": ly(s, lv.convt).b, "fwd_ws": self.A[s][lv.ws],
+                               "dw": self.dw(s, lv.conv), "dwt": self.dw(s, lv.convt), "dbt": self.db(s, lv.convt)} for s in self.S])
+
+    # ---- the blocks (csrc/step.hip: backward issues the same launches through its bwd8 / wgrad / dgrad / up_bwd / ct_bwd)
+    def conv8(self, tag, gs, x_key, act_tag, h, w):
+        """an 8 -> 8 layer (second conv of a DoubleConv at full or half resolution): returns the gradient of its input"""
+        outs, xs = self.new(8, h, w), {s: self.A[s][x_key] for s in self.S}
+        if self.fuse_bf16 or self.f32_ok(gs, xs, outs):
+            return self.bwd8(tag, gs, x_key, act_tag, outs)
+        self.wgrad(tag, x_key, gs)
+        return self.dgrad(tag, gs, outs, 0, 8, xs, act_tag)
+
+    def up(self, lv, gs, h, w, hz, wz, want_gz):
+        """An Up block from the gradient gs of its first conv's output at (h, w): that conv over cat[skip | up-sampled z] and the
+        transposed conv that up-samples z (hz, wz).  Returns (gradient of the skip tensor, gradient of z); the first only where the
+        encoder's backward will read it or the launch writes it anyway, the second only if want_gz."""
+        S, A, c, enc_ng = self.S, self.A, lv.c, self.enc_ng
+        composed = all(A[s].get(lv.ws) is not None for s in S)
+        # (encoder_no_grad: nobody reads the skip tensor's gradient -- the composed level-1 launch writes it anyway)
+        g_skip = self.new(c, h, w) if not enc_ng or (composed and c == 8) else None
+        gz = self.new(c, hz, wz) if want_gz else None
+        skips = {s: A[s][lv.skip] for s in S}
+        if composed:
+            # the skip column block: weight gradient into the first c input columns, data gradient masked by its producer
+            if c == 8:          # (one launch whatever the regime: the composed forward's geometry implies the fused backward's)
+                self.bwd8(lv.conv, gs, lv.skip, lv.skip_act, g_skip, cin_total=2 * c)
+            elif not enc_ng and (hv := self.halves(gs, lv.skip, g_skip)):
+                self.bwd_halves(lv.conv, gs, hv, lv.skip_act, 2 * c)
             else:
-                wgs("d2b", "c1", G_c2)
-                G_c1 = dg("d2b", G_c2, {s: E(16, H2, W2) for s in S}, 0, 16, {s: A[s]["c1"] for s in S}, "d2a")
-            if fuse and all(A[s].get("pb2") is not None for s in S):
-                bwd8("d2a", G_c1, "pb2", "d1b", G_b2, cin_total=16, pool_key="b2")
+                self.wgrad(lv.conv, lv.skip, gs, cin_total=2 * c)
+                if not enc_ng:
+                    self.dgrad(lv.conv, gs, g_skip, 0, c, skips, lv.skip_act)
+            self.up_bwd(lv, gs, gz)
+            return g_skip, gz
+        ups, g_up = {s: A[s][lv.up] for s in S}, self.new(c, h, w)
+        # (fp32: the launcher declines 16-channel input blocks, so level 2 keeps the separate launches)
+        if not enc_ng and (self.fuse_bf16 or (self.f32_ok(gs, skips, g_skip) and self.f32_ok(gs, ups, g_up))):
+            self.bwd_cat(lv, gs, g_skip, g_up)
+        else:
+            self.wgrad(lv.conv, lv.skip, gs, b_key=lv.up, off_key=lv.off)
+            if enc_ng:
+                self.dgrad(lv.conv, gs, g_up, c, c)
+            elif c == 16:
+                # both column blocks in one launch: the four problems read the same gradient
+                ops.conv3x3_dgrad_group(
+                    [{"g": gs[s], "w": self.ly(s, lv.conv).w, "out": g_skip[s], "act": skips[s], "act_bn": self.ly(s, lv.skip_act).bn_nobias}
+                     for s in S] + [{"g": gs[s], "w": self.ly(s, lv.conv).w, "out": g_up[s], "c0_add": c} for s in S], 0, c)
             else:
-                if all(A[s].get("pb2") is not None for s in S):
-                    wgs("d2a", "pb2", G_c1)               # the pooled map was saved by the forward pass
-                else:
-                    wgs("d2a", "b2", G_c1, a_mode=L.PC_SRC_POOL2)
-                dg("d2a", G_c1, G_b2, 0, 16, {s: A[s]["b2"] for s in S}, "d1b", pool=True, acc=True)
-        G_b1 = {s: E(16, H1, W1) for s in S}
-        # fp32, round 6: down1's two layers through the split-operand fused backward (pc_conv3x3_bwd_group with 16 gradient channels: d1b as the
-        # two 8-channel halves of its input over the same gradient, d1a with the max-pool scatter) instead of four launches; same calls
-        # in the same order as the native executor (csrc/step.hip)
-        fused_d1 = FUSED_CONV_BWD and not bf and 2 * len(S) <= L.PC_MAX_GROUP and all(
-            A[s].get("pa2") is not None and ops.conv3x3_bwd_ok(G_b2[s], A[s]["b1"][:, 8:16], G_b1[s][:, 8:16]) and
-            ops.conv3x3_bwd_ok(G_b1[s], A[s]["pa2"], G_a2[s], pool_act=A[s]["a2"]) for s in S)
-        if fuse:
-            bwd8("d1b", G_b2, "b1", "d1a", G_b1, cin_total=16)
-        elif fused_d1:
-            probs = []
-            for s in S:
-                lay = ly(s, "d1b")
-                for i in (0, 1):
-                    probs.append({"g": G_b2[s], "x": A[s]["b1"][:, 8 * i:8 * i + 8], "w": lay.w, "out": G_b1[s][:, 8 * i:8 * i + 8],
-                                  "dw": grads[prefix + lay.wname], "db": grads[prefix + lay.bname] if i == 0 else None,
-                                  "x_bn": ly(s, "d1a").bn_slice(8 * i, 8), "c0_add": 8 * i})
-            wb.conv3x3_bwd_group(probs, 16, 0)
+                self.dgrad(lv.conv, gs, g_skip, 0, c, skips, lv.skip_act)
+                self.dgrad(lv.conv, gs, g_up, c, c)
+        views = {}
+        for s in S:
+            oy, ox = A[s][lv.off]
+            views[s] = g_up[s][:, :, oy:oy + 2 * hz, ox:ox + 2 * wz]
+        self.convt_bwd(lv.convt, lv.z, lv.z_act, views, gz)
+        return g_skip, gz
+
+    def level2(self, g_out, g_in):
+        """the 32 x 32 level: both weight gradients, the data gradient chain d2b -> d2a and the pooling scatter in one launch (both
+        arithmetic modes: level2.hip / level2_cl.hip).  False: the geometry does not qualify, nothing was enqueued"""
+        S, A, ly = self.S, self.A, self.ly
+        if not (FUSED_LEVEL2 and FUSED_LEVEL2_BWD and all(
+                A[s].get("pb2") is not None and ops.level2_bwd_ok(g_out[s], A[s]["c1"], A[s]["pb2"], A[s]["b2"], g_in[s]) for s in S)):
+            return False
+        self.wb.level2_bwd_group([{"g2": g_out[s], "c1": A[s]["c1"], "x": A[s]["pb2"], "w1": ly(s, "d2a").w, "w2": ly(s, "d2b").w,
+                                   "bn1": ly(s, "d2a").bn_nobias, "act": A[s]["b2"], "act_bn": ly(s, "d1b").bn_nobias, "out": g_in[s],
+                                   "dw1": self.dw(s, "d2a"), "db1": self.db(s, "d2a"), "dw2": self.dw(s, "d2b"), "db2": self.db(s, "d2b")}
+                                  for s in S])
+        return True
+
+    def down(self, lv, g_out, g_in, h, w):
+        """A Down block's DoubleConv at (h, w), 16 channels: the second conv, then the first conv with the max-pool scatter (+=) into
+        g_in, the gradient of the full-resolution map.  fp32 (round 6, down1): both through the split-operand fused backward -- the
+        second as the two halves of its input, the first with the scatter -- instead of four launches; the launcher declines a
+        16-channel pooled map (down2)"""
+        S, A = self.S, self.A
+        pooled = all(A[s].get(lv.pooled) is not None for s in S)              # the forward pass saved the pooled map
+        fulls = {s: A[s][lv.full] for s in S}
+        g_mid = self.new(16, h, w)
+        # hv: both layers take the fp32 fused form, or neither (the pooled map is asked first: one call settles down2)
+        hv = None
+        if not self.fuse_bf16 and pooled and self.f32_ok(g_mid, {s: A[s][lv.pooled] for s in S}, g_in, fulls):
+            hv = self.halves(g_out, lv.mid, g_mid)
+        if self.fuse_bf16:
+            self.bwd8(lv.conv2, g_out, lv.mid, lv.conv1, g_mid, cin_total=16)
+        elif hv:
+            self.bwd_halves(lv.conv2, g_out, hv, lv.conv1, 16)
         else:
-            wgs("d1b", "b1", G_b2)
-            dg("d1b", G_b2, G_b1, 0, 16, {s: A[s]["b1"] for s in S}, "d1a")
-        if fused_d1:
-            probs = []
-            for s in S:
-                lay = ly(s, "d1a")
-                probs.append({"g": G_b1[s], "x": A[s]["pa2"], "w": lay.w, "out": G_a2[s], "dw": grads[prefix + lay.wname],
-                              "db": grads[prefix + lay.bname], "x_bn": ly(s, "inc2").bn_nobias, "pool_act": A[s]["a2"]})
-            wb.conv3x3_bwd_group(probs, 8, 0, accumulate=True)
-        elif fuse and all(A[s].get("pa2") is not None for s in S):
-            bwd8("d1a", G_b1, "pa2", "inc2", G_a2, cin_total=8, pool_key="a2")
+            self.wgrad(lv.conv2, lv.mid, g_out)
+            self.dgrad(lv.conv2, g_out, g_mid, 0, 16, {s: A[s][lv.mid] for s in S}, lv.conv1)
+        if hv:
+            self.bwd8(lv.conv1, g_mid, lv.pooled, lv.full_act, g_in, cin_total=lv.cin, pool_key=lv.full, accumulate=True)
+        elif self.fuse_bf16 and pooled:
+            self.bwd8(lv.conv1, g_mid, lv.pooled, lv.full_act, g_in, cin_total=lv.cin, pool_key=lv.full)
         else:
-            if all(A[s].get("pa2") is not None for s in S):
-                wgs("d1a", "pa2", G_b1)
+            if pooled:
+                self.wgrad(lv.conv1, lv.pooled, g_mid)
             else:
-                wgs("d1a", "a2", G_b1, a_mode=L.PC_SRC_POOL2)
-            dg("d1a", G_b1, G_a2, 0, 8, {s: A[s]["a2"] for s in S}, "inc2", pool=True, acc=True)
-        if fuse8(G_a2, "a1"):
-            G_a1 = bwd8("inc2", G_a2, "a1", "inc1", {s: E(8, Hp, Wp) for s in S})
-        else:
-            wgs("inc2", "a1", G_a2)
-            G_a1 = dg("inc2", G_a2, {s: E(8, Hp, Wp) for s in S}, 0, 8, {s: A[s]["a1"] for s in S}, "inc1")
+                self.wgrad(lv.conv1, lv.full, g_mid, a_mode=L.PC_SRC_POOL2)
+            self.dgrad(lv.conv1, g_mid, g_in, 0, lv.cin, fulls, lv.full_act, pool=True, acc=True)
+
+    def first_layer(self, G_a1):
+        """inc1: weight gradients only, over whichever form of the input the forward pass saved"""
+        saved, wb = self.saved, self.wb
         if saved.get("Xp8") is not None:
             # both streams' first-layer weight gradients in ONE launch of the standard 8-channel kernel over the shared input; the
             # batched reduce writes each stream's channel window
             xp8, win = saved["Xp8"]
-            wb.conv3x3_group([{"a": xp8, "g": G_a1[s], "dw": grads[prefix + ly(s, "inc1").wname], "db": grads[prefix + ly(s, "inc1").bname],
-                               "src_window": win[s]} for s in S], 8)
-        for s, chmap, cin, f0 in (self.streams if saved.get("Xp8") is None else ()):
+            wb.conv3x3_group([{"a": xp8, "g": G_a1[s], "dw": self.dw(s, "inc1"), "db": self.db(s, "inc1"), "src_window": win[s]}
+                              for s in self.S], 8)
+            return
+        pad_top, pad_left, _, _ = saved["geom"]
+        for s, chmap, cin, _ in self.eng.streams:
+            cout = self.ly(s, "inc1").w.shape[0]
             if saved.get("Xp") is not None:
-                wg(s, "inc1", saved["Xp"][s], G_a1[s])
-            else:
-                wg(s, "inc1", X, G_a1[s], a_mode=L.PC_SRC_REFLECT, a_pad=(pad_top, pad_left), chmap=chmap, a_channels=cin)
-        finish()
+                wb.conv3x3(saved["Xp"][s], G_a1[s], cout, self.dw(s, "inc1"), self.db(s, "inc1"))
+            else:           # (saved["X"] is None only when the forward pass was fed the padded input directly: Xp_all)
+                wb.conv3x3(saved["X"], G_a1[s], cout, self.dw(s, "inc1"), self.db(s, "inc1"), a_mode=L.PC_SRC_REFLECT,
+                           a_pad=(pad_top, pad_left), chmap=chmap, a_channels=cin)
 
 
 def up_bwd_w_ok(w):
     """Widths the composed Up block's backward kernel takes (pc_conv3x3_up_bwd_ok: column tiles of 64 / 128, ragged in multiples of 8)."""
     return w >= 16 and w % 8 == 0
+
+
+def compose_ok(h, w, hz, wz, fwd_only):
+    """May the first conv of an Up block at (h, w) read the low-resolution map (hz, wz) through composed weights?  fp32, exact 2x
+    geometry; the composed BACKWARD kernel takes widths that are multiples of 8 (round 5: column tiles), a forward-only pass takes any
+    geometry the forward kernel accepts, e.g. the 2076 / 1038-wide levels of an inference window."""
+    return COMPOSED_UP and FUSED_CONV_BWD and L.act_dtype() == torch.float32 and (h, w) == (2 * hz, 2 * wz) and h % 4 == 0 and \
+        (up_bwd_w_ok(w) or fwd_only)
 
 
 def stream_channel_order(streams):
@@ -556,7 +530,7 @@ def forward_multi(engines, X, pad_top, pad_left, Hp, Wp, saves, feats_list=None,
     if logit_only is None:
         logit_only = [False] * nE
     # (fp32: any geometry -- partial strips take the per-element form of the epilogue; the bf16 kernels' form needs whole strips)
-    dot_ok = len(engines[0].streams) == 2 and (L.act_dtype() == torch.float32 or (Wp % 32 == 0 and Hp % 4 == 0))
+    dot_ok = len(engines[0].streams) == 2 and (not bf or (Wp % 32 == 0 and Hp % 4 == 0))
     logit_only = [bool(lo) and dot_ok and not saves[e] and feats_list[e] is None and engines[e].fusion_w is not None
                   for e, lo in enumerate(logit_only)]
     feats = [f if f is not None else
@@ -572,6 +546,44 @@ def forward_multi(engines, X, pad_top, pad_left, Hp, Wp, saves, feats_list=None,
             raise ValueError(f"Xp_all holds {Xp_all.shape[1]} channels; the engines expect {order} (identical for all engines)")
     keys = [(e, s) for e in range(nE) for s, _, _, _ in streams]
     ly = lambda k, t: engines[k[0]].layers[(k[1], t)]  # noqa: E731
+    fwd_only = not any(saves)          # (forward-only passes -- inference windows -- take any width the composed forward kernel accepts)
+
+    def first_layer(Xp_all):
+        """inc1.  Cin differs per stream -> one launch per stream kind, over one of three forms of the input.  With real padding the
+        padded, channel-gathered input is written ONCE and every consumer -- the first conv of each (network, stream) pair and, in
+        training, its weight gradient -- reads that: fp32 with 16-byte rows as planar channel blocks through the aligned DIRECT
+        loader (pc_reflect_pad_select), bf16 as ONE channels-last tensor with a 16-byte slot per pixel, of which every first conv
+        reads a channel window (one launch for all pairs).  Otherwise the reflect padding + channel gather stay fused in the loaders
+        (bf16 mode rounds the planar fp32 input there; unpadded inference windows need no copy).
+        Returns (a1, Xp, Xp8): the outputs and the saved form -- Xp {stream: padded gathered input} (fp32), Xp8 (shared input,
+        {stream: (first channel, channels)}) (bf16), or neither."""
+        a1 = {k: E(8, Hp, Wp) for k in keys}
+        if Xp_all is None and PADDED_INPUT and Wp <= 1024 and (Hp, Wp) != tuple(X.shape[2:]) and X.dtype == torch.float32:
+            pads = (pad_top, Hp - X.shape[2] - pad_top, pad_left, Wp - X.shape[3] - pad_left)
+            if not bf and Wp % 4 == 0:
+                Xp_all = ops.reflect_pad_select(X, stream_channel_order(streams), *pads)
+            elif bf and len(streams) == 2 and len(keys) <= L.PC_MAX_GROUP and X.is_contiguous():
+                Xp_all = ops.ingest_cl8(X, stream_channel_order(streams), None, None, *pads)
+        win, off = {}, 0
+        for s, _, cin, _ in streams:
+            win[s] = (off, cin)
+            off += cin
+        if Xp_all is not None and bf:
+            if len(keys) > L.PC_MAX_GROUP:
+                raise ValueError("bf16 shared-input first layer: at most PC_MAX_GROUP (network, stream) pairs")
+            ops.conv3x3_fwd_group([{"a": Xp_all, "w": ly(k, "inc1").w, "bn": ly(k, "inc1").bn, "out": a1[k], "w_window": win[k[1]]}
+                                   for k in keys])
+            return a1, None, (Xp_all, win)
+        Xp = None if Xp_all is None else {s: Xp_all[:, c0:c0 + cin] for s, (c0, cin) in win.items()}
+        for s, chmap, cin, _ in streams:
+            probs = [{"a": X if Xp is None else Xp[s], "w": ly(k, "inc1").w, "bn": ly(k, "inc1").bn, "out": a1[k]} for k in keys if k[1] == s]
+            if Xp is not None:
+                ops.conv3x3_fwd_group(probs)
+            else:
+                for pr in probs:
+                    pr["chmap"] = chmap
+                ops.conv3x3_fwd_group(probs, a_mode=L.PC_SRC_REFLECT, a_pad=(pad_top, pad_left), out_hw=(Hp, Wp), a_channels=cin)
+        return a1, Xp, None
 
     def conv(tag, ins, c, h, w, outs=None, bs=None, pooled=None, **kw):
         """pooled: dict to receive the MaxPool2d(2) copy of every output (written by the same epilogue) -- left empty when
@@ -597,56 +609,6 @@ def forward_multi(engines, X, pad_top, pad_left, Hp, Wp, saves, feats_list=None,
             return conv(tag, pooled, c, h, w)
         return conv(tag, full, c, h, w, a_mode=L.PC_SRC_POOL2)
 
-    # first layer: Cin differs per stream -> one launch per stream kind.  fp32 with real padding and 16-byte rows: the padded,
-    # channel-gathered input is written ONCE (pc_reflect_pad_select) and every consumer -- the first conv of each (network,
-    # stream) pair and, in training, its weight gradient -- takes the aligned DIRECT loader; otherwise the reflect padding + channel
-    # gather stay fused in the loaders (bf16 mode rounds the planar fp32 input there; unpadded inference windows need no copy).
-    a1 = {}
-    Xp = None
-    Xp8 = None             # bf16 mode: (tensor, {stream: (first channel, channels)}) -- every first conv reads a channel window of it
-    if Xp_all is None and PADDED_INPUT and L.act_dtype() == torch.float32 and Wp % 4 == 0 and Wp <= 1024 \
-            and (Hp, Wp) != tuple(X.shape[2:]) and X.dtype == torch.float32:
-        sel = stream_channel_order(streams)
-        Xp_all = ops.reflect_pad_select(X, sel, pad_top, Hp - X.shape[2] - pad_top, pad_left, Wp - X.shape[3] - pad_left)
-    if Xp_all is None and PADDED_INPUT and bf and len(streams) == 2 and len(keys) <= L.PC_MAX_GROUP and Wp <= 1024 \
-            and (Hp, Wp) != tuple(X.shape[2:]) and X.dtype == torch.float32 and X.is_contiguous():
-        # bf16 mode with real padding: the padded, stream-ordered input once as channels-last bf16 (one 16-byte slot per pixel)
-        Xp_all = ops.ingest_cl8(X, stream_channel_order(streams), None, None, pad_top, Hp - X.shape[2] - pad_top, pad_left,
-                                Wp - X.shape[3] - pad_left)
-    if Xp_all is not None and bf:
-        win, off = {}, 0
-        for s, chmap, cin, f0 in streams:
-            win[s] = (off, cin)
-            off += cin
-        Xp8 = (Xp_all, win)
-        if len(keys) > L.PC_MAX_GROUP:
-            raise ValueError("bf16 shared-input first layer: at most PC_MAX_GROUP (network, stream) pairs")
-        for k in keys:
-            a1[k] = E(8, Hp, Wp)
-        ops.conv3x3_fwd_group([{"a": Xp_all, "w": ly(k, "inc1").w, "bn": ly(k, "inc1").bn, "out": a1[k], "w_window": win[k[1]]}
-                               for k in keys])
-    elif Xp_all is not None:
-        Xp, off = {}, 0
-        for s, chmap, cin, f0 in streams:
-            Xp[s] = Xp_all[:, off:off + cin]
-            off += cin
-    for s, chmap, cin, f0 in (streams if Xp8 is None else ()):
-        ks = [k for k in keys if k[1] == s]
-        probs = []
-        for k in ks:
-            a1[k] = E(8, Hp, Wp)
-            if Xp is not None:
-                probs.append({"a": Xp[s], "w": ly(k, "inc1").w, "bn": ly(k, "inc1").bn, "out": a1[k]})
-            else:
-                probs.append({"a": X, "w": ly(k, "inc1").w, "bn": ly(k, "inc1").bn, "out": a1[k], "chmap": chmap})
-        if Xp is not None:
-            ops.conv3x3_fwd_group(probs)
-        else:
-            ops.conv3x3_fwd_group(probs, a_mode=L.PC_SRC_REFLECT, a_pad=(pad_top, pad_left), out_hw=(Hp, Wp), a_channels=cin)
-    pa2, pb2 = {}, {}
-    a2 = conv("inc2", a1, 8, Hp, Wp, pooled=pa2)
-    b1 = down("d1a", a2, pa2, 16, H1, W1)
-    b2 = conv("d1b", b1, 16, H1, W1, pooled=pb2)
     def convt(tag, ins, c, h, w):
         outs = {k: E(c, h, w) for k in keys}
         ops.convt2x2_group([{"x": ins[k], "w": ly(k, tag).w, "bias": ly(k, tag).b, "out": outs[k]} for k in keys])
@@ -654,46 +616,54 @@ def forward_multi(engines, X, pad_top, pad_left, Hp, Wp, saves, feats_list=None,
 
     def up_conv(tag, ttag, skip, z, c, h, w):
         """first conv of an Up block straight from the low-resolution map z (composed weights): (outs, workspaces), or None"""
-        if not (COMPOSED_UP and FUSED_CONV_BWD and L.act_dtype() == torch.float32 and (h, w) == (2 * z[keys[0]].shape[2], 2 * z[keys[0]].shape[3])):
+        if not compose_ok(h, w, z[keys[0]].shape[2], z[keys[0]].shape[3], fwd_only):
             return None
         outs = {k: E(c, h, w) for k in keys}
-        # (the composed BACKWARD kernel takes widths that are multiples of 8 (round 5: column tiles); a forward-only pass takes any
-        # geometry the forward kernel accepts, e.g. the 2076 / 1038-wide levels of an inference window)
-        if not all(ops.conv3x3_up_fwd_ok(skip[k], z[k], outs[k]) for k in keys) or (any(saves) and not up_bwd_w_ok(w)):
+        if not all(ops.conv3x3_up_fwd_ok(skip[k], z[k], outs[k]) for k in keys):
             return None
         ws = ops.conv3x3_up_fwd_group([{"skip": skip[k], "z": z[k], "w": ly(k, tag).w, "wt": ly(k, ttag).w, "bt": ly(k, ttag).b,
                                         "bn": ly(k, tag).bn, "out": outs[k], "ws": precomp.get((tag, k))} for k in keys])
         return outs, dict(zip(keys, ws))
 
-    # with the composed first conv nobody reads the up-sampled tensors u2 / u1 -- not even the backward pass (up_bwd.hip)
-    fwd_only = not any(saves)          # (forward-only passes -- inference windows -- take any width the composed forward kernel accepts)
-    compose2 = COMPOSED_UP and FUSED_CONV_BWD and L.act_dtype() == torch.float32 and (H1, W1) == (2 * H2, 2 * W2) and H1 % 4 == 0 and \
-        (up_bwd_w_ok(W1) or fwd_only)
-    compose1 = COMPOSED_UP and FUSED_CONV_BWD and L.act_dtype() == torch.float32 and (Hp, Wp) == (2 * H1, 2 * W1) and Hp % 4 == 0 and \
-        (up_bwd_w_ok(Wp) or fwd_only)
-    precomp = {}
-    if compose1 and compose2 and 2 * len(keys) <= 2 * L.PC_MAX_GROUP:
-        # the composed operand images of both Up levels of all (network, stream) pairs: one launch (they only depend on the weights)
+    def compose_weights():
+        """the composed operand images of both Up levels of all (network, stream) pairs: one launch (they only depend on the weights)"""
         lst = [("up2a", "up2t", k) for k in keys] + [("up1a", "up1t", k) for k in keys]
         wss = ops.conv3x3_up_compose([{"w": ly(k, t).w, "wt": ly(k, tt).w, "bt": ly(k, tt).b} for t, tt, k in lst])
-        precomp = {(t, k): w_ for (t, tt, k), w_ in zip(lst, wss)}
-    u2 = None
-    if FUSED_LEVEL2 and pb2 and (H2, W2) == (32, 32):           # (both arithmetic modes: level2.hip / level2_cl.hip)
-        # whole-tile residency: one workgroup per (tile, network-stream) runs down2's two convs and up2's transposed conv with
-        # the 16 x 32 x 32 maps in LDS; c1 / c2 / u2 go to HBM only for whoever reads them
+        return {(t, k): w_ for (t, tt, k), w_ in zip(lst, wss)}
+
+    def level2(pb2, compose2):
+        """fp32 / bf16 (level2.hip / level2_cl.hip): whole-tile residency at 32 x 32 -- one workgroup per (tile, network-stream) runs
+        down2's two convs and up2's transposed conv with the 16 x 32 x 32 maps in LDS; c1 / c2 / u2 go to HBM only for whoever reads
+        them.  Returns (c1, c2, u2), or None when the geometry does not qualify"""
+        if not (FUSED_LEVEL2 and pb2 and (H2, W2) == (32, 32)):
+            return None
         u2 = {k: (None if compose2 else E(16, 2 * H2, 2 * W2)) for k in keys}
-        if all(ops.level2_fwd_ok(pb2[k], u2[k]) for k in keys):
-            c1 = {k: (E(16, H2, W2) if saves[k[0]] else None) for k in keys}
-            c2 = {k: (E(16, H2, W2) if (saves[k[0]] or compose2) else None) for k in keys}
-            ops.level2_fwd_group([{"x": pb2[k], "w1": ly(k, "d2a").w, "bn1": ly(k, "d2a").bn, "w2": ly(k, "d2b").w,
-                                   "bn2": ly(k, "d2b").bn, "wt": ly(k, "up2t").w, "bt": ly(k, "up2t").b, "c1": c1[k], "c2": c2[k],
-                                   "u2": u2[k]} for k in keys])
-        else:
-            u2 = None
-    if u2 is None:
+        if not all(ops.level2_fwd_ok(pb2[k], u2[k]) for k in keys):
+            return None
+        c1 = {k: (E(16, H2, W2) if saves[k[0]] else None) for k in keys}
+        c2 = {k: (E(16, H2, W2) if (saves[k[0]] or compose2) else None) for k in keys}
+        ops.level2_fwd_group([{"x": pb2[k], "w1": ly(k, "d2a").w, "bn1": ly(k, "d2a").bn, "w2": ly(k, "d2b").w,
+                               "bn2": ly(k, "d2b").bn, "wt": ly(k, "up2t").w, "bt": ly(k, "up2t").b, "c1": c1[k], "c2": c2[k],
+                               "u2": u2[k]} for k in keys])
+        return c1, c2, u2
+
+    # with the composed first conv nobody reads the up-sampled tensors u2 / u1 -- not even the backward pass (up_bwd.hip)
+    compose2 = compose_ok(H1, W1, H2, W2, fwd_only)
+    compose1 = compose_ok(Hp, Wp, H1, W1, fwd_only)
+    precomp, pa2, pb2 = {}, {}, {}
+    a1, Xp, Xp8 = first_layer(Xp_all)
+    a2 = conv("inc2", a1, 8, Hp, Wp, pooled=pa2)
+    b1 = down("d1a", a2, pa2, 16, H1, W1)
+    b2 = conv("d1b", b1, 16, H1, W1, pooled=pb2)
+    if compose1 and compose2 and 2 * len(keys) <= 2 * L.PC_MAX_GROUP:
+        precomp = compose_weights()
+    r = level2(pb2, compose2)
+    if r is None:
         c1 = down("d2a", b2, pb2, 16, H2, W2)
         c2 = conv("d2b", c1, 16, H2, W2)
         u2 = {k: None for k in keys}
+    else:
+        c1, c2, u2 = r
     o2 = ((H1 - 2 * H2) // 2, (W1 - 2 * W2) // 2)
     r = up_conv("up2a", "up2t", b2, c2, 8, H1, W1) if compose2 else None
     ws_up2 = {}
