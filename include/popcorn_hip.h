@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define PC_ABI_VERSION 9
+#define PC_ABI_VERSION 10
 
 /* error codes (negative; positive values are hipError_t) */
 #define PC_EINVAL (-1)     /* bad argument / unsupported channel combination */
@@ -282,13 +282,11 @@ void pc_debug_conv(int dbg, int max_grid);
 void pc_debug_conv_ts(void* buf);
 
 /* ---- conv3x3 weight/bias gradient.  x = forward input (a,b sources as in fwd), g as in dgrad.
- * dw: [Cout][Cin][3][3], db: [Cout]; (=|+=).  ws: workspace of pc_conv3x3_wgrad_ws_bytes(). */
+ * Two stages: one partial (dW[co][ci][3][3] + db[co] of the workgroup's tiles) per workgroup into ws, a workspace of
+ * pc_conv3x3_wgrad_ws_bytes() per problem; *nwg_out = number of partials.  pc_wgrad_reduce_batch then finishes the partials
+ * of many layers in ONE launch: dw [Cout][Cin][3][3], db [Cout]; (=|+=). */
 int64_t pc_conv3x3_wgrad_ws_bytes(int Cin, int Cout);
-int pc_conv3x3_wgrad(const pc_src* a, const pc_src* b, const pc_src* g, float* dw, float* db, int accumulate,
-                     void* ws, int B, int H, int W, int Cin, int Cout, void* stream);
-
-/* Deferred form: stage 1 only (one partial per workgroup into ws, *nwg_out = number of partials); the second stage of
- * many layers is then done by ONE pc_wgrad_reduce_batch launch.  Each deferred call needs its own ws slice. */
+/* one problem, with the grid of a lone problem (more workgroups than a group gives each of its problems) */
 int pc_conv3x3_wgrad_partial(const pc_src* a, const pc_src* b, const pc_src* g, void* ws, int B, int H, int W,
                              int Cin, int Cout, int* nwg_out, void* stream);
 /* grouped first stage (e.g. the SAR and optical streams of a layer): one launch, each problem with its own ws slice;
@@ -296,9 +294,7 @@ int pc_conv3x3_wgrad_partial(const pc_src* a, const pc_src* b, const pc_src* g, 
 typedef struct pc_conv_wgrad_desc { const pc_src* a; const pc_src* b; const pc_src* g; void* ws; } pc_conv_wgrad_desc;
 int pc_conv3x3_wgrad_partial_group(int n, const pc_conv_wgrad_desc* d, int B, int H, int W, int Cin, int Cout,
                                    int* nwg_out, void* stream);
-int pc_convt2x2_wgrad_partial(const pc_src* x, const pc_src* g, void* ws, int B, int H, int W, int C, int* nwg_out,
-                              void* stream);
-/* grouped form: n <= PC_MAX_GROUP problems of identical geometry (the two streams of an Up block) in one launch; every
+/* transposed conv (dw [Cin][Cout][2][2], db [Cout]): n <= PC_MAX_GROUP problems of identical geometry (the two streams of an Up block) in one launch; every
  * problem gets *nwg_out partials in its own ws */
 typedef struct pc_convt_wgrad_desc { const pc_src* x; const pc_src* g; void* ws; } pc_convt_wgrad_desc;
 int pc_convt2x2_wgrad_partial_group(int n, const pc_convt_wgrad_desc* d, int B, int H, int W, int C, int* nwg_out,
@@ -381,8 +377,6 @@ typedef struct pc_convt_dgrad_desc {
 int pc_convt2x2_fwd_group(int n, const pc_convt_fwd_desc* d, int B, int H, int W, int C, void* stream);
 int pc_convt2x2_dgrad_group(int n, const pc_convt_dgrad_desc* d, int B, int H, int W, int C, void* stream);
 int64_t pc_convt2x2_wgrad_ws_bytes(int C);
-int pc_convt2x2_wgrad(const pc_src* x, const pc_src* g, float* dw, float* db, int accumulate, void* ws,
-                      int B, int H, int W, int C, void* stream);
 
 /* ---- fusion_out_conv (1x1, 16->1) + sigmoid + crop: create_building_score's tail, popcorn.py:301,317-320;
  * networks.py:232,323-330.  feat: B x C x Hp x Wp with C = 16 (fusion_out_conv) or 8 (sar_out_conv / optical_out_conv of the
@@ -530,9 +524,6 @@ int pc_loss_fwd_bwd(const float* popcount, const float* y, const double* stats, 
                     float scale_regularization, float lam_weak, float inv_B, int B,
                     float* loss_out, float* g_popcount, float* g_scale_const, void* stream);
 
-/* L2 norm of a flat gradient buffer (torch.nn.utils.clip_grad_norm_'s total_norm, run_train.py:233-234); deterministic. */
-int pc_grad_norm(const float* g, int n, float* norm_out, void* stream);
-
 /* Parameter groups of the flat buffer for the Adam step.  The reference gives the encoder (limit1) or the whole U-Net
  * (limit2) no gradient on large samples (run_train.py:191-198; networks.py:124-132), and torch.optim.Adam skips a
  * parameter whose .grad is None entirely: no weight decay, no moment update, no per-parameter step increment.  The flat
@@ -548,16 +539,11 @@ typedef struct pc_adam_groups {
     int32_t active_mask;
 } pc_adam_groups;
 
-/* clip_grad_norm_(max_norm) + torch.optim.Adam step over flat buffers (run_train.py:82-90,233-238).  Weight decay
- * (L2, added to the gradient) applies to elements [0, n_decay) only.  hyper_dev: device float[1] {lr};
- * step_dev: device int32 step counter(s), incremented by the call (groups == NULL: one counter, everything updated).
- * max_norm <= 0 or norm_dev == NULL: no clipping. */
-int pc_adam_clip_step(float* p, const float* g, float* m, float* v, int n, int n_decay, const float* hyper_dev,
-                      float weight_decay, float beta1, float beta2, float eps, float max_norm,
-                      const float* norm_dev, int32_t* step_dev, const pc_adam_groups* groups, void* stream);
-
-/* The same in ONE launch: every workgroup computes the total norm of g itself (written to norm_out_dev if non-NULL), then
- * clips and updates; max_norm <= 0: no clipping.  g must be 16-byte aligned.  Must not run concurrently with itself on
+/* clip_grad_norm_(max_norm) + torch.optim.Adam step over flat buffers (run_train.py:82-90,233-238) in ONE launch: every
+ * workgroup computes the total L2 norm of g itself (clip_grad_norm_'s total_norm, deterministic; written to norm_out_dev if
+ * non-NULL), then clips and updates; max_norm <= 0: no clipping.  Weight decay (L2, added to the gradient) applies to elements
+ * [0, n_decay) only.  hyper_dev: device float[1] {lr}; step_dev: device int32 step counter(s), incremented by the call
+ * (groups == NULL: one counter, everything updated).  g must be 16-byte aligned.  Must not run concurrently with itself on
  * two streams of one process (a device-side ticket decides which workgroup advances the step counter). */
 int pc_adam_clip_step_fused(float* p, const float* g, float* m, float* v, int n, int n_decay, const float* hyper_dev,
                             float weight_decay, float beta1, float beta2, float eps, float max_norm,

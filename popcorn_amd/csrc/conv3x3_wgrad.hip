@@ -12,8 +12,10 @@
 //
 // A workgroup stages a (CINC x 18 x 34) input halo tile and the (COUT x 16 x 32) gradient tile in LDS with strides
 // chosen so both fragment reads are bank-conflict free, accumulates over a persistent loop of tiles in registers,
-// and writes ONE partial per workgroup; a second kernel reduces the partials in a fixed order (deterministic --
-// no atomics).
+// and writes ONE partial per workgroup; wgrad_reduce_batch_kernel then reduces the partials of any number of layers (these,
+// the transposed convs', the composed Up blocks', the head's) in a fixed order in one launch (deterministic -- no atomics).
+// Host side: wgrad_partial -> launch_wgrad (one launcher for single problems and groups) -> launch_wgrad_wave, or the
+// generic workgroup-tile kernel for sources the wave kernels do not take (unaligned, W % 4 != 0).
 #include "common.h"
 #include "tile_loader.h"
 
@@ -655,64 +657,9 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_cl_kernel(const WgradGroup 
     }
 }
 
-struct WreduceArgs {
-    const float* partial;
-    int nwg;              // partials per chunk
-    int nchunk;
-    float* dw;            // [COUT][CIN][3][3]
-    float* db;            // [COUT]
-    int Cin;
-    int accumulate;
-};
-
-// 16 outputs x 16 slices per block: every thread sums nwg/16 workgroup partials with 4 independent loads in flight,
-// then the 16 slices combine in a fixed order (deterministic).  (The first version used 4 slices and a serial
-// dependent loop: 40 us per call for a 2 KB result -- profiles/r1_v0.)
-template <int CINC, int COUT>
-__global__ __launch_bounds__(256) void conv3x3_wgrad_reduce_kernel(const WreduceArgs p) {
-    using Cfg = WgradCfg<CINC, COUT>;
-    __shared__ float red[256];
-    const int tid = threadIdx.x;
-    const int slice = tid >> 4, o = blockIdx.x * 16 + (tid & 15);
-    const int n_w = COUT * p.Cin * 9;
-    const int n_out = n_w + COUT;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    if (o < n_w) {
-        const int tap = o % 9, ci = (o / 9) % p.Cin, co = o / (9 * p.Cin);
-        const int dy = tap / 3, dx = tap % 3;
-        const int chunk = ci / CINC, cil = ci % CINC;
-        (void)dy; (void)dx;
-        const int oc = co * (CINC * 9) + cil * 9 + tap;       // compacted partial: dW[co][cil][tap]
-        const float* base = p.partial + (int64_t)chunk * p.nwg * Cfg::EC;
-        int w = slice;
-        for (; w + 48 < p.nwg; w += 64) {
-            const float* q0 = base + (int64_t)w * Cfg::EC;
-            s0 += q0[oc];
-            s1 += q0[(int64_t)16 * Cfg::EC + oc];
-            s2 += q0[(int64_t)32 * Cfg::EC + oc];
-            s3 += q0[(int64_t)48 * Cfg::EC + oc];
-        }
-        for (; w < p.nwg; w += 16) s0 += base[(int64_t)w * Cfg::EC + oc];
-    } else if (o < n_out) {
-        // bias: chunk 0 only
-        const int co = o - n_w;
-        for (int w = slice; w < p.nwg; w += 16) s0 += p.partial[(int64_t)w * Cfg::EC + COUT * CINC * 9 + co];
-    }
-    red[tid] = (s0 + s1) + (s2 + s3);
-    __syncthreads();
-    if (tid < 16 && o < n_out) {
-        float tot = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) tot += red[k * 16 + tid];
-        float* dstp = o < n_w ? p.dw + o : p.db + (o - n_w);
-        if (o >= n_w && p.db == nullptr) return;
-        *dstp = p.accumulate ? *dstp + tot : tot;
-    }
-}
-
 // geometry + loader classification of one problem; returns the loader kind (0 generic, 1 direct, 2 pool, 3 reflect)
 template <int CINC, int COUT>
-int prepare_wgrad(WgradArgs& p, int Cin, void* ws, int& nwg, int& nchunk) {
+int prepare_wgrad(WgradArgs& p, int Cin, int& nwg, int& nchunk) {
     p.tiles_x = (p.W + TW - 1) / TW;
     p.tiles_y = (p.H + TH - 1) / TH;
     p.ntiles = p.B * p.tiles_x * p.tiles_y;
@@ -721,7 +668,6 @@ int prepare_wgrad(WgradArgs& p, int Cin, void* ws, int& nwg, int& nchunk) {
     nchunk = Cin / CINC;
     nwg = p.ntiles < MAX_WG / nchunk ? p.ntiles : MAX_WG / nchunk;
     if (nwg < 1) nwg = 1;
-    p.partial = reinterpret_cast<float*>(ws);
     p.ci0 = 0;
     p.bf = g_pc_precision == PC_PREC_BF16;
     // container types follow the mode: bf16 mode = bf16 activations and gradients (the reflect-padded model input stays fp32)
@@ -800,69 +746,53 @@ int launch_wgrad_wave(const WgradGroup& g, int n, int kind, int& nwg, int nchunk
     return 0;
 }
 
+// First stage of n problems of identical geometry (blockIdx.z selects): ONE launch when they share the loader kind and it has a
+// wave-private form, else one launch per problem.  Writes the partials, returns their number per chunk in *nwg_out (per-problem
+// launches: of the last problem).
+// single: the grid rule of a lone problem (the first layers: their Cin differs per stream, so they cannot be grouped).  It gets the
+// workgroups a grouped launch would spread over its problems -- as many partials as the workspace slice holds (it is sized for the
+// largest layer), at most PC_WGRAD_SINGLE_WG; launch_wgrad_wave caps it to one resident round.  The per-problem launches of a mixed
+// group use it too.
 template <int CINC, int COUT>
-int launch_wgrad(WgradArgs& p, int Cin, float* dw, float* db, int accumulate, void* ws, hipStream_t stream,
-                 int* nwg_out = nullptr) {
+int launch_wgrad(WgradArgs* ps, int n, int Cin, bool single, hipStream_t stream, int* nwg_out) {
     using Cfg = WgradCfg<CINC, COUT>;
-    int nwg, nchunk;
-    const int kind = prepare_wgrad<CINC, COUT>(p, Cin, ws, nwg, nchunk);
-    if (kind < 0) return PC_EINVAL;
-    if (kind != 0) {
-        // A single-problem launch (the first layers: their Cin differs per stream, so they cannot be grouped) gets the
-        // workgroups a grouped launch would spread over its problems -- as many partials as the workspace slice holds
-        // (it is sized for the largest layer), at most PC_WGRAD_SINGLE_WG; launch_wgrad_wave caps it to one resident round.
-        const int64_t room = (int64_t)MAX_WG * (2 * 12 * 256 + 128) / ((int64_t)Cfg::EC * nchunk);
-        int want = PC_WGRAD_SINGLE_WG;
-        if (want > room) want = (int)room;
-        if (want > p.ntiles) want = p.ntiles;
-        if (want > nwg) nwg = want;
-        WgradGroup g{};
-        g.pr[0] = p;
-        const int rc = launch_wgrad_wave<CINC, COUT>(g, 1, kind, nwg, nchunk, stream);
+    WgradGroup g{};
+    int nwg = 0, nchunk = 0, kind0 = -1;
+    bool same = true;
+    for (int i = 0; i < n; ++i) {
+        int w, c;
+        const int k = prepare_wgrad<CINC, COUT>(ps[i], Cin, w, c);
+        if (k < 0) return PC_EINVAL;
+        if (i == 0) { kind0 = k; nwg = w; nchunk = c; }
+        same = same && k == kind0 && w == nwg;
+        g.pr[i] = ps[i];
+    }
+    if (n > 1 && !(same && kind0 != 0)) {
+        for (int i = 0; i < n; ++i) {
+            const int rc = launch_wgrad<CINC, COUT>(ps + i, 1, Cin, true, stream, nwg_out);
+            if (rc) return rc;
+        }
+        return 0;
+    }
+    if (kind0 != 0) {
+        if (single) {
+            const int64_t room = (int64_t)MAX_WG * (2 * 12 * 256 + 128) / ((int64_t)Cfg::EC * nchunk);
+            int want = PC_WGRAD_SINGLE_WG;
+            if (want > room) want = (int)room;
+            if (want > ps[0].ntiles) want = ps[0].ntiles;
+            if (want > nwg) nwg = want;
+        }
+        const int rc = launch_wgrad_wave<CINC, COUT>(g, n, kind0, nwg, nchunk, stream);
         if (rc) return rc;
     } else {
         const size_t ldsb = (size_t)Cfg::LDS_FLOATS * sizeof(float);
         static pc_launch_setup setup;
         const hipError_t e = setup(reinterpret_cast<const void*>(&conv3x3_wgrad_kernel<CINC, COUT>), ldsb, PC_SETUP_LDS, __PRETTY_FUNCTION__);
         if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL((conv3x3_wgrad_kernel<CINC, COUT>), dim3(nwg, nchunk), dim3(256), ldsb, stream, p);
+        hipLaunchKernelGGL((conv3x3_wgrad_kernel<CINC, COUT>), dim3(nwg, nchunk), dim3(256), ldsb, stream, ps[0]);
         PC_CHECK_LAUNCH();
     }
-    if (nwg_out) {            // deferred: the caller batches the reductions of many layers into one launch
-        *nwg_out = nwg;
-        return 0;
-    }
-    WreduceArgs r{};
-    r.partial = p.partial; r.nwg = nwg; r.nchunk = nchunk; r.dw = dw; r.db = db; r.Cin = Cin; r.accumulate = accumulate;
-    const int n_out = COUT * Cin * 9 + COUT;
-    hipLaunchKernelGGL((conv3x3_wgrad_reduce_kernel<CINC, COUT>), dim3((n_out + 15) / 16), dim3(256), 0, stream, r);
-    PC_CHECK_LAUNCH();
-    return 0;
-}
-
-// grouped first stage: one launch for all problems when they share the loader kind, else one launch each
-template <int CINC, int COUT>
-int launch_wgrad_group(WgradArgs* ps, void* const* wss, int n, int Cin, hipStream_t stream, int* nwg_out) {
-    WgradGroup g{};
-    int nwg = 0, nchunk = 0, kind0 = -1;
-    bool same = true;
-    for (int i = 0; i < n; ++i) {
-        int w, c;
-        const int k = prepare_wgrad<CINC, COUT>(ps[i], Cin, wss[i], w, c);
-        if (k < 0) return PC_EINVAL;
-        if (i == 0) { kind0 = k; nwg = w; nchunk = c; }
-        same = same && k == kind0 && w == nwg;
-        g.pr[i] = ps[i];
-    }
-    if (same && kind0 != 0) {
-        const int rc = launch_wgrad_wave<CINC, COUT>(g, n, kind0, nwg, nchunk, stream);
-        *nwg_out = nwg;
-        return rc;
-    }
-    for (int i = 0; i < n; ++i) {
-        const int rc = launch_wgrad<CINC, COUT>(ps[i], Cin, nullptr, nullptr, 0, wss[i], stream, nwg_out);
-        if (rc) return rc;
-    }
+    *nwg_out = nwg;
     return 0;
 }
 
@@ -1056,11 +986,11 @@ extern "C" int pc_wgrad_reduce_batch(int n, const pc_wgrad_reduce_desc* d, void*
     return 0;
 }
 
-extern "C" int pc_conv3x3_wgrad_partial_group(int n, const pc_conv_wgrad_desc* d, int B, int H, int W, int Cin, int Cout,
-                                              int* nwg_out, void* stream) {
+namespace {
+// the descriptors of n problems -> kernel arguments -> the instantiation of (Cin, Cout)
+int wgrad_partial(int n, const pc_conv_wgrad_desc* d, int B, int H, int W, int Cin, int Cout, bool single, int* nwg_out, void* stream) {
     if (n < 1 || n > PC_MAX_GROUP || !d || !nwg_out) return PC_EINVAL;
     WgradArgs ps[PC_MAX_GROUP];
-    void* wss[PC_MAX_GROUP];
     for (int i = 0; i < n; ++i) {
         if (!d[i].a || !d[i].g || !d[i].ws) return PC_EINVAL;
         ps[i] = WgradArgs{};
@@ -1069,46 +999,25 @@ extern "C" int pc_conv3x3_wgrad_partial_group(int n, const pc_conv_wgrad_desc* d
         ps[i].g = *d[i].g;
         if (ps[i].a.C + ps[i].b.C != Cin || d[i].g->C != Cout) return PC_EINVAL;
         ps[i].B = B; ps[i].H = H; ps[i].W = W;
-        wss[i] = d[i].ws;
+        ps[i].partial = reinterpret_cast<float*>(d[i].ws);
     }
     hipStream_t st = (hipStream_t)stream;
 #define PC_CASE(ci, co) \
-    if (Cin == ci && Cout == co) return launch_wgrad_group<cinc_of(ci), co>(ps, wss, n, Cin, st, nwg_out);
+    if (Cin == ci && Cout == co) return launch_wgrad<cinc_of(ci), co>(ps, n, Cin, single, st, nwg_out);
     PC_CASE(2, 8) PC_CASE(4, 8) PC_CASE(8, 8) PC_CASE(16, 8) PC_CASE(32, 8) PC_CASE(8, 16) PC_CASE(16, 16)
 #undef PC_CASE
     return PC_EINVAL;
 }
+}  // namespace
 
+extern "C" int pc_conv3x3_wgrad_partial_group(int n, const pc_conv_wgrad_desc* d, int B, int H, int W, int Cin, int Cout,
+                                              int* nwg_out, void* stream) {
+    return wgrad_partial(n, d, B, H, W, Cin, Cout, false, nwg_out, stream);
+}
+
+// a group of one with the single-problem grid rule
 extern "C" int pc_conv3x3_wgrad_partial(const pc_src* a, const pc_src* b, const pc_src* g, void* ws, int B, int H, int W,
                                         int Cin, int Cout, int* nwg_out, void* stream) {
-    if (!a || !g || !ws || !nwg_out) return PC_EINVAL;
-    WgradArgs p{};
-    p.a = *a;
-    if (b) p.b = *b;
-    p.g = *g;
-    if (p.a.C + p.b.C != Cin || g->C != Cout) return PC_EINVAL;
-    p.B = B; p.H = H; p.W = W;
-    hipStream_t st = (hipStream_t)stream;
-#define PC_CASE(ci, co) \
-    if (Cin == ci && Cout == co) return launch_wgrad<cinc_of(ci), co>(p, Cin, nullptr, nullptr, 0, ws, st, nwg_out);
-    PC_CASE(2, 8) PC_CASE(4, 8) PC_CASE(8, 8) PC_CASE(16, 8) PC_CASE(32, 8) PC_CASE(8, 16) PC_CASE(16, 16)
-#undef PC_CASE
-    return PC_EINVAL;
-}
-
-extern "C" int pc_conv3x3_wgrad(const pc_src* a, const pc_src* b, const pc_src* g, float* dw, float* db, int accumulate,
-                                void* ws, int B, int H, int W, int Cin, int Cout, void* stream) {
-    if (!a || !g || !dw || !ws) return PC_EINVAL;
-    WgradArgs p{};
-    p.a = *a;
-    if (b) p.b = *b;
-    p.g = *g;
-    if (p.a.C + p.b.C != Cin || g->C != Cout) return PC_EINVAL;
-    p.B = B; p.H = H; p.W = W;
-    hipStream_t st = (hipStream_t)stream;
-#define PC_CASE(ci, co) \
-    if (Cin == ci && Cout == co) return launch_wgrad<cinc_of(ci), co>(p, Cin, dw, db, accumulate, ws, st);
-    PC_CASE(2, 8) PC_CASE(4, 8) PC_CASE(8, 8) PC_CASE(16, 8) PC_CASE(32, 8) PC_CASE(8, 16) PC_CASE(16, 16)
-#undef PC_CASE
-    return PC_EINVAL;
+    const pc_conv_wgrad_desc d{a, b, g, ws};
+    return wgrad_partial(1, &d, B, H, W, Cin, Cout, true, nwg_out, stream);
 }

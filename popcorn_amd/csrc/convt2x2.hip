@@ -582,58 +582,6 @@ __global__ __launch_bounds__(256) void convt2x2_wgrad_kernel(const CtGroup grp_)
         part[NBK * 256 + e] = ((lds[e] + lds[NBK * 64 + e]) + lds[2 * NBK * 64 + e]) + lds[3 * NBK * 64 + e];
 }
 
-struct CtReduceArgs {
-    const float* partial;
-    int nwg;
-    float* dw;
-    float* db;
-    int accumulate;
-};
-
-template <int C>
-__global__ __launch_bounds__(256) void convt2x2_wgrad_reduce_kernel(const CtReduceArgs p) {
-    constexpr int NBK = C / 4;
-    using Cfg = CtWgradCfg<C>;
-    __shared__ float red[256];
-    const int tid = threadIdx.x;
-    const int slice = tid >> 4, o = blockIdx.x * 16 + (tid & 15);     // 16 outputs x 16 slices
-    constexpr int n_w = C * C * 4, n_out = n_w + C;
-    float s0 = 0.f, s1 = 0.f;
-    if (o < n_w) {
-        const int ci = o / (4 * C), ng = o % (4 * C);     // dw[ci][co][a][b], ng = co*4 + a*2 + b
-        const int e = (((ng >> 4) * 64) + (ci >> 2) * 16 + (ng & 15)) * 4 + (ci & 3);
-        int w = slice;
-        for (; w + 16 < p.nwg; w += 32) {
-            s0 += p.partial[(int64_t)w * Cfg::E + e];
-            s1 += p.partial[(int64_t)(w + 16) * Cfg::E + e];
-        }
-        for (; w < p.nwg; w += 16) s0 += p.partial[(int64_t)w * Cfg::E + e];
-    } else if (o < n_out) {
-        const int co = o - n_w;
-        for (int w = slice; w < p.nwg; w += 16) {
-            const float* q = p.partial + (int64_t)w * Cfg::E + NBK * 256;
-            float t = 0.f;
-#pragma unroll
-            for (int ab = 0; ab < 4; ++ab) {
-                const int ng = co * 4 + ab;
-#pragma unroll
-                for (int lk = 0; lk < 4; ++lk) t += q[(ng >> 4) * 64 + lk * 16 + (ng & 15)];
-            }
-            s0 += t;
-        }
-    }
-    red[tid] = s0 + s1;
-    __syncthreads();
-    if (tid < 16 && o < n_out) {
-        float tot = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) tot += red[k * 16 + tid];
-        float* dstp = o < n_w ? p.dw + o : p.db + (o - n_w);
-        if (o >= n_w && p.db == nullptr) return;
-        *dstp = p.accumulate ? *dstp + tot : tot;
-    }
-}
-
 constexpr int CT_MAX_WG = 512;
 
 int fill_groups(CtArgs& p) {
@@ -730,7 +678,17 @@ bool ct_wgrad_vec_ok(const CtArgs& p) {
     };
     return p.W % 16 == 0 && al(p.x) && al(p.g);
 }
-int launch_ct_wgrad_group(const CtGroup& g, int n, int C, int nwg, hipStream_t st, bool dg = false) {
+// problem i of a weight-gradient group: the fields every form shares; returns the workgroups its geometry asks for
+int fill_ct_wgrad(CtArgs& p, const pc_src* x, const pc_src* g, void* ws, int B, int H, int W) {
+    p.x = *x; p.g = *g; p.B = B; p.H = H; p.W = W; p.bf = g_pc_precision == PC_PREC_BF16;
+    p.partial = reinterpret_cast<float*>(ws);
+    return fill_groups(p);
+}
+// nwg: the workgroups the geometry asks for; the n problems share the CT_MAX_WG workgroups (= partials of a workspace) of a lone one.
+// dg: the fused form that also writes the data gradient.  *nwg_out: partials written per problem
+int launch_ct_wgrad_group(const CtGroup& g, int n, int C, int nwg, bool dg, int* nwg_out, hipStream_t st) {
+    if (nwg > CT_MAX_WG / n) nwg = CT_MAX_WG / n;
+    if (nwg < 1) nwg = 1;
     bool vec = true;
     const bool bf = g_pc_precision == PC_PREC_BF16;
     for (int i = 0; i < n; ++i) {
@@ -745,6 +703,7 @@ int launch_ct_wgrad_group(const CtGroup& g, int n, int C, int nwg, hipStream_t s
         else if (C == 8) hipLaunchKernelGGL((convt2x2_wgrad_cl_kernel<8, false>), dim3(nwg, n), dim3(256), 0, st, g);
         else return PC_EINVAL;
         PC_CHECK_LAUNCH();
+        *nwg_out = nwg;
         return 0;
     }
     if (dg && !vec) return PC_EINVAL;          // the fused form exists for aligned tensors with W % 16 == 0 only
@@ -756,28 +715,10 @@ int launch_ct_wgrad_group(const CtGroup& g, int n, int C, int nwg, hipStream_t s
     } else return PC_EINVAL;
 #undef PC_CTW
     PC_CHECK_LAUNCH();
-    return 0;
-}
-int launch_ct_wgrad(const CtArgs& p, int C, int nwg, hipStream_t st) {
-    CtGroup g{};
-    g.pr[0] = p;
-    return launch_ct_wgrad_group(g, 1, C, nwg, st);
-}
-}  // namespace
-
-extern "C" int pc_convt2x2_wgrad_partial(const pc_src* x, const pc_src* g, void* ws, int B, int H, int W, int C, int* nwg_out,
-                                         void* stream) {
-    if (!x || !g || !ws || !nwg_out) return PC_EINVAL;
-    CtArgs p{};
-    p.x = *x; p.g = *g; p.B = B; p.H = H; p.W = W; p.bf = g_pc_precision == PC_PREC_BF16;
-    p.partial = reinterpret_cast<float*>(ws);
-    int nwg = fill_groups(p);
-    if (nwg > CT_MAX_WG) nwg = CT_MAX_WG;
-    const int rc = launch_ct_wgrad(p, C, nwg, (hipStream_t)stream);
-    if (rc) return rc;
     *nwg_out = nwg;
     return 0;
 }
+}  // namespace
 
 extern "C" int pc_convt2x2_wgrad_partial_group(int n, const pc_convt_wgrad_desc* d, int B, int H, int W, int C, int* nwg_out,
                                                void* stream) {
@@ -786,17 +727,9 @@ extern "C" int pc_convt2x2_wgrad_partial_group(int n, const pc_convt_wgrad_desc*
     int nwg = 1;
     for (int i = 0; i < n; ++i) {
         if (!d[i].x || !d[i].g || !d[i].ws) return PC_EINVAL;
-        CtArgs& p = g.pr[i];
-        p.x = *d[i].x; p.g = *d[i].g; p.B = B; p.H = H; p.W = W; p.bf = g_pc_precision == PC_PREC_BF16;
-        p.partial = reinterpret_cast<float*>(d[i].ws);
-        nwg = fill_groups(p);
+        nwg = fill_ct_wgrad(g.pr[i], d[i].x, d[i].g, d[i].ws, B, H, W);
     }
-    if (nwg > CT_MAX_WG / n) nwg = CT_MAX_WG / n;      // the same total number of workgroups as a single-problem launch
-    if (nwg < 1) nwg = 1;
-    const int rc = launch_ct_wgrad_group(g, n, C, nwg, (hipStream_t)stream);
-    if (rc) return rc;
-    *nwg_out = nwg;
-    return 0;
+    return launch_ct_wgrad_group(g, n, C, nwg, false, nwg_out, (hipStream_t)stream);
 }
 
 extern "C" int pc_convt2x2_bwd_group(int n, const pc_convt_bwd_desc* d, int B, int H, int W, int C, int* nwg_out, void* stream) {
@@ -807,8 +740,8 @@ extern "C" int pc_convt2x2_bwd_group(int n, const pc_convt_bwd_desc* d, int B, i
     for (int i = 0; i < n; ++i) {
         if (!d[i].x || !d[i].g || !d[i].w || !d[i].out || !d[i].ws) return PC_EINVAL;
         CtArgs& p = g.pr[i];
-        p.x = *d[i].x; p.g = *d[i].g; p.w = d[i].w; p.out = *d[i].out; p.B = B; p.H = H; p.W = W; p.bf = bf;
-        p.partial = reinterpret_cast<float*>(d[i].ws);
+        nwg = fill_ct_wgrad(p, d[i].x, d[i].g, d[i].ws, B, H, W);
+        p.w = d[i].w; p.out = *d[i].out;
         if (d[i].x_bn) {                       // the mask is x itself (post-ReLU output of the layer x_bn belongs to)
             p.act = p.x.ptr;
             p.bn = *d[i].x_bn;
@@ -820,31 +753,6 @@ extern "C" int pc_convt2x2_bwd_group(int n, const pc_convt_bwd_desc* d, int B, i
                    p.out.bstride % 4) {
             return PC_EINVAL;
         }
-        nwg = fill_groups(p);
     }
-    if (nwg > CT_MAX_WG / n) nwg = CT_MAX_WG / n;
-    if (nwg < 1) nwg = 1;
-    const int rc = launch_ct_wgrad_group(g, n, C, nwg, (hipStream_t)stream, true);
-    if (rc) return rc;
-    *nwg_out = nwg;
-    return 0;
-}
-
-extern "C" int pc_convt2x2_wgrad(const pc_src* x, const pc_src* g, float* dw, float* db, int accumulate, void* ws,
-                                 int B, int H, int W, int C, void* stream) {
-    if (!x || !g || !dw || !ws) return PC_EINVAL;
-    CtArgs p{};
-    p.x = *x; p.g = *g; p.B = B; p.H = H; p.W = W; p.bf = g_pc_precision == PC_PREC_BF16;
-    p.partial = reinterpret_cast<float*>(ws);
-    int nwg = fill_groups(p);
-    if (nwg > CT_MAX_WG) nwg = CT_MAX_WG;
-    CtReduceArgs r{};
-    r.partial = p.partial; r.nwg = nwg; r.dw = dw; r.db = db; r.accumulate = accumulate;
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = launch_ct_wgrad(p, C, nwg, st);
-    if (rc) return rc;
-    if (C == 16) hipLaunchKernelGGL(convt2x2_wgrad_reduce_kernel<16>, dim3((16 * 16 * 4 + 16 + 15) / 16), dim3(256), 0, st, r);
-    else hipLaunchKernelGGL(convt2x2_wgrad_reduce_kernel<8>, dim3((8 * 8 * 4 + 8 + 15) / 16), dim3(256), 0, st, r);
-    PC_CHECK_LAUNCH();
-    return 0;
+    return launch_ct_wgrad_group(g, n, C, nwg, true, nwg_out, (hipStream_t)stream);
 }

@@ -1,5 +1,5 @@
-// train_ops.hip -- the O(batch) / O(parameters) kernels of a training step: loss forward+backward, global gradient
-// norm, fused clip + Adam, and the loader-side band select + normalise.
+// train_ops.hip -- the O(batch) / O(parameters) kernels of a training step: loss forward+backward, gradient norm + clip +
+// Adam in one launch, and the loader-side band select + normalise.
 //
 // Replaces (reference): utils/losses.py:49-76 (population loss + scale regulariser) and its autograd;
 // torch.nn.utils.clip_grad_norm_ + optim.Adam (run_train.py:82-90,233-238); utils/utils.py:105-127 (apply_normalize)
@@ -18,20 +18,6 @@ __global__ __launch_bounds__(256) void loss_fwd_bwd_kernel(const pc_loss_args a,
     pc_loss_block(a, popcount, stats, red);
 }
 
-// ---- gradient norm (deterministic two-level tree over a flat buffer) ---------------------------------------------------
-__global__ __launch_bounds__(1024) void grad_norm_kernel(const float* g, int n, float* norm_out) {
-    __shared__ double red[1024];
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < n; i += 1024) acc += (double)g[i] * (double)g[i];
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int off = 512; off > 0; off >>= 1) {
-        if (threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *norm_out = (float)sqrt(red[0]);
-}
-
 // ---- clip + Adam over the flat parameter buffer --------------------------------------------------------------------
 // torch.optim.Adam semantics (L2 weight decay added to the gradient, bias-corrected, eps outside the sqrt), with the
 // clip_grad_norm_ coefficient min(1, max_norm / (norm + 1e-6)) folded in.  Elements [0, n_decay) get weight decay, the
@@ -46,7 +32,8 @@ struct AdamArgs {
     float* p; const float* g; float* m; float* v;
     int n, n_decay;
     const float* hyper; float wd, beta1, beta2, eps, max_norm;
-    const float* norm; int32_t* step;
+    const float* norm;         // unread (the kernel computes the norm itself); it holds the argument layout of the kernel in place
+    int32_t* step;
     pc_adam_groups grp;        // nseg == 0: one group, always active, counter step[0]
 };
 
@@ -69,41 +56,10 @@ __device__ __forceinline__ void adam_group_constants(const AdamArgs& a, float (*
     }
 }
 
-__device__ __forceinline__ void adam_update_one(const AdamArgs& a, int i, float coef, const float (*sh)[2]) {
-    const int grp = a.grp.nseg ? adam_group_of(a, i) : 0;
-    if (a.grp.nseg && !((a.grp.active_mask >> grp) & 1)) return;      // grad is None: parameter and state untouched
-    float g = a.g[i] * coef;
-    const float p = a.p[i];
-    if (i < a.n_decay && a.wd != 0.f) g = fmaf(a.wd, p, g);
-    const float m = a.beta1 * a.m[i] + (1.f - a.beta1) * g;
-    const float v = a.beta2 * a.v[i] + (1.f - a.beta2) * g * g;
-    a.m[i] = m;
-    a.v[i] = v;
-    const float denom = sqrtf(v) / sh[grp][1] + a.eps;
-    a.p[i] = p - sh[grp][0] * (m / denom);
-}
-
-__global__ __launch_bounds__(256) void adam_clip_kernel(const AdamArgs a) {
-    __shared__ float sh[PC_ADAM_GROUPS][2];
-    adam_group_constants(a, sh, threadIdx.x);
-    __syncthreads();
-    float coef = 1.f;
-    if (a.max_norm > 0.f && a.norm) {
-        coef = a.max_norm / (*a.norm + 1e-6f);
-        coef = coef > 1.f ? 1.f : coef;
-    }
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < a.n) adam_update_one(a, i, coef, sh);
-}
-
-__global__ void adam_step_inc_kernel(int32_t* step, int ngroups, int active_mask) {
-    if ((int)threadIdx.x < ngroups && ((active_mask >> threadIdx.x) & 1)) step[threadIdx.x] += 1;
-}
-
-// One-launch variant: every workgroup first computes the total gradient norm itself (the flat buffer is ~157 KB and sits
-// in L2; all workgroups add in the same order, so they all get the same bits), then updates its 256 elements; the
-// workgroup that finishes last advances the step counter (every workgroup has read it by then).  Replaces the
-// single-workgroup norm kernel + the update + the one-thread counter kernel (3 dependent launches at the end of a step).
+// One launch: every workgroup first computes the total gradient norm itself (the flat buffer is ~157 KB and sits
+// in L2; all workgroups add in the same order, so they all get the same bits), then updates its elements; the
+// workgroup that finishes last advances the step counter (every workgroup has read it by then).  (The first form was three
+// dependent launches at the end of a step: a single-workgroup norm kernel, the update, a one-thread counter kernel.)
 constexpr int ADAM_NT = 1024;
 __global__ __launch_bounds__(ADAM_NT) void adam_clip_fused_kernel(const AdamArgs a, float* norm_out, unsigned* ticket) {
     // 39 k parameters: the kernel is a chain of memory round trips, not work.  1024-thread workgroups (every workgroup reads the
@@ -228,13 +184,6 @@ extern "C" int pc_loss_fwd_bwd(const float* popcount, const float* y, const doub
     return 0;
 }
 
-extern "C" int pc_grad_norm(const float* g, int n, float* norm_out, void* stream) {
-    if (!g || !norm_out) return PC_EINVAL;
-    hipLaunchKernelGGL(grad_norm_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, g, n, norm_out);
-    PC_CHECK_LAUNCH();
-    return 0;
-}
-
 static int fill_groups(AdamArgs& a, const pc_adam_groups* groups, int n) {
     if (!groups) return 0;
     if (groups->nseg < 1 || groups->nseg > PC_ADAM_MAX_SEG || groups->seg_end[groups->nseg - 1] != n) return PC_EINVAL;
@@ -243,23 +192,6 @@ static int fill_groups(AdamArgs& a, const pc_adam_groups* groups, int n) {
         if (s && groups->seg_end[s] < groups->seg_end[s - 1]) return PC_EINVAL;
     }
     a.grp = *groups;
-    return 0;
-}
-
-extern "C" int pc_adam_clip_step(float* p, const float* g, float* m, float* v, int n, int n_decay, const float* hyper_dev,
-                                 float weight_decay, float beta1, float beta2, float eps, float max_norm,
-                                 const float* norm_dev, int32_t* step_dev, const pc_adam_groups* groups, void* stream) {
-    if (!p || !g || !m || !v || !hyper_dev || !step_dev) return PC_EINVAL;
-    AdamArgs a{};
-    if (int rc = fill_groups(a, groups, n)) return rc;
-    a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.n_decay = n_decay; a.hyper = hyper_dev; a.wd = weight_decay;
-    a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.max_norm = max_norm; a.norm = norm_dev; a.step = step_dev;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(adam_clip_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a);
-    PC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(adam_step_inc_kernel, dim3(1), dim3(64), 0, st, step_dev, groups ? PC_ADAM_GROUPS : 1,
-                       groups ? groups->active_mask : 1);
-    PC_CHECK_LAUNCH();
     return 0;
 }
 

@@ -5,6 +5,7 @@ composite entry points instead (popcorn_amd/engine.py).
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import torch
@@ -175,23 +176,16 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
 
 def conv3x3_wgrad(a, g, cout, dw=None, db=None, b=None, accumulate=False, a_mode=L.PC_SRC_DIRECT, a_pad=(0, 0),
                   chmap=(0, 1, 2, 3), b_offset=(0, 0), a_channels=None):
-    """Weight/bias gradient of conv3x3 over x = cat[a, b] with output gradient g (already ReLU/BN-masked)."""
+    """Weight/bias gradient of conv3x3 over x = cat[a, b] with output gradient g (already ReLU/BN-masked): a WgradBatch of one."""
     L.require_device(a, g)
-    B, Cg, H, W = g.shape
-    Ca = a.shape[1] if a_channels is None else a_channels
-    Cb = 0 if b is None else b.shape[1]
-    cin = Ca + Cb
-    sa = L.src(a, C_=Ca, mode=a_mode, oy=a_pad[0], ox=a_pad[1], chmap=chmap)
-    sb = L.src(b, oy=b_offset[0], ox=b_offset[1]) if b is not None else None
-    sg = L.src(g)
+    cin = (a.shape[1] if a_channels is None else a_channels) + (0 if b is None else b.shape[1])
     if dw is None:
         dw = torch.empty(cout, cin, 3, 3, device=g.device, dtype=torch.float32)
     if db is None:
         db = torch.empty(cout, device=g.device, dtype=torch.float32)
-    ws = _workspace(L.lib().pc_conv3x3_wgrad_ws_bytes(cin, cout), g.device)
-    code = L.lib().pc_conv3x3_wgrad(C.byref(sa), C.byref(sb) if sb is not None else None, C.byref(sg), L.ptr(dw),
-                                    L.ptr(db), int(accumulate), L.ptr(ws), B, H, W, cin, cout, L.stream_ptr())
-    L.check(code, "pc_conv3x3_wgrad")
+    wb = WgradBatch(g.device, accumulate=accumulate)
+    wb.conv3x3(a, g, cout, dw, db, b=b, a_mode=a_mode, a_pad=a_pad, chmap=chmap, b_offset=b_offset, a_channels=a_channels)
+    wb.finish()
     return dw, db
 
 
@@ -409,10 +403,9 @@ def convt2x2_wgrad(x, g, dw=None, db=None, accumulate=False):
         dw = torch.empty(Cc, Cc, 2, 2, device=x.device, dtype=torch.float32)
     if db is None:
         db = torch.empty(Cc, device=x.device, dtype=torch.float32)
-    ws = _workspace(L.lib().pc_convt2x2_wgrad_ws_bytes(Cc), x.device)
-    sx, sg = L.src(x), L.src(g)
-    L.check(L.lib().pc_convt2x2_wgrad(C.byref(sx), C.byref(sg), L.ptr(dw), L.ptr(db), int(accumulate), L.ptr(ws),
-                                      B, H, W, Cc, L.stream_ptr()), "pc_convt2x2_wgrad")
+    wb = WgradBatch(x.device, accumulate=accumulate)
+    wb.convt2x2_group([{"x": x, "g": g, "dw": dw, "db": db}])
+    wb.finish()
     return dw, db
 
 
@@ -792,11 +785,6 @@ def head_popcount_loss(B, H, W, nsel_counts, y, lam4, scale_regularization, lam_
             "pc_head_popcount_loss")
 
 
-def grad_norm(flat, norm_out):
-    L.require_device(flat)
-    L.check(L.lib().pc_grad_norm(L.ptr(flat), flat.numel(), L.ptr(norm_out), L.stream_ptr()), "pc_grad_norm")
-
-
 def adam_groups(segments, active):
     """pc_adam_groups from [(end_offset, group id), ...] (consecutive segments of the flat buffer) and the set of group
     ids that are updated in this call; the others are skipped like parameters whose .grad is None in torch.optim.Adam."""
@@ -810,30 +798,22 @@ def adam_groups(segments, active):
     return g
 
 
-def _check_steps(step, groups):
-    need = L.PC_ADAM_GROUPS if groups is not None else 1
-    assert step.dtype == torch.int32 and step.numel() >= need, "step: one int32 counter per Adam group"
-
-
-def adam_clip_step(p, g, m, v, n_decay, hyper, weight_decay, beta1, beta2, eps, max_norm, norm, step, groups=None):
-    L.require_device(p, g, m, v)
-    _check_steps(step, groups)
-    L.check(L.lib().pc_adam_clip_step(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), n_decay, L.ptr(hyper),
-                                      C.c_float(weight_decay), C.c_float(beta1), C.c_float(beta2), C.c_float(eps),
-                                      C.c_float(max_norm), L.ptr(norm), L.ptr(step),
-                                      C.byref(groups) if groups is not None else None, L.stream_ptr()),
-            "pc_adam_clip_step")
-
-
 def adam_clip_step_fused(p, g, m, v, n_decay, hyper, weight_decay, beta1, beta2, eps, max_norm, norm_out, step, groups=None):
     """grad-norm + clip + Adam in one launch (norm_out receives the total norm).  groups: ops.adam_groups(...) or None."""
     L.require_device(p, g, m, v, hyper, step)
-    _check_steps(step, groups)
+    need = L.PC_ADAM_GROUPS if groups is not None else 1
+    assert step.dtype == torch.int32 and step.numel() >= need, "step: one int32 counter per Adam group"
     L.check(L.lib().pc_adam_clip_step_fused(L.ptr(p), L.ptr(g), L.ptr(m), L.ptr(v), p.numel(), n_decay, L.ptr(hyper),
                                             C.c_float(weight_decay), C.c_float(beta1), C.c_float(beta2), C.c_float(eps),
                                             C.c_float(max_norm), L.ptr(norm_out), L.ptr(step),
                                             C.byref(groups) if groups is not None else None, L.stream_ptr()),
             "pc_adam_clip_step_fused")
+
+
+# one reduction of WgradBatch.finish(): the fields of pc_wgrad_reduce_desc (partial: device address of the workspace slot; dw / db: the
+# output tensors, db may be None; dw_offset: elements into dw where the entry's first column starts)
+ReduceEntry = collections.namedtuple("ReduceEntry", "partial dw db nwg Cin Cout kind dw_co_stride dw_offset src_cin src_ci0",
+                                     defaults=(0, 0, 0, 0))
 
 
 class WgradBatch:
@@ -880,7 +860,7 @@ class WgradBatch:
         L.check(L.lib().pc_conv3x3_wgrad_partial(C.byref(sa), C.byref(sb) if sb is not None else None, C.byref(sg),
                                                  C.c_void_p(ws), B, H, W, Ca + Cb, cout, C.byref(nwg), L.stream_ptr()),
                 "pc_conv3x3_wgrad_partial")
-        self.entries.append((ws, dw, db, nwg.value, Ca + Cb, cout, 0))
+        self.entries.append(ReduceEntry(ws, dw, db, nwg.value, Ca + Cb, cout, 0))
 
     def conv3x3_group(self, problems, cout, a_mode=L.PC_SRC_DIRECT, a_pad=(0, 0), a_channels=None, cin_total=None):
         """problems: list of dicts {a, g, dw, db, b (opt), b_offset (opt), chmap (opt)} of identical geometry -> one launch.
@@ -909,11 +889,11 @@ class WgradBatch:
                 # the partials cover all Ca input channels; dw ([cout][cin][3][3]) receives the channels [ci0, ci0 + cin) only
                 ci0, cin = pr["src_window"]
                 assert pr["dw"].shape[1] == cin and ci0 + cin <= Ca + Cb and cin_total is None
-                self.entries.append((ws, pr["dw"], pr["db"], nwg.value, cin, cout, 0, 0, 0, Ca + Cb, ci0))
+                self.entries.append(ReduceEntry(ws, pr["dw"], pr["db"], nwg.value, cin, cout, 0, src_cin=Ca + Cb, src_ci0=ci0))
             elif cin_total is None:
-                self.entries.append((ws, pr["dw"], pr["db"], nwg.value, Ca + Cb, cout, 0))
+                self.entries.append(ReduceEntry(ws, pr["dw"], pr["db"], nwg.value, Ca + Cb, cout, 0))
             else:
-                self.entries.append((ws, pr["dw"], pr["db"], nwg.value, Ca + Cb, cout, 0, cin_total * 9, 0))
+                self.entries.append(ReduceEntry(ws, pr["dw"], pr["db"], nwg.value, Ca + Cb, cout, 0, dw_co_stride=cin_total * 9))
 
     def conv3x3_bwd_group(self, problems, cin_total, c0, accumulate=False):
         """bf16 mode: data gradient + weight-gradient partials of a conv layer (g: 8 / 16 channels, x: an 8- or 16-channel column
@@ -942,8 +922,8 @@ class WgradBatch:
         L.check(L.lib().pc_conv3x3_bwd_group(n, descs, cin_total, c0, int(accumulate), B, H, W, C.byref(nwg), L.stream_ptr()),
                 "pc_conv3x3_bwd_group")
         for ws, pr in zip(slots, problems):
-            self.entries.append((ws, pr["dw"], pr.get("db"), nwg.value, pr["x"].shape[1], Cg, 0, cin_total * 9,
-                                 (c0 + int(pr.get("c0_add", 0))) * 9))
+            self.entries.append(ReduceEntry(ws, pr["dw"], pr.get("db"), nwg.value, pr["x"].shape[1], Cg, 0, dw_co_stride=cin_total * 9,
+                                            dw_offset=(c0 + int(pr.get("c0_add", 0))) * 9))      # first column of the column block
 
     def up_bwd_group(self, problems):
         """Composed Up block backward, deferred form: the pass now (data gradient written, partials queued), the reduction inside
@@ -998,17 +978,8 @@ class WgradBatch:
         nwg = C.c_int(0)
         L.check(L.lib().pc_level2_bwd_group(n, descs, B, C.byref(nwg), L.stream_ptr()), "pc_level2_bwd_group")
         for (ws1, ws2), pr in zip(slices, problems):
-            self.entries.append((ws1, pr["dw1"], pr["db1"], nwg.value, 16, 16, 0))
-            self.entries.append((ws2, pr["dw2"], pr["db2"], nwg.value, 16, 16, 0))
-
-    def convt2x2(self, x, g, dw, db):
-        B, Cc, H, W = x.shape
-        sx, sg = L.src(x), L.src(g)
-        ws = self._slice()
-        nwg = C.c_int(0)
-        L.check(L.lib().pc_convt2x2_wgrad_partial(C.byref(sx), C.byref(sg), C.c_void_p(ws), B, H, W, Cc, C.byref(nwg),
-                                                  L.stream_ptr()), "pc_convt2x2_wgrad_partial")
-        self.entries.append((ws, dw, db, nwg.value, Cc, Cc, 1))
+            self.entries.append(ReduceEntry(ws1, pr["dw1"], pr["db1"], nwg.value, 16, 16, 0))
+            self.entries.append(ReduceEntry(ws2, pr["dw2"], pr["db2"], nwg.value, 16, 16, 0))
 
     def convt2x2_group(self, problems):
         """problems: list (<= 4) of dicts {x, g, dw, db} with identical geometry: one launch."""
@@ -1027,7 +998,7 @@ class WgradBatch:
         L.check(L.lib().pc_convt2x2_wgrad_partial_group(n, descs, B, H, W, Cc, C.byref(nwg), L.stream_ptr()),
                 "pc_convt2x2_wgrad_partial_group")
         for ws, pr in zip(slices, problems):
-            self.entries.append((ws, pr["dw"], pr["db"], nwg.value, Cc, Cc, 1))
+            self.entries.append(ReduceEntry(ws, pr["dw"], pr["db"], nwg.value, Cc, Cc, 1))
 
     def convt2x2_bwd_group(self, problems):
         """Whole backward of a transposed conv in one launch: problems = list of {x, g, w, out, dw, db, x_bn (opt: ReLU / BN factor
@@ -1046,7 +1017,7 @@ class WgradBatch:
         nwg = C.c_int(0)
         L.check(L.lib().pc_convt2x2_bwd_group(n, descs, B, H, W, Cc, C.byref(nwg), L.stream_ptr()), "pc_convt2x2_bwd_group")
         for ws, pr in zip(slices, problems):
-            self.entries.append((ws, pr["dw"], pr["db"], nwg.value, Cc, Cc, 1))
+            self.entries.append(ReduceEntry(ws, pr["dw"], pr["db"], nwg.value, Cc, Cc, 1))
 
     def head_reduce(self, hp):
         assert self.head is None and isinstance(hp, HeadPartials)
@@ -1063,15 +1034,11 @@ class WgradBatch:
             i = n - 1
             d[i].partial, d[i].dw, d[i].db = hp.ptr, C.cast(dhw, C.c_void_p).value, 0
             d[i].nwg, d[i].Cin, d[i].Cout, d[i].kind, d[i].accumulate, d[i].dw_co_stride = hp.nwg, 0, 0, 3, int(hp.accumulate), 0
-        for i, ent in enumerate(self.entries):
-            ws, dw, db, nwg, cin, cout, kind = ent[:7]
-            d[i].partial = ws
-            d[i].dw = dw.data_ptr() + (4 * ent[8] if len(ent) > 7 else 0)        # first column of an 8-channel column block
-            d[i].dw_co_stride = ent[7] if len(ent) > 7 else 0
-            d[i].db = 0 if db is None else db.data_ptr()
-            d[i].nwg, d[i].Cin, d[i].Cout, d[i].kind, d[i].accumulate = nwg, cin, cout, kind, int(self.accumulate)
-            if len(ent) > 9:
-                d[i].src_cin, d[i].src_ci0 = ent[9], ent[10]
+        acc = int(self.accumulate)
+        for i, e in enumerate(self.entries):
+            d[i].partial, d[i].dw, d[i].db = e.partial, e.dw.data_ptr() + 4 * e.dw_offset, 0 if e.db is None else e.db.data_ptr()
+            d[i].nwg, d[i].Cin, d[i].Cout, d[i].kind, d[i].accumulate = e.nwg, e.Cin, e.Cout, e.kind, acc
+            d[i].dw_co_stride, d[i].src_cin, d[i].src_ci0 = e.dw_co_stride, e.src_cin, e.src_ci0
         for j, (pp, tot, nwg, part) in enumerate(self.raw_entries):
             i = len(self.entries) + j
             d[i].partial, d[i].dw, d[i].db = pp, tot, 0

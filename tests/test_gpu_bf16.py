@@ -421,6 +421,120 @@ def test_bf16_convt_fwd_dgrad_wgrad_op(C_, shape):
     assert torch.equal(dw, dw2) and torch.equal(db, db2)
 
 
+# ---- op level: the single weight-gradient ops run the batched reduction (pc_wgrad_reduce_batch with n = 1) ------------------------
+def _bf16_conv_wgrad_case(cin, cout, shape, seed=40):
+    """bf16-rounded operands of a conv weight gradient as the op takes them, and fp64 autograd on the same rounded operands;
+    cin = 2: the first-layer form (planar fp32 model input through the reflect loader with a channel gather)"""
+    import torch.nn.functional as F
+    from popcorn_amd import _lib as L
+    B, H, W = shape
+    w = _mk(cout, cin, 3, 3, seed=seed + 1, scale=0.2).double().requires_grad_(True)
+    bias = torch.zeros(cout, dtype=torch.double, requires_grad=True)
+    g = _bf(_mk(B, cout, H, W, seed=seed + 2))
+    if cin == 2:
+        X = _mk(B, 6, H - 28, W - 28, seed=seed)
+        x = _bf(F.pad(X[:, [4, 5]], (14, 14, 14, 14), mode="reflect"))
+        a, kw = X.cuda(), dict(a_mode=L.PC_SRC_REFLECT, a_pad=(14, 14), chmap=(4, 5, 0, 0), a_channels=2)
+    else:
+        x = _bf(_mk(B, cin, H, W, seed=seed))
+        a, kw = _dev(x), {}
+    F.conv2d(x.double(), w, bias, padding=1).backward(g.double())
+    return a, _dev(g), kw, w.grad, bias.grad
+
+
+def _bf16_wgrad_close(dw, db, rw, rb):
+    """the bound of test_bf16_conv_wgrad_op"""
+    assert (dw.cpu().double() - rw).abs().max().item() <= 2e-5 * rw.abs().max().item()
+    assert (db.cpu().double() - rb).abs().max().item() <= 2e-5 * max(rb.abs().max().item(), 1.0)
+
+
+@pytest.mark.parametrize("shape", [(2, 32, 32), (1, 37, 53)])
+@pytest.mark.parametrize("accumulate", [False, True])
+def test_bf16_conv_wgrad_single_op_equals_the_batched_path(shape, accumulate):
+    """bf16 twin of test_conv_wgrad_single_op_equals_the_batched_path (8 -> 8; every geometry runs the channels-last kernel)."""
+    from popcorn_amd import ops, _lib as L
+    dev = torch.device("cuda")
+    a, g, _, rw, rb = _bf16_conv_wgrad_case(8, 8, shape)
+    a2, g2, _, _, _ = _bf16_conv_wgrad_case(8, 8, shape, seed=50)
+    init_w, init_b = _mk(8, 8, 3, 3, seed=7).cuda(), _mk(8, seed=8).cuda()
+
+    def fresh():
+        return (init_w.clone(), init_b.clone()) if accumulate else (torch.full_like(init_w, float("nan")), torch.full_like(init_b, float("nan")))
+
+    with L.precision("bf16"):
+        dw, db = ops.conv3x3_wgrad(a, g, 8, *fresh(), accumulate=accumulate)
+        single = ops.WgradBatch(dev, accumulate=accumulate)
+        dw_s, db_s = fresh()
+        single.conv3x3(a, g, 8, dw_s, db_s)
+        nwg_single = single.entries[0].nwg
+        single.finish()
+        assert torch.equal(dw, dw_s) and torch.equal(db, db_s)
+        base_w, base_b = (init_w.cpu().double(), init_b.cpu().double()) if accumulate else (0.0, 0.0)
+        for others in ([], [(a2, g2)]):
+            wb = ops.WgradBatch(dev, accumulate=accumulate)
+            probs = [{"a": a_, "g": g_, "dw": t[0], "db": t[1]} for (a_, g_), t in zip([(a, g)] + others, [fresh(), fresh()])]
+            wb.conv3x3_group(probs, 8)
+            nwg_group = wb.entries[0].nwg
+            wb.finish()
+            if nwg_group == nwg_single:       # else: another cut of the tiles into partials, another order of the sums -- the bound only
+                assert torch.equal(probs[0]["dw"], dw) and torch.equal(probs[0]["db"], db), len(probs)
+            _bf16_wgrad_close(probs[0]["dw"].cpu().double() - base_w, probs[0]["db"].cpu().double() - base_b, rw, rb)
+    assert nwg_single == (4 if shape == (2, 32, 32) else 6)
+
+
+@pytest.mark.parametrize("cin,cout", [(8, 8), (16, 16), (2, 8)])
+@pytest.mark.parametrize("shape,want_nwg", [((1, 48, 64), 6), ((1, 96, 176), 36), ((5, 96, 176), 180)])
+def test_bf16_conv_wgrad_every_loop_of_the_batched_reduction(cin, cout, shape, want_nwg):
+    """bf16 twin of test_conv_wgrad_every_loop_of_the_batched_reduction: partial lists of 6, 36 and 180 (one per 32 x 16 tile;
+    the smallest map still leaves the reflect loader of the 2 -> 8 case more rows than its 14 rows of padding)."""
+    from popcorn_amd import ops, _lib as L
+    dev = torch.device("cuda")
+    a, g, kw, rw, rb = _bf16_conv_wgrad_case(cin, cout, shape)
+    with L.precision("bf16"):
+        wb = ops.WgradBatch(dev)
+        dw, db = torch.full((cout, cin, 3, 3), float("nan"), device=dev), torch.full((cout,), float("nan"), device=dev)
+        wb.conv3x3(a, g, cout, dw, db, **kw)                            # = ops.conv3x3_wgrad
+        nwg = wb.entries[0].nwg
+        wb.finish()
+        dw2, db2 = ops.conv3x3_wgrad(a, g, cout, **kw)
+    assert nwg == want_nwg and nwg % 8 != 0
+    _bf16_wgrad_close(dw, db, rw, rb)
+    assert torch.equal(dw2, dw) and torch.equal(db2, db)
+
+
+@pytest.mark.parametrize("C_,shape,want_nwg", [(8, (1, 16, 16), 4), (16, (2, 16, 32), 16), (8, (1, 24, 112), 42), (16, (1, 24, 112), 42)])
+def test_bf16_convt_wgrad_single_op_equals_the_batched_path_and_its_reduction_loops(C_, shape, want_nwg):
+    """bf16 twin of the two transposed-conv tests: the single op == a group of one == the first problem of a group of two, bit for bit;
+    42 partials (>= 40, no multiple of 32) run the 4-chain loop and the remainder of the bias tail."""
+    import torch.nn.functional as F
+    from popcorn_amd import ops, _lib as L
+    dev = torch.device("cuda")
+    B, H, W = shape
+    xs, gs = [], []
+    for seed in (70, 80):
+        x = _bf(_mk(B, C_, H, W, seed=seed))
+        w = _mk(C_, C_, 2, 2, seed=seed + 1, scale=0.3).double().requires_grad_(True)
+        bias = torch.zeros(C_, dtype=torch.double, requires_grad=True)
+        y = F.conv_transpose2d(x.double(), w, bias, stride=2)
+        g = _bf(_mk(*y.shape, seed=seed + 3))
+        if seed == 70:
+            y.backward(g.double())
+            rw, rb = w.grad, bias.grad
+        xs.append(_dev(x))
+        gs.append(_dev(g))
+    with L.precision("bf16"):
+        dw, db = ops.convt2x2_wgrad(xs[0], gs[0])
+        for n in (1, 2):
+            wb = ops.WgradBatch(dev)
+            probs = [{"x": xs[i], "g": gs[i], "dw": torch.full_like(dw, float("nan")), "db": torch.full_like(db, float("nan"))} for i in range(n)]
+            wb.convt2x2_group(probs)
+            assert wb.entries[0].nwg == want_nwg
+            wb.finish()
+            assert torch.equal(probs[0]["dw"], dw) and torch.equal(probs[0]["db"], db), n
+    assert (dw.cpu().double() - rw).abs().max().item() <= 2e-5 * rw.abs().max().item()              # the bounds of test_bf16_convt_fwd_dgrad_wgrad_op
+    assert (db.cpu().double() - rb).abs().max().item() <= 2e-5 * rb.abs().max().item()
+
+
 # ---- op level: the bf16 head kernels (channels-last feature / gradient maps) -------------------------------------------
 @pytest.mark.parametrize("sparse", [True, False, "few"])
 @pytest.mark.parametrize("shape", [(3, 100, 100, 128, 128, 14, 14), (1, 37, 29, 64, 64, 13, 17), (40, 100, 100, 128, 128, 14, 14)])

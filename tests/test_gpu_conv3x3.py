@@ -490,3 +490,122 @@ def test_cross_lane_helpers_are_bit_identical_to_the_shuffle_butterflies():
         assert np.array_equal(o[128:192].view(np.uint32), (x + x[lane ^ 16]).astype(np.float32).view(np.uint32))
         assert np.array_equal(o[192:256].view(np.uint32), (x + x[lane ^ 32]).astype(np.float32).view(np.uint32))
         assert np.array_equal(o[256:320], x[lane ^ 1]) and np.array_equal(o[320:384], x[lane ^ 2])
+
+
+def _wgrad_case(cin, cout, shape, seed=40):
+    """x, g and the fp64 autograd weight / bias gradient of conv3x3 pad 1"""
+    B, H, W = shape
+    x, g = _mk(B, cin, H, W, seed=seed), _mk(B, cout, H, W, seed=seed + 2)
+    w = _mk(cout, cin, 3, 3, seed=seed + 1, scale=0.2).double().requires_grad_(True)
+    bias = torch.zeros(cout, dtype=torch.double, requires_grad=True)
+    F.conv2d(x.double(), w, bias, padding=1).backward(g.double())
+    return x.cuda(), g.cuda(), w.grad, bias.grad
+
+
+def _assert_wgrad_close(got, ref):
+    """the bar of test_conv_wgrad against the fp64 reference"""
+    torch.testing.assert_close(got.cpu().double(), ref, rtol=1e-5, atol=2e-6 * max(ref.abs().max().item(), 1.0))
+
+
+@pytest.mark.parametrize("shape", [(2, 32, 32), (1, 37, 53)])
+@pytest.mark.parametrize("accumulate", [False, True])
+def test_conv_wgrad_single_op_equals_the_batched_path(shape, accumulate):
+    """ops.conv3x3_wgrad == a WgradBatch of one group of one == the first problem of a group of two, bit for bit (8 -> 8; (1, 37, 53)
+    runs the generic workgroup-tile kernel).  The single op keeps the grid rule of a lone problem: where it cuts the tiles into another
+    number of partials than the group does, the sums differ in order, and only determinism and the fp64 bar apply to that pair."""
+    from popcorn_amd import ops
+    dev = torch.device("cuda")
+    x, g, rw, rb = _wgrad_case(8, 8, shape)
+    x2, g2, _, _ = _wgrad_case(8, 8, shape, seed=50)
+    init_w, init_b = _mk(8, 8, 3, 3, seed=7).cuda(), _mk(8, seed=8).cuda()
+
+    def fresh():
+        return (init_w.clone(), init_b.clone()) if accumulate else (torch.full_like(init_w, float("nan")), torch.full_like(init_b, float("nan")))
+
+    dw, db = ops.conv3x3_wgrad(x, g, 8, *fresh(), accumulate=accumulate)
+    dw_r, db_r = ops.conv3x3_wgrad(x, g, 8, *fresh(), accumulate=accumulate)
+    assert torch.equal(dw, dw_r) and torch.equal(db, db_r)
+    single = ops.WgradBatch(dev, accumulate=accumulate)           # what the op is made of: tells the number of partials
+    dw_s, db_s = fresh()
+    single.conv3x3(x, g, 8, dw_s, db_s)
+    nwg_single = single.entries[0].nwg
+    single.finish()
+    assert torch.equal(dw, dw_s) and torch.equal(db, db_s)
+    for others in ([], [(x2, g2)]):
+        wb = ops.WgradBatch(dev, accumulate=accumulate)
+        probs = [{"a": a_, "g": g_, "dw": t[0], "db": t[1]} for (a_, g_), t in zip([(x, g)] + others, [fresh(), fresh()])]
+        wb.conv3x3_group(probs, 8)
+        nwg_group = wb.entries[0].nwg
+        wb.finish()
+        if nwg_group == nwg_single:
+            assert torch.equal(probs[0]["dw"], dw) and torch.equal(probs[0]["db"], db), len(probs)
+        base_w, base_b = (init_w.cpu().double(), init_b.cpu().double()) if accumulate else (0.0, 0.0)
+        _assert_wgrad_close(probs[0]["dw"].cpu().double() - base_w, rw)
+        _assert_wgrad_close(probs[0]["db"].cpu().double() - base_b, rb)
+    assert nwg_single == (4 if shape == (2, 32, 32) else 6)       # one partial per 32 x 16 tile at these sizes, single and group
+
+
+# (B, H, W) -> tiles of 32 x 16 pixels = partials of a lone problem: 4 runs the single-step loop of rb_sum only, 36 its 4-chain loop
+# and remainder, 180 the 16-chain loop, the 4-chain loop and the remainder (8 slices of the partial list per output)
+_RB_GEOMS = {"few": ((1, 32, 64), 4), "mid": ((1, 96, 176), 36), "many": ((5, 96, 176), 180)}
+
+
+@pytest.mark.parametrize("cin,cout", [(8, 8), (16, 16), (2, 8)])
+@pytest.mark.parametrize("size", ["few", "mid", "many"])
+def test_conv_wgrad_every_loop_of_the_batched_reduction(cin, cout, size):
+    """The conv branch (kind 0) of wgrad_reduce_batch_kernel at op level against fp64 autograd, with partial-list lengths below 8,
+    in [32, 127] and >= 160, none a multiple of 8; at the longest list also an entry that writes the first columns of a wider
+    gradient (dw_co_stride) and one that writes a channel window of the partials (src_cin / src_ci0).
+    The bar is test_conv_wgrad's (rtol 1e-5, atol 2e-6 max(scale, 1)).  Largest error over these nine cases in units of it, on
+    an MI355X: 0.079 with the per-op reduction kernels this reduction replaced, 0.067 with this one (dw; db 0.040 / 0.028)."""
+    from popcorn_amd import ops
+    shape, want_nwg = _RB_GEOMS[size]
+    dev = torch.device("cuda")
+    x, g, rw, rb = _wgrad_case(cin, cout, shape)
+    wb = ops.WgradBatch(dev)
+    dw, db = torch.full((cout, cin, 3, 3), float("nan"), device=dev), torch.full((cout,), float("nan"), device=dev)
+    wb.conv3x3(x, g, cout, dw, db)                                  # = ops.conv3x3_wgrad
+    nwgs = [wb.entries[0].nwg]
+    if size == "many":
+        wide = torch.full((cout, cin + 8, 3, 3), -7.0, device=dev)
+        db_wide = torch.full((cout,), float("nan"), device=dev)
+        wb.conv3x3_group([{"a": x, "g": g, "dw": wide, "db": db_wide}], cout, cin_total=cin + 8)
+        ci0, cw = (1, 1) if cin == 2 else (cin // 4, cin // 2)
+        dw_win, db_win = torch.full((cout, cw, 3, 3), float("nan"), device=dev), torch.full((cout,), float("nan"), device=dev)
+        wb.conv3x3_group([{"a": x, "g": g, "dw": dw_win, "db": db_win, "src_window": (ci0, cw)}], cout)
+        nwgs += [e.nwg for e in wb.entries[1:]]
+        assert wb.entries[1].dw_co_stride == (cin + 8) * 9 and (wb.entries[2].src_cin, wb.entries[2].src_ci0) == (cin, ci0)
+    wb.finish()
+    for nwg in nwgs:
+        assert nwg == want_nwg and nwg % 8 != 0, nwgs
+    _assert_wgrad_close(dw, rw)
+    _assert_wgrad_close(db, rb)
+    if size == "many":
+        _assert_wgrad_close(wide[:, :cin], rw)
+        assert bool((wide[:, cin:] == -7.0).all())                  # the other columns of the wider gradient are not touched
+        _assert_wgrad_close(db_wide, rb)
+        torch.testing.assert_close(dw_win.cpu().double(), rw[:, ci0:ci0 + cw], rtol=1e-5, atol=2e-6 * max(rw.abs().max().item(), 1.0))
+        _assert_wgrad_close(db_win, rb)
+    assert torch.equal(ops.conv3x3_wgrad(x, g, cout)[0], dw)
+
+
+@pytest.mark.parametrize("bad", ["nwg0", "nwg_negative", "null_partial"])
+def test_wgrad_reduce_batch_refuses_an_empty_or_missing_partial_list(bad):
+    """pc_wgrad_reduce_batch: nwg < 1 or partial == NULL is PC_EINVAL before anything is launched; the outputs keep their values."""
+    from popcorn_amd import _lib as L
+    part = torch.zeros(4 * (8 * 8 * 9 + 8), device="cuda")
+    dw, db = torch.full((8, 8, 3, 3), 7.0, device="cuda"), torch.full((8,), 7.0, device="cuda")
+    d = (L.PcWgradReduceDesc * 2)()
+    for i in range(2):                                              # a good entry first: the call is refused as a whole
+        d[i].partial, d[i].dw, d[i].db = part.data_ptr(), dw.data_ptr(), db.data_ptr()
+        d[i].nwg, d[i].Cin, d[i].Cout, d[i].kind = 4, 8, 8, 0
+    if bad == "null_partial":
+        d[1].partial = None
+    else:
+        d[1].nwg = 0 if bad == "nwg0" else -3
+    code = L.lib().pc_wgrad_reduce_batch(2, d, L.stream_ptr())
+    assert code == L.PC_EINVAL
+    with pytest.raises(L.PopcornHipError):
+        L.check(code, "pc_wgrad_reduce_batch")
+    torch.cuda.synchronize()
+    assert bool((dw == 7.0).all()) and bool((db == 7.0).all())

@@ -51,6 +51,74 @@ def test_convt_fwd_dgrad_wgrad(C_, shape):
     assert torch.equal(dw, dw2) and torch.equal(db, db2)
 
 
+def _convt_wgrad_case(C_, shape, seed=1):
+    """x, g and the fp64 autograd weight / bias gradient of ConvTranspose2d(C, C, 2, stride=2)"""
+    B, H, W = shape
+    x = _mk(B, C_, H, W, seed=seed)
+    w = _mk(C_, C_, 2, 2, seed=seed + 1, scale=0.3).double().requires_grad_(True)
+    bias = torch.zeros(C_, dtype=torch.double, requires_grad=True)
+    y = F.conv_transpose2d(x.double(), w, bias, stride=2)
+    g = _mk(*y.shape, seed=seed + 3)
+    y.backward(g.double())
+    return x.cuda(), g.cuda(), w.grad, bias.grad
+
+
+def _assert_wgrad_close(got, ref):
+    """the bar of test_convt_fwd_dgrad_wgrad against the fp64 reference"""
+    torch.testing.assert_close(got.cpu().double(), ref, rtol=1e-5, atol=2e-6 * max(ref.abs().max().item(), 1.0))
+
+
+@pytest.mark.parametrize("C_,shape", [(8, (1, 16, 16)), (16, (2, 16, 32))])
+@pytest.mark.parametrize("accumulate", [False, True])
+def test_convt_wgrad_single_op_equals_the_batched_path(C_, shape, accumulate):
+    """ops.convt2x2_wgrad == a WgradBatch of one group of one == the first problem of a group of two, bit for bit: at these sizes a
+    group of two gives each problem as many partials as a lone problem gets (the test checks that it does)."""
+    from popcorn_amd import ops
+    dev = torch.device("cuda")
+    x, g, rw, rb = _convt_wgrad_case(C_, shape)
+    x2, g2, _, _ = _convt_wgrad_case(C_, shape, seed=11)
+    init_w, init_b = _mk(C_, C_, 2, 2, seed=7).cuda(), _mk(C_, seed=8).cuda()
+
+    def fresh():
+        return (init_w.clone(), init_b.clone()) if accumulate else (torch.full_like(init_w, float("nan")), torch.full_like(init_b, float("nan")))
+
+    dw, db = ops.convt2x2_wgrad(x, g, *fresh(), accumulate=accumulate)
+    nwgs = []
+    for others in ([], [(x2, g2)]):
+        wb = ops.WgradBatch(dev, accumulate=accumulate)
+        probs = [{"x": x_, "g": g_, "dw": t[0], "db": t[1]} for (x_, g_), t in zip([(x, g)] + others, [fresh(), fresh()])]
+        wb.convt2x2_group(probs)
+        nwgs.append(wb.entries[0].nwg)
+        wb.finish()
+        assert torch.equal(probs[0]["dw"], dw) and torch.equal(probs[0]["db"], db), len(probs)
+    B, H, W = shape
+    assert nwgs == [B * H * ((W + 15) // 16) // 4] * 2              # a workgroup per four 16-pixel row groups, single and group
+    base_w, base_b = (init_w.cpu().double(), init_b.cpu().double()) if accumulate else (0.0, 0.0)
+    _assert_wgrad_close(dw.cpu().double() - base_w, rw)
+    _assert_wgrad_close(db.cpu().double() - base_b, rb)
+
+
+@pytest.mark.parametrize("C_", [8, 16])
+def test_convt_wgrad_through_the_loops_of_the_batched_reduction(C_):
+    """The transposed-conv branch (kind 1) of wgrad_reduce_batch_kernel at op level against fp64 autograd with 42 partials: at least
+    40 and no multiple of 32, so the bias tail runs its 4-chain loop and its remainder, the weights the 4-chain loop of rb_sum and
+    its remainder (8 slices of the partial list per output).  Largest error in units of the bar (test_convt_fwd_dgrad_wgrad's),
+    on an MI355X: 0.058 with the per-op reduction kernel this reduction replaced, 0.051 with this one."""
+    from popcorn_amd import ops
+    dev = torch.device("cuda")
+    x, g, rw, rb = _convt_wgrad_case(C_, (1, 24, 112))
+    wb = ops.WgradBatch(dev)
+    dw, db = torch.full((C_, C_, 2, 2), float("nan"), device=dev), torch.full((C_,), float("nan"), device=dev)
+    wb.convt2x2_group([{"x": x, "g": g, "dw": dw, "db": db}])       # = ops.convt2x2_wgrad
+    nwg = wb.entries[0].nwg
+    wb.finish()
+    assert nwg == 42 and nwg >= 40 and nwg % 32 != 0
+    _assert_wgrad_close(dw, rw)
+    _assert_wgrad_close(db, rb)
+    dw2, db2 = ops.convt2x2_wgrad(x, g)
+    assert torch.equal(dw2, dw) and torch.equal(db2, db)
+
+
 @pytest.mark.parametrize("C_", [8, 16])
 @pytest.mark.parametrize("shape", [(2, 32, 32), (3, 16, 64), (1, 40, 16)])
 @pytest.mark.parametrize("masked", [True, False])
