@@ -708,6 +708,30 @@ int pc_block_sum(const float* map, int H, int W, int cell, float* out, void* str
 int64_t pc_nan_fill_ws_bytes(int B, int C, int H, int W);
 int pc_nan_fill(float* x, const int32_t* hw, int64_t* counts, void* ws, int B, int C, int H, int W, int flags, void* stream);
 
+/* ---- gradient w.r.t. the model input (autograd of the first convolution of each stream through add_padding and the channel reorder,
+ * popcorn.py:109-156,231-258; networks.py:130-133) ----
+ * For each of the n = 1 or 2 active streams s, from G_s = dL/d(first conv output) (already times relu' * bn scale of that layer):
+ *   dXp_s[b,c,p,q]       = sum_{o<8} sum_{ky,kx<3} w_s[o,c,ky,kx] * G_s[b,o,p-ky+1,q-kx+1]        (G_s = 0 outside Hp x Wp)
+ *   dX[b,chmap_s[c],h,w] = sum_{p: r_H(p)=h} sum_{q: r_W(q)=w} dXp_s[b,c,p,q]
+ *   r_H(p) = |p-pt| if |p-pt| < H else 2(H-1) - (p-pt)                                              (likewise r_W with pl, W)
+ * i.e. the data gradient of the conv folded back through the reflect padding (Hp = H + pt + pb, Wp = W + pl + pr; every pad <= extent - 1,
+ * torch's reflect rule) and scattered through the channel gather -- the adjoint of the PC_SRC_REFLECT loader.  ONE launch, a gather: no
+ * atomics, a fixed summation order (equal inputs give equal bits), every element of dX written exactly once with `=`.
+ *   g    : PC_SRC_DIRECT source of 8 channels and extent Hp x Wp at (0, 0).  PC_PREC_FP32: planar fp32, any row / channel / batch strides;
+ *          PC_PREC_BF16: channels-last bf16 (one 16-byte slot per pixel).
+ *   w    : the layer's fp32 weight [8][cin][3][3], cin = 2 or 4.  PC_PREC_BF16: each weight is rounded to bf16 where it is used; the sums
+ *          are fp32 and the result is not rounded.
+ *   dx   : contiguous fp32 (B, Cx, H, W), Cx = 2, 4 or 6; the chmaps of the n streams must cover its channels exactly once.
+ * Anything else returns PC_EINVAL before a launch. */
+typedef struct pc_input_grad_desc {
+    const pc_src* g; const float* w;
+    int32_t cin;          /* 2 or 4 */
+    int32_t chmap[4];     /* conv input channel c is channel chmap[c] of dx (c < cin) */
+    int32_t _pad;
+} pc_input_grad_desc;
+int pc_input_grad(int n, const pc_input_grad_desc* d, float* dx, int B, int Cx, int H, int W, int pad_top, int pad_bottom, int pad_left,
+                  int pad_right, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

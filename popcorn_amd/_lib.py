@@ -99,6 +99,10 @@ class PcLevel2BwdDesc(C.Structure):
                 ("ws1", C.c_void_p), ("ws2", C.c_void_p)]
 
 
+class PcInputGradDesc(C.Structure):
+    _fields_ = [("g", C.POINTER(PcSrc)), ("w", C.c_void_p), ("cin", C.c_int32), ("chmap", C.c_int32 * 4), ("_pad", C.c_int32)]
+
+
 PC_ABI_VERSION = 10
 PC_MAX_GROUP = 4
 PC_ADAM_MAX_SEG, PC_ADAM_GROUPS = 8, 4
@@ -191,6 +195,7 @@ def lib():
                                                C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.pc_product_finalize.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.pc_block_sum.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib.pc_input_grad.argtypes = [C.c_int, C.POINTER(PcInputGradDesc), C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]
     return _lib
 
 

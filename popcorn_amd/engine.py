@@ -177,11 +177,14 @@ class UNetEngine:
                 self.layers[("optical_stream", "up1b")].bn_nobias if "optical_stream" in names else plain)
 
     # ----------------------------------------------------------------------------------------------- backward
-    def backward(self, saved, G, grads, accumulate=False, encoder_no_grad=False, prefix="", head_reduce=None):
+    def backward(self, saved, G, grads, accumulate=False, encoder_no_grad=False, prefix="", head_reduce=None, input_grad=None):
         """G: (B,16,Hp,Wp) gradient w.r.t. the conv outputs of the two up1b layers (i.e. already multiplied by
         relu-mask * bn-scale -- the head-backward epilogue does that).  Writes dW/db into ``grads[prefix+name]``
         (= or += per ``accumulate``).  encoder_no_grad: networks.py:124-132 semantics.  head_reduce: the ``ops.HeadPartials`` of the
-        pass's ``head_bwd(defer_reduce=True)`` -- finished by this pass's batched reduction launch.
+        pass's ``head_bwd(defer_reduce=True)`` -- finished by this pass's batched reduction launch.  input_grad: a contiguous fp32
+        tensor of the model input's shape to fill with the gradient w.r.t. that input (one more launch, csrc/input_grad.hip); None: the
+        pass is what it was.  Under encoder_no_grad the pass ends before the encoder and the tensor is left untouched: no such gradient
+        exists (networks.py:124-132 runs ``inc`` under no_grad).
         Data-gradient launches are grouped over the two streams (same shapes); weight-gradient launches are per
         stream (each owns its partial-sum workspace).  The network in reverse, one call per block (``_Backward`` below; the native
         executor's counterpart, same calls in the same order: csrc/step.hip: backward)."""
@@ -201,7 +204,7 @@ class UNetEngine:
             p.down(DOWN2, G_c2, G_b2, H2, W2)
         p.down(DOWN1, G_b2, G_a2, H1, W1)
         G_a1 = p.conv8("inc2", G_a2, "a1", "inc1", Hp, Wp)
-        p.first_layer(G_a1)
+        p.first_layer(G_a1, input_grad)
         p.wb.finish()
 
 
@@ -448,8 +451,18 @@ class _Backward:
                 self.wgrad(lv.conv1, lv.full, g_mid, a_mode=L.PC_SRC_POOL2)
             self.dgrad(lv.conv1, g_mid, g_in, 0, lv.cin, fulls, lv.full_act, pool=True, acc=True)
 
-    def first_layer(self, G_a1):
-        """inc1: weight gradients only, over whichever form of the input the forward pass saved"""
+    def first_layer(self, G_a1, input_grad=None):
+        """inc1: weight gradients over whichever form of the input the forward pass saved; then, when asked for, the gradient of the
+        model input itself"""
+        self.first_layer_wgrad(G_a1)
+        if input_grad is not None:
+            # data gradient of inc1 + the adjoint of its loader (reflect padding, channel gather), all streams in one launch
+            pt, pl, Hp, Wp = self.saved["geom"]
+            H, W = input_grad.shape[2:]
+            ops.input_grad([{"g": G_a1[s], "w": self.ly(s, "inc1").w, "chmap": chmap[:cin]} for s, chmap, cin, _ in self.eng.streams],
+                           input_grad, (pt, Hp - H - pt, pl, Wp - W - pl))
+
+    def first_layer_wgrad(self, G_a1):
         saved, wb = self.saved, self.wb
         if saved.get("Xp8") is not None:
             # both streams' first-layer weight gradients in ONE launch of the standard 8-channel kernel over the shared input; the

@@ -4,6 +4,11 @@ Same constructor, same ``forward(inputs, train, padding, return_features, encode
 signature, same output dict, same state-dict keys, real ``nn.Parameter``s with ``.grad`` -- but every op on the path
 runs in the hand-written HIP kernels of libpopcorn_hip.so (popcorn_amd/engine.py).  The module refuses to run on CPU
 tensors: there is no stock-PyTorch fallback.
+
+``inputs["input"]`` is differentiable like the parameters: when it requires grad, ``backward`` fills its ``.grad`` (sensitivity maps,
+gradient x input) unless ``unet_no_grad`` or ``encoder_no_grad`` cuts the graph in front of it, exactly where the reference's autograd
+leaves ``X.grad`` at None.  The other inputs (``building_counts``, ``admin_mask``, ...) get no gradient; in particular a gradient for a
+user-supplied ``building_counts`` is out of scope.
 """
 from __future__ import annotations
 
@@ -258,7 +263,9 @@ class POPCORN(nn.Module):
             building = torch.ones_like(building)
 
         names, params = self.trainable()
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        # a differentiable input makes a graph as well, frozen parameters or not (unet_no_grad cuts it off, as in the reference)
+        need_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or
+                                                 (inputs["input"].requires_grad and not unet_no_grad))
         if unet_no_grad:
             self.unetmodel.eval()
         with L.precision(self.precision):
@@ -294,7 +301,8 @@ def _forward_nograd(model, X, building, mask, admin, census, geom, sparse):
 
 
 class _PopcornFn(torch.autograd.Function):
-    """One autograd node for unetmodel + head + occupancy product + census reduction."""
+    """One autograd node for unetmodel + head + occupancy product + census reduction.  Gradients: the parameters and the model input X
+    (not under unet_no_grad / encoder_no_grad); building, mask, admin and census get none."""
 
     @staticmethod
     def forward(ctx, model, X, building, mask, admin, census, geom, sparse, encoder_no_grad, unet_no_grad, *params):
@@ -329,8 +337,12 @@ class _PopcornFn(torch.autograd.Function):
                                 g_scale_map=g_scale_map, grads=khgrads,
                                 feat_bn=None if unet_no_grad else eng.feat_bn())
             fix()
+            g_x = None
             if not unet_no_grad:
-                eng.backward(ctx.saved, G, grads, accumulate=False, encoder_no_grad=encoder_no_grad, prefix="unetmodel.")
+                if ctx.needs_input_grad[1] and not encoder_no_grad:
+                    g_x = torch.empty_like(X)          # every element is written by the one launch that computes it
+                eng.backward(ctx.saved, G, grads, accumulate=False, encoder_no_grad=encoder_no_grad, prefix="unetmodel.",
+                             input_grad=g_x)
         n_unet = len(names) - 8
         if unet_no_grad:
             out = [None] * n_unet + hgrads
@@ -341,4 +353,4 @@ class _PopcornFn(torch.autograd.Function):
                 out.append(None if (encoder_no_grad and is_enc) else grads[n])
             out += hgrads
         ctx.saved = None
-        return (None,) * 10 + tuple(out)
+        return (None, g_x) + (None,) * 8 + tuple(out)

@@ -738,6 +738,40 @@ def nan_fill_(x, hw=None, count_only=False):
     return counts if x.dim() == 4 else counts[0]
 
 
+def input_grad(problems, out, pads):
+    """Gradient w.r.t. the model input from the gradients at the first convolutions' outputs (pc_input_grad, csrc/input_grad.hip): the
+    data gradient of each stream's first conv, folded back through the reflect padding and scattered through the channel gather -- ONE
+    launch, no atomics, bit-reproducible.  problems = list (1 or 2) of dicts {g: (B, 8, Hp, Wp) gradient w.r.t. the conv output (planar
+    fp32 with any strides, or channels-last bf16 in bf16 mode), w: the conv weight (8, Cin, 3, 3) fp32 with Cin = 2 or 4, chmap: the Cin
+    channels of ``out`` the conv's input channels were gathered from}; out: contiguous fp32 (B, Cx, H, W), every element written (=);
+    pads = (top, bottom, left, right) of the reflect padding, each smaller than the extent it mirrors.  The chmaps must cover the channels
+    of ``out`` exactly once.  Returns out."""
+    n = len(problems)
+    L.require_device(out, *[t for pr in problems for t in (pr["g"], pr["w"])])
+    if out.dim() != 4 or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError(f"input_grad: out must be a contiguous fp32 (B, C, H, W) tensor, got {out.dtype} {tuple(out.shape)}")
+    B, Cx, H, W = out.shape
+    pt, pb, pl, pr_ = (int(v) for v in pads)
+    keep = []
+    descs = (L.PcInputGradDesc * max(n, 1))()
+    for i, pr in enumerate(problems):
+        w = pr["w"]
+        if w.dtype != torch.float32 or not w.is_contiguous() or w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or pr["g"].shape[0] != B:
+            raise ValueError(f"input_grad: problem {i}: a contiguous fp32 (8, Cin, 3, 3) weight and a gradient of batch {B}")
+        chmap = [int(c) for c in pr["chmap"]][:w.shape[1]]
+        if len(chmap) != w.shape[1] or w.shape[1] > 4:
+            raise ValueError(f"input_grad: problem {i}: chmap {pr['chmap']} does not name the {w.shape[1]} input channels of the weight")
+        sg = L.src(pr["g"])
+        keep.append(sg)
+        descs[i].g = C.pointer(sg)
+        descs[i].w = w.data_ptr()
+        descs[i].cin = w.shape[1]
+        for c, ch in enumerate(chmap):
+            descs[i].chmap[c] = ch
+    L.check(L.lib().pc_input_grad(n, descs, L.ptr(out), B, Cx, H, W, pt, pb, pl, pr_, L.stream_ptr()), "pc_input_grad")
+    return out
+
+
 def augment_raw(s2, s1, admin_mask, params, out=None, admin_out=None):
     """The trainer's augmentations (run_train.py:386-402) with parameters drawn on the host (utils/transform.py: draw_fused_params), applied
     while the raw 6-channel tile [S2 | S1] is assembled -- ONE launch (pc_augment_raw).  s2 (B, 4, H, W) digital numbers, s1 (B, 2, H, W),
