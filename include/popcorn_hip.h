@@ -690,6 +690,34 @@ int pc_product_finalize(const float* cells, int M, int64_t n, float* mean, float
 /* out[Hc][Wc] = the cell x cell sum pooling of map[H][W] (every cell of out is written). */
 int pc_block_sum(const float* map, int H, int W, int cell, float* out, void* stream);
 
+/* ---- census table: every member's census-unit totals, accumulated while the windows are stitched (csrc/census_table.hip) ----
+ * The ensemble spread of a unit total is the spread over members of each member's own total, completed across windows with every pixel
+ * weighted by 1 / its visit count: table[M][T] int64, T = sum of num_ids[l] over the L <= PC_CENSUS_MAX_LEVELS census levels, level l in
+ * columns [off[l], off[l] + num_ids[l]).  Sums are 64-bit fixed point on a 2^-PC_CENSUS_FIX_SHIFT grid: integer addition is associative,
+ * so equal inputs give equal bits for any window order, grid size and rank sharding (ranks add their tables with an exact int64 sum).
+ * Range: every term in [0, 2^32), a unit total below 2^33 ~ 8.6e9 per member.
+ *
+ * One sliding window of an M-member ensemble (geometry as for pc_product_accumulate; an empty interior returns 0 without a launch):
+ * for every interior pixel p inside the raster, member m and level l with id = boundaries[l][p] in [0, num_ids[l]) (other ids ignored)
+ *     table[m][off[l] + id] += llrint((double)(popdense[m][p] / float(visits[p])) * 2^30)        (the quotient: one fp32 division).
+ * A term that is NaN, +-Inf, negative or >= 2^32 adds nothing and sets bit 0 of the device word *flags (never a silent wrap).
+ * boundaries / num_ids / off: HOST arrays of L entries; boundaries[l]: device int32 [H][W].  table and *flags are zeroed by the caller
+ * before the first window. */
+#define PC_CENSUS_MAX_LEVELS 4
+#define PC_CENSUS_FIX_SHIFT 30
+#define PC_CENSUS_MAX_PLANES 8
+int pc_census_accumulate(const float* popdense, int M, int ps_y, int ps_x, int overlap, int yl, int xl, const int16_t* visits, int H,
+                         int W, int L, const int32_t* const* boundaries, const int32_t* num_ids, const int32_t* off, int64_t* table,
+                         int64_t T, int32_t* flags, void* stream);
+/* totals[m][j] = (double)table[m][j] * 2^-30 (float64 [M][T]); mean[j] / stdv[j] (float32 [T]) over the members as pc_product_finalize:
+ * two passes in double, the n - 1 form, 0 for M == 1. */
+int pc_census_finalize(const int64_t* table, int M, int64_t T, double* totals, float* mean, float* stdv, void* stream);
+/* K <= PC_CENSUS_MAX_PLANES per-unit tables painted onto the raster in one pass over the boundary plane:
+ * out[k][i] = tables[k][boundary[i]] for boundary[i] in [0, num_ids), 0 elsewhere, i in [0, n).  tables / out: HOST arrays of K device
+ * pointers (tables[k]: float32 [num_ids]).  boundary / out[k]: any 4-byte aligned address (a row band of a larger map): scalar head,
+ * 16-byte loads and stores where aligned, scalar tail. */
+int pc_census_paint(const int32_t* boundary, int64_t n, int num_ids, int K, const float* const* tables, float* const* out, void* stream);
+
 /* ---- NaN fill of Sentinel inputs (data/PopulationDataset.py:526-551 interpolate_nan, scipy griddata "nearest") ----
  * x: contiguous fp32 (B, C, H, W), filled in place.  Per sample b, over its extent rows [0, h_b) x columns [0, w_b) (hw: DEVICE int32
  * [B][2] = {h_b, w_b}, NULL = the whole H x W; anchored top-left like the collate's zero padding; entries outside the extent are neither

@@ -108,6 +108,7 @@ PC_MAX_GROUP = 4
 PC_ADAM_MAX_SEG, PC_ADAM_GROUPS = 8, 4
 PC_EINVAL, PC_ENOGPU, PC_ENOMEM, PC_ENOTSUP = -1, -2, -3, -4
 PC_NAN_FILL_MAX_C, PC_NAN_FILL_MAX_HW, PC_NAN_FILL_COUNT_ONLY = 8, 16384, 1
+PC_CENSUS_MAX_LEVELS, PC_CENSUS_FIX_SHIFT, PC_CENSUS_MAX_PLANES = 4, 30, 8
 
 
 class PcAdamGroups(C.Structure):
@@ -196,6 +197,10 @@ def lib():
         _lib.pc_product_finalize.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.pc_block_sum.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib.pc_input_grad.argtypes = [C.c_int, C.POINTER(PcInputGradDesc), C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]
+        _lib.pc_census_accumulate.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        _lib.pc_census_finalize.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.pc_census_paint.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]
     return _lib
 
 

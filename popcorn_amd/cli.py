@@ -123,6 +123,13 @@ def eval_parser():
                         "the reference recommends for the final product and for evaluation)")
     p.add_argument("--product_out", type=str, default=None,
                    help="--product_cell: torch.save the product {mean, std, adjusted, cell} here (rank 0)")
+    p.add_argument("--census_table", action="store_true",
+                   help="accumulate every member's census-unit totals on the device while stitching and report the census metrics of "
+                        "the ensemble mean with their spread over members (<key>_members_mean / <key>_members_std)")
+    p.add_argument("--census_out", type=str, default=None,
+                   help="--census_table: torch.save {totals, mean, std, num_ids[, details]} here (rank 0)")
+    p.add_argument("--census_details", action="store_true",
+                   help="--census_table: also paint the reference's six per-unit detail maps (+ totals_std) into --census_out")
     return p
 
 
@@ -525,9 +532,12 @@ def run_eval(argv=None):
                                raw=args.raw_input, nan_clouds=args.nan_clouds, s1_gap=args.s1_gap)
     reducer = FlatReducer()
     product = E.ProductGrid(args.raster_hw[0], args.raster_hw[1], args.product_cell, n, dev) if args.product_cell > 0 else None
+    num_ids = int(data.census_idx.max()) + 1
+    census = E.CensusTable(args.raster_hw[0], args.raster_hw[1], [data.boundary], [num_ids], n, dev) if args.census_table else None
     t0 = time.time()
     out, out_std, scale, scale_std = E.evaluate_raster(models, data.raster, args.patchsize, args.overlap, args.fourseasons,
-                                                       reducer, rank, raw=args.raw_input, ascfill=args.ascfill, product=product)
+                                                       reducer, rank, raw=args.raw_input, ascfill=args.ascfill, product=product,
+                                                       census=census)
     res = {}
     cp, cg = E.convert_popmap_to_census(out, data.boundary, data.census_idx, data.census_pop)
     res.update({k: float(v) for k, v in get_test_metrics(cp, cg, tag="MainCensus_synthetic_fine").items()})
@@ -542,6 +552,14 @@ def run_eval(argv=None):
         if args.product_out and rank == 0:
             torch.save({"mean": product.mean.cpu(), "std": product.std.cpu(), "adjusted": padj.cpu(), "cell": product.cell},
                        args.product_out)
+    if census is not None:
+        res.update(census.metrics(0, data.census_idx, data.census_pop, tag="TableCensus_synthetic_fine"))
+        if args.census_out and rank == 0:
+            saved = {"totals": census.totals.cpu(), "mean": census.mean.cpu(), "std": census.std.cpu(), "num_ids": census.num_ids}
+            if args.census_details:
+                maps = E.census_detail_maps(census.mean, data.boundary, data.census_idx, data.census_pop, pred_std=census.std)
+                saved["details"] = {k: v.cpu() for k, v in maps.items()}
+            torch.save(saved, args.census_out)
     torch.cuda.synchronize()
     if rank == 0:
         res["seconds"] = time.time() - t0

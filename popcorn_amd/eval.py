@@ -236,6 +236,162 @@ class ProductGrid:
         return self.mean, self.std
 
 
+class CensusTable:
+    """Census-unit totals of every ensemble member, accumulated on the device as the windows go by (``csrc/census_table.hip``): what the
+    evaluation is judged on (``convert_popmap_to_census`` -> ``get_test_metrics``), with the ensemble spread per unit.
+
+    As for ``ProductGrid``, the spread of a unit total is the standard deviation over members of each member's own total, which is no
+    function of the 10 m std map and is complete only once every window that touches the unit has been added, each pixel weighted by
+    1 / its visit count.  ``boundaries``: one (h, w) id raster per census level (the reference's ``testlevels_eval``, e.g. fine and
+    coarse), at most ``PC_CENSUS_MAX_LEVELS``; ``num_ids[l]``: ids of level l are [0, num_ids[l]), anything else is ignored.  The table is
+    ``table`` (M, T) int64, T = sum(num_ids), level l in columns ``offsets[l] : offsets[l] + num_ids[l]``: 64-bit fixed point with 30
+    fractional bits, so it holds the same bits for any window order and rank sharding (a unit total must stay below 2^33 per member).
+    ``visits`` (h, w) int16 is the visit count of one member over the whole window list; pass a ``ProductGrid``'s to share it.
+
+    Multi-GPU: every rank sets the complete window list and adds its own windows; ``all_reduce`` is an exact int64 sum."""
+
+    def __init__(self, h, w, boundaries, num_ids, members, device, visits=None):
+        if torch.device(device).type != "cuda":
+            raise L.PopcornHipError("CensusTable accumulates on a HIP device only")
+        boundaries, num_ids = list(boundaries), [int(n) for n in num_ids]
+        if int(members) < 1 or not boundaries or len(boundaries) != len(num_ids) or min(num_ids) < 1:
+            raise ValueError(f"CensusTable: members >= 1 and one num_ids >= 1 per boundary, got members {members}, {len(boundaries)} "
+                             f"boundaries, num_ids {num_ids}")
+        if len(boundaries) > L.PC_CENSUS_MAX_LEVELS:
+            raise ValueError(f"CensusTable: at most {L.PC_CENSUS_MAX_LEVELS} census levels, got {len(boundaries)}")
+        self.h, self.w, self.members, self.num_ids = int(h), int(w), int(members), num_ids
+        for b in boundaries:
+            if tuple(b.shape) != (self.h, self.w):
+                raise ValueError(f"CensusTable: boundary of shape {tuple(b.shape)} for a raster of {self.h} x {self.w}")
+        self.boundaries = [b.to(device=device, dtype=torch.int32).contiguous() for b in boundaries]     # converted once
+        self.offsets = [sum(num_ids[:l]) for l in range(len(num_ids))]
+        self.T = sum(num_ids)
+        self.table = torch.zeros(self.members, self.T, dtype=torch.int64, device=device)
+        self.flags = torch.zeros(1, dtype=torch.int32, device=device)
+        if visits is not None and (tuple(visits.shape) != (self.h, self.w) or visits.dtype != torch.int16 or not visits.is_cuda
+                                   or not visits.is_contiguous()):
+            raise ValueError("CensusTable: visits must be a contiguous (h, w) int16 device map")
+        self.shared_visits = visits is not None
+        self.visits = visits if visits is not None else torch.zeros(self.h, self.w, dtype=torch.int16, device=device)
+        nl = len(num_ids)
+        self._bptr = (C.c_void_p * nl)(*[b.data_ptr() for b in self.boundaries])
+        self._nids, self._off = (C.c_int32 * nl)(*num_ids), (C.c_int32 * nl)(*self.offsets)
+        self.totals = self.mean = self.std = None
+
+    def set_windows(self, idx, patchsize=INFERENCE_PATCH_SIZE, overlap=OVERLAP):
+        """The complete window list of the evaluation (as ``ProductGrid.set_windows``) -> the visit map.  Starts a new accumulation: the
+        table and the flags are zeroed.  A shared visit map is left to its owner, whose ``set_windows`` must have run."""
+        self.table.zero_()
+        self.flags.zero_()
+        self.totals = self.mean = self.std = None
+        if not self.shared_visits:
+            self.visits.zero_()
+            count_windows(self.visits, [(r[0], r[1]) for r in idx], 1, patchsize, overlap)
+
+    def add_window(self, xl, yl, popdense, overlap=OVERLAP):
+        """popdense: (M, ps, ps) member outputs of the window whose origin is row xl, column yl, as for ``Stitcher.add_window``."""
+        L.require_device(popdense)
+        M, psx, psy = popdense.shape
+        if M != self.members:
+            raise ValueError(f"CensusTable of {self.members} members got a window of {M}")
+        popdense = popdense.contiguous().float()
+        L.check(L.lib().pc_census_accumulate(L.ptr(popdense), M, psx, psy, int(overlap), int(xl), int(yl), L.ptr(self.visits), self.h,
+                                             self.w, len(self.num_ids), self._bptr, self._nids, self._off, L.ptr(self.table),
+                                             C.c_int64(self.T), L.ptr(self.flags), L.stream_ptr()), "pc_census_accumulate")
+
+    def all_reduce(self, reducer: FlatReducer):
+        """Multi-GPU: the exact int64 sum of every rank's table (and the OR of the flags) on every rank."""
+        if reducer.active:
+            import torch.distributed as dist
+            dist.all_reduce(self.table, group=reducer.group)
+            dist.all_reduce(self.flags, op=dist.ReduceOp.MAX, group=reducer.group)
+
+    def finalize(self):
+        """(totals (M, T) float64, mean (T,), std (T,)) over the members; std is the n - 1 form, 0 for a single member.  Raises when a
+        window held a value the table cannot take (NaN, +-Inf, negative or >= 2^32 after the division by the visit count)."""
+        if int(self.flags.item()) != 0:
+            raise L.PopcornHipError("CensusTable: a window held a NaN, infinite, negative or >= 2^32 value inside a census unit; "
+                                    "the table is incomplete")
+        if self.totals is None:
+            dev = self.table.device
+            self.totals = torch.empty(self.members, self.T, dtype=torch.float64, device=dev)
+            self.mean, self.std = torch.empty(self.T, dtype=torch.float32, device=dev), torch.empty(self.T, dtype=torch.float32, device=dev)
+        L.check(L.lib().pc_census_finalize(L.ptr(self.table), self.members, C.c_int64(self.T), L.ptr(self.totals), L.ptr(self.mean),
+                                           L.ptr(self.std), L.stream_ptr()), "pc_census_finalize")
+        return self.totals, self.mean, self.std
+
+    def level(self, l):
+        """(totals (M, num_ids[l]), mean, std) of census level l: views of the finalised table."""
+        if self.totals is None:
+            self.finalize()
+        a, b = self.offsets[l], self.offsets[l] + self.num_ids[l]
+        return self.totals[:, a:b], self.mean[a:b], self.std[a:b]
+
+    def census(self, l, census_idx, census_pop):
+        """(pred_mean (n,), pred_std (n,), pred_members (M, n), gt (n,)) for the census rows ``census_idx`` (unit ids of level l) /
+        ``census_pop`` (POP20): the per-unit counterpart of ``convert_popmap_to_census`` with the ensemble spread."""
+        totals, mean, std = self.level(l)
+        census_idx = torch.as_tensor(census_idx, dtype=torch.int64, device=mean.device)
+        gt = torch.as_tensor(census_pop, dtype=torch.float32, device=mean.device)
+        return mean[census_idx], std[census_idx], totals[:, census_idx].to(torch.float32), gt
+
+    def metrics(self, l, census_idx, census_pop, tag=""):
+        """``get_test_metrics`` of the ensemble mean under its usual keys, plus ``<key>_members_mean`` / ``<key>_members_std``: the mean
+        and the n - 1 standard deviation (0 for one member) over members of the metric computed for each member's own totals."""
+        from .utils.metrics import get_test_metrics
+        pm, _, members, gt = self.census(l, census_idx, census_pop)
+        res = {k: float(v) for k, v in get_test_metrics(pm, gt, tag=tag).items()}
+        per = [get_test_metrics(members[m], gt, tag=tag) for m in range(self.members)]
+        for k in list(res):
+            v = torch.tensor([float(p[k]) for p in per], dtype=torch.float64)
+            res[k + "_members_mean"] = v.mean().item()
+            res[k + "_members_std"] = v.std(unbiased=True).item() if self.members > 1 else 0.0
+        return res
+
+
+def census_detail_maps(pred_totals, boundary, census_idx, census_pop, pred_std=None):
+    """The six per-unit detail maps of the reference's ``full`` evaluation mode (``details_to=``, data/PopulationDataset.py:747-804) as
+    one gather launch instead of six Python loops over the census rows.  pred_totals: (num_ids,) predicted total per unit id (a level of
+    a ``CensusTable``, or ``census_sums``); boundary: (h, w) id raster; census_idx / census_pop: the census rows (unit id, POP20).
+    With ``count`` the pixel count of the unit (``pc_census_sum``'s counts) the maps hold, on every pixel of a unit with a census row:
+
+      densities      pred / count                          (:748-753)
+      totals         pred                                  (:756-761)
+      densities_gt   POP20 / count                         (:764-769)
+      totals_gt      POP20                                 (:772-777)
+      residuals      pred - POP20 in fp32                  (:780-785)
+      residuals_rel  (pred - POP20) / count, inf / NaN -> 0  (:788-804)
+      totals_std     pred_std (only when given; no counterpart in the reference)
+
+    and 0 on pixels of units without a census row and of ids outside [0, num_ids).  The per-unit values are computed once in float64
+    from the fp32 totals and rounded to fp32, then painted by ``ops.census_paint``.  Returns a dict of (h, w) fp32 device maps."""
+    from . import ops
+    L.require_device(pred_totals, boundary)
+    dev = pred_totals.device
+    num_ids = pred_totals.numel()
+    b32 = boundary.to(torch.int32).contiguous()
+    census_idx = torch.as_tensor(census_idx, dtype=torch.int64, device=dev)
+    # the pixel counts: pc_census_sum over the boundary plane itself (its bits read as fp32; the sums are not used)
+    _, counts = census_sums(b32.view(torch.float32), b32, num_ids, want_counts=True)
+    count = counts.double()
+    has = torch.zeros(num_ids, dtype=torch.bool, device=dev)
+    has[census_idx] = True
+    pred = pred_totals.to(torch.float32).double()
+    pop = torch.zeros(num_ids, dtype=torch.float64, device=dev)
+    pop[census_idx] = torch.as_tensor(census_pop, dtype=torch.float32, device=dev).double()
+    res = (pred - pop).to(torch.float32).double()
+    rel = res / count
+    rel[torch.isinf(rel) | torch.isnan(rel)] = 0
+    tabs = {"densities": pred / count, "totals": pred, "densities_gt": pop / count, "totals_gt": pop, "residuals": res,
+            "residuals_rel": rel}
+    if pred_std is not None:
+        tabs["totals_std"] = pred_std.to(device=dev, dtype=torch.float32).double()
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    names = list(tabs)
+    maps = ops.census_paint(b32, [torch.where(has, tabs[k], zero).to(torch.float32) for k in names])
+    return {k: maps[i] for i, k in enumerate(names)}
+
+
 def census_sums(pred, boundary, num_ids, want_counts=False):
     """sums[id] = sum(pred[boundary == id]) for id in [0, num_ids) -- one pass (segment sum).  pred: (h,w) f32,
     boundary: (h,w) int32.  Returns float64 sums (and int32 counts)."""
@@ -307,7 +463,7 @@ def raw_window_input(win, ascfill=False):
 
 def evaluate_raster(models, raster, patchsize=INFERENCE_PATCH_SIZE, overlap=OVERLAP, fourseasons=False,
                     reducer: FlatReducer | None = None, rank=0, band_reduce=True, gather=True, return_stitcher=False, raw=False,
-                    ascfill=False, product: ProductGrid | None = None):
+                    ascfill=False, product: ProductGrid | None = None, census: CensusTable | None = None):
     """Ensemble sliding-window inference over ``raster`` = callable (x, y, season, ps) -> normalised model input
     (1,6,ps,ps) on the device (the reference's Population_Dataset(mode="test") item, PopulationDataset.py:336-420), or a
     (S,6,h,w) device tensor of pre-normalised seasons.  Returns the finalised (mean map, std map, scale mean, scale std).
@@ -322,7 +478,9 @@ def evaluate_raster(models, raster, patchsize=INFERENCE_PATCH_SIZE, overlap=OVER
     "S1_asc" callable (the ascending orbit); every window is NaN-filled on the device and then normalised (``raw_window_input``; one
     host synchronisation per window for the 5 % orbit rule).  ``ascfill``: the reference's per-region switch to the ascending orbit.
     ``product``: a ``ProductGrid`` of this raster and ensemble; it is given the window list, fed every window this rank computes,
-    all-reduced and finalised on every rank (read ``product.mean`` / ``.std`` / ``.cells``); what is returned does not change."""
+    all-reduced and finalised on every rank (read ``product.mean`` / ``.std`` / ``.cells``); what is returned does not change.
+    ``census``: a ``CensusTable`` of this raster and ensemble, handled exactly like ``product`` (read ``census.totals`` / ``.mean`` /
+    ``.std``, ``census.level(l)``, ``census.metrics(...)``)."""
     reducer = reducer or FlatReducer()
     if torch.is_tensor(raster):
         h, w = raster.shape[-2:]
@@ -339,6 +497,11 @@ def evaluate_raster(models, raster, patchsize=INFERENCE_PATCH_SIZE, overlap=OVER
             raise ValueError(f"product grid of {product.h} x {product.w} x {product.members} members for a raster of {h} x {w} and "
                              f"{len(models)} models")
         product.set_windows(idx, patchsize, overlap)
+    if census is not None:
+        if (census.h, census.w, census.members) != (h, w, len(models)):
+            raise ValueError(f"census table of {census.h} x {census.w} x {census.members} members for a raster of {h} x {w} and "
+                             f"{len(models)} models")
+        census.set_windows(idx, patchsize, overlap)
     if band_reduce and reducer.world > 1:
         # the visit count needs no collective: the windows of the OTHER ranks enter this rank's count map analytically, all at once
         st.add_counts_only([(int(idx[i][0]), int(idx[i][1])) for i in range(idx.shape[0]) if i not in mine], len(models), patchsize, overlap)
@@ -370,9 +533,14 @@ def evaluate_raster(models, raster, patchsize=INFERENCE_PATCH_SIZE, overlap=OVER
         st.add_window(x, y, pd, torch.stack(scs) if scs else None, overlap)
         if product is not None:
             product.add_window(x, y, pd, overlap)
+        if census is not None:
+            census.add_window(x, y, pd, overlap)
     if product is not None:
         product.all_reduce(reducer)
         product.finalize()
+    if census is not None:
+        census.all_reduce(reducer)
+        census.finalize()
     if band_reduce and reducer.world > 1:
         # one reduce-scatter by row band (half the bytes of an all-reduce, no count collective), every rank finalises its band
         st.reduce_scatter(reducer, rank)

@@ -703,6 +703,31 @@ def block_sum(map, cell):
     return out
 
 
+def census_paint(boundary, tables, out=None):
+    """Per-unit tables painted onto the raster (csrc/census_table.hip, pc_census_paint): out[k][i] = tables[k][boundary[i]] for ids in
+    [0, num_ids), 0 elsewhere, for K <= PC_CENSUS_MAX_PLANES tables in ONE pass over the boundary plane.  boundary: int32 device map
+    (h, w) with contiguous rows stacked without gaps (a row band of a larger map is fine: any 4-byte aligned start); tables: (K, num_ids)
+    fp32 or a list of K (num_ids,) fp32 tensors.  out: optional (K, h, w) fp32 result (or a list of K band views).  Returns (K, h, w)."""
+    tables = [t.contiguous() for t in tables]
+    L.require_device(boundary, *tables)
+    K = len(tables)
+    if boundary.dim() != 2 or boundary.dtype != torch.int32 or not boundary.is_contiguous():
+        raise ValueError(f"census_paint: a contiguous int32 (h, w) boundary, got {boundary.dtype} {tuple(boundary.shape)}")
+    if not 1 <= K <= L.PC_CENSUS_MAX_PLANES or any(t.dtype != torch.float32 or t.dim() != 1 or t.numel() != tables[0].numel() or
+                                                   t.numel() < 1 for t in tables):
+        raise ValueError(f"census_paint: 1 .. {L.PC_CENSUS_MAX_PLANES} fp32 tables of one length >= 1, got {K}")
+    if out is None:
+        out = torch.empty(K, *boundary.shape, dtype=torch.float32, device=boundary.device)
+    planes = [out[k] for k in range(K)]
+    if any(p.shape != boundary.shape or p.dtype != torch.float32 or not p.is_contiguous() or not p.is_cuda for p in planes):
+        raise ValueError("census_paint: out must hold K contiguous fp32 device planes of the boundary's shape")
+    tp = (C.c_void_p * K)(*[t.data_ptr() for t in tables])
+    op = (C.c_void_p * K)(*[p.data_ptr() for p in planes])
+    L.check(L.lib().pc_census_paint(L.ptr(boundary), C.c_int64(boundary.numel()), tables[0].numel(), K, tp, op, L.stream_ptr()),
+            "pc_census_paint")
+    return out
+
+
 def nan_fill_(x, hw=None, count_only=False):
     """Nearest-value NaN fill in place (data/PopulationDataset.py:526-551 interpolate_nan, pc_nan_fill): x = contiguous fp32 device tensor
     (B, C, H, W) or (C, H, W), each sample's (C, h, w) array filled on its own -- every NaN takes the value of the nearest known entry in
