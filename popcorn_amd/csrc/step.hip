@@ -12,6 +12,11 @@
 //   * the up-sampled map of an Up block is allocated with the extent and strides of the skip tensor it is concatenated with (the
 //     transposed conv fills the top-left 2h x 2w of it): the two-source conv then sees two sources of identical layout;
 //   * a pooled source is handed over cropped to even extents (MaxPool2d(2) floors).
+//
+// The backward pass (struct Backward) is the network in reverse, one function per U-Net block, to be read next to engine.py: _Backward.
+// It has the COMPOSED form of the two Up blocks only: the trainable U-Net works on the add_padding domain, whose sides are multiples of
+// 32 (pad_geometry), so both levels have exact 2x geometry, widths that are multiples of 16 and 16-byte rows -- everything the composed
+// forward and backward ask for.  forward_nets refuses (PC_ENOTSUP, in the sizing pass) a network that saves activations otherwise.
 #include "common.h"
 #include <chrono>
 
@@ -82,8 +87,8 @@ struct Arena {
 
 // ---- the executor -------------------------------------------------------------------------------------------------------------------
 struct Saved {                 // activations of one (network, stream) pair that the backward pass reads
-    Ten a1, a2, b1, b2, c1, c2, u2, e1, e2, u1, f1, pa2, pb2;
-    void* ws_up1 = nullptr;
+    Ten a1, a2, b1, b2, c1, c2, e1, e2, f1, pa2, pb2;
+    void* ws_up1 = nullptr;    // composed operand images of the two Up blocks (never null: forward_nets)
     void* ws_up2 = nullptr;
 };
 
@@ -255,6 +260,8 @@ void forward_nets(Step& X, const Net* nets, int nE, const Ten& Xp, int Hp, int W
     };
     const bool compose2 = can_compose(H1, W1, H2, W2, 16);
     const bool compose1 = can_compose(Hp, Wp, H1, W1, 8);
+    // backward() has the composed form only.  Cannot fail today: a saving network runs on the add_padding domain (sides % 32 == 0, fp32).
+    if (any_save && !(compose1 && compose2)) return X.rc(PC_ENOTSUP);
     if (compose1 || compose2) {
         // the composed operand images of the levels in use, all (network, stream) pairs: one launch (they depend on the weights only)
         pc_conv_up_fwd_desc d[2 * MAXK];
@@ -278,18 +285,18 @@ void forward_nets(Step& X, const Net* nets, int nE, const Ten& Xp, int Hp, int W
     }
 
     // the 32 x 32 level in one launch (down2's DoubleConv + up2's transposed conv with the maps in LDS)
+    // (a saved pooled map has W1 % 32 == 0 and H1 % 4 == 0, so this is H1 = W1 = 64 exactly: a geometry every composed predicate takes,
+    // extractor included -- the launch writes c2 for the composed conv and never the up-sampled map)
     bool level2 = false;
-    if (pb2[0].ok() && H2 == 32 && W2 == 32) {
+    if (compose2 && pb2[0].ok() && H2 == 32 && W2 == 32) {
         pc_src sx[MAXK];
-        pc_dst d1[MAXK], d2[MAXK], du[MAXK];
+        pc_dst d1[MAXK], d2[MAXK];
         pc_level2_fwd_desc d[MAXK];
         level2 = true;
         const int64_t mark = A.off;
         for (int i = 0; i < K; ++i) {
-            const bool sv = nets[keys[i].e].save;
-            u2[i] = compose2 ? Ten{} : A.act(B, 16, 64, 64);
-            c1[i] = sv ? A.act(B, 16, 32, 32) : Ten{};
-            c2[i] = (sv || compose2) ? A.act(B, 16, 32, 32) : Ten{};
+            c1[i] = nets[keys[i].e].save ? A.act(B, 16, 32, 32) : Ten{};
+            c2[i] = A.act(B, 16, 32, 32);
             sx[i] = S(pb2[i]);
             memset(&d[i], 0, sizeof(d[i]));
             d[i].x = &sx[i];
@@ -297,15 +304,14 @@ void forward_nets(Step& X, const Net* nets, int nE, const Ten& Xp, int Hp, int W
             d[i].w2 = lay(keys[i]).w[L_D2B]; d[i].bn2 = &lay(keys[i]).bn[L_D2B];
             d[i].wt = lay(keys[i]).wt[T_UP2]; d[i].bt = lay(keys[i]).bt[T_UP2];
             if (c1[i].ok()) { d1[i] = D(c1[i]); d[i].c1 = &d1[i]; }
-            if (c2[i].ok()) { d2[i] = D(c2[i]); d[i].c2 = &d2[i]; }
-            if (u2[i].ok()) { du[i] = D(u2[i]); d[i].u2 = &du[i]; }
-            if (!pc_level2_fwd_ok(&sx[i], u2[i].ok() ? &du[i] : nullptr)) level2 = false;
+            d2[i] = D(c2[i]); d[i].c2 = &d2[i];
+            if (!pc_level2_fwd_ok(&sx[i], nullptr)) level2 = false;
         }
         if (level2) {
             if (X.go()) X.rc(pc_level2_fwd_group(K, d, B, X.st));
         } else {
             A.off = mark;
-            for (int i = 0; i < K; ++i) c1[i] = c2[i] = u2[i] = Ten{};
+            for (int i = 0; i < K; ++i) c1[i] = c2[i] = Ten{};
         }
     }
     if (!level2) {
@@ -344,7 +350,7 @@ void forward_nets(Step& X, const Net* nets, int nE, const Ten& Xp, int Hp, int W
     if (compose2) {
         up_conv(L_UP2A, T_UP2, b2, c2, e1, ws2, H1, W1);
     } else {
-        if (!u2[0].ok()) convt(T_UP2, c2, u2, 16, H2, W2, H1, W1);
+        convt(T_UP2, c2, u2, 16, H2, W2, H1, W1);
         conv(L_UP2A, b2, u2, e1, 8, H1, W1, PC_SRC_DIRECT, nullptr);
     }
     conv(L_UP2B, e1, nullptr, e2, 8, H1, W1, PC_SRC_DIRECT, nullptr);
@@ -380,8 +386,8 @@ void forward_nets(Step& X, const Net* nets, int nE, const Ten& Xp, int Hp, int W
     for (int i = 0; i < K; ++i) {
         if (!saved || !nets[keys[i].e].save) continue;
         Saved& sv = saved[keys[i].e][keys[i].s];
-        sv.a1 = a1[i]; sv.a2 = a2[i]; sv.b1 = b1[i]; sv.b2 = b2[i]; sv.c1 = c1[i]; sv.c2 = c2[i]; sv.u2 = u2[i]; sv.e1 = e1[i];
-        sv.e2 = e2[i]; sv.u1 = u1[i]; sv.f1 = f1[i]; sv.pa2 = pa2[i]; sv.pb2 = pb2[i]; sv.ws_up1 = ws1[i]; sv.ws_up2 = ws2[i];
+        sv.a1 = a1[i]; sv.a2 = a2[i]; sv.b1 = b1[i]; sv.b2 = b2[i]; sv.c1 = c1[i]; sv.c2 = c2[i]; sv.e1 = e1[i];
+        sv.e2 = e2[i]; sv.f1 = f1[i]; sv.pa2 = pa2[i]; sv.pb2 = pb2[i]; sv.ws_up1 = ws1[i]; sv.ws_up2 = ws2[i];
     }
 }
 
@@ -450,9 +456,15 @@ void forward(Step& X, pc_step_io& io) {
     Ten feats[2];
     Saved (*sv)[2] = nullptr;
     Saved svbuf[2][2];
-    const pc_src* featsrc = nullptr;
-    pc_src fs{};
     const float* am = io.admin_mask;
+    // building score + mask + census counts from the extractor's partial logits, which start (oy, ox) inside its domain
+    auto score_mask = [&](const Ten& logits, int oy, int ox) {
+        const pc_src fs = S(logits);
+        const pc_dst db = D(X.building);
+        if (X.go())
+            X.rc(pc_building_score_mask(&fs, X.ones2, P.extractor.fusion_b, &db, am, io.census_idx, X.sel, X.sel + H, P.occupancymodel, X.mask,
+                                        X.counts, B, H, W, oy, ox, X.st));
+    };
     if (same_domain) {
         unpack_sel();
         const Ten Xp = ingest(X, io, pt, pb, pl, pr);
@@ -462,11 +474,7 @@ void forward(Step& X, pc_step_io& io) {
         forward_nets(X, nets, 2, Xp, Hp, Wp, feats, sv);
         X.feats = feats[1];
         X.sv[0] = svbuf[1][0]; X.sv[1] = svbuf[1][1];
-        fs = S(feats[0]);
-        const pc_dst db = D(X.building);
-        if (X.go())
-            X.rc(pc_building_score_mask(&fs, X.ones2, P.extractor.fusion_b, &db, am, io.census_idx, X.sel, X.sel + H, P.occupancymodel, X.mask,
-                                        X.counts, B, H, W, pt, pl, X.st));
+        score_mask(feats[0], pt, pl);
     } else {
         // the frozen extractor on its own 14-pixel reflect-padded domain (popcorn.py:279-322)
         const bool two = X.side != nullptr && (int64_t)B * Hp * Wp <= X.side_px;
@@ -483,11 +491,7 @@ void forward(Step& X, pc_step_io& io) {
             const Ten Xb = ingest(X, io, p, p, p, p);
             const Net nb[1] = {Net{&P.extractor, false, true}};
             forward_nets(X, nb, 1, Xb, H + 2 * p, W + 2 * p, feats, nullptr);
-            fs = S(feats[0]);
-            const pc_dst db = D(X.building);
-            if (X.go())
-                X.rc(pc_building_score_mask(&fs, X.ones2, P.extractor.fusion_b, &db, am, io.census_idx, X.sel, X.sel + H, P.occupancymodel,
-                                            X.mask, X.counts, B, H, W, p, p, X.st));
+            score_mask(feats[0], p, p);
         }
         if (two) {
             if (X.go()) X.rc((int)hipEventRecord(X.ev_join, X.side));
@@ -504,15 +508,12 @@ void forward(Step& X, pc_step_io& io) {
         X.sv[0] = svbuf[0][0]; X.sv[1] = svbuf[0][1];
         if (two && X.go()) X.rc((int)hipStreamWaitEvent(main_st, X.ev_join, 0));      // join: the head needs the building score and the mask
     }
-    (void)featsrc;
     // sparse head + occupancy product + census sums (popcorn.py:161-190,195-228)
     const float* bld = X.building.p;
-    Ten ones{};
     if (!P.occupancymodel) {
         // popcorn.py:179-181: popdensemap = relu(out), no building product
         return X.rc(PC_ENOTSUP);
     }
-    (void)ones;
     const pc_src sf = S(X.feats);
     X.deferred_popcount = io.dp == 0;
     if (X.go())
@@ -528,12 +529,290 @@ struct Reduce {                // the batched second stage of all weight gradien
     pc_wgrad_reduce_desc e[40];
     int n = 0;
     float* head_ptrs[8];
-    int64_t slot_bytes = 0;
     // composed Up blocks: chain-rule launches behind the reduction
     pc_conv_up_bwd_desc ch8[2], ch16[2];
     pc_src ch_g[2][2], ch_z[2][2];
     pc_dst ch_gz[2][2];
     int n8 = 0, n16 = 0, nwg8 = 0, nwg16 = 0;
+
+    // one entry (popcorn_hip.h: pc_wgrad_reduce_desc).  kind 0: a conv's partials -> dw (rows co_stride apart, 0 = dense) and db;
+    // 2: a composed level's -> their total of Cin floats at dw; 3: the head's -> its 8 tensors (dw: the table of their pointers)
+    void add(const void* partial, float* dw, float* db, int nwg, int Cin, int Cout, int kind, int co_stride = 0) {
+        pc_wgrad_reduce_desc& d = e[n++];
+        memset(&d, 0, sizeof(d));
+        d.partial = reinterpret_cast<const float*>(partial);
+        d.dw = dw; d.db = db; d.nwg = nwg; d.Cin = Cin; d.Cout = Cout; d.kind = kind; d.accumulate = 0; d.dw_co_stride = co_stride;
+    }
+};
+
+struct T2 {                    // one tensor per stream
+    Ten t[2];
+    Ten& operator[](int s) { return t[s]; }
+    const Ten& operator[](int s) const { return t[s]; }
+};
+
+// The blocks of the network as the backward pass walks them (engine.py: _Up / _Down): layer indices and saved activations.
+// Up: first conv (over cat[skip | up-sampled z]) and transposed conv; c = channels of the skip tensor = of z
+struct UpLv { int conv, convt; Ten Saved::*skip; int skip_act; Ten Saved::*z; int z_act; void* Saved::*ws; int c; };
+constexpr UpLv UP1 = {L_UP1A, T_UP1, &Saved::a2, L_INC2, &Saved::e2, L_UP2B, &Saved::ws_up1, 8};
+constexpr UpLv UP2 = {L_UP2A, T_UP2, &Saved::b2, L_D1B, &Saved::c2, L_D2B, &Saved::ws_up2, 16};
+// Down: the DoubleConv behind a MaxPool2d(2); cin = channels of the pooled map (`pooled`: its saved copy, `full`: what it was pooled from)
+struct DownLv { int conv1, conv2; Ten Saved::*mid; Ten Saved::*pooled; Ten Saved::*full; int full_act, cin; };
+constexpr DownLv DOWN1 = {L_D1A, L_D1B, &Saved::b1, &Saved::pa2, &Saved::a2, L_INC2, 8};
+constexpr DownLv DOWN2 = {L_D2A, L_D2B, &Saved::c1, &Saved::pb2, &Saved::b2, L_D1B, 16};
+
+// One backward pass of the trainable U-Net: its context, the launch helpers (bwd8 ... up_bwd: one grouped entry point each, both streams)
+// and one function per block of the network (conv8, up, level2, down, first_layer), each of which decides its launch form where it
+// stands -- engine.py: _Backward issues the same launches in the same order.
+struct Backward {
+    Step& X;
+    const pc_step_stream* ST;
+    const Saved* sv;
+    const int B;
+    const bool enc_ng;
+    Reduce R;
+    // The weight-gradient-only launches (16-channel encoder layers, first layers) run on the side stream next to the data-gradient chain:
+    // they only feed the batched reduction at the end.
+    const hipStream_t main_st;
+    const bool two;
+    bool side_used = false;
+    const int64_t slot_bytes = pc_conv3x3_wgrad_ws_bytes(32, 8);      // partials of one weight-gradient problem
+
+    explicit Backward(Step& x)
+        : X(x), ST(x.plan.unet.s), sv(x.sv), B(x.B), enc_ng(x.enc_ng), main_st(x.st),
+          two(x.side != nullptr && (int64_t)x.B * x.Hp * x.Wp <= x.side_bwd_px) {}
+
+    void* slot(int64_t bytes = 0) { return X.ar.raw(bytes > slot_bytes ? bytes : slot_bytes); }
+    T2 fresh(int C, int h, int w) {
+        T2 t;
+        for (int s = 0; s < 2; ++s) t[s] = X.ar.act(B, C, h, w);
+        return t;
+    }
+    T2 saved(Ten Saved::*m) const { return T2{{sv[0].*m, sv[1].*m}}; }
+    // side_on(): everything enqueued on the caller's stream so far (the producers of the launch's operands) is ordered in front of the
+    // side stream's next launch
+    void side_on() {
+        if (!two) return;
+        if (X.go()) {
+            hipEvent_t ev = X.ev_dep[X.ev_next];
+            X.ev_next = (X.ev_next + 1) & 7;
+            X.rc((int)hipEventRecord(ev, main_st));
+            X.rc((int)hipStreamWaitEvent(X.side, ev, 0));
+        }
+        X.st = X.side;
+        side_used = true;
+    }
+    void side_off() { X.st = main_st; }
+
+    // ---- launch helpers
+    // data + weight gradient of an 8 -> 8 layer (or of an 8-channel column block of a wider one) in ONE launch, both streams
+    struct Blk { const Ten* g; const Ten* x; const pc_bn* x_bn; Ten* out; int L; int s; int c0_add; bool with_db; const Ten* pool_act = nullptr; };
+    void bwd8(const Blk* blk, int n, int cin_total, int h, int w) {
+        pc_src sg[MAXK], sx[MAXK], spa[MAXK];
+        pc_dst dout[MAXK];
+        pc_conv_bwd_desc d[MAXK];
+        void* ws[MAXK];
+        for (int i = 0; i < n; ++i) {
+            sg[i] = S(*blk[i].g); sx[i] = S(*blk[i].x); dout[i] = D(*blk[i].out);
+            ws[i] = slot();
+            memset(&d[i], 0, sizeof(d[i]));
+            d[i].g = &sg[i]; d[i].x = &sx[i]; d[i].w = ST[blk[i].s].w[blk[i].L]; d[i].x_bn = blk[i].x_bn; d[i].out = &dout[i]; d[i].ws = ws[i];
+            d[i].c0_add = blk[i].c0_add;
+            if (blk[i].pool_act) { spa[i] = S(*blk[i].pool_act); d[i].pool_act = &spa[i]; }     // Down block: scatter (+=) into the full-resolution gradient
+        }
+        int nwg = 0;
+        if (X.go()) X.rc(pc_conv3x3_bwd_group(n, d, cin_total, 0, blk[0].pool_act ? 1 : 0, B, h, w, &nwg, X.st));
+        for (int i = 0; i < n; ++i)
+            R.add(ws[i], ST[blk[i].s].dw[blk[i].L] + blk[i].c0_add * 9, blk[i].with_db ? ST[blk[i].s].db[blk[i].L] : nullptr, nwg, 8, blk[i].g->C, 0,
+                  cin_total * 9);
+    }
+    // a layer with a 16-channel input as ONE launch of bwd8: the two 8-channel halves of x (masked by half_bn[s][i]) are two problems per
+    // stream over the same gradient, each writing its half of the data gradient and its column block of the weight gradient
+    void bwd_halves(int L, const T2& g, const T2& x, const pc_bn (*half_bn)[2], T2& out, int cin_total, int h, int w) {
+        Blk b[4];
+        Ten xh[2][2], oh[2][2];
+        for (int s = 0; s < 2; ++s)
+            for (int i = 0; i < 2; ++i) {
+                xh[s][i] = chans(x[s], 8 * i, 8);
+                oh[s][i] = chans(out[s], 8 * i, 8);
+                b[2 * s + i] = Blk{&g[s], &xh[s][i], &half_bn[s][i], &oh[s][i], L, s, 8 * i, i == 0};
+            }
+        bwd8(b, 4, cin_total, h, w);
+    }
+    // does the fused launch take this (gradient, input block, output, pooled-from) combination?  (split-operand form, aligned fp32 tensors)
+    bool bwd_ok(const Ten& g, const Ten& x, const Ten& out, const Ten* pool_act, int h, int w) const {
+        const pc_src sg = S(g), sx = S(x);
+        const pc_dst dout = D(out);
+        pc_src spa;
+        if (pool_act) spa = S(*pool_act);
+        return pc_conv3x3_bwd_ok(&sg, &sx, &dout, pool_act ? &spa : nullptr, B, h, w) != 0;
+    }
+    // grouped weight gradient of layer L over both streams (side stream); cin_total: the layer's input channels where a is a column block
+    void wgrad(int L, const T2& a, int mode, const T2& g, int h, int w, int cin_total = 0) {
+        side_on();
+        pc_src sa[2], sg[2];
+        pc_conv_wgrad_desc d[2];
+        void* ws[2];
+        int Cin = 0;
+        for (int s = 0; s < 2; ++s) {
+            Ten src = a[s];
+            if (mode == PC_SRC_POOL2) src = crop(src, 2 * h, 2 * w);
+            sa[s] = S(src, mode); sg[s] = S(g[s]);
+            ws[s] = slot();
+            d[s] = pc_conv_wgrad_desc{&sa[s], nullptr, &sg[s], ws[s]};
+            Cin = src.C;
+        }
+        int nwg = 0;
+        if (X.go()) X.rc(pc_conv3x3_wgrad_partial_group(2, d, B, h, w, Cin, g[0].C, &nwg, X.st));
+        for (int s = 0; s < 2; ++s) R.add(ws[s], ST[s].dw[L], ST[s].db[L], nwg, Cin, g[0].C, 0, cin_total * 9);
+        side_off();
+    }
+    // data gradient of layer L w.r.t. all its cin input channels, masked by the producer actL of act; pool: scattered (+=) through the
+    // MaxPool2d(2) that act went into
+    void dgrad(int L, const T2& g, T2& out, int cin, const T2& act, int actL, bool pool, int h, int w) {
+        pc_src sg[2], sa[2];
+        pc_dst dout[2];
+        pc_conv_dgrad_desc d[2];
+        for (int s = 0; s < 2; ++s) {
+            sg[s] = S(g[s]); sa[s] = S(act[s]); dout[s] = D(out[s]);
+            d[s] = pc_conv_dgrad_desc{&sg[s], ST[s].w[L], &sa[s], &X.bn_nobias[s][actL], &dout[s]};
+        }
+        if (X.go()) X.rc(pc_conv3x3_dgrad_group(2, d, cin, 0, cin, pool ? 1 : 0, pool ? 1 : 0, B, h, w, g[0].C, X.st));
+    }
+    // composed Up block: dz, the composed weight gradient and the border sums from one pass over g (up_bwd.hip)
+    void up_bwd(const UpLv& lv, const T2& g, const T2* gz, int h, int w) {
+        pc_conv_up_bwd_desc* d = lv.c == 8 ? R.ch8 : R.ch16;
+        const int k = lv.c == 8 ? 0 : 1;
+        void* ws[2];
+        for (int s = 0; s < 2; ++s) {
+            R.ch_g[k][s] = S(g[s]); R.ch_z[k][s] = S(sv[s].*lv.z);
+            if (gz) R.ch_gz[k][s] = D((*gz)[s]);
+            ws[s] = slot(pc_conv3x3_up_bwd_ws_bytes(B, h, lv.c));
+            memset(&d[s], 0, sizeof(d[s]));
+            d[s].g = &R.ch_g[k][s]; d[s].z = &R.ch_z[k][s]; d[s].z_bn = &X.bn_nobias[s][lv.z_act]; d[s].gz = gz ? &R.ch_gz[k][s] : nullptr;
+            d[s].w = ST[s].w[lv.conv]; d[s].wt = ST[s].wt[lv.convt]; d[s].bt = ST[s].bt[lv.convt]; d[s].fwd_ws = sv[s].*lv.ws; d[s].ws = ws[s];
+            d[s].dw = ST[s].dw[lv.conv]; d[s].dwt = ST[s].dwt[lv.convt]; d[s].dbt = ST[s].dbt[lv.convt];
+        }
+        int nwg = 0, part = 0;
+        if (X.go()) X.rc(pc_conv3x3_up_bwd_partial_group(2, d, B, h, w, lv.c, lv.c, &nwg, &part, X.st));
+        else { nwg = 1; part = 1; }
+        for (int s = 0; s < 2; ++s) R.add(ws[s], reinterpret_cast<float*>(ws[s]) + (int64_t)nwg * part, nullptr, nwg, part, 0, 2);
+        if (lv.c == 8) { R.n8 = 2; R.nwg8 = nwg; } else { R.n16 = 2; R.nwg16 = nwg; }
+    }
+
+    // ---- the blocks
+    // an 8 -> 8 layer L (second conv of a DoubleConv at full or half resolution) over the saved x, made by layer actL: returns the
+    // gradient of its input
+    T2 conv8(int L, const T2& g, Ten Saved::*x, int actL, int h, int w) {
+        T2 out = fresh(8, h, w);
+        Blk b[2];
+        for (int s = 0; s < 2; ++s) b[s] = Blk{&g[s], &(sv[s].*x), &X.bn_nobias[s][actL], &out[s], L, s, 0, true};
+        bwd8(b, 2, 8, h, w);
+        return out;
+    }
+    // An Up block from the gradient g of its first conv's output at (h, w): the skip column block of that conv (weight gradient into the
+    // first c input columns, data gradient masked by the skip tensor's producer), then the composed pass for the up-sampled half and the
+    // transposed conv.  g_skip: gradient of the skip tensor (level 2 under encoder_no_grad: none, nobody reads it); gz: gradient of z
+    // (nullptr: not wanted)
+    void up(const UpLv& lv, const T2& g, int h, int w, T2& g_skip, T2* gz) {
+        const T2 skip = saved(lv.skip);
+        if (lv.c == 8) {            // one problem per stream, whatever the regime
+            g_skip = fresh(8, h, w);
+            Blk b[2];
+            for (int s = 0; s < 2; ++s) b[s] = Blk{&g[s], &skip[s], &X.bn_nobias[s][lv.skip_act], &g_skip[s], lv.conv, s, 0, true};
+            bwd8(b, 2, 16, h, w);
+        } else if (!enc_ng) {       // the two 8-channel halves of the 16-channel skip tensor
+            g_skip = fresh(16, h, w);
+            bwd_halves(lv.conv, g, skip, X.bn_half, g_skip, 32, h, w);
+        } else {
+            wgrad(lv.conv, skip, PC_SRC_DIRECT, g, h, w, 32);
+        }
+        if (gz) *gz = fresh(lv.c, h / 2, w / 2);
+        up_bwd(lv, g, gz, h, w);
+    }
+    // the 32 x 32 level: both weight gradients, the data gradient chain d2b -> d2a and the pooling scatter in one launch.  false: the
+    // geometry does not qualify, nothing was enqueued
+    bool level2(const T2& g_out, const T2& g_in, int h, int w) {
+        if (!sv[0].pb2.ok() || h != 32 || w != 32) return false;
+        pc_src sg[2], sc[2], sx[2], sa[2];
+        pc_dst dout[2];
+        pc_level2_bwd_desc d[2];
+        void* w1[2];
+        void* w2[2];
+        const int64_t mark = X.ar.off;
+        for (int s = 0; s < 2; ++s) {
+            sg[s] = S(g_out[s]); sc[s] = S(sv[s].c1); sx[s] = S(sv[s].pb2); sa[s] = S(sv[s].b2); dout[s] = D(g_in[s]);
+            w1[s] = slot(pc_level2_bwd_ws_bytes(B)); w2[s] = slot(pc_level2_bwd_ws_bytes(B));
+            d[s] = pc_level2_bwd_desc{&sg[s], &sc[s], &sx[s], ST[s].w[L_D2A], ST[s].w[L_D2B], &X.bn_nobias[s][L_D2A], &sa[s],
+                                      &X.bn_nobias[s][L_D1B], &dout[s], w1[s], w2[s]};
+            if (!pc_level2_bwd_ok(&sg[s], &sc[s], &sx[s], &sa[s], &dout[s])) {
+                X.ar.off = mark;
+                return false;
+            }
+        }
+        int nwg = 0;
+        if (X.go()) X.rc(pc_level2_bwd_group(2, d, B, &nwg, X.st));
+        for (int s = 0; s < 2; ++s) {
+            R.add(w1[s], ST[s].dw[L_D2A], ST[s].db[L_D2A], nwg, 16, 16, 0);
+            R.add(w2[s], ST[s].dw[L_D2B], ST[s].db[L_D2B], nwg, 16, 16, 0);
+        }
+        return true;
+    }
+    // A Down block's DoubleConv at (h, w), 16 channels: the second conv, then the first conv with the max-pool scatter (+=) into g_in, the
+    // gradient of the full-resolution map.
+    void down(const DownLv& lv, const T2& g_out, T2& g_in, int h, int w) {
+        const T2 mid = saved(lv.mid), pooled = saved(lv.pooled), full = saved(lv.full);
+        T2 g_mid = fresh(16, h, w);
+        // down1, round 6: data + weight gradient of each layer in ONE launch of the split-operand kernel -- the second conv as the two
+        // 8-channel halves of its input over the same 16-channel gradient (two problems per stream), the first with the max-pool scatter
+        // into inc2's gradient -- instead of four launches (weight gradient 16 -> 16, data gradient 16 -> 16, weight gradient 8 -> 16,
+        // pooled data gradient 16 -> 8).  Both layers take it, or neither; the launcher declines a 16-channel pooled map (down2).
+        bool fused = lv.cin == 8;
+        for (int s = 0; s < 2 && fused; ++s)
+            fused = bwd_ok(g_out[s], chans(mid[s], 8, 8), chans(g_mid[s], 8, 8), nullptr, h, w) && bwd_ok(g_mid[s], pooled[s], g_in[s], &full[s], h, w);
+        if (fused) {
+            bwd_halves(lv.conv2, g_out, mid, X.bn_half_d1a, g_mid, 16, h, w);
+            Blk a[2];
+            for (int s = 0; s < 2; ++s) a[s] = Blk{&g_mid[s], &pooled[s], &X.bn_nobias[s][lv.full_act], &g_in[s], lv.conv1, s, 0, true, &full[s]};
+            bwd8(a, 2, lv.cin, h, w);
+            return;
+        }
+        wgrad(lv.conv2, mid, PC_SRC_DIRECT, g_out, h, w);
+        dgrad(lv.conv2, g_out, g_mid, 16, mid, lv.conv1, false, h, w);
+        // (the forward saves the pooled map where the full one's width is a multiple of 32: always at level 1, at level 2 when W1 % 32 == 0)
+        if (pooled[0].ok()) wgrad(lv.conv1, pooled, PC_SRC_DIRECT, g_mid, h, w);
+        else wgrad(lv.conv1, full, PC_SRC_POOL2, g_mid, h, w);
+        dgrad(lv.conv1, g_mid, g_in, lv.cin, full, lv.full_act, true, h, w);
+    }
+    // first layers: weight gradients only, one launch per stream (2 / 4 input channels) over the padded input
+    void first_layer(const T2& G_a1) {
+        int c0 = 0;
+        side_on();
+        for (int s = 0; s < 2; ++s) {
+            const Ten xin = chans(X.Xp_u, c0, ST[s].cin);
+            const pc_src sa = S(xin), sg = S(G_a1[s]);
+            void* ws = slot();
+            int nwg = 0;
+            if (X.go()) X.rc(pc_conv3x3_wgrad_partial(&sa, nullptr, &sg, ws, B, X.Hp, X.Wp, ST[s].cin, 8, &nwg, X.st));
+            R.add(ws, ST[s].dw[L_INC1], ST[s].db[L_INC1], nwg, ST[s].cin, 8, 0);
+            c0 += ST[s].cin;
+        }
+        side_off();
+    }
+    // ONE batched fixed-order reduction for all layers (+ the head), then the chain rule of the composed levels
+    void finish() {
+        if (side_used && X.go()) {         // join: the reduction reads the side stream's partials
+            X.rc((int)hipEventRecord(X.ev_join, X.side));
+            X.rc((int)hipStreamWaitEvent(main_st, X.ev_join, 0));
+        }
+        if (X.go()) X.rc(pc_wgrad_reduce_batch(R.n, R.e, X.st));
+        if (R.n8 && R.n16) {
+            if (X.go()) X.rc(pc_conv3x3_up_chain_both(R.n8, R.ch8, R.nwg8, R.n16, R.ch16, R.nwg16, 0, X.st));
+        } else {
+            if (R.n8 && X.go()) X.rc(pc_conv3x3_up_chain_group(R.n8, R.ch8, 0, R.nwg8, 8, 8, X.st));
+            if (R.n16 && X.go()) X.rc(pc_conv3x3_up_chain_group(R.n16, R.ch16, 0, R.nwg16, 16, 16, X.st));
+        }
+    }
 };
 
 void backward(Step& X, pc_step_io& io) {
@@ -564,403 +843,35 @@ void backward(Step& X, pc_step_io& io) {
                              PC_HEAD_BWD_PACKED | (defer ? PC_HEAD_BWD_DEFER_REDUCE : 0), X.st));
         if (!defer) X.launches += 1;
     }
-    const int n_unet = P.n - P.n_head;
     if (X.unet_ng || X.enc_ng) {
         // parameters without a gradient in this regime keep exact zeros in the flat buffer (the clip norm runs over all of it)
-        if (X.go()) X.rc(pc_zero_fill(P.flat_g, n_unet, X.st));
+        if (X.go()) X.rc(pc_zero_fill(P.flat_g, P.n - P.n_head, X.st));
     }
     if (X.unet_ng) return;
 
-    Reduce R;
-    R.slot_bytes = pc_conv3x3_wgrad_ws_bytes(32, 8);
-    if (pc_convt2x2_wgrad_ws_bytes(16) > R.slot_bytes) R.slot_bytes = pc_convt2x2_wgrad_ws_bytes(16);
-    auto slot = [&](int64_t bytes = 0) { return A.raw(bytes > R.slot_bytes ? bytes : R.slot_bytes); };
-    auto entry = [&](const void* partial, float* dw, float* db, int nwg, int Cin, int Cout, int kind, int co_stride = 0, int col0 = 0) {
-        pc_wgrad_reduce_desc& e = R.e[R.n++];
-        memset(&e, 0, sizeof(e));
-        e.partial = reinterpret_cast<const float*>(partial);
-        e.dw = dw + col0; e.db = db; e.nwg = nwg; e.Cin = Cin; e.Cout = Cout; e.kind = kind; e.accumulate = 0; e.dw_co_stride = co_stride;
-    };
+    Backward p(X);
     {
-        // the head's partials: kind 3
+        // the head's partials
         const float* pp = nullptr;
         int nwg = 0;
         pc_head_bwd_partials(X.head_ws, B, H, W, &pp, &nwg);
-        pc_wgrad_reduce_desc& e = R.e[R.n++];
-        memset(&e, 0, sizeof(e));
-        for (int t = 0; t < 8; ++t) R.head_ptrs[t] = P.head_dw[t];
-        e.partial = pp; e.dw = reinterpret_cast<float*>(R.head_ptrs); e.nwg = nwg; e.kind = 3;
+        for (int t = 0; t < 8; ++t) p.R.head_ptrs[t] = P.head_dw[t];
+        p.R.add(pp, reinterpret_cast<float*>(p.R.head_ptrs), nullptr, nwg, 0, 0, 3);
     }
-    const pc_step_stream* ST = P.unet.s;
-    const Saved* sv = X.sv;
-    const bool enc_ng = X.enc_ng;
-
-    // data + weight gradient of an 8 -> 8 layer (or of an 8-channel column block of a wider one) in ONE launch, both streams
-    struct Blk { const Ten* g; const Ten* x; const pc_bn* x_bn; Ten* out; int L; int s; int c0_add; bool with_db; const Ten* pool_act = nullptr; };
-    auto bwd8 = [&](const Blk* blk, int n, int cin_total, int h, int w) {
-        pc_src sg[MAXK], sx[MAXK], spa[MAXK];
-        pc_dst dout[MAXK];
-        pc_conv_bwd_desc d[MAXK];
-        void* ws[MAXK];
-        for (int i = 0; i < n; ++i) {
-            sg[i] = S(*blk[i].g); sx[i] = S(*blk[i].x); dout[i] = D(*blk[i].out);
-            ws[i] = slot();
-            memset(&d[i], 0, sizeof(d[i]));
-            d[i].g = &sg[i]; d[i].x = &sx[i]; d[i].w = ST[blk[i].s].w[blk[i].L]; d[i].x_bn = blk[i].x_bn; d[i].out = &dout[i]; d[i].ws = ws[i];
-            d[i].c0_add = blk[i].c0_add;
-            if (blk[i].pool_act) { spa[i] = S(*blk[i].pool_act); d[i].pool_act = &spa[i]; }     // Down block: scatter (+=) into the full-resolution gradient
-        }
-        int nwg = 0;
-        if (X.go()) X.rc(pc_conv3x3_bwd_group(n, d, cin_total, 0, blk[0].pool_act ? 1 : 0, B, h, w, &nwg, X.st));
-        for (int i = 0; i < n; ++i)
-            entry(ws[i], ST[blk[i].s].dw[blk[i].L], blk[i].with_db ? ST[blk[i].s].db[blk[i].L] : nullptr, nwg, 8, blk[i].g->C, 0, cin_total * 9,
-                  blk[i].c0_add * 9);
-    };
-    // does the fused launch take this (gradient, input block, output, pooled-from) combination?  (split-operand form, aligned fp32 tensors)
-    auto bwd_ok = [&](const Ten& g, const Ten& x, const Ten& out, const Ten* pool_act, int h, int w) {
-        const pc_src sg = S(g), sx = S(x);
-        const pc_dst dout = D(out);
-        pc_src spa;
-        if (pool_act) spa = S(*pool_act);
-        return pc_conv3x3_bwd_ok(&sg, &sx, &dout, pool_act ? &spa : nullptr, B, h, w) != 0;
-    };
-    // The weight-gradient-only launches (16-channel encoder layers, first layers) run on the side stream next to the data-gradient chain:
-    // they only feed the batched reduction at the end.  side_on(): everything enqueued on the caller's stream so far (the producers of the
-    // launch's operands) is ordered in front of the side stream's next launch.
-    hipStream_t main_st = X.st;
-    const bool two = X.side != nullptr && (int64_t)B * Hp * Wp <= X.side_bwd_px;
-    bool side_used = false;
-    auto side_on = [&]() {
-        if (!two) return;
-        if (X.go()) {
-            hipEvent_t ev = X.ev_dep[X.ev_next];
-            X.ev_next = (X.ev_next + 1) & 7;
-            X.rc((int)hipEventRecord(ev, main_st));
-            X.rc((int)hipStreamWaitEvent(X.side, ev, 0));
-        }
-        X.st = X.side;
-        side_used = true;
-    };
-    auto side_off = [&]() { X.st = main_st; };
-    // grouped weight gradient of layer L over both streams: x = cat[a, b]
-    auto wgrad = [&](int L, const Ten* a, int mode, const Ten* b, const Ten* g, int Cout, int h, int w, int cin_total) {
-        side_on();
-        pc_src sa[2], sb[2], sg[2];
-        pc_conv_wgrad_desc d[2];
-        void* ws[2];
-        int Cin = 0;
-        for (int s = 0; s < 2; ++s) {
-            Ten src = a[s];
-            if (mode == PC_SRC_POOL2) src = crop(src, 2 * h, 2 * w);
-            sa[s] = S(src, mode); sg[s] = S(g[s]);
-            ws[s] = slot();
-            d[s] = pc_conv_wgrad_desc{&sa[s], nullptr, &sg[s], ws[s]};
-            Cin = src.C;
-            if (b) { sb[s] = S(b[s]); d[s].b = &sb[s]; Cin += b[s].C; }
-        }
-        int nwg = 0;
-        if (X.go()) X.rc(pc_conv3x3_wgrad_partial_group(2, d, B, h, w, Cin, Cout, &nwg, X.st));
-        for (int s = 0; s < 2; ++s) entry(ws[s], ST[s].dw[L], ST[s].db[L], nwg, Cin, Cout, 0, cin_total ? cin_total * 9 : 0, 0);
-        side_off();
-    };
-    struct Dg { const Ten* g; int s; int L; const Ten* act; const pc_bn* act_bn; Ten* out; int c0_add; };
-    auto dgrad = [&](const Dg* q, int n, int Cin_total, int c0, int cn, int pool, int acc, int h, int w, int Cg) {
-        pc_src sg[MAXK], sa[MAXK];
-        pc_dst dout[MAXK];
-        pc_conv_dgrad_desc d[MAXK];
-        for (int i = 0; i < n; ++i) {
-            sg[i] = S(*q[i].g); dout[i] = D(*q[i].out);
-            memset(&d[i], 0, sizeof(d[i]));
-            d[i].g = &sg[i]; d[i].w = ST[q[i].s].w[q[i].L] + 9 * q[i].c0_add; d[i].out = &dout[i];
-            if (q[i].act) { sa[i] = S(*q[i].act); d[i].act = &sa[i]; d[i].act_bn = q[i].act_bn; }
-        }
-        if (X.go()) X.rc(pc_conv3x3_dgrad_group(n, d, Cin_total, c0, cn, pool, acc, B, h, w, Cg, X.st));
-    };
-    // composed Up block: dz, the composed weight gradient and the border sums from one pass over g (up_bwd.hip)
-    auto up_bwd = [&](int T, int L, const Ten* g, const Ten* z, int zL, Ten* gz, void* const* fwd_ws, int h, int w, int Cz) {
-        pc_conv_up_bwd_desc* d = Cz == 8 ? R.ch8 : R.ch16;
-        const int lv = Cz == 8 ? 0 : 1;
-        void* ws[2];
-        for (int s = 0; s < 2; ++s) {
-            R.ch_g[lv][s] = S(g[s]); R.ch_z[lv][s] = S(z[s]);
-            if (gz) R.ch_gz[lv][s] = D(gz[s]);
-            ws[s] = slot(pc_conv3x3_up_bwd_ws_bytes(B, h, Cz));
-            memset(&d[s], 0, sizeof(d[s]));
-            d[s].g = &R.ch_g[lv][s]; d[s].z = &R.ch_z[lv][s]; d[s].z_bn = &X.bn_nobias[s][zL]; d[s].gz = gz ? &R.ch_gz[lv][s] : nullptr;
-            d[s].w = ST[s].w[L]; d[s].wt = ST[s].wt[T]; d[s].bt = ST[s].bt[T]; d[s].fwd_ws = fwd_ws[s]; d[s].ws = ws[s];
-            d[s].dw = ST[s].dw[L]; d[s].dwt = ST[s].dwt[T]; d[s].dbt = ST[s].dbt[T];
-        }
-        int nwg = 0, part = 0;
-        if (X.go()) X.rc(pc_conv3x3_up_bwd_partial_group(2, d, B, h, w, Cz, Cz, &nwg, &part, X.st));
-        else { nwg = 1; part = 1; }
-        for (int s = 0; s < 2; ++s) {
-            pc_wgrad_reduce_desc& e = R.e[R.n++];
-            memset(&e, 0, sizeof(e));
-            e.partial = reinterpret_cast<const float*>(ws[s]);
-            e.dw = reinterpret_cast<float*>(ws[s]) + (int64_t)nwg * part;
-            e.nwg = nwg; e.Cin = part; e.kind = 2;
-        }
-        if (Cz == 8) { R.n8 = 2; R.nwg8 = nwg; } else { R.n16 = 2; R.nwg16 = nwg; }
-    };
-    // transposed conv T: weight gradient + data gradient (masked by x's producer xL) -- one launch when the fused form applies
-    auto ct_bwd = [&](int T, const Ten* x, int xL, const Ten* g, Ten* out, int h, int w, int C, bool want_dx) {
-        pc_src sx[2], sg[2];
-        pc_dst dout[2];
-        void* ws[2];
-        bool fused = want_dx && (w % 16 == 0);
-        for (int s = 0; s < 2; ++s) {
-            sx[s] = S(x[s]); sg[s] = S(g[s]);
-            if (want_dx) dout[s] = D(out[s]);
-            ws[s] = slot();
-        }
-        int nwg = 0;
-        if (fused) {
-            pc_convt_bwd_desc d[2];
-            for (int s = 0; s < 2; ++s) d[s] = pc_convt_bwd_desc{&sx[s], &sg[s], ST[s].wt[T], &X.bn_nobias[s][xL], &dout[s], ws[s]};
-            if (X.go()) X.rc(pc_convt2x2_bwd_group(2, d, B, h, w, C, &nwg, X.st));
-        } else {
-            pc_convt_wgrad_desc d[2];
-            for (int s = 0; s < 2; ++s) d[s] = pc_convt_wgrad_desc{&sx[s], &sg[s], ws[s]};
-            if (X.go()) X.rc(pc_convt2x2_wgrad_partial_group(2, d, B, h, w, C, &nwg, X.st));
-            if (want_dx) {
-                pc_convt_dgrad_desc q[2];
-                for (int s = 0; s < 2; ++s) q[s] = pc_convt_dgrad_desc{&sg[s], ST[s].wt[T], &sx[s], &X.bn_nobias[s][xL], &dout[s]};
-                if (X.go()) X.rc(pc_convt2x2_dgrad_group(2, q, B, h, w, C, X.st));
-            }
-        }
-        for (int s = 0; s < 2; ++s) entry(ws[s], ST[s].dwt[T], ST[s].dbt[T], nwg, C, C, 1);
-    };
-
-    Ten G_f2[2], G_f1[2], G_e2[2], G_a2[2], G_e1[2], G_b2[2], G_c2[2], G_c1[2], G_b1[2], G_a1[2], g_u1[2], g_u2[2];
-    for (int s = 0; s < 2; ++s) G_f2[s] = chans(G, ST[s].feat_c0, 8);
-    // up1b
-    {
-        Blk b[2];
-        for (int s = 0; s < 2; ++s) {
-            G_f1[s] = A.act(B, 8, Hp, Wp);
-            b[s] = Blk{&G_f2[s], &sv[s].f1, &X.bn_nobias[s][L_UP1A], &G_f1[s], L_UP1B, s, 0, true};
-        }
-        bwd8(b, 2, 8, Hp, Wp);
+    // the network in reverse, one call per block (engine.py: UNetEngine.backward)
+    T2 G_f2, G_a2, G_e2, G_b2, G_c2;
+    for (int s = 0; s < 2; ++s) G_f2[s] = chans(G, p.ST[s].feat_c0, 8);
+    const T2 G_f1 = p.conv8(L_UP1B, G_f2, &Saved::f1, L_UP1A, Hp, Wp);
+    p.up(UP1, G_f1, Hp, Wp, G_a2, &G_e2);
+    const T2 G_e1 = p.conv8(L_UP2B, G_e2, &Saved::e1, L_UP2A, H1, W1);
+    p.up(UP2, G_e1, H1, W1, G_b2, X.enc_ng ? nullptr : &G_c2);
+    if (!X.enc_ng) {
+        if (!p.level2(G_c2, G_b2, H2, W2)) p.down(DOWN2, G_c2, G_b2, H2, W2);
+        p.down(DOWN1, G_b2, G_a2, H1, W1);
+        const T2 G_a1 = p.conv8(L_INC2, G_a2, &Saved::a1, L_INC1, Hp, Wp);
+        p.first_layer(G_a1);
     }
-    for (int s = 0; s < 2; ++s) G_e2[s] = A.act(B, 8, H1, W1);
-    const bool composed1 = sv[0].ws_up1 != nullptr, composed2 = sv[0].ws_up2 != nullptr;
-    if (composed1) {
-        Blk b[2];
-        for (int s = 0; s < 2; ++s) {
-            G_a2[s] = A.act(B, 8, Hp, Wp);
-            b[s] = Blk{&G_f1[s], &sv[s].a2, &X.bn_nobias[s][L_INC2], &G_a2[s], L_UP1A, s, 0, true};
-        }
-        bwd8(b, 2, 16, Hp, Wp);
-        Ten z[2] = {sv[0].e2, sv[1].e2};
-        void* fw[2] = {sv[0].ws_up1, sv[1].ws_up1};
-        up_bwd(T_UP1, L_UP1A, G_f1, z, L_UP2B, G_e2, fw, Hp, Wp, 8);
-    } else {
-        if (!enc_ng) {
-            // both column blocks of the concat layer (networks.py:318: [skip | up]) in ONE launch over the same gradient
-            Blk b[4];
-            for (int s = 0; s < 2; ++s) {
-                G_a2[s] = A.act(B, 8, Hp, Wp);
-                g_u1[s] = A.act(B, 8, Hp, Wp);
-                b[s] = Blk{&G_f1[s], &sv[s].a2, &X.bn_nobias[s][L_INC2], &G_a2[s], L_UP1A, s, 0, true};
-            }
-            Ten u1full[2];
-            for (int s = 0; s < 2; ++s) {
-                u1full[s] = crop(sv[s].u1, Hp, Wp);
-                b[2 + s] = Blk{&G_f1[s], &u1full[s], nullptr, &g_u1[s], L_UP1A, s, 8, false};
-            }
-            bwd8(b, 4, 16, Hp, Wp);
-        } else {
-            Ten a[2] = {sv[0].a2, sv[1].a2}, u[2] = {crop(sv[0].u1, Hp, Wp), crop(sv[1].u1, Hp, Wp)};
-            wgrad(L_UP1A, a, PC_SRC_DIRECT, u, G_f1, 8, Hp, Wp, 0);
-            Dg q[2];
-            for (int s = 0; s < 2; ++s) {
-                g_u1[s] = A.act(B, 8, Hp, Wp);
-                q[s] = Dg{&G_f1[s], s, L_UP1A, nullptr, nullptr, &g_u1[s], 0};
-            }
-            dgrad(q, 2, 16, 8, 8, 0, 0, Hp, Wp, 8);
-        }
-        Ten x[2] = {sv[0].e2, sv[1].e2};
-        Ten gv[2] = {crop(g_u1[0], 2 * H1, 2 * W1), crop(g_u1[1], 2 * H1, 2 * W1)};
-        ct_bwd(T_UP1, x, L_UP2B, gv, G_e2, H1, W1, 8, true);
-    }
-    // up2b
-    {
-        Blk b[2];
-        for (int s = 0; s < 2; ++s) {
-            G_e1[s] = A.act(B, 8, H1, W1);
-            b[s] = Blk{&G_e2[s], &sv[s].e1, &X.bn_nobias[s][L_UP2A], &G_e1[s], L_UP2B, s, 0, true};
-        }
-        bwd8(b, 2, 8, H1, W1);
-    }
-    if (composed2) {
-        if (!enc_ng) {
-            // the two 8-channel halves of the 16-channel skip tensor: two problems per stream over the same gradient, each writing its half
-            // of the data gradient and its column block of the weight gradient
-            Blk b[4];
-            Ten xh[2][2], oh[2][2];
-            for (int s = 0; s < 2; ++s) {
-                G_b2[s] = A.act(B, 16, H1, W1);
-                for (int i = 0; i < 2; ++i) {
-                    xh[s][i] = chans(sv[s].b2, 8 * i, 8);
-                    oh[s][i] = chans(G_b2[s], 8 * i, 8);
-                    b[2 * s + i] = Blk{&G_e1[s], &xh[s][i], &X.bn_half[s][i], &oh[s][i], L_UP2A, s, 8 * i, i == 0};
-                }
-            }
-            bwd8(b, 4, 32, H1, W1);
-            for (int s = 0; s < 2; ++s) G_c2[s] = A.act(B, 16, H2, W2);
-        } else {
-            Ten a[2] = {sv[0].b2, sv[1].b2};
-            wgrad(L_UP2A, a, PC_SRC_DIRECT, nullptr, G_e1, 8, H1, W1, 32);
-        }
-        Ten z[2] = {sv[0].c2, sv[1].c2};
-        void* fw[2] = {sv[0].ws_up2, sv[1].ws_up2};
-        up_bwd(T_UP2, L_UP2A, G_e1, z, L_D2B, enc_ng ? nullptr : G_c2, fw, H1, W1, 16);
-    } else {
-        Ten a[2] = {sv[0].b2, sv[1].b2}, u[2] = {crop(sv[0].u2, H1, W1), crop(sv[1].u2, H1, W1)};
-        wgrad(L_UP2A, a, PC_SRC_DIRECT, u, G_e1, 8, H1, W1, 0);
-        if (!enc_ng) {
-            Dg q[4];
-            for (int s = 0; s < 2; ++s) {
-                G_b2[s] = A.act(B, 16, H1, W1);
-                g_u2[s] = A.act(B, 16, H1, W1);
-                q[s] = Dg{&G_e1[s], s, L_UP2A, &sv[s].b2, &X.bn_nobias[s][L_D1B], &G_b2[s], 0};
-                q[2 + s] = Dg{&G_e1[s], s, L_UP2A, nullptr, nullptr, &g_u2[s], 16};
-            }
-            dgrad(q, 4, 32, 0, 16, 0, 0, H1, W1, 8);
-        } else {
-            Dg q[2];
-            for (int s = 0; s < 2; ++s) {
-                g_u2[s] = A.act(B, 16, H1, W1);
-                q[s] = Dg{&G_e1[s], s, L_UP2A, nullptr, nullptr, &g_u2[s], 0};
-            }
-            dgrad(q, 2, 32, 16, 16, 0, 0, H1, W1, 8);
-        }
-        Ten x[2] = {sv[0].c2, sv[1].c2};
-        Ten gv[2] = {crop(g_u2[0], 2 * H2, 2 * W2), crop(g_u2[1], 2 * H2, 2 * W2)};
-        if (!enc_ng)
-            for (int s = 0; s < 2; ++s) G_c2[s] = A.act(B, 16, H2, W2);
-        ct_bwd(T_UP2, x, L_D2B, gv, G_c2, H2, W2, 16, !enc_ng);
-    }
-    if (!enc_ng) {
-        // encoder.  The 32 x 32 level: both weight gradients, the data gradient chain d2b -> d2a and the pooling scatter in one launch
-        bool l2 = sv[0].pb2.ok() && H2 == 32 && W2 == 32;
-        if (l2) {
-            pc_src sg[2], sc[2], sx[2], sa[2];
-            pc_dst dout[2];
-            pc_level2_bwd_desc d[2];
-            void* w1[2];
-            void* w2[2];
-            const int64_t mark = A.off;
-            for (int s = 0; s < 2; ++s) {
-                sg[s] = S(G_c2[s]); sc[s] = S(sv[s].c1); sx[s] = S(sv[s].pb2); sa[s] = S(sv[s].b2); dout[s] = D(G_b2[s]);
-                w1[s] = slot(pc_level2_bwd_ws_bytes(B)); w2[s] = slot(pc_level2_bwd_ws_bytes(B));
-                d[s] = pc_level2_bwd_desc{&sg[s], &sc[s], &sx[s], ST[s].w[L_D2A], ST[s].w[L_D2B], &X.bn_nobias[s][L_D2A], &sa[s],
-                                          &X.bn_nobias[s][L_D1B], &dout[s], w1[s], w2[s]};
-                if (!pc_level2_bwd_ok(&sg[s], &sc[s], &sx[s], &sa[s], &dout[s])) l2 = false;
-            }
-            if (l2) {
-                int nwg = 0;
-                if (X.go()) X.rc(pc_level2_bwd_group(2, d, B, &nwg, X.st));
-                for (int s = 0; s < 2; ++s) {
-                    entry(w1[s], ST[s].dw[L_D2A], ST[s].db[L_D2A], nwg, 16, 16, 0);
-                    entry(w2[s], ST[s].dw[L_D2B], ST[s].db[L_D2B], nwg, 16, 16, 0);
-                }
-            } else {
-                A.off = mark;
-            }
-        }
-        if (!l2) {
-            Ten c1[2] = {sv[0].c1, sv[1].c1};
-            wgrad(L_D2B, c1, PC_SRC_DIRECT, nullptr, G_c2, 16, H2, W2, 0);
-            Dg q[2];
-            for (int s = 0; s < 2; ++s) {
-                G_c1[s] = A.act(B, 16, H2, W2);
-                q[s] = Dg{&G_c2[s], s, L_D2B, &sv[s].c1, &X.bn_nobias[s][L_D2A], &G_c1[s], 0};
-            }
-            dgrad(q, 2, 16, 0, 16, 0, 0, H2, W2, 16);
-            if (sv[0].pb2.ok()) {
-                Ten x[2] = {sv[0].pb2, sv[1].pb2};
-                wgrad(L_D2A, x, PC_SRC_DIRECT, nullptr, G_c1, 16, H2, W2, 0);
-            } else {
-                Ten x[2] = {sv[0].b2, sv[1].b2};
-                wgrad(L_D2A, x, PC_SRC_POOL2, nullptr, G_c1, 16, H2, W2, 0);
-            }
-            for (int s = 0; s < 2; ++s) q[s] = Dg{&G_c1[s], s, L_D2A, &sv[s].b2, &X.bn_nobias[s][L_D1B], &G_b2[s], 0};
-            dgrad(q, 2, 16, 0, 16, 1, 1, H2, W2, 16);
-        }
-        for (int s = 0; s < 2; ++s) G_b1[s] = A.act(B, 16, H1, W1);
-        // down1 (16 channels @ H1 x W1), round 6: data + weight gradient of each layer in ONE launch of the split-operand kernel -- d1b as the two
-        // 8-channel halves of its input over the same 16-channel gradient (two problems per stream), d1a with the max-pool scatter into
-        // inc2's gradient -- instead of four launches (weight gradient 16 -> 16, data gradient 16 -> 16, weight gradient 8 -> 16, pooled
-        // data gradient 16 -> 8)
-        bool fused_d1 = sv[0].pa2.ok() && 4 <= MAXK;
-        for (int s = 0; s < 2 && fused_d1; ++s) {
-            const Ten xh = chans(sv[s].b1, 8, 8), oh = chans(G_b1[s], 8, 8);
-            fused_d1 = bwd_ok(G_b2[s], xh, oh, nullptr, H1, W1) && bwd_ok(G_b1[s], sv[s].pa2, G_a2[s], &sv[s].a2, H1, W1);
-        }
-        if (fused_d1) {
-            Blk b[4];
-            Ten xh[2][2], oh[2][2];
-            for (int s = 0; s < 2; ++s)
-                for (int i = 0; i < 2; ++i) {
-                    xh[s][i] = chans(sv[s].b1, 8 * i, 8);
-                    oh[s][i] = chans(G_b1[s], 8 * i, 8);
-                    b[2 * s + i] = Blk{&G_b2[s], &xh[s][i], &X.bn_half_d1a[s][i], &oh[s][i], L_D1B, s, 8 * i, i == 0};
-                }
-            bwd8(b, 4, 16, H1, W1);
-            Blk a[2];
-            for (int s = 0; s < 2; ++s) a[s] = Blk{&G_b1[s], &sv[s].pa2, &X.bn_nobias[s][L_INC2], &G_a2[s], L_D1A, s, 0, true, &sv[s].a2};
-            bwd8(a, 2, 8, H1, W1);
-        } else {
-            Ten x[2] = {sv[0].b1, sv[1].b1};
-            wgrad(L_D1B, x, PC_SRC_DIRECT, nullptr, G_b2, 16, H1, W1, 0);
-            Dg q[2];
-            for (int s = 0; s < 2; ++s) q[s] = Dg{&G_b2[s], s, L_D1B, &sv[s].b1, &X.bn_nobias[s][L_D1A], &G_b1[s], 0};
-            dgrad(q, 2, 16, 0, 16, 0, 0, H1, W1, 16);
-            if (sv[0].pa2.ok()) {
-                Ten xa[2] = {sv[0].pa2, sv[1].pa2};
-                wgrad(L_D1A, xa, PC_SRC_DIRECT, nullptr, G_b1, 16, H1, W1, 0);
-            } else {
-                Ten xa[2] = {sv[0].a2, sv[1].a2};
-                wgrad(L_D1A, xa, PC_SRC_POOL2, nullptr, G_b1, 16, H1, W1, 0);
-            }
-            for (int s = 0; s < 2; ++s) q[s] = Dg{&G_b1[s], s, L_D1A, &sv[s].a2, &X.bn_nobias[s][L_INC2], &G_a2[s], 0};
-            dgrad(q, 2, 8, 0, 8, 1, 1, H1, W1, 16);
-        }
-        {
-            Blk b[2];
-            for (int s = 0; s < 2; ++s) {
-                G_a1[s] = A.act(B, 8, Hp, Wp);
-                b[s] = Blk{&G_a2[s], &sv[s].a1, &X.bn_nobias[s][L_INC1], &G_a1[s], L_INC2, s, 0, true};
-            }
-            bwd8(b, 2, 8, Hp, Wp);
-        }
-        // first layers: one launch per stream (2 / 4 input channels) over the padded input
-        int c0 = 0;
-        side_on();
-        for (int s = 0; s < 2; ++s) {
-            const Ten xin = chans(X.Xp_u, c0, ST[s].cin);
-            const pc_src sa = S(xin), sg = S(G_a1[s]);
-            void* ws = slot();
-            int nwg = 0;
-            if (X.go()) X.rc(pc_conv3x3_wgrad_partial(&sa, nullptr, &sg, ws, B, Hp, Wp, ST[s].cin, 8, &nwg, X.st));
-            entry(ws, ST[s].dw[L_INC1], ST[s].db[L_INC1], nwg, ST[s].cin, 8, 0);
-            c0 += ST[s].cin;
-        }
-        side_off();
-    }
-    if (side_used && X.go()) {         // join: the reduction reads the side stream's partials
-        X.rc((int)hipEventRecord(X.ev_join, X.side));
-        X.rc((int)hipStreamWaitEvent(main_st, X.ev_join, 0));
-    }
-    // ONE batched fixed-order reduction for all layers (+ the head), then the chain rule of the composed levels
-    if (X.go()) X.rc(pc_wgrad_reduce_batch(R.n, R.e, X.st));
-    if (R.n8 && R.n16) {
-        if (X.go()) X.rc(pc_conv3x3_up_chain_both(R.n8, R.ch8, R.nwg8, R.n16, R.ch16, R.nwg16, 0, X.st));
-    } else {
-        if (R.n8 && X.go()) X.rc(pc_conv3x3_up_chain_group(R.n8, R.ch8, 0, R.nwg8, 8, 8, X.st));
-        if (R.n16 && X.go()) X.rc(pc_conv3x3_up_chain_group(R.n16, R.ch16, 0, R.nwg16, 16, 16, X.st));
-    }
+    p.finish();
 }
 
 void update(Step& X) {

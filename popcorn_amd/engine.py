@@ -353,7 +353,8 @@ class _Backward:
                                "w": ly(s, lv.conv).w, "wt": ly(s, lv.convt).w, "bt": ly(s, lv.convt).b, "fwd_ws": self.A[s][lv.ws],
                                "dw": self.dw(s, lv.conv), "dwt": self.dw(s, lv.convt), "dbt": self.db(s, lv.convt)} for s in self.S])
 
-    # ---- the blocks (csrc/step.hip: backward issues the same launches through its bwd8 / wgrad / dgrad / up_bwd / ct_bwd)
+    # ---- the blocks (csrc/step.hip: struct Backward has the same five, over its bwd8 / bwd_halves / wgrad / dgrad / up_bwd; it has no
+    # non-composed Up block -- bwd_cat / convt_bwd -- because its trainable network always runs on a domain whose levels compose)
     def conv8(self, tag, gs, x_key, act_tag, h, w):
         """an 8 -> 8 layer (second conv of a DoubleConv at full or half resolution): returns the gradient of its input"""
         outs, xs = self.new(8, h, w), {s: self.A[s][x_key] for s in self.S}

@@ -141,6 +141,53 @@ def test_c_abi_exports_every_declared_symbol():
     assert ctypes.sizeof(L.PcLevel2FwdDesc) == lib.pc_sizeof(5)
 
 
+def test_every_training_domain_takes_the_composed_up_blocks():
+    """The native executor's backward (csrc/step.hip) has the composed form of the two Up blocks only, and d1a always reads the saved
+    pooled map.  That rests on: add_padding domains have sides that are multiples of 32, and on such a domain, in the executor's arena
+    layout (planar fp32, rows padded to 4 floats, 16-byte aligned base), the library's own predicates take both levels.  Descriptors
+    only: nothing is dereferenced."""
+    from popcorn_amd import _lib as L
+    from popcorn_amd.model.popcorn import pad_geometry
+    lib = L.lib()
+    assert lib.pc_get_precision() == L.PC_PREC_FP32
+    base = 1 << 40
+
+    def views(B, c, h, w):
+        sr = (w + 3) & ~3
+        sc = h * sr
+        src = L.PcSrc(ptr=base, C=c, H=h, W=w, bstride=c * sc, cstride=sc, rstride=sr, mode=L.PC_SRC_DIRECT, oy=0, ox=0,
+                      chmap=(ctypes.c_int32 * 4)(0, 1, 2, 3), dtype=L.PC_F32_T, xstride=1)
+        dst = L.PcDst(ptr=base, bstride=c * sc, cstride=sc, rstride=sr, dtype=L.PC_F32_T, xstride=1)
+        return src, dst
+
+    declined = []
+    for B in (1, 3):
+        for Hp in range(32, 2049, 32):
+            for Wp in range(32, 2049, 32):
+                for c, h, w in ((8, Hp, Wp), (16, Hp // 2, Wp // 2)):            # level 1, level 2
+                    skip, _ = views(B, c, h, w)
+                    z, gz = views(B, c, h // 2, w // 2)
+                    g, out = views(B, 8, h, w)
+                    ok = (lib.pc_conv3x3_up_fwd_ok(ctypes.byref(skip), ctypes.byref(z), ctypes.byref(out), h, w, c, c)
+                          and lib.pc_conv3x3_up_bwd_ok(ctypes.byref(g), ctypes.byref(z), ctypes.byref(gz), h, w, c, c)
+                          and lib.pc_conv3x3_up_bwd_ok(ctypes.byref(g), ctypes.byref(z), None, h, w, c, c))
+                    if not ok:
+                        declined.append(("up", B, c, h, w))
+                _, a2 = views(B, 8, Hp, Wp)
+                if not lib.pc_conv3x3_pool_out_ok(ctypes.byref(a2), Hp, Wp):
+                    declined.append(("pool", B, 8, Hp, Wp))
+    assert not declined, declined[:8]
+    # what pc_train_step accepts (padding smaller than the input, like the extractor's 14) is padded to a multiple of 32, at least 32
+    accepted = 0
+    for H in range(15, 1201):
+        pt, pb, _, _ = pad_geometry(H, H, False)
+        if pt >= H or pb >= H:
+            continue
+        accepted += 1
+        assert (H + pt + pb) % 32 == 0 and H + pt + pb >= 32, (H, pt, pb)
+    assert accepted > 1100
+
+
 def test_graft_entry_build_passes_on_the_current_tree():
     """`__graft_entry__.build()` is the driver's "does it build" check: make (a no-op when the in-tree library is current), import,
     ABI assertion.  (Round 4 bumped the ABI twice; the assertion inside build() must follow the binding.)"""
