@@ -760,6 +760,40 @@ typedef struct pc_input_grad_desc {
 int pc_input_grad(int n, const pc_input_grad_desc* d, float* dx, int B, int Cx, int H, int W, int pad_top, int pad_bottom, int pad_left,
                   int pad_right, void* stream);
 
+/* ---- multi-unit census supervision: all listed census units of a crop in one step (csrc/units.hip) ----
+ * The reference supervises one census unit per sample (popcorn.py:184-190,361-377).  A multi-unit batch lists K_b >= 1 units per sample and
+ * is defined as the reference's result on the replicated batch (input[b], admin_mask[b], unit, y) of N = sum K_b samples with the same two
+ * multinomial draws.  The lists arrive flattened: units = DEVICE int64 [N], non-negative, distinct and ASCENDING within each sample;
+ * unit_off = DEVICE int32 [B + 1], sample b owns units[unit_off[b] .. unit_off[b + 1]), unit_off[0] = 0, unit_off[B] = N.  No compile-time
+ * cap on K_b.  Ids compare as the one-unit kernels do, admin_mask == (float)id: ids above 2^24 that round to one float are one unit.
+ *
+ * pc_unit_mask, ONE launch (last-block ticket as pc_building_score_mask; must not run concurrently with itself on two streams of one
+ * device).  building (B, 1, H, W), admin_mask (B, H, W) float ids, rowsel / colsel as for pc_sparsity_mask:
+ *   slot[b,y,x]  int32: the flat index n in [0, N) of the listed unit of sample b that owns the pixel, else -1 (unlisted neighbours, the
+ *                collate's -1 padding, the rotation's -1 fill, NaN)
+ *   mask[b,y,x]  uint8 = slot >= 0 && (base || (rowsel[y] && colsel[x])), base = occupancymodel ? building > 0 : true  (popcorn.py:365-372
+ *                with the union of the listed units as the region)
+ *   counts       int32[2] = {nsel, nregion}; if the whole batch selects nothing, mask := slot >= 0 and nsel := nregion (popcorn.py:374-375)
+ *   unit_pixels  optional (NULL) int32 [N]: pixels of each unit in the crop (exact integer atomics; one more tiny launch zeroes it)
+ * B * H * W < 2^31.  16-byte accesses of four pixels per thread when W % 4 == 0 and the maps are 16-byte aligned, a scalar path otherwise. */
+int pc_unit_mask(const float* building, const float* admin_mask, const int64_t* units, const int32_t* unit_off, const uint8_t* rowsel,
+                 const uint8_t* colsel, int occupancymodel, int32_t* slot, uint8_t* mask, int32_t* counts, int32_t* unit_pixels,
+                 int B, int H, int W, int N, void* stream);
+/* popcount[n] = sum of popdense (B, H, W) over slot == n, n in [0, N): the N region sums of popcorn.py:186-188.  Bit-reproducible: each
+ * term q is split exactly into trunc(q) and its fraction, the integer parts and the fractions rounded to a 2^-PC_CENSUS_FIX_SHIFT grid are
+ * summed as two 64-bit integers per unit (associative: equal bits for any batch position of the sample, launch geometry and arrival
+ * order), and popcount = float(double(int) + double(frac) * 2^-30).  Grid quantum q = 2^-30 per term: |popcount - exact sum| <=
+ * 2^-24 |sum| + n_px(unit) * 2^-31 (+ 2^-53 relative from the double sum).  Range: |term| < 2^32, H * W < 2^27 -- the integers cannot
+ * wrap; a term that is NaN, +-Inf or out of range makes its unit's popcount NaN, the other units are unaffected.  Pixels with slot outside
+ * [0, N) add nothing.  unit_off (optional, as above): lets a workgroup keep bins in LDS in front of the global atomics where the
+ * sample's K_b fits.  ws: pc_unit_ws_bytes(N) bytes, 16-byte aligned (zeroed by the call's first launch). */
+int64_t pc_unit_ws_bytes(int64_t N);
+int pc_unit_popcount(const float* popdense, const int32_t* slot, const int32_t* unit_off, float* popcount, void* ws, int B, int H, int W,
+                     int N, void* stream);
+/* The autograd of pc_unit_popcount: g_popdense[i] = slot[i] in [0, N) ? g_popcount[slot[i]] : 0 for i < n = B * H * W; every element is
+ * written (no zero fill needed).  16-byte loads and stores when both maps are 16-byte aligned. */
+int pc_unit_paint(const float* g_popcount, const int32_t* slot, float* g_popdense, int64_t n, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,9 @@ def train_parser():
     p.add_argument("--nan_clouds", type=float, default=0.0,
                    help="synthetic datasets: NaN cloud discs over about this fraction of S2, orbit gaps in S1 (pair with --nan_fill)")
     p.add_argument("--ascfill", action="store_true", help="always take the ascending S1 where the descending one holds NaNs")
+    p.add_argument("--units_per_crop", type=int, default=0,
+                   help="multi-unit census supervision: train on synthetic crops that list this many census units each (all of them "
+                        "supervised in one eager step; 0 = off, the reference's one unit per sample)")
     return p
 
 
@@ -238,15 +241,24 @@ class Trainer:
             raise SystemExit("--torch_optimizer is the single-process reference recipe: it has no gradient all-reduce; "
                              "data-parallel runs use the fused step (drop the flag)")
         seed_all(args.seed)
-        ds = SyntheticWeaksupDataset(args.synthetic_regions, min_hw=args.synthetic_hw_range[0], max_hw=args.synthetic_hw_range[1],
-                                     seed=args.seed, fixed_hw=args.fixed_hw, nan_clouds=args.nan_clouds, ascfill=args.ascfill)
+        collate = Population_Dataset_collate_fn
+        if args.units_per_crop > 0:
+            if args.torch_optimizer or self.world > 1:
+                raise SystemExit("--units_per_crop trains with the fused eager step in a single process (no --torch_optimizer, no data parallelism)")
+            from .data.units import SyntheticMultiUnitDataset, collate_units
+            ds = SyntheticMultiUnitDataset(args.synthetic_regions, units=args.units_per_crop, min_hw=args.synthetic_hw_range[0],
+                                           max_hw=args.synthetic_hw_range[1], seed=args.seed, fixed_hw=args.fixed_hw, ragged=True)
+            collate = collate_units
+        else:
+            ds = SyntheticWeaksupDataset(args.synthetic_regions, min_hw=args.synthetic_hw_range[0], max_hw=args.synthetic_hw_range[1],
+                                         seed=args.seed, fixed_hw=args.fixed_hw, nan_clouds=args.nan_clouds, ascfill=args.ascfill)
         self.sampler = None
         if self.world > 1:
             self.sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=self.world, rank=self.rank,
                                                                            shuffle=True, seed=args.seed, drop_last=True)
         self.loader = torch.utils.data.DataLoader(ds, batch_size=args.weak_batch_size, num_workers=args.num_workers,
                                                   shuffle=self.sampler is None, sampler=self.sampler,
-                                                  collate_fn=Population_Dataset_collate_fn, drop_last=True,
+                                                  collate_fn=collate, drop_last=True,
                                                   persistent_workers=args.num_workers > 0)
         # weak validation set (run_train.py:410-414: a second Population_Dataset in weaksup mode, batch size -wvb)
         self.val_loader = torch.utils.data.DataLoader(
@@ -280,7 +292,7 @@ class Trainer:
             self.fused = FusedTrainStep(self.model, lr=args.learning_rate, weight_decay=args.weightdecay,
                                         gradient_clip=args.gradient_clip, loss=args.loss, lam=args.lam,
                                         scale_regularization=args.scale_regularization, lam_weak=args.lam_weak,
-                                        reducer=self.reducer, use_graph=args.fixed_hw is not None,
+                                        reducer=self.reducer, use_graph=args.fixed_hw is not None and args.units_per_crop == 0,
                                         raw_norm=(tuple(range(6)), stats.MEAN6, stats.STD6))
         if args.resume:
             self.resume(args.resume)
@@ -344,6 +356,8 @@ class Trainer:
             s = prepare_sample_fused(sample, self.data_transform, nan_fill=a.nan_fill)
         if s is None:
             s = normalize_sample(sample, self.device, self.data_transform, nan_fill=a.nan_fill)
+        if sample.get("census_n") is not None:             # multi-unit items (--units_per_crop): the valid units per row, host data
+            s["census_n"] = sample["census_n"]
         dk = "raw" if "raw" in s else "input"
         num_pix = s[dk].shape[0] * s[dk].shape[2] * s[dk].shape[3]
         if self.world > 1 and a.fixed_hw is None:
@@ -363,7 +377,11 @@ class Trainer:
             # by the next log step does not copy them (two launches per step on the smallest regions)
             to_log = a.logstep_train - (self.info["iter"] % a.logstep_train)
             if to_log * s["y"].numel() <= 300 + s["y"].numel():
-                self._buffer_r2(self.fused.last["popcount"], s["y"])
+                y = s["y"]
+                if s.get("census_n") is not None:           # (B, K) padded -> the flat N of the step's popcount, (b, k) order
+                    from .data.units import flat_valid
+                    y = flat_valid(y, s["census_n"])
+                self._buffer_r2(self.fused.last["popcount"], y)
             return loss
         from torch.nn.utils import clip_grad_norm_
         from .utils.losses import get_loss

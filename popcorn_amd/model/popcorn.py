@@ -9,6 +9,14 @@ tensors: there is no stock-PyTorch fallback.
 gradient x input) unless ``unet_no_grad`` or ``encoder_no_grad`` cuts the graph in front of it, exactly where the reference's autograd
 leaves ``X.grad`` at None.  The other inputs (``building_counts``, ``admin_mask``, ...) get no gradient; in particular a gradient for a
 user-supplied ``building_counts`` is out of scope.
+
+Multi-unit census supervision (build-specific, opt-in): a 2-D ``inputs["census_idx"]`` (B, K) int64 on the device lists K census units
+of each crop -- ids non-negative and distinct within a row -- and ``inputs["census_n"]`` (optional HOST list / CPU tensor, default K)
+the valid count per row; slots past it are ignored whatever they hold.  The result is what the one-unit path gives on the replicated
+batch (input[b], admin_mask[b], census_idx[b, k]) of N = sum(census_n) samples with the same two multinomial draws: ``popcount`` (N,) in
+(b, k) order over the valid slots (``get_loss(output, {"y": y_flat})`` works unchanged), ``popdensemap`` (B, H, W) = the sum of the
+replicas' maps (``sparse=True``: disjoint supports; the dense path's replicas all carry the one full map, which is returned), ``scale`` = ``scale[mask]`` in (b, y, x) order of the union mask with ``sparse=True``, else the map.  One U-Net pass, one
+head pass over the union of the units, K segmented sums (csrc/units.hip).  A 1-D ``census_idx`` takes exactly the one-unit path.
 """
 from __future__ import annotations
 
@@ -224,8 +232,9 @@ class POPCORN(nn.Module):
         mask, _ = self._sparsity_mask_u8(inputs)
         return mask.bool(), None
 
-    def _sparsity_mask_u8(self, inputs):
-        admin = inputs["admin_mask"]
+    @staticmethod
+    def _draw_selection(admin):
+        """The two CPU-generator draws of get_sparsity_mask (popcorn.py:366-369) as uint8 row / column flags on admin's device."""
         B, H, W = admin.shape
         sub = 60
         xi = torch.ones(H).multinomial(num_samples=min(sub, H), replacement=False)
@@ -233,10 +242,23 @@ class POPCORN(nn.Module):
         sel = torch.zeros(H + W, dtype=torch.uint8)
         sel[xi] = 1
         sel[H + yi] = 1
-        sel = sel.to(admin.device, non_blocking=True)
+        return sel.to(admin.device, non_blocking=True)
+
+    def _sparsity_mask_u8(self, inputs):
+        admin = inputs["admin_mask"]
+        B, H, W = admin.shape
+        sel = self._draw_selection(admin)
         bc = inputs["building_counts"]
         return ops.sparsity_mask(bc.contiguous(), admin.contiguous().float(), inputs["census_idx"].contiguous(),
                                  sel[:H], sel[H:], self.occupancymodel)
+
+    def _unit_mask(self, inputs, lay):
+        """The multi-unit counterpart of ``_sparsity_mask_u8``: the same two draws, then (slot, mask, counts) of ``ops.unit_mask``."""
+        admin = inputs["admin_mask"]
+        B, H, W = admin.shape
+        sel = self._draw_selection(admin)
+        return ops.unit_mask(inputs["building_counts"].contiguous().float(), admin.contiguous().float(), lay["units"], lay["unit_off"],
+                             sel[:H], sel[H:], self.occupancymodel)
 
     # ------------------------------------------------------------------------------------------------ forward
     def forward(self, inputs, train=False, padding=True, return_features=True, encoder_no_grad=False,
@@ -250,6 +272,9 @@ class POPCORN(nn.Module):
         if "building_counts" not in inputs.keys() or self.sentinelbuildings:
             inputs["building_counts"] = self.create_building_score(inputs)
         building = inputs["building_counts"].contiguous()
+        multi = "admin_mask" in inputs.keys() and torch.is_tensor(inputs.get("census_idx")) and inputs["census_idx"].dim() == 2
+        if multi:
+            return self._forward_units(inputs, X, building, padding, encoder_no_grad, unet_no_grad, sparse)
         mask = None
         if sparse:
             mask, _ = self._sparsity_mask_u8(inputs)
@@ -276,6 +301,42 @@ class POPCORN(nn.Module):
                 popcount, popdense, scale = _forward_nograd(self, X, building, mask, admin, census, geom, sparse)
         aux = {"scale": scale if self.occupancymodel else None}
         return {"popcount": popcount, "popdensemap": popdense, **aux}
+
+    def _forward_units(self, inputs, X, building, padding, encoder_no_grad, unet_no_grad, sparse):
+        """forward() for a 2-D ``census_idx`` (module docstring): the head runs on the union mask without a region reduction, the N region sums
+        are ``ops.UnitPopcount`` behind ``popdensemap`` -- parameter and input gradients follow from the one-unit machinery."""
+        B, _, H, W = X.shape
+        lay = ops.unit_layout(inputs["census_idx"].contiguous(), inputs.get("census_n"))
+        admin = inputs["admin_mask"].contiguous().float()
+        if tuple(admin.shape) != (B, H, W):
+            raise ValueError(f"admin_mask must be (B, H, W) = {(B, H, W)}, got {tuple(admin.shape)}")
+        if sparse:
+            slot, mask, _ = self._unit_mask(inputs, lay)
+        else:
+            # no draws, as in the reference's dense path; the lookup alone (mask and counts unused)
+            none = torch.zeros(H + W, dtype=torch.uint8, device=X.device)
+            slot, _, _ = ops.unit_mask(building.float(), admin, lay["units"], lay["unit_off"], none[:H], none[H:], self.occupancymodel)
+            mask = None
+        self.unetmodel.freeze_bn_layers()
+        pt, pb, pl, pr = pad_geometry(H, W, padding)
+        geom = (pt, pl, H + pt + pb, W + pl + pr)
+        if not self.occupancymodel:
+            building = torch.ones_like(building)
+        names, params = self.trainable()
+        need_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or
+                                                 (inputs["input"].requires_grad and not unet_no_grad))
+        if unet_no_grad:
+            self.unetmodel.eval()
+        with L.precision(self.precision):
+            if need_grad:
+                _, popdense, scale = _PopcornFn.apply(self, X, building, mask, None, None, geom, sparse, encoder_no_grad, unet_no_grad,
+                                                      *params)
+                popcount = ops.UnitPopcount.apply(popdense, slot, lay["N"], lay["unit_off"])
+            else:
+                _, popdense, scale = _forward_nograd(self, X, building, mask, None, None, geom, sparse)
+                popcount = ops.unit_popcount(popdense, slot, lay["N"], lay["unit_off"])
+        popcount = popcount.index_select(0, lay["to_caller"])          # sorted order -> the caller's (b, k) order
+        return {"popcount": popcount, "popdensemap": popdense, "scale": scale if self.occupancymodel else None}
 
 
 def _forward_core(model, X, building, mask, admin, census, geom, sparse, save):

@@ -163,8 +163,8 @@ _ws_cache = {}
 _ws_retired = []       # outgrown workspaces stay allocated: a captured HIP graph may hold their device pointers
 
 
-def _workspace(nbytes: int, device) -> torch.Tensor:
-    key = (str(device), "ws")
+def _workspace(nbytes: int, device, tag="ws") -> torch.Tensor:
+    key = (str(device), tag)
     t = _ws_cache.get(key)
     if t is None or t.numel() < nbytes:
         if t is not None:
@@ -511,6 +511,120 @@ def scatter_masked(src, mask):
     L.check(L.lib().pc_scatter_masked(L.ptr(src), L.ptr(mask), L.ptr(out), L.ptr(ws), C.c_int64(n), L.stream_ptr()),
             "pc_scatter_masked")
     return out
+
+
+def unit_layout(census_idx, census_n=None):
+    """The flattened unit lists of a multi-unit batch (include/popcorn_hip.h, "multi-unit census supervision") from ``census_idx`` (B, K)
+    int64 on the device -- ids non-negative and distinct within a row -- and ``census_n``: HOST data (list / CPU tensor; it sizes N), the
+    valid count per row, default K; slots past it are ignored whatever they hold.  Rows are sorted on the device; nothing synchronises.
+    Returns a dict: units int64 [N] (ascending per sample), unit_off int32 [B + 1], N, counts (the host list), and the two index vectors
+    that carry per-slot data between the caller's (b, k) order and the sorted one: ``to_sorted`` (indices into a flattened (B, K) tensor:
+    ``y.reshape(-1)[to_sorted]`` is y in sorted order) and ``to_caller`` (``popcount_sorted[to_caller]`` is in (b, k) order)."""
+    L.require_device(census_idx)
+    if census_idx.dim() != 2 or census_idx.dtype != torch.int64:
+        raise ValueError(f"unit_layout: census_idx must be an int64 (B, K) tensor, got {census_idx.dtype} {tuple(census_idx.shape)}")
+    B, K = census_idx.shape
+    if census_n is None:
+        counts = [K] * B
+    else:
+        if torch.is_tensor(census_n) and census_n.is_cuda:
+            raise ValueError("census_n is host data (a list or a CPU tensor): it sizes the result")
+        counts = [int(v) for v in (census_n.tolist() if torch.is_tensor(census_n) else census_n)]
+    if len(counts) != B or any(c < 1 or c > K for c in counts):
+        raise ValueError(f"census_n must hold B = {B} counts in [1, K = {K}], got {counts}")
+    N = sum(counts)
+    off = [0]
+    for c in counts:
+        off.append(off[-1] + c)
+    # host-built index plumbing (B + 1 + N + B integers) in one host-to-device copy
+    rows = torch.tensor([b for b, c in enumerate(counts) for _ in range(c)], dtype=torch.int64)
+    cols = torch.tensor([j for c in counts for j in range(c)], dtype=torch.int64)
+    host = torch.cat([torch.tensor(off, dtype=torch.int64), rows * K + cols, torch.tensor(counts, dtype=torch.int64)])
+    dev = host.to(census_idx.device, non_blocking=True)
+    off_d, flat, cnt_d = dev[:B + 1], dev[B + 1:B + 1 + N], dev[B + 1 + N:]
+    valid = torch.arange(K, device=census_idx.device).unsqueeze(0) < cnt_d.unsqueeze(1)
+    srt, perm = torch.sort(census_idx.masked_fill(~valid, torch.iinfo(torch.int64).max), dim=1)
+    units = srt.reshape(-1)[flat].contiguous()
+    # sorted slot (b, j) holds the caller's slot (b, perm[b, j]); the padding sorts behind every valid id, so perm[b, j] < counts[b]
+    to_sorted = (perm + torch.arange(B, device=perm.device).unsqueeze(1) * K).reshape(-1)[flat]
+    dest = (perm + off_d[:B].unsqueeze(1)).reshape(-1)[flat]          # flat (b, k) position of sorted slot n
+    to_caller = torch.empty(N, dtype=torch.int64, device=perm.device).scatter_(0, dest, torch.arange(N, device=perm.device))
+    return {"units": units, "unit_off": off_d.to(torch.int32).contiguous(), "N": N, "counts": counts, "to_sorted": to_sorted,
+            "to_caller": to_caller}
+
+
+def unit_mask(building, admin_mask, units, unit_off, rowsel, colsel, occupancymodel=True, want_pixels=False):
+    """pc_unit_mask: unit lookup + the multi-unit sparsity mask (popcorn.py:361-377 with the union of the listed units as the region) in
+    one launch.  units int64 [N] ascending per sample, unit_off int32 [B + 1] (``unit_layout``).  Returns (slot int32 (B,H,W): the flat
+    index of the listed unit that owns the pixel or -1, mask uint8 (B,H,W), counts int32[2] = {nsel, nregion}[, unit_pixels int32 [N]])."""
+    L.require_device(building, admin_mask, units, unit_off, rowsel, colsel)
+    B, H, W = admin_mask.shape
+    N = units.numel()
+    if units.dtype != torch.int64 or unit_off.dtype != torch.int32 or unit_off.numel() != B + 1 or N < 1:
+        raise ValueError("unit_mask: units int64 [N >= 1], unit_off int32 [B + 1]")
+    if admin_mask.dtype != torch.float32 or building.dtype != torch.float32 or building.numel() != B * H * W:
+        raise ValueError("unit_mask: fp32 building (B, 1, H, W) and admin_mask (B, H, W)")
+    if rowsel.numel() < H or colsel.numel() < W or rowsel.dtype != torch.uint8 or colsel.dtype != torch.uint8:
+        raise ValueError("unit_mask: uint8 rowsel [H] / colsel [W]")
+    building, admin_mask, units, unit_off = building.contiguous(), admin_mask.contiguous(), units.contiguous(), unit_off.contiguous()
+    dev = building.device
+    slot = torch.empty(B, H, W, dtype=torch.int32, device=dev)
+    mask = torch.empty(B, H, W, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    pixels = torch.empty(N, dtype=torch.int32, device=dev) if want_pixels else None
+    L.check(L.lib().pc_unit_mask(L.ptr(building), L.ptr(admin_mask), L.ptr(units), L.ptr(unit_off), L.ptr(rowsel.contiguous()),
+                                 L.ptr(colsel.contiguous()), int(occupancymodel), L.ptr(slot), L.ptr(mask), L.ptr(counts), L.ptr(pixels),
+                                 B, H, W, N, L.stream_ptr()), "pc_unit_mask")
+    return (slot, mask, counts, pixels) if want_pixels else (slot, mask, counts)
+
+
+def unit_popcount(popdense, slot, N, unit_off=None, out=None):
+    """pc_unit_popcount: popcount[n] = sum of popdense (B,H,W) over slot == n -- bit-reproducible (fixed-point sums, quantum
+    ``L.PC_UNIT_QUANTUM`` per term); a NaN / +-Inf / out-of-range term makes its unit's popcount NaN.  unit_off (optional): the sample
+    ranges, for the LDS bins.  Returns popcount fp32 [N]."""
+    L.require_device(popdense, slot)
+    if popdense.dim() != 3 or popdense.dtype != torch.float32 or slot.dtype != torch.int32 or slot.shape != popdense.shape or int(N) < 1:
+        raise ValueError(f"unit_popcount: fp32 popdense (B, H, W) and int32 slot of the same shape, N >= 1; got {popdense.dtype} "
+                         f"{tuple(popdense.shape)}, {slot.dtype} {tuple(slot.shape)}, N = {N}")
+    popdense, slot = popdense.contiguous(), slot.contiguous()
+    B, H, W = popdense.shape
+    if unit_off is not None and (unit_off.dtype != torch.int32 or unit_off.numel() != B + 1 or not unit_off.is_cuda):
+        raise ValueError("unit_popcount: unit_off int32 [B + 1] on the device")
+    if out is None:
+        out = torch.empty(int(N), dtype=torch.float32, device=popdense.device)
+    # a workspace of its own: the head's (packed weight images of a training step) must survive between head_fwd and head_bwd
+    ws = _workspace(L.lib().pc_unit_ws_bytes(int(N)), popdense.device, "units")
+    L.check(L.lib().pc_unit_popcount(L.ptr(popdense), L.ptr(slot), L.ptr(None if unit_off is None else unit_off.contiguous()), L.ptr(out),
+                                     L.ptr(ws), B, H, W, int(N), L.stream_ptr()), "pc_unit_popcount")
+    return out
+
+
+def unit_paint(g_popcount, slot, out=None):
+    """pc_unit_paint: out[b,y,x] = g_popcount[slot[b,y,x]] (0 where slot < 0), every element written: the autograd of ``unit_popcount``."""
+    L.require_device(g_popcount, slot)
+    if g_popcount.dtype != torch.float32 or g_popcount.dim() != 1 or g_popcount.numel() < 1 or slot.dtype != torch.int32:
+        raise ValueError("unit_paint: fp32 g_popcount [N >= 1] and an int32 slot map")
+    g_popcount, slot = g_popcount.contiguous(), slot.contiguous()
+    if out is None:
+        out = torch.empty(slot.shape, dtype=torch.float32, device=slot.device)
+    if out.shape != slot.shape or out.dtype != torch.float32 or not out.is_contiguous():
+        raise ValueError("unit_paint: out must be a contiguous fp32 tensor of the slot map's shape")
+    L.check(L.lib().pc_unit_paint(L.ptr(g_popcount), L.ptr(slot), L.ptr(out), C.c_int64(slot.numel()), g_popcount.numel(),
+                                  L.stream_ptr()), "pc_unit_paint")
+    return out
+
+
+class UnitPopcount(torch.autograd.Function):
+    """popcount[N] = ``unit_popcount(popdense, slot, N)``; backward: ``unit_paint``.  slot / unit_off get no gradient."""
+
+    @staticmethod
+    def forward(ctx, popdense, slot, N, unit_off=None):
+        ctx.slot = slot
+        return unit_popcount(popdense.detach(), slot, N, unit_off)
+
+    @staticmethod
+    def backward(ctx, g):
+        return unit_paint(g.contiguous().float(), ctx.slot), None, None, None
 
 
 def reflect_pad(x, top, bottom, left, right):

@@ -9,6 +9,11 @@ clip_grad_norm_(0.01) -> Adam step -> zero_grad), with everything on the device 
 The 56 trainable tensors (39,298 elements) are re-homed as views of one flat buffer, so the optimiser and the
 all-reduce are single kernels / a single collective.  The static-shape step can be captured into HIP graphs
 (``use_graph=True``) and replayed with no per-launch host cost.
+
+Multi-unit census supervision (opt-in; csrc/units.hip): a sample whose ``census_idx`` is 2-D (B, K) -- with ``y`` (B, K) and the optional
+host-side ``census_n`` -- supervises every listed unit of each crop in one step: one crop, K popcounts, one loss over the N = sum(census_n)
+(b, k) pairs, one backward.  It computes what the one-unit step computes on the replicated batch.  Such a step runs eagerly through the
+per-launch engine; graph mode and data parallelism raise for it (``FusedTrainStep.step``).
 """
 from __future__ import annotations
 
@@ -129,6 +134,12 @@ def data_keys(sample):
     if sample.get("raw_s2") is not None:
         return ("raw_s2", "raw_s1")
     raise KeyError("sample needs 'input', 'raw' or 'raw_s2' + 'raw_s1'")
+
+
+def _is_multi_unit(sample):
+    """A sample with a 2-D ``census_idx`` (B, K): multi-unit census supervision."""
+    c = sample.get("census_idx")
+    return torch.is_tensor(c) and c.dim() == 2
 
 
 LOSS_INDEX = {"l1_loss": 0, "log_l1_loss": 1, "mse_loss": 2, "log_mse_loss": 3}
@@ -330,6 +341,8 @@ class FusedTrainStep:
         m = self.model
         if not NATIVE_STEP or m.precision != "fp32" or not (m.S1 and m.S2) or not m.occupancymodel:
             return False
+        if _is_multi_unit(sample):
+            return False               # pc_train_step supervises one unit per sample
         if not (E.PADDED_INPUT and E.COMPOSED_UP and E.FUSED_LEVEL2 and E.FUSED_CONV_BWD and DEFER_HEAD_REDUCE):
             return False               # an A/B switch of the per-launch engine is off its default: that engine is what is being asked for
         if (not m.sentinelbuildings) and sample.get("building_counts") is not None:
@@ -481,6 +494,10 @@ class FusedTrainStep:
         raw = s.get("raw") if dk == ("raw",) else None
         B, _, H, W = s[dk[0]].shape
         eng_u, eng_b = m.engines()
+        # multi-unit supervision: the flattened unit lists; the mask is then ops.unit_mask on the building score and the head runs on the
+        # union mask without a region (the N region sums follow it: ops.unit_popcount)
+        lay = ops.unit_layout(s["census_idx"], s.get("census_n")) if _is_multi_unit(s) else None
+        slot = None
         pt, pb, pl, pr = pad_geometry(H, W, False)
         fused = (pt, pb, pl, pr) == (m.p, m.p, m.p, m.p)      # e.g. 100x100 tiles: both networks see the same 128x128 domain
         Xp_all = None
@@ -523,21 +540,40 @@ class FusedTrainStep:
             building = s["building_counts"].contiguous().float()
             if tuple(building.shape) != (B, 1, H, W):
                 raise ValueError(f"building_counts must be (B, 1, H, W) = {(B, 1, H, W)}, got {tuple(building.shape)}")
-            mask, counts = ops.sparsity_mask(building, s["admin_mask"], s["census_idx"], sel[:H], sel[H:], m.occupancymodel)
+            if lay is None:
+                mask, counts = ops.sparsity_mask(building, s["admin_mask"], s["census_idx"], sel[:H], sel[H:], m.occupancymodel)
+            else:
+                slot, mask, counts = ops.unit_mask(building, s["admin_mask"], lay["units"], lay["unit_off"], sel[:H], sel[H:], m.occupancymodel)
             (feats,), (saved,) = E.forward_multi([eng_u], X, pt, pl, H + pt + pb, W + pl + pr, [not unet_no_grad], Xp_all=Xp_all)
         elif fused:
             (f_b, feats), (_, saved) = E.forward_multi([eng_b, eng_u], X, pt, pl, H + pt + pb, W + pl + pr,
                                                        [False, not unet_no_grad], logit_only=[True, False], Xp_all=Xp_all)
-            building, mask, counts = eng_b.score_and_mask(f_b, H, W, pt, pl, s["admin_mask"], s["census_idx"], sel[:H],
-                                                          sel[H:], m.occupancymodel)
+            if lay is None:
+                building, mask, counts = eng_b.score_and_mask(f_b, H, W, pt, pl, s["admin_mask"], s["census_idx"], sel[:H],
+                                                              sel[H:], m.occupancymodel)
+            else:
+                building = eng_b.score_from_features(f_b, H, W, pt, pl)
+                slot, mask, counts = ops.unit_mask(building, s["admin_mask"], lay["units"], lay["unit_off"], sel[:H], sel[H:], m.occupancymodel)
         else:
             building = eng_b.building_score(X, m.p)
-            mask, counts = ops.sparsity_mask(building, s["admin_mask"], s["census_idx"], sel[:H], sel[H:], m.occupancymodel)
+            if lay is None:
+                mask, counts = ops.sparsity_mask(building, s["admin_mask"], s["census_idx"], sel[:H], sel[H:], m.occupancymodel)
+            else:
+                slot, mask, counts = ops.unit_mask(building, s["admin_mask"], lay["units"], lay["unit_off"], sel[:H], sel[H:], m.occupancymodel)
         s["building_counts"] = building
         if not m.occupancymodel:
             building = torch.ones_like(building)
         if not fused and not given:
             feats, saved = eng_u.forward(X, pt, pl, H + pt + pb, W + pl + pr, save=not unet_no_grad)
+        if lay is not None:
+            # the head on the union mask, no region; stats {Nsel, sum scale} finished by the call; then the N region sums
+            scale_map, popdense, _ = ops.head_fwd(feats, pt, pl, H, W, m.head_tensors(), building, mask=mask, stats=self.stats,
+                                                  nsel_counts=counts, pack_both=True)
+            pc_sorted = ops.unit_popcount(popdense, slot, lay["N"], lay["unit_off"])
+            self._ctx = (feats, saved, building, mask, (pt, pl), (B, H, W), counts, slot, lay, pc_sorted)
+            self.last = {"popcount": pc_sorted.index_select(0, lay["to_caller"]), "popdensemap": popdense, "scale_map": scale_map,
+                         "mask": mask, "slot": slot}
+            return
         scale_map, popdense, popcount = ops.head_fwd(feats, pt, pl, H, W, m.head_tensors(), building, mask=mask,
                                                      admin_mask=s["admin_mask"], census_idx=s["census_idx"],
                                                      stats=self.stats, nsel_counts=counts, pack_both=True,
@@ -548,21 +584,28 @@ class FusedTrainStep:
 
     def _backward(self, s, encoder_no_grad, unet_no_grad):
         m = self.model
-        feats, saved, building, mask, (pt, pl), (B, H, W), counts = self._ctx
-        g_pc = torch.empty(B, device=self.device, dtype=torch.float32)
-        inv_B = 1.0 / self.reducer.global_batch(B)
-        if self.reducer.active:
-            ops.loss_fwd_bwd(self.last["popcount"], s["y"], self.stats, self.lam4, self.sreg, self.lam_weak, inv_B,
-                             self.loss_out, g_pc, self.g_scale_const)
+        g_pd = None
+        if len(self._ctx) > 7:
+            feats, saved, building, mask, (pt, pl), (B, H, W), counts, slot, lay, pc_sorted = self._ctx
+            g_pc, admin, census = None, None, None
+            g_pd = self._unit_loss(s, slot, lay, pc_sorted)
         else:
-            ops.head_popcount_loss(B, H, W, counts, s["y"], self.lam4, self.sreg, self.lam_weak, inv_B, self.last["popcount"], self.stats,
-                                   self.loss_out, g_pc, self.g_scale_const)
+            feats, saved, building, mask, (pt, pl), (B, H, W), counts = self._ctx
+            admin, census = s["admin_mask"], s["census_idx"]
+            g_pc = torch.empty(B, device=self.device, dtype=torch.float32)
+            inv_B = 1.0 / self.reducer.global_batch(B)
+            if self.reducer.active:
+                ops.loss_fwd_bwd(self.last["popcount"], s["y"], self.stats, self.lam4, self.sreg, self.lam_weak, inv_B,
+                                 self.loss_out, g_pc, self.g_scale_const)
+            else:
+                ops.head_popcount_loss(B, H, W, counts, s["y"], self.lam4, self.sreg, self.lam_weak, inv_B, self.last["popcount"], self.stats,
+                                       self.loss_out, g_pc, self.g_scale_const)
         eng_u = m.engines()[0]
         hgrads = [self.grads[n_] for n_ in self.names[-8:]]
         khgrads, fix = m.head_grad_targets(hgrads)
         # the head's weight-gradient partials are finished by the U-Net backward's batched reduction launch when there is one
-        hp, G = ops.head_bwd(feats, pt, pl, H, W, m.head_tensors(), building, mask=mask, admin_mask=s["admin_mask"],
-                             census_idx=s["census_idx"], g_popcount=g_pc, g_scale_const=self.g_scale_const, grads=khgrads,
+        hp, G = ops.head_bwd(feats, pt, pl, H, W, m.head_tensors(), building, mask=mask, admin_mask=admin,
+                             census_idx=census, g_popcount=g_pc, g_popdense=g_pd, g_scale_const=self.g_scale_const, grads=khgrads,
                              feat_bn=None if unet_no_grad else eng_u.feat_bn(), packed=True, defer_reduce=DEFER_HEAD_REDUCE and not unet_no_grad)
         if unet_no_grad:
             self.flat_g[: self.n - sum(g.numel() for g in hgrads)].zero_()
@@ -573,6 +616,18 @@ class FusedTrainStep:
                            head_reduce=hp if isinstance(hp, ops.HeadPartials) else None)
         fix()                    # (single modality: the padded first-layer gradient -> the parameter's shape; after the reduction)
         self._ctx = None
+
+    def _unit_loss(self, s, slot, lay, pc_sorted):
+        """Multi-unit step: the population loss is the mean over the N (b, k) pairs (pc_loss_fwd_bwd with B := N, inv_B = 1 / N); its
+        gradient g_popcount[N] painted onto the units' pixels is the head backward's g_popdense."""
+        N, y = lay["N"], s["y"].float()
+        if tuple(y.shape) != tuple(s["census_idx"].shape):
+            raise ValueError(f"y must be (B, K) like census_idx {tuple(s['census_idx'].shape)}, got {tuple(y.shape)}")
+        y_sorted = y.reshape(-1)[lay["to_sorted"]]
+        g_pc = torch.empty(N, device=self.device, dtype=torch.float32)
+        ops.loss_fwd_bwd(pc_sorted, y_sorted, self.stats, self.lam4, self.sreg, self.lam_weak, 1.0 / N, self.loss_out, g_pc,
+                         self.g_scale_const)
+        return ops.unit_paint(g_pc, slot)
 
     def _update(self, encoder_no_grad=False, unet_no_grad=False):
         active = {2} if unet_no_grad else ({1, 2} if encoder_no_grad else {0, 1, 2})
@@ -626,9 +681,19 @@ class FusedTrainStep:
 
     def step(self, sample, encoder_no_grad=False, unet_no_grad=False):
         """One optimisation step on ``sample`` = {input (B,6,H,W) normalised -- or raw (B,Craw,H,W), see ``raw_norm`` --,
-        admin_mask, census_idx, y}.  Returns the device tensor loss_out[2] = {loss, regulariser} (no host sync)."""
+        admin_mask, census_idx, y}.  Returns the device tensor loss_out[2] = {loss, regulariser} (no host sync).
+
+        Multi-unit supervision: ``census_idx`` (B, K) int64 on the device (ids non-negative, distinct within a row), ``y`` (B, K) and optionally ``census_n`` (HOST list / CPU tensor: valid units per row, default K).  The step is the
+        one-unit step on the replicated batch of N = sum(census_n) samples; ``last["popcount"]`` is (N,) in (b, k) order.  It always runs
+        eagerly through the per-launch engine (``native_steps`` does not count it).  Out of scope, and refused: ``use_graph=True`` raises
+        ValueError, an active data-parallel reducer raises NotImplementedError."""
         dkey = data_keys(sample)[0]
         B, _, H, W = sample[dkey].shape
+        if _is_multi_unit(sample):
+            if self.use_graph:
+                raise ValueError("multi-unit samples (2-D census_idx) run eagerly: build the FusedTrainStep with use_graph=False")
+            if self.reducer.active:
+                raise NotImplementedError("multi-unit samples (2-D census_idx) are not supported with a data-parallel reducer")
         sel_host = self._draw_selection(H, W)
         if not self.use_graph:
             s = {k: (v.contiguous() if torch.is_tensor(v) else v) for k, v in sample.items() if not k.startswith("_")}
