@@ -20,6 +20,7 @@ head pass over the union of the units, K segmented sums (csrc/units.hip).  A 1-D
 """
 from __future__ import annotations
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -61,6 +62,32 @@ def pad_geometry(H, W, force):
         pl = (64 - W % 64) // 2
         pr = (64 - W % 64) - pl
     return pt, pb, pl, pr
+
+
+_ONES = {}
+
+
+def _ones(n):
+    """torch.ones(n) of the two multinomial draws per call, kept per size (the draw reads it only)."""
+    t = _ONES.get(n)
+    if t is None:
+        if len(_ONES) > 4096:
+            _ONES.clear()
+        t = _ONES[n] = torch.ones(n)
+    return t
+
+
+def draw_selection(H, W, sub=60):
+    """The two CPU-generator multinomial draws of get_sparsity_mask (popcorn.py:366-369; sub = 250: the sparse_unet grid, :336-343) as
+    CPU uint8 flags [H + W]: rows, then columns.  The ONE copy of the draw -- the model API and the fused step (train.py) both call it --
+    and it consumes the generator exactly like the reference's ``torch.ones(H).multinomial(min(sub, H), replacement=False)``, then
+    the same for W (tests/test_selection_cpu.py)."""
+    xi = _ones(H).multinomial(num_samples=min(sub, H), replacement=False)
+    yi = _ones(W).multinomial(num_samples=min(sub, W), replacement=False)
+    sel = np.zeros(H + W, dtype=np.uint8)          # (numpy: two index_put calls cost more than the draws' own bookkeeping)
+    sel[xi.numpy()] = 1
+    sel[H + yi.numpy()] = 1
+    return torch.from_numpy(sel)
 
 
 class POPCORN(nn.Module):
@@ -219,46 +246,43 @@ class POPCORN(nn.Module):
         if sparse_unet:
             # popcorn.py:336-359: threshold 0.001, a 250 x 250 grid, per-sample undersampling ratio
             admin = inputs["admin_mask"]
-            B, H, W = admin.shape
-            xi = torch.ones(H).multinomial(num_samples=min(250, H), replacement=False)
-            yi = torch.ones(W).multinomial(num_samples=min(250, W), replacement=False)
-            sel = torch.zeros(H + W, dtype=torch.uint8)
-            sel[xi] = 1
-            sel[H + yi] = 1
-            sel = sel.to(admin.device, non_blocking=True)
+            rows, cols = self._selection(admin, sub=250)
             mask, ratio = ops.sparsity_mask_unet(inputs["building_counts"].contiguous(), admin.contiguous().float(),
-                                                 inputs["census_idx"].contiguous(), sel[:H], sel[H:], 0.001)
+                                                 inputs["census_idx"].contiguous(), rows, cols, 0.001)
             return mask.bool(), ratio
         mask, _ = self._sparsity_mask_u8(inputs)
         return mask.bool(), None
 
     @staticmethod
-    def _draw_selection(admin):
-        """The two CPU-generator draws of get_sparsity_mask (popcorn.py:366-369) as uint8 row / column flags on admin's device."""
+    def _selection(admin, sub=60):
+        """``draw_selection`` for admin (B, H, W), on its device: (row flags [H], column flags [W])."""
         B, H, W = admin.shape
-        sub = 60
-        xi = torch.ones(H).multinomial(num_samples=min(sub, H), replacement=False)
-        yi = torch.ones(W).multinomial(num_samples=min(sub, W), replacement=False)
-        sel = torch.zeros(H + W, dtype=torch.uint8)
-        sel[xi] = 1
-        sel[H + yi] = 1
-        return sel.to(admin.device, non_blocking=True)
+        sel = draw_selection(H, W, sub).to(admin.device, non_blocking=True)
+        return sel[:H], sel[H:]
 
     def _sparsity_mask_u8(self, inputs):
         admin = inputs["admin_mask"]
-        B, H, W = admin.shape
-        sel = self._draw_selection(admin)
+        rows, cols = self._selection(admin)
         bc = inputs["building_counts"]
         return ops.sparsity_mask(bc.contiguous(), admin.contiguous().float(), inputs["census_idx"].contiguous(),
-                                 sel[:H], sel[H:], self.occupancymodel)
+                                 rows, cols, self.occupancymodel)
 
-    def _unit_mask(self, inputs, lay):
-        """The multi-unit counterpart of ``_sparsity_mask_u8``: the same two draws, then (slot, mask, counts) of ``ops.unit_mask``."""
-        admin = inputs["admin_mask"]
-        B, H, W = admin.shape
-        sel = self._draw_selection(admin)
-        return ops.unit_mask(inputs["building_counts"].contiguous().float(), admin.contiguous().float(), lay["units"], lay["unit_off"],
-                             sel[:H], sel[H:], self.occupancymodel)
+    def _unit_slots(self, inputs, X, building, sparse):
+        """The mask stage of a 2-D ``census_idx`` (module docstring): (lay, slot, mask) -- the flattened unit lists, the owning listed unit
+        per pixel and (``sparse``) the union mask of ``_sparsity_mask_u8``'s multi-unit counterpart, from the same two draws."""
+        B, _, H, W = X.shape
+        lay = ops.unit_layout(inputs["census_idx"].contiguous(), inputs.get("census_n"))
+        admin = inputs["admin_mask"].contiguous().float()
+        if tuple(admin.shape) != (B, H, W):
+            raise ValueError(f"admin_mask must be (B, H, W) = {(B, H, W)}, got {tuple(admin.shape)}")
+        if sparse:
+            rows, cols = self._selection(admin)
+        else:
+            # no draws, as in the reference's dense path; the lookup alone (mask and counts unused)
+            none = torch.zeros(H + W, dtype=torch.uint8, device=X.device)
+            rows, cols = none[:H], none[H:]
+        slot, mask, _ = ops.unit_mask(building.float(), admin, lay["units"], lay["unit_off"], rows, cols, self.occupancymodel)
+        return lay, slot, (mask if sparse else None)
 
     # ------------------------------------------------------------------------------------------------ forward
     def forward(self, inputs, train=False, padding=True, return_features=True, encoder_no_grad=False,
@@ -272,17 +296,22 @@ class POPCORN(nn.Module):
         if "building_counts" not in inputs.keys() or self.sentinelbuildings:
             inputs["building_counts"] = self.create_building_score(inputs)
         building = inputs["building_counts"].contiguous()
+        # the two entry forms differ in how the mask is obtained and in how ``popcount`` is produced, nothing else.  One unit per sample:
+        # the head reduces over the sample's region (admin, census).  A 2-D ``census_idx``: the head runs on the union mask WITHOUT a
+        # region, the N region sums are ``ops.UnitPopcount`` behind ``popdensemap`` -- parameter and input gradients follow from the
+        # one-unit machinery
         multi = "admin_mask" in inputs.keys() and torch.is_tensor(inputs.get("census_idx")) and inputs["census_idx"].dim() == 2
+        mask = admin = census = None
         if multi:
-            return self._forward_units(inputs, X, building, padding, encoder_no_grad, unet_no_grad, sparse)
-        mask = None
-        if sparse:
-            mask, _ = self._sparsity_mask_u8(inputs)
+            lay, slot, mask = self._unit_slots(inputs, X, building, sparse)
+        else:
+            if sparse:
+                mask, _ = self._sparsity_mask_u8(inputs)
+            if "admin_mask" in inputs.keys():
+                admin, census = inputs["admin_mask"].contiguous().float(), inputs["census_idx"].contiguous()
         self.unetmodel.freeze_bn_layers()
         pt, pb, pl, pr = pad_geometry(H, W, padding)
         geom = (pt, pl, H + pt + pb, W + pl + pr)
-        admin = inputs["admin_mask"].contiguous().float() if "admin_mask" in inputs.keys() else None
-        census = inputs["census_idx"].contiguous() if admin is not None else None
         if not self.occupancymodel:
             # popcorn.py:179-181: popdensemap = relu(out), no building product
             building = torch.ones_like(building)
@@ -299,43 +328,10 @@ class POPCORN(nn.Module):
                                                              encoder_no_grad, unet_no_grad, *params)
             else:
                 popcount, popdense, scale = _forward_nograd(self, X, building, mask, admin, census, geom, sparse)
-        aux = {"scale": scale if self.occupancymodel else None}
-        return {"popcount": popcount, "popdensemap": popdense, **aux}
-
-    def _forward_units(self, inputs, X, building, padding, encoder_no_grad, unet_no_grad, sparse):
-        """forward() for a 2-D ``census_idx`` (module docstring): the head runs on the union mask without a region reduction, the N region sums
-        are ``ops.UnitPopcount`` behind ``popdensemap`` -- parameter and input gradients follow from the one-unit machinery."""
-        B, _, H, W = X.shape
-        lay = ops.unit_layout(inputs["census_idx"].contiguous(), inputs.get("census_n"))
-        admin = inputs["admin_mask"].contiguous().float()
-        if tuple(admin.shape) != (B, H, W):
-            raise ValueError(f"admin_mask must be (B, H, W) = {(B, H, W)}, got {tuple(admin.shape)}")
-        if sparse:
-            slot, mask, _ = self._unit_mask(inputs, lay)
-        else:
-            # no draws, as in the reference's dense path; the lookup alone (mask and counts unused)
-            none = torch.zeros(H + W, dtype=torch.uint8, device=X.device)
-            slot, _, _ = ops.unit_mask(building.float(), admin, lay["units"], lay["unit_off"], none[:H], none[H:], self.occupancymodel)
-            mask = None
-        self.unetmodel.freeze_bn_layers()
-        pt, pb, pl, pr = pad_geometry(H, W, padding)
-        geom = (pt, pl, H + pt + pb, W + pl + pr)
-        if not self.occupancymodel:
-            building = torch.ones_like(building)
-        names, params = self.trainable()
-        need_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or
-                                                 (inputs["input"].requires_grad and not unet_no_grad))
-        if unet_no_grad:
-            self.unetmodel.eval()
-        with L.precision(self.precision):
-            if need_grad:
-                _, popdense, scale = _PopcornFn.apply(self, X, building, mask, None, None, geom, sparse, encoder_no_grad, unet_no_grad,
-                                                      *params)
-                popcount = ops.UnitPopcount.apply(popdense, slot, lay["N"], lay["unit_off"])
-            else:
-                _, popdense, scale = _forward_nograd(self, X, building, mask, None, None, geom, sparse)
-                popcount = ops.unit_popcount(popdense, slot, lay["N"], lay["unit_off"])
-        popcount = popcount.index_select(0, lay["to_caller"])          # sorted order -> the caller's (b, k) order
+            if multi:
+                popcount = (ops.UnitPopcount.apply if need_grad else ops.unit_popcount)(popdense, slot, lay["N"], lay["unit_off"])
+        if multi:
+            popcount = popcount.index_select(0, lay["to_caller"])          # sorted order -> the caller's (b, k) order
         return {"popcount": popcount, "popdensemap": popdense, "scale": scale if self.occupancymodel else None}
 
 

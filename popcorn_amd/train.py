@@ -21,15 +21,15 @@ import contextlib
 import ctypes as C
 import gc
 import os
+from types import SimpleNamespace
 
-import numpy as np
 import torch
 
 from . import _lib as L
 from . import engine as E
 from . import ops
 from .distributed import FlatReducer
-from .model.popcorn import pad_geometry
+from .model.popcorn import draw_selection, pad_geometry
 
 # The head backward hands its weight-gradient partials to the U-Net backward's batched reduction (False: it reduces them itself, one launch
 # more per step -- what the head-only regime does anyway).  A test hook, not an environment switch any more (round 6).
@@ -41,19 +41,6 @@ DEFER_HEAD_REDUCE = True
 NATIVE_STEP = os.environ.get("POPCORN_NATIVE_STEP", "1") != "0"
 _LAYER_TAGS = ("inc1", "inc2", "d1a", "d1b", "d2a", "d2b", "up2a", "up2b", "up1a", "up1b")      # pc_step_stream's layer order
 _CONVT_TAGS = ("up2t", "up1t")
-
-
-_ONES = {}
-
-
-def _ones(n):
-    """torch.ones(n) of the two multinomial draws per step, kept per size (the draw reads it only)."""
-    t = _ONES.get(n)
-    if t is None:
-        if len(_ONES) > 4096:
-            _ONES.clear()
-        t = _ONES[n] = torch.ones(n)
-    return t
 
 
 class _ArenaOutputs:
@@ -142,6 +129,26 @@ def _is_multi_unit(sample):
     return torch.is_tensor(c) and c.dim() == 2
 
 
+def _data_form(sample, u16=False):
+    """(form, tensors) of a sample's image: ("input", (x,)), ("raw", (raw,)) or ("split", (s2, s1)).  The one copy of the split form's
+    channel check; u16: the dtype too (the native executor reads the bytes through a raw pointer, the engine's ops check their own)."""
+    dk = data_keys(sample)
+    if len(dk) == 1:
+        return dk[0], (sample[dk[0]],)
+    s2, s1 = sample["raw_s2"], sample["raw_s1"]
+    if s2.shape[1] != 4 or s1.shape[1] != 2 or (u16 and s2.dtype != torch.uint16):
+        raise ValueError("raw_s2 / raw_s1: the 4 selected S2 bands [R, G, B, NIR] as uint16 and the 2 S1 bands [VV, VH] as fp32")
+    return "split", (s2, s1)
+
+
+# The one-launch ingest of a raw form -- band selection + normalisation + reflect padding + stream order, the unpadded input never
+# written -- per (form, bf16 mode): (op, looked up in ``ops`` when called; needs real padding; needs 16-byte fp32 rows).  fp32 writes the
+# padded planar input; bf16 ONE channels-last bf16 tensor (8-channel slots) that both networks' first convolutions and the first-layer
+# weight gradients read through the standard 8-channel kernels.  The four rules differ; each is what its kernel takes.
+_PADDED_INGEST = {("split", False): ("ingest_split", True, True), ("split", True): ("ingest_split", True, False),
+                  ("raw", False): ("select_normalize_pad", False, True), ("raw", True): ("ingest_cl8", True, False)}
+
+
 LOSS_INDEX = {"l1_loss": 0, "log_l1_loss": 1, "mse_loss": 2, "log_mse_loss": 3}
 HEAD_NO_DECAY = ("head.6.weight", "head.6.bias")        # run_train.py:82
 
@@ -219,6 +226,7 @@ class FusedTrainStep:
         self._graph_cache_max = max(1, int(graph_cache_max if graph_cache_max is not None      # alternating truncation regimes)
                                            else os.environ.get("POPCORN_GRAPH_CACHE_MAX", "6")))  # replay instead of being re-captured
         self._static = None
+        self._ctx = None                # what _forward leaves for _backward (a record; None between steps)
         self._sel_ring, self._sel_next = [], 0          # pinned host slots for the per-step selection grid (H2D without a host sync)
         self.last = {}
         self._native = None             # (handle, plan, the engine objects it was built from) of pc_train_step
@@ -431,13 +439,12 @@ class FusedTrainStep:
             if t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != shape):
                 raise ValueError(f"{key}: expected a contiguous {dtype} tensor" + (f" of shape {shape}" if shape else "") +
                                  f", got {t.dtype} {tuple(t.shape)}" + ("" if t.is_contiguous() else " (non-contiguous)"))
-        if dk == ("raw_s2", "raw_s1"):
-            if s["raw_s2"].shape[1] != 4 or s["raw_s1"].shape[1] != 2 or s["raw_s2"].dtype != torch.uint16:
-                raise ValueError("raw_s2 / raw_s1: the 4 selected S2 bands [R, G, B, NIR] as uint16 and the 2 S1 bands [VV, VH] as fp32")
+        form, _ = _data_form(s, u16=True)
+        if form == "split":
             want("raw_s2", torch.uint16, (B, 4, H, W))
             want("raw_s1", torch.float32, (B, 2, H, W))
             io.data_kind, io.data, io.data2 = L.PC_DATA_SPLIT, s["raw_s2"].data_ptr(), s["raw_s1"].data_ptr()
-        elif dk == ("raw",):
+        elif form == "raw":
             want("raw", torch.float32)
             io.data_kind, io.data, io.craw = L.PC_DATA_RAW, s["raw"].data_ptr(), s["raw"].shape[1]
         else:
@@ -489,108 +496,109 @@ class FusedTrainStep:
 
     # ---- the three stream-ordered sections -------------------------------------------------------------------------
     def _forward(self, s, sel, encoder_no_grad, unet_no_grad):
+        """ingest -> building score, mask and U-Net features, in the launch order of the building source -> head -> context.  Each decision
+        is taken once: the input form and the one-launch ingest (``_ingest``), the domain (``same``), the building source (below), the mask
+        kind (``_mask``: one unit / multi-unit) and the head's form (``_head``)."""
         m = self.model
-        dk = data_keys(s)
-        raw = s.get("raw") if dk == ("raw",) else None
-        B, _, H, W = s[dk[0]].shape
         eng_u, eng_b = m.engines()
         # multi-unit supervision: the flattened unit lists; the mask is then ops.unit_mask on the building score and the head runs on the
         # union mask without a region (the N region sums follow it: ops.unit_popcount)
         lay = ops.unit_layout(s["census_idx"], s.get("census_n")) if _is_multi_unit(s) else None
-        slot = None
-        pt, pb, pl, pr = pad_geometry(H, W, False)
-        fused = (pt, pb, pl, pr) == (m.p, m.p, m.p, m.p)      # e.g. 100x100 tiles: both networks see the same 128x128 domain
-        Xp_all = None
-        if dk == ("raw_s2", "raw_s1"):
-            # the loader's own tensors: S2 as uint16 digital numbers [R, G, B, NIR] (two thirds of the PCIe bytes of fp32), S1 fp32
-            # [VV, VH]; their concatenation IS the model's channel order, so band index = model channel
-            _, mean, std = self.raw_norm
-            s2, s1 = s["raw_s2"], s["raw_s1"]
-            if s2.shape[1] != 4 or s1.shape[1] != 2:
-                raise ValueError("raw_s2 / raw_s1: the 4 selected S2 bands [R, G, B, NIR] as uint16 and the 2 S1 bands [VV, VH] as fp32")
-            bf16 = L.act_dtype() == torch.bfloat16
-            if fused and E.PADDED_INPUT and len(eng_u.streams) == 2 and (pt or pb or pl or pr) and (bf16 or (W + pl + pr) % 4 == 0):
-                order = E.stream_channel_order(eng_u.streams)
-                Xp_all = ops.ingest_split(s2, s1, order, [mean[c] for c in order], [std[c] for c in order], pt, pb, pl, pr)
-                X = None
-            else:
-                X = ops.select_normalize(torch.cat([s2.to(torch.float32), s1], 1).contiguous(), tuple(range(6)), mean, std)
-        elif raw is not None:
-            band, mean, std = self.raw_norm
-            if fused and E.PADDED_INPUT and L.act_dtype() == torch.float32 and (W + pl + pr) % 4 == 0 and len(eng_u.streams) == 2:
-                # raw tile -> padded, normalised, stream-ordered input in ONE launch; the unpadded input is never written
-                order = E.stream_channel_order(eng_u.streams)
-                Xp_all = ops.select_normalize_pad(raw, [band[c] for c in order], [mean[c] for c in order], [std[c] for c in order],
-                                                  pt, pb, pl, pr)
-                X = None
-            elif fused and E.PADDED_INPUT and L.act_dtype() == torch.bfloat16 and len(eng_u.streams) == 2 and (pt or pb or pl or pr):
-                # bf16 mode: the same one-launch ingest, written as ONE channels-last bf16 tensor (8-channel slots) that both
-                # networks' first convolutions and the first-layer weight gradients read through the standard 8-channel kernels
-                order = E.stream_channel_order(eng_u.streams)
-                Xp_all = ops.ingest_cl8(raw, [band[c] for c in order], [mean[c] for c in order], [std[c] for c in order], pt, pb, pl, pr)
-                X = None
-            else:
-                X = ops.select_normalize(raw, band, mean, std)
-        else:
-            X = s["input"]
+        form, data = _data_form(s)
+        B, _, H, W = data[0].shape
+        pads = pt, pb, pl, pr = pad_geometry(H, W, False)
+        same = pads == (m.p, m.p, m.p, m.p)      # e.g. 100x100 tiles: both networks see the same 128x128 domain
+        X, Xp_all = self._ingest(form, data, pads, same)
+        dom = (X, pt, pl, H + pt + pb, W + pl + pr)
+        rowcol = (sel[:H], sel[H:])
         # popcorn.py:113-114: the building score comes from the frozen extractor unless the model was built with sentinelbuildings =
         # False AND the sample brings its own "building_counts" (a dataset that ships a building layer)
         given = (not m.sentinelbuildings) and s.get("building_counts") is not None
-        if given:
-            building = s["building_counts"].contiguous().float()
-            if tuple(building.shape) != (B, 1, H, W):
-                raise ValueError(f"building_counts must be (B, 1, H, W) = {(B, 1, H, W)}, got {tuple(building.shape)}")
-            if lay is None:
-                mask, counts = ops.sparsity_mask(building, s["admin_mask"], s["census_idx"], sel[:H], sel[H:], m.occupancymodel)
-            else:
-                slot, mask, counts = ops.unit_mask(building, s["admin_mask"], lay["units"], lay["unit_off"], sel[:H], sel[H:], m.occupancymodel)
-            (feats,), (saved,) = E.forward_multi([eng_u], X, pt, pl, H + pt + pb, W + pl + pr, [not unet_no_grad], Xp_all=Xp_all)
-        elif fused:
-            (f_b, feats), (_, saved) = E.forward_multi([eng_b, eng_u], X, pt, pl, H + pt + pb, W + pl + pr,
-                                                       [False, not unet_no_grad], logit_only=[True, False], Xp_all=Xp_all)
-            if lay is None:
-                building, mask, counts = eng_b.score_and_mask(f_b, H, W, pt, pl, s["admin_mask"], s["census_idx"], sel[:H],
-                                                              sel[H:], m.occupancymodel)
-            else:
-                building = eng_b.score_from_features(f_b, H, W, pt, pl)
-                slot, mask, counts = ops.unit_mask(building, s["admin_mask"], lay["units"], lay["unit_off"], sel[:H], sel[H:], m.occupancymodel)
+        if same and not given:
+            # both networks layer by layer in shared launches; score (+ mask) from the extractor's partial logits
+            (f_b, feats), (_, saved) = E.forward_multi([eng_b, eng_u], *dom, [False, not unet_no_grad], logit_only=[True, False],
+                                                       Xp_all=Xp_all)
+            building, mask, counts, slot = self._mask(f_b, s, rowcol, lay, window=(H, W, pt, pl))
         else:
-            building = eng_b.building_score(X, m.p)
-            if lay is None:
-                mask, counts = ops.sparsity_mask(building, s["admin_mask"], s["census_idx"], sel[:H], sel[H:], m.occupancymodel)
+            # the score first (given, or the extractor on its own 14-px domain), then the mask, then the trainable U-Net
+            if given:
+                building = s["building_counts"].contiguous().float()
+                if tuple(building.shape) != (B, 1, H, W):
+                    raise ValueError(f"building_counts must be (B, 1, H, W) = {(B, 1, H, W)}, got {tuple(building.shape)}")
             else:
-                slot, mask, counts = ops.unit_mask(building, s["admin_mask"], lay["units"], lay["unit_off"], sel[:H], sel[H:], m.occupancymodel)
+                building = eng_b.building_score(X, m.p)
+            building, mask, counts, slot = self._mask(building, s, rowcol, lay)
+            if given:
+                (feats,), (saved,) = E.forward_multi([eng_u], *dom, [not unet_no_grad], Xp_all=Xp_all)
+            else:
+                feats, saved = eng_u.forward(*dom, save=not unet_no_grad)
         s["building_counts"] = building
         if not m.occupancymodel:
             building = torch.ones_like(building)
-        if not fused and not given:
-            feats, saved = eng_u.forward(X, pt, pl, H + pt + pb, W + pl + pr, save=not unet_no_grad)
-        if lay is not None:
-            # the head on the union mask, no region; stats {Nsel, sum scale} finished by the call; then the N region sums
-            scale_map, popdense, _ = ops.head_fwd(feats, pt, pl, H, W, m.head_tensors(), building, mask=mask, stats=self.stats,
-                                                  nsel_counts=counts, pack_both=True)
-            pc_sorted = ops.unit_popcount(popdense, slot, lay["N"], lay["unit_off"])
-            self._ctx = (feats, saved, building, mask, (pt, pl), (B, H, W), counts, slot, lay, pc_sorted)
-            self.last = {"popcount": pc_sorted.index_select(0, lay["to_caller"]), "popdensemap": popdense, "scale_map": scale_map,
-                         "mask": mask, "slot": slot}
-            return
-        scale_map, popdense, popcount = ops.head_fwd(feats, pt, pl, H, W, m.head_tensors(), building, mask=mask,
-                                                     admin_mask=s["admin_mask"], census_idx=s["census_idx"],
-                                                     stats=self.stats, nsel_counts=counts, pack_both=True,
-                                                     defer_reduce=not self.reducer.active)
-        # (single process: popcount / stats are finished by the loss launch of _backward; data parallel: here, for the stats all-reduce)
-        self._ctx = (feats, saved, building, mask, (pt, pl), (B, H, W), counts)
-        self.last = {"popcount": popcount, "popdensemap": popdense, "scale_map": scale_map, "mask": mask}
+        ctx = SimpleNamespace(feats=feats, saved=saved, building=building, mask=mask, pads=(pt, pl), shape=(B, H, W), counts=counts,
+                              slot=slot, lay=lay, pc_sorted=None)          # (slot, lay, pc_sorted: multi-unit steps only)
+        self._head(s, ctx)
+        self._ctx = ctx
+
+    def _ingest(self, form, data, pads, same):
+        """(X, Xp_all): the normalised model input -- or, where the one-launch padded ingest applies (``_PADDED_INGEST``; both networks on
+        the same padded domain, two streams), (None, the padded, normalised, stream-ordered input of both networks)."""
+        if form == "input":
+            return data[0], None
+        band, mean, std = self.raw_norm
+        if form == "split":
+            # the loader's own tensors: S2 as uint16 digital numbers [R, G, B, NIR] (two thirds of the PCIe bytes of fp32), S1 fp32
+            # [VV, VH]; their concatenation IS the model's channel order, so band index = model channel
+            band = tuple(range(6))
+        streams = self.model.engines()[0].streams
+        if same and E.PADDED_INPUT and len(streams) == 2:
+            pt, pb, pl, pr = pads
+            op, need_pad, need_rows16 = _PADDED_INGEST[form, L.act_dtype() == torch.bfloat16]
+            if (not need_pad or pt or pb or pl or pr) and (not need_rows16 or (data[0].shape[3] + pl + pr) % 4 == 0):
+                order = E.stream_channel_order(streams)
+                return None, getattr(ops, op)(*data, [band[c] for c in order], [mean[c] for c in order], [std[c] for c in order],
+                                              pt, pb, pl, pr)
+        raw = data[0] if form == "raw" else torch.cat([data[0].to(torch.float32), data[1]], 1).contiguous()
+        return ops.select_normalize(raw, band, mean, std), None
+
+    def _mask(self, src, s, rowcol, lay, window=None):
+        """(building, mask, counts, slot) from the building score ``src`` -- or, with ``window`` = (H, W, pt, pl), from the extractor's
+        features on the shared domain, where the one-unit form is ONE launch (``score_and_mask``).  One unit per sample (``lay`` None,
+        ``slot`` None): ops.sparsity_mask; multi-unit: ops.unit_mask."""
+        occ = self.model.occupancymodel
+        if window is not None:
+            eng_b = self.model.engines()[1]
+            if lay is None:
+                return (*eng_b.score_and_mask(src, *window, s["admin_mask"], s["census_idx"], *rowcol, occ), None)
+            src = eng_b.score_from_features(src, *window)
+        if lay is None:
+            return (src, *ops.sparsity_mask(src, s["admin_mask"], s["census_idx"], *rowcol, occ), None)
+        slot, mask, counts = ops.unit_mask(src, s["admin_mask"], lay["units"], lay["unit_off"], *rowcol, occ)
+        return src, mask, counts, slot
+
+    def _head(self, s, c):
+        """The sparse head on the step's mask; fills ``last``.  One unit: the head reduces each sample's region (single process: popcount /
+        stats are finished by the loss launch of ``_backward``; data parallel: here, for the stats all-reduce).  Multi-unit: the union
+        mask, no region, stats {Nsel, sum scale} finished by the call; then the N region sums."""
+        (pt, pl), (B, H, W) = c.pads, c.shape
+        one = c.lay is None
+        scale_map, popdense, popcount = ops.head_fwd(c.feats, pt, pl, H, W, self.model.head_tensors(), c.building, mask=c.mask,
+                                                     admin_mask=s["admin_mask"] if one else None,
+                                                     census_idx=s["census_idx"] if one else None, stats=self.stats,
+                                                     nsel_counts=c.counts, pack_both=True,
+                                                     defer_reduce=one and not self.reducer.active)
+        self.last = {"popcount": popcount, "popdensemap": popdense, "scale_map": scale_map, "mask": c.mask}
+        if not one:
+            c.pc_sorted = ops.unit_popcount(popdense, c.slot, c.lay["N"], c.lay["unit_off"])
+            self.last.update(popcount=c.pc_sorted.index_select(0, c.lay["to_caller"]), slot=c.slot)
 
     def _backward(self, s, encoder_no_grad, unet_no_grad):
-        m = self.model
-        g_pd = None
-        if len(self._ctx) > 7:
-            feats, saved, building, mask, (pt, pl), (B, H, W), counts, slot, lay, pc_sorted = self._ctx
-            g_pc, admin, census = None, None, None
-            g_pd = self._unit_loss(s, slot, lay, pc_sorted)
+        m, c = self.model, self._ctx
+        (pt, pl), (B, H, W) = c.pads, c.shape
+        g_pc = g_pd = admin = census = None
+        if c.lay is not None:
+            g_pd = self._unit_loss(s, c)
         else:
-            feats, saved, building, mask, (pt, pl), (B, H, W), counts = self._ctx
             admin, census = s["admin_mask"], s["census_idx"]
             g_pc = torch.empty(B, device=self.device, dtype=torch.float32)
             inv_B = 1.0 / self.reducer.global_batch(B)
@@ -598,13 +606,13 @@ class FusedTrainStep:
                 ops.loss_fwd_bwd(self.last["popcount"], s["y"], self.stats, self.lam4, self.sreg, self.lam_weak, inv_B,
                                  self.loss_out, g_pc, self.g_scale_const)
             else:
-                ops.head_popcount_loss(B, H, W, counts, s["y"], self.lam4, self.sreg, self.lam_weak, inv_B, self.last["popcount"], self.stats,
+                ops.head_popcount_loss(B, H, W, c.counts, s["y"], self.lam4, self.sreg, self.lam_weak, inv_B, self.last["popcount"], self.stats,
                                        self.loss_out, g_pc, self.g_scale_const)
         eng_u = m.engines()[0]
         hgrads = [self.grads[n_] for n_ in self.names[-8:]]
         khgrads, fix = m.head_grad_targets(hgrads)
         # the head's weight-gradient partials are finished by the U-Net backward's batched reduction launch when there is one
-        hp, G = ops.head_bwd(feats, pt, pl, H, W, m.head_tensors(), building, mask=mask, admin_mask=admin,
+        hp, G = ops.head_bwd(c.feats, pt, pl, H, W, m.head_tensors(), c.building, mask=c.mask, admin_mask=admin,
                              census_idx=census, g_popcount=g_pc, g_popdense=g_pd, g_scale_const=self.g_scale_const, grads=khgrads,
                              feat_bn=None if unet_no_grad else eng_u.feat_bn(), packed=True, defer_reduce=DEFER_HEAD_REDUCE and not unet_no_grad)
         if unet_no_grad:
@@ -612,22 +620,34 @@ class FusedTrainStep:
         else:
             if encoder_no_grad:
                 self.flat_g[: self.n - sum(g.numel() for g in hgrads)].zero_()
-            eng_u.backward(saved, G, self.grads, accumulate=False, encoder_no_grad=encoder_no_grad, prefix="unetmodel.",
+            eng_u.backward(c.saved, G, self.grads, accumulate=False, encoder_no_grad=encoder_no_grad, prefix="unetmodel.",
                            head_reduce=hp if isinstance(hp, ops.HeadPartials) else None)
         fix()                    # (single modality: the padded first-layer gradient -> the parameter's shape; after the reduction)
         self._ctx = None
 
-    def _unit_loss(self, s, slot, lay, pc_sorted):
+    def _unit_loss(self, s, c):
         """Multi-unit step: the population loss is the mean over the N (b, k) pairs (pc_loss_fwd_bwd with B := N, inv_B = 1 / N); its
         gradient g_popcount[N] painted onto the units' pixels is the head backward's g_popdense."""
-        N, y = lay["N"], s["y"].float()
+        lay, y = c.lay, s["y"].float()
+        N = lay["N"]
         if tuple(y.shape) != tuple(s["census_idx"].shape):
             raise ValueError(f"y must be (B, K) like census_idx {tuple(s['census_idx'].shape)}, got {tuple(y.shape)}")
         y_sorted = y.reshape(-1)[lay["to_sorted"]]
         g_pc = torch.empty(N, device=self.device, dtype=torch.float32)
-        ops.loss_fwd_bwd(pc_sorted, y_sorted, self.stats, self.lam4, self.sreg, self.lam_weak, 1.0 / N, self.loss_out, g_pc,
+        ops.loss_fwd_bwd(c.pc_sorted, y_sorted, self.stats, self.lam4, self.sreg, self.lam_weak, 1.0 / N, self.loss_out, g_pc,
                          self.g_scale_const)
-        return ops.unit_paint(g_pc, slot)
+        return ops.unit_paint(g_pc, c.slot)
+
+    def _sections(self, st, sel, enc_ng, unet_ng, collectives=True):
+        """The step: forward -> [all-reduce {Nsel, sum scale}] -> backward -> [all-reduce the flat gradient] -> update.  The reducer's calls
+        return at once in a single process; ``collectives=False``: the capture's warm-up, which must not pair with the peers' collectives."""
+        self._forward(st, sel, enc_ng, unet_ng)
+        if collectives:
+            self.reducer.reduce_stats(self.stats)
+        self._backward(st, enc_ng, unet_ng)
+        if collectives:
+            self.reducer.reduce_grads(self.flat_g)
+        self._update(enc_ng, unet_ng)
 
     def _update(self, encoder_no_grad=False, unet_no_grad=False):
         active = {2} if unet_no_grad else ({1, 2} if encoder_no_grad else {0, 1, 2})
@@ -638,14 +658,8 @@ class FusedTrainStep:
     # ------------------------------------------------------------------------------------------------------------
     @staticmethod
     def _draw_selection(H, W):
-        """The two CPU-generator multinomial draws of get_sparsity_mask (popcorn.py:366-369)."""
-        sub = 60
-        xi = _ones(H).multinomial(num_samples=min(sub, H), replacement=False)
-        yi = _ones(W).multinomial(num_samples=min(sub, W), replacement=False)
-        sel = np.zeros(H + W, dtype=np.uint8)          # (numpy: two index_put calls cost more than the draws' own bookkeeping)
-        sel[xi.numpy()] = 1
-        sel[H + yi.numpy()] = 1
-        return torch.from_numpy(sel)
+        """The two CPU-generator multinomial draws of get_sparsity_mask (popcorn.py:366-369): ``draw_selection``, the model API's draw."""
+        return draw_selection(H, W)
 
     def _sel_to_device(self, sel_host, dst=None):
         """The per-step row / column selection (H + W bytes drawn on the CPU generator, like the reference) goes to the device
@@ -695,25 +709,19 @@ class FusedTrainStep:
             if self.reducer.active:
                 raise NotImplementedError("multi-unit samples (2-D census_idx) are not supported with a data-parallel reducer")
         sel_host = self._draw_selection(H, W)
-        if not self.use_graph:
-            s = {k: (v.contiguous() if torch.is_tensor(v) else v) for k, v in sample.items() if not k.startswith("_")}
-            s["admin_mask"] = s["admin_mask"].float()
-            with L.precision(self.model.precision), L.stream_scope():      # (one stream lookup for the step's ~40 launches)
-                if self._native_ok(s):
-                    if H + W <= L.PC_STEP_SEL_MAX:
-                        self._throttle()
-                        self._native_step(s, sel_host, encoder_no_grad, unet_no_grad)       # (consumed during the call: no ring slot)
-                    else:
-                        self._native_step(s, self._sel_to_device(sel_host), encoder_no_grad, unet_no_grad)
-                    return self.loss_out
-                sel = self._sel_to_device(sel_host)
-                self._forward(s, sel, encoder_no_grad, unet_no_grad)
-                self.reducer.reduce_stats(self.stats)
-                self._backward(s, encoder_no_grad, unet_no_grad)
-                self.reducer.reduce_grads(self.flat_g)
-                self._update(encoder_no_grad, unet_no_grad)
-            return self.loss_out
-        return self._graph_step(sample, sel_host, encoder_no_grad, unet_no_grad)
+        if self.use_graph:
+            return self._graph_step(sample, sel_host, encoder_no_grad, unet_no_grad)
+        s = {k: (v.contiguous() if torch.is_tensor(v) else v) for k, v in sample.items() if not k.startswith("_")}
+        s["admin_mask"] = s["admin_mask"].float()
+        with L.precision(self.model.precision), L.stream_scope():      # (one stream lookup for the step's ~40 launches)
+            if not self._native_ok(s):
+                self._sections(s, self._sel_to_device(sel_host), encoder_no_grad, unet_no_grad)
+            elif H + W <= L.PC_STEP_SEL_MAX:
+                self._throttle()
+                self._native_step(s, sel_host, encoder_no_grad, unet_no_grad)       # (consumed during the call: no ring slot)
+            else:
+                self._native_step(s, self._sel_to_device(sel_host), encoder_no_grad, unet_no_grad)
+        return self.loss_out
 
     def _graph_step(self, sample, sel_host, encoder_no_grad, unet_no_grad):
         dks = data_keys(sample)
@@ -748,10 +756,8 @@ class FusedTrainStep:
             if sample[k] is not st[k]:            # a loader that fills static_buffers() in place skips the copy
                 st[k].copy_(sample[k], non_blocking=True)
         self._sel_to_device(sel_host, sel)
-        if len(graphs) == 1:                      # single process, or both collectives captured inside the one graph (RCCL)
-            graphs[0].replay()
-        else:
-            graphs[0].replay()
+        graphs[0].replay()
+        if len(graphs) > 1:                       # (one graph: single process, or both collectives captured inside it (RCCL))
             self.reducer.reduce_stats(self.stats)
             graphs[1].replay()
             self.reducer.reduce_grads(self.flat_g)
@@ -818,17 +824,15 @@ class FusedTrainStep:
         mine = [d for d in (self._static or {}).values() if all(sample.get(k) is d[k] for k in d)]
         if mine:
             st = dict(mine[0])
-            if key[-1] and "building_counts" not in st:
-                # a static set built without ``building=True`` + a sample that brings its own building layer (sentinelbuildings = False
-                # models, popcorn.py:113-114): the layer is an INPUT of the captured step -- it gets its own static tensor, which
-                # ``_graph_step`` refreshes from the sample before every replay (round 4 dropped it here: the capture then recorded the
-                # frozen-extractor path and training ran on the extractor's score without an error)
-                st["building_counts"] = sample["building_counts"].detach().clone().contiguous().float()
         else:
             st = {k: sample[k].detach().clone().contiguous() for k in data_keys(sample) + ("admin_mask", "census_idx", "y")}
-            if not self.model.sentinelbuildings and sample.get("building_counts") is not None:
-                st["building_counts"] = sample["building_counts"].detach().clone().contiguous().float()     # an INPUT of this model (see _forward)
             st["admin_mask"] = st["admin_mask"].float()
+        if key[-1] and "building_counts" not in st:
+            # a sample that brings its own building layer (sentinelbuildings = False models, popcorn.py:113-114; key[-1]) -- also with a
+            # static set built without ``building=True``: the layer is an INPUT of the captured step -- it gets its own static tensor, which
+            # ``_graph_step`` refreshes from the sample before every replay (round 4 dropped it for static sets: the capture then recorded
+            # the frozen-extractor path and training ran on the extractor's score without an error)
+            st["building_counts"] = sample["building_counts"].detach().clone().contiguous().float()
         if key[-1] and st.get("building_counts") is None:
             raise L.PopcornHipError("graph capture of a step with a given building layer needs 'building_counts' among its static inputs")
         sel = sel_host.to(self.device)
@@ -838,9 +842,7 @@ class FusedTrainStep:
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(2):
-                self._forward(st, sel, enc_ng, unet_ng)
-                self._backward(st, enc_ng, unet_ng)
-                self._update(enc_ng, unet_ng)
+                self._sections(st, sel, enc_ng, unet_ng, collectives=False)
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.flat_p.copy_(snap[0]); self.m.copy_(snap[1]); self.v.copy_(snap[2]); self.step_count.copy_(snap[3])
@@ -853,11 +855,7 @@ class FusedTrainStep:
             try:
                 g = torch.cuda.CUDAGraph()
                 with _capturing(g):
-                    self._forward(st, sel, enc_ng, unet_ng)
-                    self.reducer.reduce_stats(self.stats)
-                    self._backward(st, enc_ng, unet_ng)
-                    self.reducer.reduce_grads(self.flat_g)
-                    self._update(enc_ng, unet_ng)
+                    self._sections(st, sel, enc_ng, unet_ng)
                 graphs = [g]
             except RuntimeError as e:
                 # only a failed CAPTURE of the collectives falls back; programming errors propagate.  An allocation failure of a

@@ -347,6 +347,62 @@ def test_fused_step_multi_unit(case, autograd_pair):
         trg.step(dict(s))
 
 
+def _fused_pair(H, W, given, seed=33):
+    """One multi-unit fused step (B = 2, the ``case`` fixture's units at H x W) and the one-unit fused step on the replicated batch: fresh
+    trainers on the same model state, the same seed in front of both (the same selection grid).  given: a sentinelbuildings = False model
+    and a fixed building layer in the sample, which ``U.replicate`` carries along.  Returns (multi-unit trainer, loss, one-unit trainer,
+    loss)."""
+    from popcorn_amd.train import FusedTrainStep
+    inputs, y = U.make_case(B=2, H=H, W=W, units=((12, 3, 7), (9, 5)), channels=6, seed=11)
+    if given:
+        inputs["building_counts"] = torch.rand(2, 1, H, W, generator=torch.Generator().manual_seed(4))
+    rep, y_flat, _ = U.replicate(inputs, y)
+    out = []
+    for smp, yy in ((inputs, y), (rep, y_flat)):
+        m = _new_model()
+        m.sentinelbuildings = not given
+        tr = FusedTrainStep(m, lr=1e-4, weight_decay=1e-5, gradient_clip=0.01)
+        s = _cuda(smp)
+        s["y"] = yy.cuda()
+        torch.manual_seed(seed)
+        loss = tr.step(s)
+        out += [tr, loss[0].item()]
+    return out
+
+
+def _assert_fused_pair(tag, tr, loss, tr1, loss1):
+    """The bars of ``test_fused_step_multi_unit``: loss 1e-4 relative, the 56 gradients 2e-4, popcount 1e-4."""
+    worst = max(grad_err(tr.grads[n].cpu(), tr1.grads[n].cpu()) for n in tr.names)
+    pc = rel(tr.last["popcount"], tr1.last["popcount"])
+    print(f"\n[{tag}] loss {loss:.6f} vs one-unit {loss1:.6f}; worst gradient {worst:.2e}; popcount {pc:.2e}")
+    assert len(tr.names) == 56 and tuple(tr.last["popcount"].shape) == (5,)
+    assert abs(loss - loss1) <= 1e-4 * max(1.0, abs(loss1))
+    assert worst <= 2e-4
+    assert pc <= 1e-4
+    assert "slot" in tr.last and tr._ctx is None                   # the step's context does not outlive the step
+
+
+def test_fused_step_multi_unit_same_domain():
+    """2 x 100 x 100: pads of 14 on every side = the extractor's pad, so both networks run on ONE padded domain and the multi-unit step
+    takes score_from_features + unit_mask behind the shared forward (the one-unit step there: the fused score_and_mask).  Seed 33, the
+    first tried."""
+    tr, loss, tr1, loss1 = _fused_pair(100, 100, given=False)
+    assert tr.native_steps == 0 and tr1.native_steps == 1          # the replicated one-unit step goes through the native executor
+    assert getattr(tr1, "_ctx", None) is None
+    _assert_fused_pair("multi-unit fused step, same domain", tr, loss, tr1, loss1)
+
+
+@pytest.mark.parametrize("H,W", [(96, 80), (100, 100)])
+def test_fused_step_multi_unit_given_buildings(H, W):
+    """A given building layer (sentinelbuildings = False + ``building_counts`` in the sample) x multi-unit, on separate domains (96 x 80)
+    and on the shared one (100 x 100): unit_mask on the given layer, then the trainable U-Net alone.  Both sides run the per-launch
+    engine (the executor declines a given layer).  Seed 33, the first tried."""
+    tr, loss, tr1, loss1 = _fused_pair(H, W, given=True)
+    assert tr.native_steps == 0 and tr1.native_steps == 0
+    assert tr1._ctx is None
+    _assert_fused_pair(f"multi-unit fused step, given buildings {H}x{W}", tr, loss, tr1, loss1)
+
+
 def test_run_train_units_per_crop(tmp_path):
     """run_train.py --units_per_crop 4 --max_steps 4 on the synthetic multi-unit dataset: finishes with finite losses."""
     from popcorn_amd.cli import run_train

@@ -6,6 +6,11 @@ functions and ``WgradBatch`` methods), one JSON line per call, one file per case
 A tensor is rendered as (token, shape, strides, dtype), token = index of first appearance of its data_ptr() in the case; a PcBn as the
 index of first appearance of its id.  Every rendered object stays referenced until the case ends, so no address is reused.  The
 ``*_ok`` geometry predicates enqueue nothing and are not recorded (which launch follows them is).  Needs a GPU; a case is one step.
+
+The cases: the fused step at the three geometries (same padded domain for both networks, separate domains with B = 2 and B = 1), in both
+precisions, the three truncation regimes, every engine switch, the three input forms, single modality, a given building layer; the same
+step with multi-unit supervision (2-D ``census_idx``, K = 3 with one padded slot and one absent unit: ``units-*``), also on a given building
+layer and on the split form; the model API (autograd and eval) and the engine called directly.
 """
 import inspect
 import json
@@ -81,9 +86,16 @@ def model(prec="fp32", ic=6, senb=True):
     return POPCORN(ic, occupancymodel=True, pretrained=True, biasinit=0.9407, sentinelbuildings=senb).cuda().set_precision(prec)
 
 
-def sample(B, H, W, form="input", ic=6):
+def sample(B, H, W, form="input", ic=6, units=False):
     b = make_raw_batch(B, H, W, seed=H * 1000 + W, device="cuda", region="disc")
     s = {k: b[k] for k in ("admin_mask", "census_idx", "y")}
+    if units:
+        # multi-unit supervision: per crop the ring, the disc and a unit that is not in it; the first row's last slot is padding
+        ids = b["census_idx"]
+        s["census_idx"] = torch.stack([ids + B, ids, torch.full_like(ids, 999)], 1)
+        s["census_idx"][0, 2] = -1
+        s["census_n"] = [2] + [3] * (B - 1)
+        s["y"] = torch.rand(B, 3, generator=torch.Generator().manual_seed(5)).cuda() * 500.0
     sel = b["raw"][:, list(stats.BAND6)]
     if form == "raw":
         s["raw"] = b["raw"]
@@ -96,8 +108,8 @@ def sample(B, H, W, form="input", ic=6):
     return s
 
 
-def step(prec, B, H, W, form="input", ic=6, senb=True, **regime):
-    s = sample(B, H, W, form, ic)
+def step(prec, B, H, W, form="input", ic=6, senb=True, units=False, **regime):
+    s = sample(B, H, W, form, ic, units)
     if not senb:
         s["building_counts"] = torch.rand(B, 1, H, W, generator=torch.Generator().manual_seed(4)).cuda()
     tr = T.FusedTrainStep(model(prec, ic, senb), lr=1e-4, weight_decay=1e-5, gradient_clip=0.01)
@@ -149,6 +161,12 @@ def cases():
             yield f"{prec}-engine-padded-{rname}-1x77x59", {}, (lambda: engine_pass(prec, 1, 77, 59, **regime))
         yield f"{prec}-engine-accumulate-2x100x100", {}, (lambda: engine_pass(prec, 2, 100, 100, accumulate=True))
         yield f"{prec}-given-buildings", {}, (lambda: step(prec, 2, 100, 100, senb=False))
+        for rname, regime in REGIMES.items():
+            for shp in SHAPES:
+                yield f"{prec}-units-{rname}-{'x'.join(map(str, shp))}", {}, (lambda: step(prec, *shp, units=True, **regime))
+        for shp in SHAPES[:2]:
+            yield f"{prec}-units-given-buildings-{'x'.join(map(str, shp))}", {}, (lambda: step(prec, *shp, senb=False, units=True))
+        yield f"{prec}-units-split", {}, (lambda: step(prec, 2, 100, 100, form="split", units=True))
     for ic in (2, 4):           # one stream; 64 x 48: the extractor runs on its own domain (UNetEngine.building_score)
         for shp in SHAPES[:2]:
             yield f"fp32-single-modality-{ic}-{'x'.join(map(str, shp))}", {}, (lambda: step("fp32", *shp, ic=ic))
