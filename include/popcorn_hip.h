@@ -89,7 +89,7 @@ int pc_abi_version(void);
 int pc_device_count(void);
 const char* pc_error_string(int code);
 /* sizeof of the ABI structs as compiled: 0 = pc_src, 1 = pc_dst, 2 = pc_bn, 3 = pc_conv_fwd_desc, 4 = pc_adam_groups,
-   5 = pc_level2_fwd_desc, 6 = pc_step_plan, 7 = pc_step_io (lets a binding verify its struct layout) */
+   5 = pc_level2_fwd_desc, 6 = pc_step_plan, 7 = pc_step_io, 8 = pc_step_units (lets a binding verify its struct layout) */
 int pc_sizeof(int which);
 
 /* ---- arithmetic mode -----------------------------------------------------------------------------------
@@ -793,6 +793,52 @@ int pc_unit_popcount(const float* popdense, const int32_t* slot, const int32_t* 
 /* The autograd of pc_unit_popcount: g_popdense[i] = slot[i] in [0, N) ? g_popcount[slot[i]] : 0 for i < n = B * H * W; every element is
  * written (no zero fill needed).  16-byte loads and stores when both maps are 16-byte aligned. */
 int pc_unit_paint(const float* g_popcount, const int32_t* slot, float* g_popdense, int64_t n, int N, void* stream);
+
+/* The flattened lists above from the caller's padded batch, ONE launch with one workgroup per sample row (what ops.unit_layout does with
+ * a sort, a masked fill, three gathers, a scatter and a host-to-device copy).  census_idx (B, K) int64 and y (B, K) fp32 on the DEVICE;
+ * census_n = HOST int32 [B], the valid count of each row, 1 <= census_n[b] <= K: the counts travel in the kernel arguments (no
+ * host-to-device copy command).  Slots at or past census_n[b] are ignored whatever they hold.  Each row is sorted in LDS (a bitonic network
+ * over (id, slot) pairs padded to a power of two; every trip count is fixed by K).  Writes, with N = sum census_n:
+ *   units     int64 [N]      ascending per row             unit_off  int32 [B + 1]
+ *   y_sorted  fp32 [N]       y in the sorted order         dest      int32 [N]: the flat (b, k) position, in the caller's order over the
+ *                                                                     valid slots, of sorted slot n (popcount_caller[dest[n]] = popcount[n])
+ *   ws        the first 20 * N bytes of the pc_unit_ws_bytes(N) workspace of the population sum := 0 (16-byte aligned; NULL: skipped), so
+ *             that pc_unit_popcount_loss needs no zeroing launch
+ * Duplicate ids inside the valid range break the contract of the lists; the call still terminates and stays in bounds.
+ * Caps: K <= PC_UNIT_LAYOUT_MAX_K (the LDS id list of pc_unit_mask) and B <= PC_UNIT_LAYOUT_MAX_B (16-bit counts in the kernel-argument
+ * block); beyond either the call returns PC_ENOTSUP before a launch and the caller keeps its own plumbing. */
+#define PC_UNIT_LAYOUT_MAX_K 1024
+#define PC_UNIT_LAYOUT_MAX_B 256
+int pc_unit_layout(const int64_t* census_idx, const float* y, const int32_t* census_n, int B, int K, int64_t* units, int32_t* unit_off,
+                   float* y_sorted, int32_t* dest, void* ws, void* stream);
+/* pc_unit_popcount + pc_loss_fwd_bwd over the N (b, k) pairs (B := N, inv_B := 1 / N) in TWO launches instead of four: the accumulate
+ * launch of pc_unit_popcount on a workspace that pc_unit_layout zeroed, then one block that finishes popcount_sorted[n] (the arithmetic of
+ * pc_unit_popcount), writes the same value to popcount_caller[dest[n]] (optional, NULL) and runs the loss block on (popcount_sorted,
+ * y_sorted).  Bit-identical to the two separate calls on the same inputs: same device functions, same order.  g_popcount [N] is in the
+ * sorted order (what pc_unit_paint takes).  stats, lam4, loss_out, g_scale_const as for pc_loss_fwd_bwd. */
+int pc_unit_popcount_loss(const float* popdense, const int32_t* slot, const int32_t* unit_off, const int32_t* dest, const float* y_sorted,
+                          void* ws, float* popcount_sorted, float* popcount_caller, const double* stats, const float* lam4,
+                          float scale_regularization, float lam_weak, int B, int H, int W, int N, float* loss_out, float* g_popcount,
+                          float* g_scale_const, void* stream);
+
+/* ---- the native step executor for a multi-unit batch (csrc/step.hip) ----
+ * pc_train_step for a batch whose samples list K units each: io as for pc_train_step, except that io->census_idx, io->y and
+ * io->off_popcount are unused; the unit lists travel here.  Stage order: pc_unit_layout (on the stream whose chain ends in the mask) ->
+ * ingest and networks as pc_train_step -> pc_outconv_sigmoid_crop -> pc_unit_mask -> pc_head_fwd on the union mask without a region ->
+ * pc_unit_popcount_loss -> pc_unit_paint -> pc_head_bwd with g_popdense -> U-Net backward and update as pc_train_step.  popdensemap is
+ * written at EVERY pixel by the head (0 * building where the mask does not select), which is what the unit sums rely on.  The unit sums,
+ * the loss and popcount belong to the PC_STEP_BWD phase.  PC_ENOTSUP (nothing enqueued; the caller keeps the per-launch path): K or B
+ * beyond pc_unit_layout's caps, io->dp != 0 (N differs per rank: the global mean needs a collective), a stream under capture, and what
+ * pc_train_step declines. */
+typedef struct pc_step_units {
+    const int64_t* census_idx; const float* y;      /* DEVICE (B, K) */
+    const int32_t* census_n;                        /* HOST [B]: valid units per row, 1 <= census_n[b] <= K */
+    int32_t K, N;                                   /* N = sum census_n */
+    /* results: byte offsets inside the arena, valid until the next call */
+    int64_t off_slot;                               /* slot i32 [B][H][W] (pc_unit_mask) */
+    int64_t off_popcount;                           /* popcount f32 [N] in the caller's (b, k) order */
+} pc_step_units;
+int pc_train_step_units(void* handle, pc_step_io* io, pc_step_units* u, int phases, void* stream);
 
 #ifdef __cplusplus
 }

@@ -154,6 +154,15 @@ class PcStepIo(C.Structure):
                 ("launches", C.c_int32), ("_pad2", C.c_int32)]
 
 
+class PcStepUnits(C.Structure):
+    """pc_step_units: the unit lists of a multi-unit batch for pc_train_step_units (census_n: HOST int32 [B])."""
+    _fields_ = [("census_idx", C.c_void_p), ("y", C.c_void_p), ("census_n", C.POINTER(C.c_int32)), ("K", C.c_int32), ("N", C.c_int32),
+                ("off_slot", C.c_int64), ("off_popcount", C.c_int64)]
+
+
+PC_UNIT_LAYOUT_MAX_K, PC_UNIT_LAYOUT_MAX_B = 1024, 256
+
+
 class PopcornHipError(RuntimeError):
     pass
 
@@ -172,8 +181,8 @@ def lib():
         cand = C.CDLL(LIB_PATH)
         # the .so is a build artefact (git-ignored): refuse a stale one instead of handing it descriptors of another layout
         ver = cand.pc_abi_version() if hasattr(cand, "pc_abi_version") else -1
-        sizes = [cand.pc_sizeof(i) for i in range(8)] if hasattr(cand, "pc_sizeof") else []
-        want = [C.sizeof(t) for t in (PcSrc, PcDst, PcBn, PcConvFwdDesc, PcAdamGroups, PcLevel2FwdDesc, PcStepPlan, PcStepIo)]
+        sizes = [cand.pc_sizeof(i) for i in range(9)] if hasattr(cand, "pc_sizeof") else []
+        want = [C.sizeof(t) for t in (PcSrc, PcDst, PcBn, PcConvFwdDesc, PcAdamGroups, PcLevel2FwdDesc, PcStepPlan, PcStepIo, PcStepUnits)]
         if ver != PC_ABI_VERSION or sizes != want:
             raise PopcornHipError(f"{LIB_PATH} is stale: ABI version {ver} (binding: {PC_ABI_VERSION}), struct sizes {sizes} "
                                   f"(binding: {want}); rebuild it with `make -C popcorn_amd/csrc`")
@@ -207,6 +216,10 @@ def lib():
         _lib.pc_unit_mask.argtypes = [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]
         _lib.pc_unit_popcount.argtypes = [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]
         _lib.pc_unit_paint.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+        _lib.pc_unit_layout.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int] + [C.c_void_p] * 6
+        _lib.pc_unit_popcount_loss.argtypes = ([C.c_void_p] * 9 + [C.POINTER(C.c_float), C.c_float, C.c_float] + [C.c_int] * 4 +
+                                               [C.c_void_p] * 4)
+        _lib.pc_train_step_units.argtypes = [C.c_void_p, C.POINTER(PcStepIo), C.POINTER(PcStepUnits), C.c_int, C.c_void_p]
     return _lib
 
 

@@ -92,6 +92,9 @@ def train_parser():
     p.add_argument("--units_per_crop", type=int, default=0,
                    help="multi-unit census supervision: train on synthetic crops that list this many census units each (all of them "
                         "supervised in one eager step; 0 = off, the reference's one unit per sample)")
+    p.add_argument("--native_units", action="store_true",
+                   help="--units_per_crop steps through the native step executor (pc_train_step_units: one call per step, the same "
+                        "bits as the per-launch engine); experimental, off by default")
     return p
 
 
@@ -293,7 +296,7 @@ class Trainer:
                                         gradient_clip=args.gradient_clip, loss=args.loss, lam=args.lam,
                                         scale_regularization=args.scale_regularization, lam_weak=args.lam_weak,
                                         reducer=self.reducer, use_graph=args.fixed_hw is not None and args.units_per_crop == 0,
-                                        raw_norm=(tuple(range(6)), stats.MEAN6, stats.STD6))
+                                        raw_norm=(tuple(range(6)), stats.MEAN6, stats.STD6), native_units=args.native_units)
         if args.resume:
             self.resume(args.resume)
 

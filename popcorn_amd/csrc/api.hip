@@ -48,7 +48,7 @@ extern "C" const char* pc_error_string(int code) {
 }
 
 // sizeof() of the ABI structs as the compiler laid them out: 0 = pc_src, 1 = pc_dst, 2 = pc_bn,
-// 3 = pc_conv_fwd_desc, 4 = pc_adam_groups, 5 = pc_level2_fwd_desc, 6 = pc_step_plan, 7 = pc_step_io (binding self-check)
+// 3 = pc_conv_fwd_desc, 4 = pc_adam_groups, 5 = pc_level2_fwd_desc, 6 = pc_step_plan, 7 = pc_step_io, 8 = pc_step_units (binding self-check)
 extern "C" int pc_sizeof(int which) {
     switch (which) {
         case 0: return (int)sizeof(pc_src);
@@ -59,6 +59,7 @@ extern "C" int pc_sizeof(int which) {
         case 5: return (int)sizeof(pc_level2_fwd_desc);
         case 6: return (int)sizeof(pc_step_plan);
         case 7: return (int)sizeof(pc_step_io);
+        case 8: return (int)sizeof(pc_step_units);
         default: return -1;
     }
 }

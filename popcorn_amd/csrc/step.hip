@@ -13,6 +13,10 @@
 //     transposed conv fills the top-left 2h x 2w of it): the two-source conv then sees two sources of identical layout;
 //   * a pooled source is handed over cropped to even extents (MaxPool2d(2) floors).
 //
+// A multi-unit batch (pc_train_step_units, Step::un / Step::U: K census units per crop, units.hip) takes the same path with another
+// tail around the head: unit lists -> score -> unit mask -> head without a region -> unit sums + loss -> paint -> head backward on
+// g_popdense; everything between ingest and the U-Net update is shared, and a one-unit call (un == nullptr) issues what it always did.
+//
 // The backward pass (struct Backward) is the network in reverse, one function per U-Net block, to be read next to engine.py: _Backward.
 // It has the COMPOSED form of the two Up blocks only: the trainable U-Net works on the add_padding domain, whose sides are multiples of
 // 32 (pad_geometry), so both levels have exact 2x geometry, widths that are multiples of 16 and 16-byte rows -- everything the composed
@@ -124,6 +128,14 @@ struct Step {
     void* head_ws = nullptr;
     Saved sv[2];
     bool unet_ng = false, enc_ng = false, deferred_popcount = false;
+    // multi-unit batch (pc_train_step_units; null: one unit per sample): the lists of the call, and what forward() carved for them
+    pc_step_units* un = nullptr;
+    bool fwd_units = false;                     // the forward pass in the arena was a multi-unit one
+    struct Units {
+        int64_t* units = nullptr; int32_t* unit_off = nullptr; float* y_sorted = nullptr; int32_t* dest = nullptr;
+        void* ws = nullptr; int32_t* slot = nullptr; float* pc_sorted = nullptr; float* pc_caller = nullptr; float* g_pc = nullptr;
+        int N = 0;
+    } U;
     int64_t fwd_end = 0;                        // arena offset behind the forward pass's tensors
     // per call
     Arena ar;
@@ -451,6 +463,29 @@ void forward(Step& X, pc_step_io& io) {
     };
     X.g_pc = reinterpret_cast<float*>(A.raw((int64_t)B * 4));
     X.head_ws = A.raw(pc_head_ws_bytes(B, H, W));
+    X.fwd_units = X.un != nullptr;
+    if (X.un) {
+        // multi-unit batch: the flattened lists, the slot map and the N popcounts (sorted order for the loss, caller's order as the result)
+        Step::Units& U = X.U;
+        const int64_t N = U.N = X.un->N;
+        U.pc_caller = reinterpret_cast<float*>(A.raw(N * 4));
+        X.un->off_popcount = reinterpret_cast<char*>(U.pc_caller) - A.base;
+        U.slot = reinterpret_cast<int32_t*>(A.raw((int64_t)B * H * W * 4));
+        X.un->off_slot = reinterpret_cast<char*>(U.slot) - A.base;
+        U.units = reinterpret_cast<int64_t*>(A.raw(N * 8));
+        U.unit_off = reinterpret_cast<int32_t*>(A.raw((int64_t)(B + 1) * 4));
+        U.y_sorted = reinterpret_cast<float*>(A.raw(N * 4));
+        U.dest = reinterpret_cast<int32_t*>(A.raw(N * 4));
+        U.ws = A.raw(pc_unit_ws_bytes(N));
+        U.pc_sorted = reinterpret_cast<float*>(A.raw(N * 4));
+        U.g_pc = reinterpret_cast<float*>(A.raw(N * 4));
+    }
+    // the lists (and the zeroed workspace of the unit sums) are made once per step, in front of the chain that ends in the mask
+    auto unit_layout = [&]() {
+        if (!X.un || !X.go()) return;
+        X.rc(pc_unit_layout(X.un->census_idx, X.un->y, X.un->census_n, B, X.un->K, X.U.units, X.U.unit_off, X.U.y_sorted, X.U.dest, X.U.ws,
+                            X.st));
+    };
 
     const bool same_domain = pt == p && pb == p && pl == p && pr == p;     // e.g. 100 x 100 tiles: both networks on the 128 x 128 domain
     Ten feats[2];
@@ -461,12 +496,21 @@ void forward(Step& X, pc_step_io& io) {
     auto score_mask = [&](const Ten& logits, int oy, int ox) {
         const pc_src fs = S(logits);
         const pc_dst db = D(X.building);
+        if (X.un) {
+            // multi-unit: the score as a map, then the unit lookup + union mask (train.py: score_from_features + ops.unit_mask)
+            if (X.go()) X.rc(pc_outconv_sigmoid_crop(&fs, X.ones2, P.extractor.fusion_b, &db, B, H, W, oy, ox, X.st));
+            if (X.go())
+                X.rc(pc_unit_mask(X.building.p, am, X.U.units, X.U.unit_off, X.sel, X.sel + H, P.occupancymodel, X.U.slot, X.mask, X.counts,
+                                  nullptr, B, H, W, X.U.N, X.st));
+            return;
+        }
         if (X.go())
             X.rc(pc_building_score_mask(&fs, X.ones2, P.extractor.fusion_b, &db, am, io.census_idx, X.sel, X.sel + H, P.occupancymodel, X.mask,
                                         X.counts, B, H, W, oy, ox, X.st));
     };
     if (same_domain) {
         unpack_sel();
+        unit_layout();
         const Ten Xp = ingest(X, io, pt, pb, pl, pr);
         X.Xp_u = Xp;
         const Net nets[2] = {Net{&P.extractor, false, true}, Net{&P.unet, !X.unet_ng, false}};
@@ -488,6 +532,7 @@ void forward(Step& X, pc_step_io& io) {
         if (two) X.st = X.side;
         {
             unpack_sel();
+            unit_layout();
             const Ten Xb = ingest(X, io, p, p, p, p);
             const Net nb[1] = {Net{&P.extractor, false, true}};
             forward_nets(X, nb, 1, Xb, H + 2 * p, W + 2 * p, feats, nullptr);
@@ -515,6 +560,18 @@ void forward(Step& X, pc_step_io& io) {
         return X.rc(PC_ENOTSUP);
     }
     const pc_src sf = S(X.feats);
+    if (X.un) {
+        // the union mask, no region: popdensemap is written at every pixel (0 * building outside the mask -- what the unit sums of
+        // backward() rely on), {Nsel, sum scale} finished by the call, popcount[B] = the plain sums (unused)
+        X.deferred_popcount = false;
+        if (X.go())
+            X.rc(pc_head_fwd(&sf, pt, pl, P.head_w, X.mask, bld, nullptr, nullptr, X.scale_map, X.popdense, X.popcount, P.stats_dev, X.counts,
+                             X.head_ws, B, H, W, PC_HEAD_FWD_PACK_BOTH, X.st));
+        X.launches += 2;           // (pack + kernel + reduction)
+        X.fwd_end = A.off;
+        X.have_fwd = true;
+        return;
+    }
     X.deferred_popcount = io.dp == 0;
     if (X.go())
         X.rc(pc_head_fwd(&sf, pt, pl, P.head_w, X.mask, bld, am, io.census_idx, X.scale_map, X.popdense, X.popcount, P.stats_dev, X.counts,
@@ -822,7 +879,17 @@ void backward(Step& X, pc_step_io& io) {
     const int H1 = Hp / 2, W1 = Wp / 2, H2 = H1 / 2, W2 = W1 / 2;
     A.off = X.fwd_end;
     // loss forward + backward (utils/losses.py:49-76); single process: also finishes popcount / stats of the head forward
-    if (X.deferred_popcount) {
+    float* g_pd = nullptr;
+    if (X.fwd_units) {
+        // multi-unit: the N unit sums and the loss over the N (b, k) pairs, then its gradient painted onto the units' pixels
+        const Step::Units& U = X.U;
+        g_pd = reinterpret_cast<float*>(A.raw((int64_t)B * H * W * 4));
+        if (X.go())
+            X.rc(pc_unit_popcount_loss(X.popdense, U.slot, U.unit_off, U.dest, U.y_sorted, U.ws, U.pc_sorted, U.pc_caller, P.stats_dev, P.lam4,
+                                       P.scale_regularization, P.lam_weak, B, H, W, U.N, P.loss_dev, U.g_pc, P.g_scale_const_dev, X.st));
+        X.launches += 1;           // (accumulate + finish / loss)
+        if (X.go()) X.rc(pc_unit_paint(U.g_pc, U.slot, g_pd, (int64_t)B * H * W, U.N, X.st));
+    } else if (X.deferred_popcount) {
         if (X.go())
             X.rc(pc_head_popcount_loss(X.head_ws, B, H, W, X.counts, io.y, P.lam4, P.scale_regularization, P.lam_weak, io.inv_B, X.popcount,
                                        P.stats_dev, P.loss_dev, X.g_pc, P.g_scale_const_dev, X.st));
@@ -837,7 +904,8 @@ void backward(Step& X, pc_step_io& io) {
         const pc_dst dg = D(G);
         const bool defer = !X.unet_ng;
         if (X.go())
-            X.rc(pc_head_bwd(&sf, X.pt, X.pl, P.head_w, X.mask, X.building.p, io.admin_mask, io.census_idx, X.g_pc, nullptr, nullptr,
+            X.rc(pc_head_bwd(&sf, X.pt, X.pl, P.head_w, X.mask, X.building.p, g_pd ? nullptr : io.admin_mask, g_pd ? nullptr : io.census_idx,
+                             g_pd ? nullptr : X.g_pc, g_pd, nullptr,
                              P.g_scale_const_dev, P.head_dw, 0, &dg, X.unet_ng ? nullptr : &X.bn_nobias[0][L_UP1B],
                              X.unet_ng ? nullptr : &X.bn_nobias[1][L_UP1B], Hp, Wp, X.head_ws, B, H, W,
                              PC_HEAD_BWD_PACKED | (defer ? PC_HEAD_BWD_DEFER_REDUCE : 0), X.st));
@@ -1054,14 +1122,18 @@ extern "C" void pc_step_destroy(void* handle) {
     delete X;
 }
 
-extern "C" int pc_train_step(void* handle, pc_step_io* io, int phases, void* stream) {
+// un: the unit lists of pc_train_step_units (checked by it), or null: one unit per sample, io->census_idx / io->y
+static int train_step(void* handle, pc_step_io* io, pc_step_units* un, int phases, void* stream) {
     Step* X = reinterpret_cast<Step*>(handle);
     if (!X || !io || io->B < 1 || io->H < 1 || io->W < 1 || !(phases & 7)) return PC_EINVAL;
     if (g_pc_precision != PC_PREC_FP32) return PC_ENOTSUP;
-    if ((phases & PC_STEP_FWD) && (!io->data || !io->admin_mask || !io->census_idx || (!io->sel && !io->sel_host) ||
+    if ((phases & PC_STEP_FWD) && (!io->data || !io->admin_mask || (!un && !io->census_idx) || (!io->sel && !io->sel_host) ||
                                    (io->sel_host && io->H + io->W > PC_STEP_SEL_MAX) || (io->data_kind == PC_DATA_SPLIT && !io->data2)))
         return PC_EINVAL;
-    if ((phases & PC_STEP_BWD) && !io->y) return PC_EINVAL;
+    if ((phases & PC_STEP_BWD) && !un && !io->y) return PC_EINVAL;
+    // a backward phase continues the forward pass that is in the arena: of the same kind
+    if ((phases & PC_STEP_BWD) && !(phases & PC_STEP_FWD) && X->have_fwd && X->fwd_units != (un != nullptr)) return PC_EINVAL;
+    X->un = un;
     if (phases & PC_STEP_FWD) {
         int pt, pb, pl, pr;
         pad_geometry(io->H, io->W, pt, pb, pl, pr);
@@ -1093,5 +1165,24 @@ extern "C" int pc_train_step(void* handle, pc_step_io* io, int phases, void* str
     io->launches = X->launches;
     g_step_host_ns[0] = std::chrono::duration<double, std::nano>(t_b - t_a).count();
     g_step_host_ns[1] = std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t_b).count();
+    return rc;
+}
+
+extern "C" int pc_train_step(void* handle, pc_step_io* io, int phases, void* stream) { return train_step(handle, io, nullptr, phases, stream); }
+
+extern "C" int pc_train_step_units(void* handle, pc_step_io* io, pc_step_units* u, int phases, void* stream) {
+    // every check of the lists comes before the handle is looked at: nothing here touches a device
+    if (!handle || !io || !u || !u->census_idx || !u->y || !u->census_n || u->K < 1 || u->N < 1 || io->B < 1) return PC_EINVAL;
+    if (u->K > PC_UNIT_LAYOUT_MAX_K || io->B > PC_UNIT_LAYOUT_MAX_B || io->dp != 0) return PC_ENOTSUP;
+    int64_t n = 0;
+    for (int b = 0; b < io->B; ++b) {
+        if (u->census_n[b] < 1 || u->census_n[b] > u->K) return PC_EINVAL;
+        n += u->census_n[b];
+    }
+    if (n != u->N) return PC_EINVAL;
+    // (the unit sums' range, pc_unit_popcount: a unit's integer sums cannot wrap below 2^27 pixels per sample)
+    if ((int64_t)io->H * io->W >= ((int64_t)1 << 27) || (int64_t)io->B * io->H * io->W >= ((int64_t)1 << 31)) return PC_ENOTSUP;
+    const int rc = train_step(handle, io, u, phases, stream);
+    reinterpret_cast<Step*>(handle)->un = nullptr;          // (the lists are the caller's: no pointer to them outlives the call)
     return rc;
 }

@@ -11,6 +11,10 @@
 //                     mask.hip: score_mask_kernel)
 //   pc_unit_popcount  popcount[n] = sum of popdense over slot == n: the N region sums of :186-188, bit-reproducible
 //   pc_unit_paint     g_popdense[b,y,x] = g_popcount[slot] (0 for slot < 0): the autograd of those sums
+// and, for the native step executor (step.hip: pc_train_step_units), what surrounds them without torch launches:
+//   pc_unit_layout         the sorted, flattened unit lists from the caller's padded (B, K) batch -- rows sorted in LDS, the host's valid
+//                          counts in the kernel arguments -- and the zeroed workspace of the sums: ONE launch
+//   pc_unit_popcount_loss  the accumulate launch of pc_unit_popcount, then one block: finish, scatter to the caller's order, loss
 //
 // Arithmetic of the sums.  A term q is split exactly into trunc(q) and its fraction; the integer parts and the fractions on a
 // 2^-PC_CENSUS_FIX_SHIFT grid (census_table.hip's grid) are summed as two 64-bit integers per unit.  Integer addition is associative, so
@@ -264,11 +268,96 @@ static_assert(PC_CENSUS_FIX_SHIFT == 30, "unit_popcount_kernel scales the fracti
 static_assert(UN_PX_PER_BLOCK % (4 * UN_THREADS) == 0, "a chunk is whole rounds of four pixels per lane");
 
 // popcount = int + frac * 2^-30: both conversions are exact below 2^53 and the sum rounds once; then once more to fp32
+__device__ __forceinline__ float un_finish(long long acc_int, long long acc_frac, int32_t bad) {
+    const double s = (double)acc_int + (double)acc_frac * (1.0 / 1073741824.0);
+    return bad ? __builtin_nanf("") : (float)s;
+}
+
 __global__ __launch_bounds__(256) void unit_popcount_finish_kernel(const long long* __restrict__ acc_int, const long long* __restrict__ acc_frac,
                                                                    const int32_t* __restrict__ bad, float* __restrict__ popcount, int N) {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) {
-        const double s = (double)acc_int[i] + (double)acc_frac[i] * (1.0 / 1073741824.0);
-        popcount[i] = bad[i] ? __builtin_nanf("") : (float)s;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < N; i += gridDim.x * 256) popcount[i] = un_finish(acc_int[i], acc_frac[i], bad[i]);
+}
+
+// pc_unit_popcount_loss's second launch, ONE block (the pattern of head.hip: head_popcount_loss_kernel): the finish above for all N units,
+// the same value scattered to the caller's (b, k) order, then the loss block over the N pairs.  Thread t finishes and reads back the units
+// t, t + 256, ...: pc_loss_block walks them with the same stride.
+__global__ __launch_bounds__(256) void unit_finish_loss_kernel(const long long* __restrict__ acc_int, const long long* __restrict__ acc_frac,
+                                                               const int32_t* __restrict__ bad, const int32_t* __restrict__ dest,
+                                                               float* popcount, float* __restrict__ popcount_caller, const double* stats,
+                                                               const pc_loss_args a) {
+    __shared__ double red[256];
+    const int N = a.B;
+    for (int i = threadIdx.x; i < N; i += 256) {
+        const float v = un_finish(acc_int[i], acc_frac[i], bad[i]);
+        popcount[i] = v;
+        if (popcount_caller) {
+            const int d = dest[i];
+            if ((unsigned)d < (unsigned)N) popcount_caller[d] = v;
+        }
+    }
+    __syncthreads();
+    pc_loss_block(a, popcount, stats, red);
+}
+
+// ---- the flattened lists from the padded batch ------------------------------------------------------------------------------------------
+constexpr int UL_MAX_K = PC_UNIT_LAYOUT_MAX_K;
+constexpr int UL_MAX_B = PC_UNIT_LAYOUT_MAX_B;
+static_assert(UL_MAX_K <= UN_LDS_IDS, "a row that pc_unit_layout sorts fits the LDS id list of unit_mask_kernel");
+static_assert(UL_MAX_K < 65536, "a count fits 16 bits");
+
+struct UnitLayoutArgs {
+    const int64_t* census_idx; const float* y;
+    int64_t* units; int32_t* unit_off; float* y_sorted; int32_t* dest;
+    un_u64* acc_int; un_u64* acc_frac; int32_t* bad;          // the population sum's workspace (NULL: not zeroed)
+    int B, K, P, N;                                              // P: K rounded up to a power of two
+    uint16_t n[UL_MAX_B];                                        // the host's valid counts: 512 bytes of kernel arguments
+};
+
+// (key, tag) pairs in ascending order; tag = the slot k of a valid entry, 65536 + k of a padding entry, so that the order is total and a
+// valid INT64_MAX still sorts in front of the padding
+__device__ __forceinline__ bool ul_less(long long ka, int ta, long long kb, int tb) { return ka != kb ? ka < kb : ta < tb; }
+
+__global__ __launch_bounds__(UN_THREADS) void unit_layout_kernel(const UnitLayoutArgs a) {
+    __shared__ long long key[UL_MAX_K];
+    __shared__ int tag[UL_MAX_K];
+    const int t = threadIdx.x, b = blockIdx.x;
+    const int nb = a.n[b];
+    int off = 0;
+    for (int i = 0; i < b; ++i) off += a.n[i];
+    const int64_t* row = a.census_idx + (int64_t)b * a.K;
+    for (int i = t; i < a.P; i += UN_THREADS) {
+        const bool valid = i < nb;                                // nb <= K (checked by the host)
+        key[i] = valid ? (long long)row[i] : 0x7fffffffffffffffll;
+        tag[i] = valid ? i : 65536 + i;
+    }
+    __syncthreads();
+    // bitonic network: log2(P) (log2(P) + 1) / 2 rounds of P / 2 disjoint compare-exchanges, a barrier between rounds
+    for (int k = 2; k <= a.P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = t; i < a.P; i += UN_THREADS) {
+                const int p = i ^ j;
+                if (p > i) {
+                    const long long ki = key[i], kp = key[p];
+                    const int ti = tag[i], tp = tag[p];
+                    const bool up = (i & k) == 0;
+                    if (up ? ul_less(kp, tp, ki, ti) : ul_less(ki, ti, kp, tp)) { key[i] = kp; key[p] = ki; tag[i] = tp; tag[p] = ti; }
+                }
+            }
+            __syncthreads();
+        }
+    if (t == 0) {
+        a.unit_off[b] = off;
+        if (b == a.B - 1) a.unit_off[a.B] = off + nb;
+    }
+    // the nb valid entries sort in front of the padding: sorted slot j < nb holds the caller's slot tag[j] < nb.  off + nb <= N (host)
+    for (int j = t; j < nb; j += UN_THREADS) {
+        const int n = off + j;
+        int src = tag[j] & 65535;
+        if (src >= nb) src = j;                                   // (cannot happen; keeps every index in the row whatever the sort did)
+        a.units[n] = key[j];
+        a.y_sorted[n] = a.y[(int64_t)b * a.K + src];
+        a.dest[n] = off + src;
+        if (a.acc_int) { a.acc_int[n] = 0; a.acc_frac[n] = 0; a.bad[n] = 0; }
     }
 }
 
@@ -368,6 +457,67 @@ extern "C" int pc_unit_paint(const float* g_popcount, const int32_t* slot, float
     if (g > 4096) g = 4096;
     if (g < 1) g = 1;
     hipLaunchKernelGGL(unit_paint_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, g_popcount, slot, g_popdense, n, N, vec);
+    PC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pc_unit_layout(const int64_t* census_idx, const float* y, const int32_t* census_n, int B, int K, int64_t* units,
+                              int32_t* unit_off, float* y_sorted, int32_t* dest, void* ws, void* stream) {
+    if (!census_idx || !y || !census_n || !units || !unit_off || !y_sorted || !dest || B < 1 || K < 1) return PC_EINVAL;
+    if (K > UL_MAX_K || B > UL_MAX_B) return PC_ENOTSUP;
+    if ((reinterpret_cast<uintptr_t>(census_idx) | reinterpret_cast<uintptr_t>(units)) & 7) return PC_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(y_sorted) | reinterpret_cast<uintptr_t>(unit_off) |
+         reinterpret_cast<uintptr_t>(dest)) & 3)
+        return PC_EINVAL;
+    if (reinterpret_cast<uintptr_t>(ws) & 15) return PC_EINVAL;
+    UnitLayoutArgs a{};
+    int N = 0;
+    for (int b = 0; b < B; ++b) {
+        if (census_n[b] < 1 || census_n[b] > K) return PC_EINVAL;
+        a.n[b] = (uint16_t)census_n[b];
+        N += census_n[b];
+    }
+    a.census_idx = census_idx; a.y = y; a.units = units; a.unit_off = unit_off; a.y_sorted = y_sorted; a.dest = dest;
+    if (ws) {
+        a.acc_int = reinterpret_cast<un_u64*>(ws);
+        a.acc_frac = a.acc_int + N;
+        a.bad = reinterpret_cast<int32_t*>(a.acc_frac + N);
+    }
+    a.B = B; a.K = K; a.N = N;
+    a.P = 1;
+    while (a.P < K) a.P <<= 1;
+    hipLaunchKernelGGL(unit_layout_kernel, dim3(B), dim3(UN_THREADS), 0, (hipStream_t)stream, a);
+    PC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pc_unit_popcount_loss(const float* popdense, const int32_t* slot, const int32_t* unit_off, const int32_t* dest,
+                                     const float* y_sorted, void* ws, float* popcount_sorted, float* popcount_caller, const double* stats,
+                                     const float* lam4, float scale_regularization, float lam_weak, int B, int H, int W, int N,
+                                     float* loss_out, float* g_popcount, float* g_scale_const, void* stream) {
+    if (!popdense || !slot || !y_sorted || !ws || !popcount_sorted || !lam4 || !loss_out || !g_popcount || !g_scale_const) return PC_EINVAL;
+    if (popcount_caller && !dest) return PC_EINVAL;
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || N < 1 || (int64_t)H * W >= ((int64_t)1 << 27)) return PC_EINVAL;      // as pc_unit_popcount
+    if ((reinterpret_cast<uintptr_t>(ws) & 15) || ((reinterpret_cast<uintptr_t>(popdense) | reinterpret_cast<uintptr_t>(slot)) & 3)) return PC_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    UnitSumArgs a{};
+    a.popdense = popdense; a.slot = slot; a.unit_off = unit_off;
+    a.acc_int = reinterpret_cast<un_u64*>(ws);
+    a.acc_frac = a.acc_int + N;
+    a.bad = reinterpret_cast<int32_t*>(a.acc_frac + N);
+    a.HW = H * W; a.N = N;
+    a.chunks = (a.HW + UN_PX_PER_BLOCK - 1) / UN_PX_PER_BLOCK;
+    const int cap = 4 * UN_MAX_BLOCKS / B > 1 ? 4 * UN_MAX_BLOCKS / B : 1;
+    hipLaunchKernelGGL(unit_popcount_kernel, dim3(a.chunks < cap ? a.chunks : cap, B), dim3(UN_THREADS), 0, st, a);
+    PC_CHECK_LAUNCH();
+    pc_loss_args l{};
+    l.y = y_sorted;
+    for (int i = 0; i < 4; ++i) l.lam[i] = lam4[i];
+    l.sreg = scale_regularization; l.lam_weak = lam_weak; l.B = N;
+    l.inv_B = (float)(1.0 / (double)N);           // (the double quotient rounded once more: what a caller of pc_loss_fwd_bwd passes)
+    l.loss_out = loss_out; l.g_popcount = g_popcount; l.g_scale_const = g_scale_const;
+    hipLaunchKernelGGL(unit_finish_loss_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<const long long*>(a.acc_int),
+                       reinterpret_cast<const long long*>(a.acc_frac), a.bad, dest, popcount_sorted, popcount_caller, stats, l);
     PC_CHECK_LAUNCH();
     return 0;
 }

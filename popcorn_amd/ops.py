@@ -614,6 +614,70 @@ def unit_paint(g_popcount, slot, out=None):
     return out
 
 
+def _unit_counts(census_n, B, K):
+    """The host list of valid counts per row (``unit_layout``'s rules)."""
+    if census_n is None:
+        return [K] * B
+    if torch.is_tensor(census_n) and census_n.is_cuda:
+        raise ValueError("census_n is host data (a list or a CPU tensor): it sizes the result")
+    counts = [int(v) for v in (census_n.tolist() if torch.is_tensor(census_n) else census_n)]
+    if len(counts) != B or any(c < 1 or c > K for c in counts):
+        raise ValueError(f"census_n must hold B = {B} counts in [1, K = {K}], got {counts}")
+    return counts
+
+
+def unit_layout_device(census_idx, y, census_n=None, ws=None):
+    """pc_unit_layout: ``unit_layout`` as ONE launch (rows sorted in LDS, the host counts in the kernel arguments: no sort, gather or
+    host-to-device copy), for the executor-style tail ``unit_popcount_loss``.  census_idx (B, K) int64 and y (B, K) fp32 on the device,
+    census_n host data.  Returns a dict: units, unit_off, N, counts as ``unit_layout``; y_sorted fp32 [N]; dest int32 [N], the flat
+    (b, k) position over the valid slots of sorted slot n; ws, the workspace of the unit sums, zeroed over its 20 N bytes by the launch
+    (``ws``: a uint8 tensor of at least pc_unit_ws_bytes(N) bytes to use instead of a fresh one).  K above L.PC_UNIT_LAYOUT_MAX_K or B
+    above L.PC_UNIT_LAYOUT_MAX_B raises (PC_ENOTSUP): ``unit_layout`` takes those."""
+    L.require_device(census_idx, y)
+    if census_idx.dim() != 2 or census_idx.dtype != torch.int64:
+        raise ValueError(f"unit_layout_device: census_idx must be an int64 (B, K) tensor, got {census_idx.dtype} {tuple(census_idx.shape)}")
+    if y.dtype != torch.float32 or tuple(y.shape) != tuple(census_idx.shape):
+        raise ValueError(f"unit_layout_device: y must be fp32 {tuple(census_idx.shape)} like census_idx, got {y.dtype} {tuple(y.shape)}")
+    B, K = census_idx.shape
+    counts = _unit_counts(census_n, B, K)
+    N = sum(counts)
+    dev = census_idx.device
+    census_idx, y = census_idx.contiguous(), y.contiguous()
+    units = torch.empty(N, dtype=torch.int64, device=dev)
+    unit_off = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    y_sorted = torch.empty(N, dtype=torch.float32, device=dev)
+    dest = torch.empty(N, dtype=torch.int32, device=dev)
+    need = L.lib().pc_unit_ws_bytes(N)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_cuda or ws.data_ptr() % 16:
+        raise ValueError(f"unit_layout_device: ws must be a 16-byte aligned uint8 device tensor of at least {need} bytes")
+    L.check(L.lib().pc_unit_layout(L.ptr(census_idx), L.ptr(y), (C.c_int32 * B)(*counts), B, K, L.ptr(units), L.ptr(unit_off),
+                                   L.ptr(y_sorted), L.ptr(dest), L.ptr(ws), L.stream_ptr()), "pc_unit_layout")
+    return {"units": units, "unit_off": unit_off, "N": N, "counts": counts, "y_sorted": y_sorted, "dest": dest, "ws": ws}
+
+
+def unit_popcount_loss(popdense, slot, lay, stats, lam4, scale_regularization, lam_weak, loss_out, g_popcount, g_scale_const):
+    """pc_unit_popcount_loss on a ``unit_layout_device`` result: ``unit_popcount`` + ``loss_fwd_bwd`` over the N pairs (inv_B = 1 / N)
+    in two launches, bit-identical to the two calls.  Consumes the zeroed workspace ``lay["ws"]`` (one call per layout).  g_popcount
+    fp32 [N], in the sorted order (``unit_paint``'s).  Returns (popcount in the sorted order, popcount in the caller's (b, k) order)."""
+    L.require_device(popdense, slot, g_popcount)
+    N = int(lay["N"])
+    if popdense.dim() != 3 or popdense.dtype != torch.float32 or slot.dtype != torch.int32 or slot.shape != popdense.shape:
+        raise ValueError("unit_popcount_loss: fp32 popdense (B, H, W) and an int32 slot map of the same shape")
+    if g_popcount.dtype != torch.float32 or g_popcount.numel() != N or not g_popcount.is_contiguous():
+        raise ValueError(f"unit_popcount_loss: g_popcount must be a contiguous fp32 tensor of N = {N} elements")
+    popdense, slot = popdense.contiguous(), slot.contiguous()
+    B, H, W = popdense.shape
+    pc_sorted = torch.empty(N, dtype=torch.float32, device=popdense.device)
+    pc_caller = torch.empty(N, dtype=torch.float32, device=popdense.device)
+    L.check(L.lib().pc_unit_popcount_loss(L.ptr(popdense), L.ptr(slot), L.ptr(lay["unit_off"]), L.ptr(lay["dest"]), L.ptr(lay["y_sorted"]),
+                                          L.ptr(lay["ws"]), L.ptr(pc_sorted), L.ptr(pc_caller), L.ptr(stats), (C.c_float * 4)(*lam4),
+                                          C.c_float(scale_regularization), C.c_float(lam_weak), B, H, W, N, L.ptr(loss_out),
+                                          L.ptr(g_popcount), L.ptr(g_scale_const), L.stream_ptr()), "pc_unit_popcount_loss")
+    return pc_sorted, pc_caller
+
+
 class UnitPopcount(torch.autograd.Function):
     """popcount[N] = ``unit_popcount(popdense, slot, N)``; backward: ``unit_paint``.  slot / unit_off get no gradient."""
 

@@ -13,7 +13,8 @@ all-reduce are single kernels / a single collective.  The static-shape step can 
 Multi-unit census supervision (opt-in; csrc/units.hip): a sample whose ``census_idx`` is 2-D (B, K) -- with ``y`` (B, K) and the optional
 host-side ``census_n`` -- supervises every listed unit of each crop in one step: one crop, K popcounts, one loss over the N = sum(census_n)
 (b, k) pairs, one backward.  It computes what the one-unit step computes on the replicated batch.  Such a step runs eagerly through the
-per-launch engine; graph mode and data parallelism raise for it (``FusedTrainStep.step``).
+per-launch engine -- or, with ``native_units=True``, through the native executor (pc_train_step_units: one C-ABI call, the same bits);
+graph mode and data parallelism raise for it (``FusedTrainStep.step``).
 """
 from __future__ import annotations
 
@@ -47,12 +48,14 @@ class _ArenaOutputs:
     """The outputs of a native step -- views into the step's arena, built on first access (``popcount``, ``popdensemap``, ``scale_map``,
     ``mask``, ``building_counts``).  Valid until the trainer's next step (the arena is reused), like the static outputs of a replayed graph."""
 
-    def __init__(self, arena, io):
+    def __init__(self, arena, io, units=None):
         B, H, W = io.B, io.H, io.W
         self._arena = arena
         self._spec = {"popcount": (io.off_popcount, torch.float32, (B,)), "popdensemap": (io.off_popdense, torch.float32, (B, H, W)),
                       "scale_map": (io.off_scale, torch.float32, (B, H, W)), "mask": (io.off_mask, torch.uint8, (B, H, W)),
                       "building_counts": (io.off_building, torch.float32, (B, 1, H, W))}
+        if units is not None:           # a multi-unit step (pc_step_units): popcount (N,) in (b, k) order, and the slot map
+            self._spec.update(popcount=(units.off_popcount, torch.float32, (units.N,)), slot=(units.off_slot, torch.int32, (B, H, W)))
         self._views = {}
 
     def __getitem__(self, k):
@@ -62,7 +65,7 @@ class _ArenaOutputs:
             n = 1
             for d in shape:
                 n *= d
-            nbytes = n * (4 if dt == torch.float32 else 1)
+            nbytes = n * (1 if dt == torch.uint8 else 4)
             v = self._views[k] = self._arena[off:off + nbytes].view(dt).view(shape)
         return v
 
@@ -156,14 +159,16 @@ HEAD_NO_DECAY = ("head.6.weight", "head.6.bias")        # run_train.py:82
 class FusedTrainStep:
     def __init__(self, model, lr=1e-4, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, gradient_clip=0.01,
                  loss=("log_l1_loss",), lam=(1.0,), scale_regularization=0.01, lam_weak=100.0,
-                 reducer: FlatReducer | None = None, use_graph=False, raw_norm=None, graph_cache_max=None):
+                 reducer: FlatReducer | None = None, use_graph=False, raw_norm=None, graph_cache_max=None, native_units=False):
         """raw_norm = (band6, mean6, std6): how a RAW tile (sample key "raw" instead of "input": (B, Craw, H, W) reflectances /
         backscatter) becomes the model input -- band selection (data/PopulationDataset.py:566-568) + apply_normalize
         (utils/utils.py:105-127); default: the reference's dataset statistics (popcorn_amd.data.stats).  With a raw sample the
         step's first launch does select + normalise + reflect padding in one pass (pc_select_normalize_pad).
         graph_cache_max: how many captured steps (one per (tile shape, truncation regime, precision)) stay alive -- each owns a
         private memory pool with every activation and gradient of its step; default 6 or POPCORN_GRAPH_CACHE_MAX.  A capture that
-        runs out of memory drops ALL cached graphs (and their pools) and is retried once."""
+        runs out of memory drops ALL cached graphs (and their pools) and is retried once.
+        native_units: multi-unit samples (2-D census_idx) go through the native executor (pc_train_step_units) where it takes them --
+        opt-in, experimental; off: the per-launch engine, as before.  The two compute the same bits."""
         from .data import stats as _stats
         self.raw_norm = raw_norm or (_stats.BAND6, _stats.MEAN6, _stats.STD6)
         self.model = model
@@ -232,6 +237,8 @@ class FusedTrainStep:
         self._native = None             # (handle, plan, the engine objects it was built from) of pc_train_step
         self._arena = None
         self.native_steps = 0           # eager steps that went through pc_train_step (tests / tools read it)
+        self.native_units = bool(native_units)
+        self.native_unit_steps = 0      # multi-unit steps that went through pc_train_step_units (native_steps counts one-unit steps only)
 
     def __del__(self):
         nat = getattr(self, "_native", None)
@@ -349,8 +356,8 @@ class FusedTrainStep:
         m = self.model
         if not NATIVE_STEP or m.precision != "fp32" or not (m.S1 and m.S2) or not m.occupancymodel:
             return False
-        if _is_multi_unit(sample):
-            return False               # pc_train_step supervises one unit per sample
+        if _is_multi_unit(sample) and not self.native_units:
+            return False               # opt-in (pc_train_step_units); pc_train_step supervises one unit per sample
         if not (E.PADDED_INPUT and E.COMPOSED_UP and E.FUSED_LEVEL2 and E.FUSED_CONV_BWD and DEFER_HEAD_REDUCE):
             return False               # an A/B switch of the per-launch engine is off its default: that engine is what is being asked for
         if (not m.sentinelbuildings) and sample.get("building_counts") is not None:
@@ -433,6 +440,7 @@ class FusedTrainStep:
         # the executor takes raw device pointers: everything the per-launch engine checks tensor by tensor (device, dtype, layout) is
         # checked here, so that a CPU tensor or a wrong dtype raises instead of faulting on the GPU / training on reinterpreted bytes
         L.require_device(*(s[k] for k in dk), s["admin_mask"], s["census_idx"], s["y"])
+        units = None
 
         def want(key, dtype, shape=None):
             t = s[key]
@@ -452,10 +460,22 @@ class FusedTrainStep:
                 raise ValueError("input must be a (B, 6, H, W) fp32 tensor")
             want("input", torch.float32, (B, 6, H, W))
             io.data_kind, io.data = L.PC_DATA_INPUT, s["input"].data_ptr()
-        want("census_idx", torch.int64, (B,))
-        want("y", torch.float32, (B,))
         want("admin_mask", torch.float32, (B, H, W))
-        io.admin_mask, io.census_idx, io.y = s["admin_mask"].data_ptr(), s["census_idx"].data_ptr(), s["y"].data_ptr()
+        io.admin_mask = s["admin_mask"].data_ptr()
+        if _is_multi_unit(s):
+            # the unit lists travel in their own struct (pc_step_units); census_n is host data, default K per row
+            K = s["census_idx"].shape[1]
+            want("census_idx", torch.int64, (B, K))
+            want("y", torch.float32, (B, K))
+            counts = ops._unit_counts(s.get("census_n"), B, K)
+            units = L.PcStepUnits()
+            units._counts = (C.c_int32 * B)(*counts)             # (kept alive with the struct)
+            units.census_idx, units.y, units.census_n = s["census_idx"].data_ptr(), s["y"].data_ptr(), units._counts
+            units.K, units.N = K, sum(counts)
+        else:
+            want("census_idx", torch.int64, (B,))
+            want("y", torch.float32, (B,))
+            io.census_idx, io.y = s["census_idx"].data_ptr(), s["y"].data_ptr()
         if sel.is_cuda:
             io.sel = sel.data_ptr()
         else:                       # host flags: they travel in the kernel arguments of the executor's first launch (no H2D copy command)
@@ -463,26 +483,42 @@ class FusedTrainStep:
         io.encoder_no_grad, io.unet_no_grad = int(bool(encoder_no_grad)), int(bool(unet_no_grad))
         io.inv_B = 1.0 / self.reducer.global_batch(B)
         io.dp = int(bool(self.reducer.active))
-        return io
+        return io if units is None else (io, units)
 
-    def _native_call(self, h, io, phases, stream):
+    def _native_call(self, h, io, phases, stream, units=None):
+        """pc_train_step (``units``: pc_train_step_units) with the arena grown to what the geometry takes.  With ``units`` a PC_ENOTSUP is
+        returned instead of raised: nothing was enqueued, the caller takes the per-launch engine."""
         lib = L.lib()
         for _ in range(2):
             if self._arena is not None:
                 io.arena, io.arena_bytes = self._arena.data_ptr(), self._arena.numel()
-            rc = lib.pc_train_step(h, C.byref(io), phases, stream)
+            if units is None:
+                rc = lib.pc_train_step(h, C.byref(io), phases, stream)
+            else:
+                rc = lib.pc_train_step_units(h, C.byref(io), C.byref(units), phases, stream)
             if rc != L.PC_ENOMEM or not (phases & L.PC_STEP_FWD):
                 break               # (a backward / update phase never grows the arena: the forward's activations live in it)
             # the arena grows to what this geometry takes (+ 1/8: the next region is a little larger more often than not); the old one is
             # released to torch's stream-ordered allocator, so work still in flight on it finishes first
             self._arena = None
             self._arena = torch.empty(int(io.arena_needed * 9 // 8), dtype=torch.uint8, device=self.device)
-        L.check(rc, "pc_train_step")
+        if units is not None and rc == L.PC_ENOTSUP:
+            return rc
+        L.check(rc, "pc_train_step" if units is None else "pc_train_step_units")
+        return rc
 
     def _native_step(self, s, sel, encoder_no_grad, unet_no_grad):
+        """One executor step; False: a multi-unit batch the executor declines (nothing enqueued, nothing updated)."""
         h = self._native_handle()
         io = self._native_io(s, sel, encoder_no_grad, unet_no_grad)
         stream = L.stream_ptr()
+        if isinstance(io, tuple):
+            io, units = io
+            if self._native_call(h, io, L.PC_STEP_FWD | L.PC_STEP_BWD | L.PC_STEP_UPD, stream, units) == L.PC_ENOTSUP:
+                return False
+            self.last = _ArenaOutputs(self._arena, io, units)
+            self.native_unit_steps += 1
+            return True
         if not self.reducer.active:
             self._native_call(h, io, L.PC_STEP_FWD | L.PC_STEP_BWD | L.PC_STEP_UPD, stream)
         else:
@@ -493,6 +529,7 @@ class FusedTrainStep:
             self._native_call(h, io, L.PC_STEP_UPD, stream)
         self.last = _ArenaOutputs(self._arena, io)
         self.native_steps += 1
+        return True
 
     # ---- the three stream-ordered sections -------------------------------------------------------------------------
     def _forward(self, s, sel, encoder_no_grad, unet_no_grad):
@@ -698,9 +735,11 @@ class FusedTrainStep:
         admin_mask, census_idx, y}.  Returns the device tensor loss_out[2] = {loss, regulariser} (no host sync).
 
         Multi-unit supervision: ``census_idx`` (B, K) int64 on the device (ids non-negative, distinct within a row), ``y`` (B, K) and optionally ``census_n`` (HOST list / CPU tensor: valid units per row, default K).  The step is the
-        one-unit step on the replicated batch of N = sum(census_n) samples; ``last["popcount"]`` is (N,) in (b, k) order.  It always runs
-        eagerly through the per-launch engine (``native_steps`` does not count it).  Out of scope, and refused: ``use_graph=True`` raises
-        ValueError, an active data-parallel reducer raises NotImplementedError."""
+        one-unit step on the replicated batch of N = sum(census_n) samples; ``last["popcount"]`` is (N,) in (b, k) order.  It runs
+        eagerly through the per-launch engine (``native_steps`` does not count it) or, with ``native_units=True``, through
+        pc_train_step_units (counted in ``native_unit_steps``; what that entry declines -- K or B beyond its caps -- falls back to the
+        per-launch engine within the step).  Out of scope, and refused: ``use_graph=True`` raises ValueError, an active data-parallel
+        reducer raises NotImplementedError."""
         dkey = data_keys(sample)[0]
         B, _, H, W = sample[dkey].shape
         if _is_multi_unit(sample):
@@ -714,13 +753,16 @@ class FusedTrainStep:
         s = {k: (v.contiguous() if torch.is_tensor(v) else v) for k, v in sample.items() if not k.startswith("_")}
         s["admin_mask"] = s["admin_mask"].float()
         with L.precision(self.model.precision), L.stream_scope():      # (one stream lookup for the step's ~40 launches)
-            if not self._native_ok(s):
+            done = False
+            if self._native_ok(s):
+                if H + W <= L.PC_STEP_SEL_MAX:
+                    self._throttle()
+                    sel = sel_host                                 # (consumed during the call: no ring slot)
+                else:
+                    sel = self._sel_to_device(sel_host)
+                done = self._native_step(s, sel, encoder_no_grad, unet_no_grad)
+            if not done:                                           # (not covered, or a multi-unit batch the executor declined)
                 self._sections(s, self._sel_to_device(sel_host), encoder_no_grad, unet_no_grad)
-            elif H + W <= L.PC_STEP_SEL_MAX:
-                self._throttle()
-                self._native_step(s, sel_host, encoder_no_grad, unet_no_grad)       # (consumed during the call: no ring slot)
-            else:
-                self._native_step(s, self._sel_to_device(sel_host), encoder_no_grad, unet_no_grad)
         return self.loss_out
 
     def _graph_step(self, sample, sel_host, encoder_no_grad, unet_no_grad):
