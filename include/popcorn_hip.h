@@ -821,6 +821,31 @@ int pc_unit_popcount_loss(const float* popdense, const int32_t* slot, const int3
                           float scale_regularization, float lam_weak, int B, int H, int W, int N, float* loss_out, float* g_popcount,
                           float* g_scale_const, void* stream);
 
+/* The device-N forms of the two entries above, for a step that is replayed from a captured graph or runs data parallel: nothing in a launch
+ * depends on the counts.  Every buffer has the capacity Ncap = B * K and every launch runs at it.
+ *
+ * pc_unit_layout_dev: pc_unit_layout with census_n_dev = DEVICE int32 [B] (a loader rewrites it between replays).  The device cannot raise:
+ * a count outside [1, K] is CLAMPED into [1, K] (a caller that wants an error validates on the host).  Same LDS sort and total order (a
+ * valid INT64_MAX sorts in front of the padding); row b's offset is the sum of the clamped counts in front of it.  With N = the sum of the
+ * clamped counts, every element of every output is written on every call:
+ *   units [Ncap], y_sorted [Ncap], dest [Ncap]: entries [0, N) as pc_unit_layout; units[N..) = INT64_MAX, y_sorted[N..) = 0, dest[N..) = -1
+ *   unit_off [B + 1], unit_off[B] = N
+ *   ws        20 * Ncap bytes := 0: the sums' workspace LAID OUT BY Ncap (pc_unit_ws_bytes(Ncap); 16-byte aligned; NULL: skipped)
+ *   n_dev     int32 [1] = N        stats (optional, NULL): stats[2] = (double)N, the local N next to {Nsel, sum scale} in stats[0..1]
+ * Caps as pc_unit_layout (PC_ENOTSUP beyond them).  One workgroup per row; every trip count is fixed by (B, K). */
+int pc_unit_layout_dev(const int64_t* census_idx, const float* y, const int32_t* census_n_dev, int B, int K, int64_t* units,
+                       int32_t* unit_off, float* y_sorted, int32_t* dest, void* ws, int32_t* n_dev, double* stats, void* stream);
+/* pc_unit_popcount_loss on a pc_unit_layout_dev result: the accumulate launch with the workspace laid out by Ncap, then ONE block that reads
+ * N_local = n_dev[0] and N_global = stats[2] (the local N, or its sum after the caller's all-reduce of stats: an exact integer in a double),
+ * forms inv_N = (float)(1.0 / N_global) in double arithmetic -- pc_unit_popcount_loss's host expression: with stats[2] = N_local the results
+ * equal that entry's bit for bit --, finishes popcount_sorted[0..N_local), scatters it to popcount_caller[dest] (optional, NULL) and runs
+ * the loss block over the N_local pairs with inv_N.  popcount_sorted, popcount_caller and g_popcount have Ncap elements; their tails
+ * [N_local, Ncap) := 0, so pc_unit_paint runs with N := Ncap.  loss_out[0] is this rank's part of the global mean plus the regulariser. */
+int pc_unit_popcount_loss_dev(const float* popdense, const int32_t* slot, const int32_t* unit_off, const int32_t* dest,
+                              const float* y_sorted, void* ws, const int32_t* n_dev, float* popcount_sorted, float* popcount_caller,
+                              const double* stats, const float* lam4, float scale_regularization, float lam_weak, int B, int H, int W,
+                              int Ncap, float* loss_out, float* g_popcount, float* g_scale_const, void* stream);
+
 /* ---- the native step executor for a multi-unit batch (csrc/step.hip) ----
  * pc_train_step for a batch whose samples list K units each: io as for pc_train_step, except that io->census_idx, io->y and
  * io->off_popcount are unused; the unit lists travel here.  Stage order: pc_unit_layout (on the stream whose chain ends in the mask) ->

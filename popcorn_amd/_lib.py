@@ -219,6 +219,9 @@ def lib():
         _lib.pc_unit_layout.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_int, C.c_int] + [C.c_void_p] * 6
         _lib.pc_unit_popcount_loss.argtypes = ([C.c_void_p] * 9 + [C.POINTER(C.c_float), C.c_float, C.c_float] + [C.c_int] * 4 +
                                                [C.c_void_p] * 4)
+        _lib.pc_unit_layout_dev.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_int] + [C.c_void_p] * 8
+        _lib.pc_unit_popcount_loss_dev.argtypes = ([C.c_void_p] * 10 + [C.POINTER(C.c_float), C.c_float, C.c_float] + [C.c_int] * 4 +
+                                                   [C.c_void_p] * 4)
         _lib.pc_train_step_units.argtypes = [C.c_void_p, C.POINTER(PcStepIo), C.POINTER(PcStepUnits), C.c_int, C.c_void_p]
     return _lib
 

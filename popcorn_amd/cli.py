@@ -95,6 +95,9 @@ def train_parser():
     p.add_argument("--native_units", action="store_true",
                    help="--units_per_crop steps through the native step executor (pc_train_step_units: one call per step, the same "
                         "bits as the per-launch engine); experimental, off by default")
+    p.add_argument("--device_units", action="store_true",
+                   help="--units_per_crop steps in the device-N form (counts, N and 1 / N read from device memory): allowed with --fixed_hw "
+                        "(replayed HIP graph) and under data parallelism; implies nothing without --units_per_crop")
     return p
 
 
@@ -246,8 +249,9 @@ class Trainer:
         seed_all(args.seed)
         collate = Population_Dataset_collate_fn
         if args.units_per_crop > 0:
-            if args.torch_optimizer or self.world > 1:
-                raise SystemExit("--units_per_crop trains with the fused eager step in a single process (no --torch_optimizer, no data parallelism)")
+            if args.torch_optimizer or (self.world > 1 and not args.device_units):
+                raise SystemExit("--units_per_crop trains with the fused eager step in a single process (no --torch_optimizer, no data "
+                                 "parallelism); --device_units lifts the second restriction and the eager one")
             from .data.units import SyntheticMultiUnitDataset, collate_units
             ds = SyntheticMultiUnitDataset(args.synthetic_regions, units=args.units_per_crop, min_hw=args.synthetic_hw_range[0],
                                            max_hw=args.synthetic_hw_range[1], seed=args.seed, fixed_hw=args.fixed_hw, ragged=True)
@@ -295,8 +299,10 @@ class Trainer:
             self.fused = FusedTrainStep(self.model, lr=args.learning_rate, weight_decay=args.weightdecay,
                                         gradient_clip=args.gradient_clip, loss=args.loss, lam=args.lam,
                                         scale_regularization=args.scale_regularization, lam_weak=args.lam_weak,
-                                        reducer=self.reducer, use_graph=args.fixed_hw is not None and args.units_per_crop == 0,
-                                        raw_norm=(tuple(range(6)), stats.MEAN6, stats.STD6), native_units=args.native_units)
+                                        reducer=self.reducer,
+                                        use_graph=args.fixed_hw is not None and (args.units_per_crop == 0 or args.device_units),
+                                        raw_norm=(tuple(range(6)), stats.MEAN6, stats.STD6), native_units=args.native_units,
+                                        device_units=args.device_units and args.units_per_crop > 0)
         if args.resume:
             self.resume(args.resume)
 
@@ -361,6 +367,13 @@ class Trainer:
             s = normalize_sample(sample, self.device, self.data_transform, nan_fill=a.nan_fill)
         if sample.get("census_n") is not None:             # multi-unit items (--units_per_crop): the valid units per row, host data
             s["census_n"] = sample["census_n"]
+            K = s["census_idx"].shape[1]
+            if a.device_units and a.fixed_hw is not None and K < a.units_per_crop:
+                # the collate pads to the batch's own maximum; the captured step is keyed by K: pad on to the data set's K, so that every
+                # batch (and, data parallel, every rank) replays one capture.  The padding is behind census_n: the step ignores it
+                pad = (0, a.units_per_crop - K)
+                s["census_idx"] = torch.nn.functional.pad(s["census_idx"], pad, value=-1)
+                s["y"] = torch.nn.functional.pad(s["y"], pad, value=0.0)
         dk = "raw" if "raw" in s else "input"
         num_pix = s[dk].shape[0] * s[dk].shape[2] * s[dk].shape[3]
         if self.world > 1 and a.fixed_hw is None:
@@ -380,11 +393,12 @@ class Trainer:
             # by the next log step does not copy them (two launches per step on the smallest regions)
             to_log = a.logstep_train - (self.info["iter"] % a.logstep_train)
             if to_log * s["y"].numel() <= 300 + s["y"].numel():
-                y = s["y"]
+                y, pc = s["y"], self.fused.last["popcount"]
                 if s.get("census_n") is not None:           # (B, K) padded -> the flat N of the step's popcount, (b, k) order
                     from .data.units import flat_valid
                     y = flat_valid(y, s["census_n"])
-                self._buffer_r2(self.fused.last["popcount"], y)
+                    pc = pc[:y.numel()]                     # (a device-N step's popcount has the capacity B * K: the first N count)
+                self._buffer_r2(pc, y)
             return loss
         from torch.nn.utils import clip_grad_norm_
         from .utils.losses import get_loss
@@ -469,6 +483,8 @@ class Trainer:
             # the fused step is fed one batch ahead through pinned memory and a copy stream (data/feed.py: RegionFeed); the torch-optimizer
             # recipe keeps the reference's synchronous loop
             feed = RegionFeed(self.loader, self.device) if self.fused is not None else self.loader
+            if self.fused is not None:
+                self.fused.capture_guard = feed.pause              # (the feed's producer thread keeps still while a step is captured)
             for i, sample in enumerate(feed):
                 loss = self.train_step(sample)
                 if loss is not None:

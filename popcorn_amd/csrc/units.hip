@@ -15,6 +15,9 @@
 //   pc_unit_layout         the sorted, flattened unit lists from the caller's padded (B, K) batch -- rows sorted in LDS, the host's valid
 //                          counts in the kernel arguments -- and the zeroed workspace of the sums: ONE launch
 //   pc_unit_popcount_loss  the accumulate launch of pc_unit_popcount, then one block: finish, scatter to the caller's order, loss
+// and, for steps that are replayed from a captured graph or run data parallel, the same two with N out of the host's hands:
+//   pc_unit_layout_dev         pc_unit_layout with the counts in device memory; outputs of capacity B K, every element written
+//   pc_unit_popcount_loss_dev  pc_unit_popcount_loss at that capacity; N and the (global) 1 / N read on the device
 //
 // Arithmetic of the sums.  A term q is split exactly into trunc(q) and its fraction; the integer parts and the fractions on a
 // 2^-PC_CENSUS_FIX_SHIFT grid (census_table.hip's grid) are summed as two 64-bit integers per unit.  Integer addition is associative, so
@@ -361,6 +364,118 @@ __global__ __launch_bounds__(UN_THREADS) void unit_layout_kernel(const UnitLayou
     }
 }
 
+// ---- the device-N forms: the valid counts, N and 1 / N come from device memory, every launch runs at the capacity Ncap = B * K ---------------
+// A captured step replays its kernel arguments, and a data-parallel rank knows only its own N: neither can carry N in a launch.  Here the
+// launches are shaped by (B, K) alone; what depends on the counts is read from memory that the loader (census_n) or the stats all-reduce
+// (the global N in stats[2]) rewrites between replays.
+struct UnitLayoutDevArgs {
+    const int64_t* census_idx; const float* y; const int32_t* census_n;      // census_n: DEVICE int32 [B]
+    int64_t* units; int32_t* unit_off; float* y_sorted; int32_t* dest;      // capacity Ncap each (unit_off: B + 1)
+    un_u64* acc_int; un_u64* acc_frac; int32_t* bad;                         // the population sum's workspace laid out by Ncap (NULL: not zeroed)
+    int32_t* n_dev; double* stats;                                           // N as int32; N as a double in stats[2] (NULL: not written)
+    int B, K, P;                                                             // P: K rounded up to a power of two
+};
+
+// unit_layout_kernel with the counts read from memory.  Workgroup b writes exactly K elements of every capacity-sized output: its nb valid
+// entries at [off, off + nb) and K - nb tail entries at N + (b K - off) + ..., the paddings of the rows in front of it -- together the B
+// workgroups cover [0, Ncap) once, whatever the counts are.  Every trip count is fixed by (B, K).
+__global__ __launch_bounds__(UN_THREADS) void unit_layout_dev_kernel(const UnitLayoutDevArgs a) {
+    __shared__ long long key[UL_MAX_K];
+    __shared__ int tag[UL_MAX_K];
+    __shared__ int cnt[UL_MAX_B];
+    const int t = threadIdx.x, b = blockIdx.x;
+    // the device cannot raise: a count outside [1, K] is clamped into it
+    for (int i = t; i < a.B; i += UN_THREADS) cnt[i] = min(max(a.census_n[i], 1), a.K);
+    __syncthreads();
+    int off = 0, N = 0;
+    for (int i = 0; i < a.B; ++i) {
+        const int c = cnt[i];                                     // (an LDS broadcast)
+        if (i < b) off += c;
+        N += c;
+    }
+    const int nb = cnt[b];
+    const int64_t* row = a.census_idx + (int64_t)b * a.K;
+    for (int i = t; i < a.P; i += UN_THREADS) {
+        const bool valid = i < nb;
+        key[i] = valid ? (long long)row[i] : 0x7fffffffffffffffll;
+        tag[i] = valid ? i : 65536 + i;
+    }
+    __syncthreads();
+    for (int k = 2; k <= a.P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = t; i < a.P; i += UN_THREADS) {
+                const int p = i ^ j;
+                if (p > i) {
+                    const long long ki = key[i], kp = key[p];
+                    const int ti = tag[i], tp = tag[p];
+                    const bool up = (i & k) == 0;
+                    if (up ? ul_less(kp, tp, ki, ti) : ul_less(ki, ti, kp, tp)) { key[i] = kp; key[p] = ki; tag[i] = tp; tag[p] = ti; }
+                }
+            }
+            __syncthreads();
+        }
+    if (t == 0) {
+        a.unit_off[b] = off;
+        if (b == a.B - 1) a.unit_off[a.B] = N;
+        if (b == 0) {
+            *a.n_dev = N;
+            if (a.stats) a.stats[2] = (double)N;
+        }
+    }
+    const int tail0 = N + b * a.K - off;                          // N + the paddings of rows 0 .. b - 1; tail0 + (K - nb) <= B K
+    for (int j = t; j < a.K; j += UN_THREADS) {
+        int n;
+        if (j < nb) {
+            n = off + j;
+            int src = tag[j] & 65535;
+            if (src >= nb) src = j;                               // (cannot happen; keeps every index in the row whatever the sort did)
+            a.units[n] = key[j];
+            a.y_sorted[n] = a.y[(int64_t)b * a.K + src];
+            a.dest[n] = off + src;
+        } else {
+            n = tail0 + (j - nb);
+            a.units[n] = 0x7fffffffffffffffll;
+            a.y_sorted[n] = 0.f;
+            a.dest[n] = -1;
+        }
+        if (a.acc_int) { a.acc_int[n] = 0; a.acc_frac[n] = 0; a.bad[n] = 0; }
+    }
+}
+
+// unit_finish_loss_kernel at capacity: N_local from n_dev, N_global from stats[2] (the local N, or its sum over the ranks after the stats
+// all-reduce: an exact integer in a double), inv_N = (float)(1.0 / N_global) -- the host's expression in pc_unit_popcount_loss, so one
+// process gets that entry's bits.  Tails [N_local, Ncap) of both popcount orders and of g_popcount := 0.
+__global__ __launch_bounds__(256) void unit_finish_loss_dev_kernel(const long long* __restrict__ acc_int, const long long* __restrict__ acc_frac,
+                                                                   const int32_t* __restrict__ bad, const int32_t* __restrict__ dest,
+                                                                   const int32_t* __restrict__ n_dev, float* popcount,
+                                                                   float* __restrict__ popcount_caller, const double* stats,
+                                                                   const pc_loss_args a) {
+    __shared__ double red[256];
+    const int Ncap = a.B;
+    const int N = min(max(*n_dev, 1), Ncap);
+    double Ng = stats[2];
+    if (!(Ng >= 1.0)) Ng = (double)N;                             // (never written / NaN: the local count; the device cannot raise)
+    for (int i = threadIdx.x; i < Ncap; i += 256) {
+        if (i < N) {
+            const float v = un_finish(acc_int[i], acc_frac[i], bad[i]);
+            popcount[i] = v;
+            if (popcount_caller) {
+                const int d = dest[i];
+                if ((unsigned)d < (unsigned)N) popcount_caller[d] = v;
+            }
+        } else {
+            popcount[i] = 0.f;
+            if (popcount_caller) popcount_caller[i] = 0.f;
+            a.g_popcount[i] = 0.f;
+        }
+    }
+    __syncthreads();
+    pc_loss_args l = a;
+    l.B = N;
+    l.inv_B = (float)(1.0 / Ng);
+    pc_loss_block(l, popcount, stats, red);
+}
+
 // ---- gradient paint ------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float un_pick(const float* g, int s, int N) { return (unsigned)s < (unsigned)N ? g[s] : 0.f; }
 
@@ -487,6 +602,66 @@ extern "C" int pc_unit_layout(const int64_t* census_idx, const float* y, const i
     a.P = 1;
     while (a.P < K) a.P <<= 1;
     hipLaunchKernelGGL(unit_layout_kernel, dim3(B), dim3(UN_THREADS), 0, (hipStream_t)stream, a);
+    PC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pc_unit_layout_dev(const int64_t* census_idx, const float* y, const int32_t* census_n_dev, int B, int K, int64_t* units,
+                                  int32_t* unit_off, float* y_sorted, int32_t* dest, void* ws, int32_t* n_dev, double* stats, void* stream) {
+    if (!census_idx || !y || !census_n_dev || !units || !unit_off || !y_sorted || !dest || !n_dev || B < 1 || K < 1) return PC_EINVAL;
+    if (K > UL_MAX_K || B > UL_MAX_B) return PC_ENOTSUP;
+    if ((reinterpret_cast<uintptr_t>(census_idx) | reinterpret_cast<uintptr_t>(units) | reinterpret_cast<uintptr_t>(stats)) & 7) return PC_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(y_sorted) | reinterpret_cast<uintptr_t>(unit_off) |
+         reinterpret_cast<uintptr_t>(dest) | reinterpret_cast<uintptr_t>(census_n_dev) | reinterpret_cast<uintptr_t>(n_dev)) & 3)
+        return PC_EINVAL;
+    if (reinterpret_cast<uintptr_t>(ws) & 15) return PC_EINVAL;
+    UnitLayoutDevArgs a{};
+    const int64_t Ncap = (int64_t)B * K;
+    a.census_idx = census_idx; a.y = y; a.census_n = census_n_dev;
+    a.units = units; a.unit_off = unit_off; a.y_sorted = y_sorted; a.dest = dest; a.n_dev = n_dev; a.stats = stats;
+    if (ws) {
+        a.acc_int = reinterpret_cast<un_u64*>(ws);
+        a.acc_frac = a.acc_int + Ncap;
+        a.bad = reinterpret_cast<int32_t*>(a.acc_frac + Ncap);
+    }
+    a.B = B; a.K = K;
+    a.P = 1;
+    while (a.P < K) a.P <<= 1;
+    hipLaunchKernelGGL(unit_layout_dev_kernel, dim3(B), dim3(UN_THREADS), 0, (hipStream_t)stream, a);
+    PC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int pc_unit_popcount_loss_dev(const float* popdense, const int32_t* slot, const int32_t* unit_off, const int32_t* dest,
+                                         const float* y_sorted, void* ws, const int32_t* n_dev, float* popcount_sorted,
+                                         float* popcount_caller, const double* stats, const float* lam4, float scale_regularization,
+                                         float lam_weak, int B, int H, int W, int Ncap, float* loss_out, float* g_popcount,
+                                         float* g_scale_const, void* stream) {
+    if (!popdense || !slot || !y_sorted || !ws || !n_dev || !popcount_sorted || !stats || !lam4 || !loss_out || !g_popcount || !g_scale_const)
+        return PC_EINVAL;
+    if (popcount_caller && !dest) return PC_EINVAL;
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || Ncap < 1 || (int64_t)H * W >= ((int64_t)1 << 27)) return PC_EINVAL;   // as pc_unit_popcount
+    if ((reinterpret_cast<uintptr_t>(ws) & 15) || ((reinterpret_cast<uintptr_t>(popdense) | reinterpret_cast<uintptr_t>(slot) |
+                                                    reinterpret_cast<uintptr_t>(n_dev)) & 3) || (reinterpret_cast<uintptr_t>(stats) & 7))
+        return PC_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    UnitSumArgs a{};
+    a.popdense = popdense; a.slot = slot; a.unit_off = unit_off;
+    a.acc_int = reinterpret_cast<un_u64*>(ws);
+    a.acc_frac = a.acc_int + Ncap;
+    a.bad = reinterpret_cast<int32_t*>(a.acc_frac + Ncap);
+    a.HW = H * W; a.N = Ncap;
+    a.chunks = (a.HW + UN_PX_PER_BLOCK - 1) / UN_PX_PER_BLOCK;
+    const int cap = 4 * UN_MAX_BLOCKS / B > 1 ? 4 * UN_MAX_BLOCKS / B : 1;
+    hipLaunchKernelGGL(unit_popcount_kernel, dim3(a.chunks < cap ? a.chunks : cap, B), dim3(UN_THREADS), 0, st, a);
+    PC_CHECK_LAUNCH();
+    pc_loss_args l{};
+    l.y = y_sorted;
+    for (int i = 0; i < 4; ++i) l.lam[i] = lam4[i];
+    l.sreg = scale_regularization; l.lam_weak = lam_weak; l.B = Ncap;     // (the capacity; N and inv_B are read on the device)
+    l.loss_out = loss_out; l.g_popcount = g_popcount; l.g_scale_const = g_scale_const;
+    hipLaunchKernelGGL(unit_finish_loss_dev_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<const long long*>(a.acc_int),
+                       reinterpret_cast<const long long*>(a.acc_frac), a.bad, dest, n_dev, popcount_sorted, popcount_caller, stats, l);
     PC_CHECK_LAUNCH();
     return 0;
 }

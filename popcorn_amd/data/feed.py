@@ -14,6 +14,7 @@ rate).  ``pick_copy_stream`` therefore MEASURES: a pinned copy on the candidate 
 (about max of the two) or serialises (about their sum); the first candidate that overlaps is kept."""
 from __future__ import annotations
 
+import threading
 import time
 
 import torch
@@ -150,7 +151,10 @@ class RegionFeed:
     (``pick_copy_stream``); the consumer waits on the copy's event and steps.  Region shapes never recur, so the device tensors come from
     torch's caching allocator (``record_stream`` keeps a block alive until the step that reads it has run).  Non-tensor items pass
     through.  Determinism: the FIRST batch is pulled on the caller's thread -- that is where a shuffling sampler draws its seed from the
-    global generator -- so the producer never touches the generators the augmentation coins and selection grids come from."""
+    global generator -- so the producer never touches the generators the augmentation coins and selection grids come from.
+    Graph capture: while a stream of the process captures, a pinned allocation, a device allocation or an event wait on ANY thread
+    invalidates the capture -- everything the producer does with the device happens under a gate, and ``pause()`` hands that gate to a
+    consumer that is about to capture (``FusedTrainStep.capture_guard``); the dataset access and the collate stay outside it."""
 
     TENSOR_KEYS = ("S2", "S1", "admin_mask", "y", "census_idx", "building_counts", "data_hw")
     DEPTH = 3                       # staged batches in flight (ring slots of pinned memory)
@@ -162,6 +166,12 @@ class RegionFeed:
         self._pin = [{} for _ in range(self.DEPTH)]      # per slot: key -> pinned staging tensor (grow-only)
         self._done = [None] * self.DEPTH                 # per slot: event behind the slot's last copy
         self._n = 0
+        self._gate = threading.Lock()
+
+    def pause(self):
+        """``with feed.pause():`` -- the producer thread issues no device or pinned-memory call inside the block (it finishes the batch
+        it is staging first, then waits)."""
+        return self._gate
 
     def __len__(self):
         return len(self.loader)
@@ -244,10 +254,14 @@ class RegionFeed:
                 batch = first
                 while batch is not None and not stop.is_set():
                     if direct:
-                        slot = self._slot()
-                        q.put(self._stage(collate_into([ds[i] for i in batch], self._alloc(slot)), cur, slot))
+                        items = [ds[i] for i in batch]
+                        with self._gate:
+                            slot = self._slot()
+                            staged = self._stage(collate_into(items, self._alloc(slot)), cur, slot)
                     else:
-                        q.put(self._stage(batch, cur))
+                        with self._gate:
+                            staged = self._stage(batch, cur)
+                    q.put(staged)                       # (outside the gate: a full queue must not block a consumer that wants it)
                     batch = pull()
                 q.put(None)
             except BaseException as ex:                 # surfaces in the consumer

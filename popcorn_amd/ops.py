@@ -678,6 +678,78 @@ def unit_popcount_loss(popdense, slot, lay, stats, lam4, scale_regularization, l
     return pc_sorted, pc_caller
 
 
+def unit_layout_dev(census_idx, y, census_n_dev, stats=None, ws=None):
+    """pc_unit_layout_dev: ``unit_layout_device`` with the counts on the DEVICE (``census_n_dev`` int32 [B]; a count outside [1, K] is
+    clamped into it -- the device cannot raise, callers validate on the host) and nothing sized by them: every result has the capacity
+    Ncap = B * K and is written completely by the one launch.  Returns a dict: units int64 [Ncap] (tail INT64_MAX), unit_off int32 [B + 1]
+    (unit_off[B] = N), y_sorted fp32 [Ncap] (tail 0), dest int32 [Ncap] (tail -1), ws (20 Ncap bytes zeroed: the sums' workspace laid out
+    by Ncap), n_dev int32 [1] = N, Ncap.  stats (optional): a float64 tensor of at least 3 elements, stats[2] := N.  K above
+    L.PC_UNIT_LAYOUT_MAX_K or B above L.PC_UNIT_LAYOUT_MAX_B raises (PC_ENOTSUP)."""
+    L.require_device(census_idx, y, census_n_dev, stats)
+    if census_idx.dim() != 2 or census_idx.dtype != torch.int64:
+        raise ValueError(f"unit_layout_dev: census_idx must be an int64 (B, K) tensor, got {census_idx.dtype} {tuple(census_idx.shape)}")
+    if y.dtype != torch.float32 or tuple(y.shape) != tuple(census_idx.shape):
+        raise ValueError(f"unit_layout_dev: y must be fp32 {tuple(census_idx.shape)} like census_idx, got {y.dtype} {tuple(y.shape)}")
+    B, K = census_idx.shape
+    if census_n_dev.dtype != torch.int32 or census_n_dev.numel() != B or not census_n_dev.is_contiguous():
+        raise ValueError(f"unit_layout_dev: census_n_dev must be a contiguous int32 [B = {B}] device tensor, got {census_n_dev.dtype} "
+                         f"{tuple(census_n_dev.shape)}")
+    if stats is not None and (stats.dtype != torch.float64 or stats.numel() < 3 or not stats.is_contiguous()):
+        raise ValueError("unit_layout_dev: stats must be a contiguous float64 tensor of at least 3 elements")
+    Ncap = B * K
+    if Ncap < 1:
+        raise ValueError("unit_layout_dev: B >= 1 and K >= 1")
+    dev = census_idx.device
+    census_idx, y = census_idx.contiguous(), y.contiguous()
+    units = torch.empty(Ncap, dtype=torch.int64, device=dev)
+    unit_off = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    y_sorted = torch.empty(Ncap, dtype=torch.float32, device=dev)
+    dest = torch.empty(Ncap, dtype=torch.int32, device=dev)
+    n_dev = torch.empty(1, dtype=torch.int32, device=dev)
+    need = L.lib().pc_unit_ws_bytes(Ncap)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif ws.dtype != torch.uint8 or ws.numel() < need or not ws.is_cuda or ws.data_ptr() % 16:
+        raise ValueError(f"unit_layout_dev: ws must be a 16-byte aligned uint8 device tensor of at least {need} bytes")
+    L.check(L.lib().pc_unit_layout_dev(L.ptr(census_idx), L.ptr(y), L.ptr(census_n_dev), B, K, L.ptr(units), L.ptr(unit_off),
+                                       L.ptr(y_sorted), L.ptr(dest), L.ptr(ws), L.ptr(n_dev), L.ptr(stats), L.stream_ptr()),
+            "pc_unit_layout_dev")
+    return {"units": units, "unit_off": unit_off, "Ncap": Ncap, "y_sorted": y_sorted, "dest": dest, "ws": ws, "n_dev": n_dev}
+
+
+def unit_popcount_loss_dev(popdense, slot, lay, stats, lam4, scale_regularization, lam_weak, loss_out, g_popcount, g_scale_const,
+                           out=None):
+    """pc_unit_popcount_loss_dev on a ``unit_layout_dev`` result: ``unit_popcount_loss`` at the capacity Ncap, with N read from
+    ``lay["n_dev"]`` and 1 / N formed on the device from stats[2] (``unit_layout_dev`` left the local N there; a data-parallel step
+    all-reduces ``stats`` in between).  Consumes the zeroed workspace (one call per layout).  g_popcount fp32 [Ncap], sorted order, tail
+    0.  out: (popcount_sorted, popcount_caller) to write into.  Returns (popcount in the sorted order, in the caller's (b, k) order),
+    Ncap elements each, the first N valid, the rest 0."""
+    L.require_device(popdense, slot, g_popcount, stats)
+    Ncap = int(lay["Ncap"])
+    if popdense.dim() != 3 or popdense.dtype != torch.float32 or slot.dtype != torch.int32 or slot.shape != popdense.shape:
+        raise ValueError("unit_popcount_loss_dev: fp32 popdense (B, H, W) and an int32 slot map of the same shape")
+    if g_popcount.dtype != torch.float32 or g_popcount.numel() != Ncap or not g_popcount.is_contiguous():
+        raise ValueError(f"unit_popcount_loss_dev: g_popcount must be a contiguous fp32 tensor of Ncap = {Ncap} elements")
+    if stats.dtype != torch.float64 or stats.numel() < 3 or not stats.is_contiguous():
+        raise ValueError("unit_popcount_loss_dev: stats must be a contiguous float64 tensor of at least 3 elements {Nsel, sum scale, N}")
+    popdense, slot = popdense.contiguous(), slot.contiguous()
+    B, H, W = popdense.shape
+    if lay["unit_off"].numel() != B + 1 or lay["ws"].numel() < L.lib().pc_unit_ws_bytes(Ncap):
+        raise ValueError("unit_popcount_loss_dev: the layout belongs to another batch")
+    if out is None:
+        out = (torch.empty(Ncap, dtype=torch.float32, device=popdense.device), torch.empty(Ncap, dtype=torch.float32, device=popdense.device))
+    pc_sorted, pc_caller = out
+    for t in out:
+        if t.dtype != torch.float32 or t.numel() != Ncap or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"unit_popcount_loss_dev: out must be two contiguous fp32 device tensors of Ncap = {Ncap} elements")
+    L.check(L.lib().pc_unit_popcount_loss_dev(L.ptr(popdense), L.ptr(slot), L.ptr(lay["unit_off"]), L.ptr(lay["dest"]),
+                                              L.ptr(lay["y_sorted"]), L.ptr(lay["ws"]), L.ptr(lay["n_dev"]), L.ptr(pc_sorted),
+                                              L.ptr(pc_caller), L.ptr(stats), (C.c_float * 4)(*lam4), C.c_float(scale_regularization),
+                                              C.c_float(lam_weak), B, H, W, Ncap, L.ptr(loss_out), L.ptr(g_popcount), L.ptr(g_scale_const),
+                                              L.stream_ptr()), "pc_unit_popcount_loss_dev")
+    return pc_sorted, pc_caller
+
+
 class UnitPopcount(torch.autograd.Function):
     """popcount[N] = ``unit_popcount(popdense, slot, N)``; backward: ``unit_paint``.  slot / unit_off get no gradient."""
 

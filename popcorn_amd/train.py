@@ -14,7 +14,9 @@ Multi-unit census supervision (opt-in; csrc/units.hip): a sample whose ``census_
 host-side ``census_n`` -- supervises every listed unit of each crop in one step: one crop, K popcounts, one loss over the N = sum(census_n)
 (b, k) pairs, one backward.  It computes what the one-unit step computes on the replicated batch.  Such a step runs eagerly through the
 per-launch engine -- or, with ``native_units=True``, through the native executor (pc_train_step_units: one C-ABI call, the same bits);
-graph mode and data parallelism raise for it (``FusedTrainStep.step``).
+graph mode and data parallelism raise for it (``FusedTrainStep.step``) -- unless the trainer was built with ``device_units=True``: the
+device-N step (pc_unit_layout_dev, pc_unit_popcount_loss_dev) runs every launch at the capacity B * K and reads the counts, N and 1 / N
+from device memory, so that one captured graph serves every N and the global N of a data-parallel step rides in the stats all-reduce.
 """
 from __future__ import annotations
 
@@ -159,7 +161,8 @@ HEAD_NO_DECAY = ("head.6.weight", "head.6.bias")        # run_train.py:82
 class FusedTrainStep:
     def __init__(self, model, lr=1e-4, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, gradient_clip=0.01,
                  loss=("log_l1_loss",), lam=(1.0,), scale_regularization=0.01, lam_weak=100.0,
-                 reducer: FlatReducer | None = None, use_graph=False, raw_norm=None, graph_cache_max=None, native_units=False):
+                 reducer: FlatReducer | None = None, use_graph=False, raw_norm=None, graph_cache_max=None, native_units=False,
+                 device_units=False):
         """raw_norm = (band6, mean6, std6): how a RAW tile (sample key "raw" instead of "input": (B, Craw, H, W) reflectances /
         backscatter) becomes the model input -- band selection (data/PopulationDataset.py:566-568) + apply_normalize
         (utils/utils.py:105-127); default: the reference's dataset statistics (popcorn_amd.data.stats).  With a raw sample the
@@ -168,7 +171,9 @@ class FusedTrainStep:
         private memory pool with every activation and gradient of its step; default 6 or POPCORN_GRAPH_CACHE_MAX.  A capture that
         runs out of memory drops ALL cached graphs (and their pools) and is retried once.
         native_units: multi-unit samples (2-D census_idx) go through the native executor (pc_train_step_units) where it takes them --
-        opt-in, experimental; off: the per-launch engine, as before.  The two compute the same bits."""
+        opt-in, experimental; off: the per-launch engine, as before.  The two compute the same bits.
+        device_units: multi-unit samples take the device-N step (``step``): eager, captured (``use_graph=True``) and with an active
+        data-parallel reducer; the native executor is not asked.  Off: as before, refusals included.  One-unit samples are unaffected."""
         from .data import stats as _stats
         self.raw_norm = raw_norm or (_stats.BAND6, _stats.MEAN6, _stats.STD6)
         self.model = model
@@ -221,7 +226,9 @@ class FusedTrainStep:
         # scale regulariser, whatever --scale_regularization says (round 4: the fused step used to add it)
         self.sreg, self.lam_weak = (scale_regularization if model.occupancymodel else 0.0), lam_weak
         self.reducer = reducer or FlatReducer()
-        self.stats = torch.zeros(2, device=dev, dtype=torch.float64)
+        # {Nsel, sum scale, N, reserved}: the first two as ever (the head / the loss launch write them); N = the pairs of a device-N multi-unit
+        # step (pc_unit_layout_dev writes the local count).  ONE tensor: the global N rides in the stats all-reduce the step already has
+        self.stats = torch.zeros(4, device=dev, dtype=torch.float64)
         self.loss_out = torch.zeros(2, device=dev, dtype=torch.float32)
         self.g_scale_const = torch.zeros(1, device=dev, dtype=torch.float32)
         self.norm = torch.zeros(1, device=dev, dtype=torch.float32)
@@ -239,6 +246,13 @@ class FusedTrainStep:
         self.native_steps = 0           # eager steps that went through pc_train_step (tests / tools read it)
         self.native_units = bool(native_units)
         self.native_unit_steps = 0      # multi-unit steps that went through pc_train_step_units (native_steps counts one-unit steps only)
+        self.device_units = bool(device_units)
+        self.device_unit_steps = 0      # multi-unit steps that took the device-N form (eager or replayed)
+        self.captures = 0               # graph captures so far (tests / tools read it)
+        self._cn_ring, self._cn_next = [], 0            # pinned host slots for census_n (as the selection's ring)
+        # a callable returning a context manager that a capture runs inside (None: nothing): a loader whose producer thread allocates
+        # pinned or device memory hands in its pause here (data/feed.py: RegionFeed.pause) -- such a call invalidates an open capture
+        self.capture_guard = None
 
     def __del__(self):
         nat = getattr(self, "_native", None)
@@ -356,8 +370,8 @@ class FusedTrainStep:
         m = self.model
         if not NATIVE_STEP or m.precision != "fp32" or not (m.S1 and m.S2) or not m.occupancymodel:
             return False
-        if _is_multi_unit(sample) and not self.native_units:
-            return False               # opt-in (pc_train_step_units); pc_train_step supervises one unit per sample
+        if _is_multi_unit(sample) and (self.device_units or not self.native_units):
+            return False               # opt-in (pc_train_step_units); pc_train_step supervises one unit per sample.  device_units: not asked
         if not (E.PADDED_INPUT and E.COMPOSED_UP and E.FUSED_LEVEL2 and E.FUSED_CONV_BWD and DEFER_HEAD_REDUCE):
             return False               # an A/B switch of the per-launch engine is off its default: that engine is what is being asked for
         if (not m.sentinelbuildings) and sample.get("building_counts") is not None:
@@ -540,7 +554,9 @@ class FusedTrainStep:
         eng_u, eng_b = m.engines()
         # multi-unit supervision: the flattened unit lists; the mask is then ops.unit_mask on the building score and the head runs on the
         # union mask without a region (the N region sums follow it: ops.unit_popcount)
-        lay = ops.unit_layout(s["census_idx"], s.get("census_n")) if _is_multi_unit(s) else None
+        lay = None
+        if _is_multi_unit(s):
+            lay = self._layout_dev(s) if self._device_n(s) else ops.unit_layout(s["census_idx"], s.get("census_n"))
         form, data = _data_form(s)
         B, _, H, W = data[0].shape
         pads = pt, pb, pl, pr = pad_geometry(H, W, False)
@@ -625,7 +641,14 @@ class FusedTrainStep:
                                                      nsel_counts=c.counts, pack_both=True,
                                                      defer_reduce=one and not self.reducer.active)
         self.last = {"popcount": popcount, "popdensemap": popdense, "scale_map": scale_map, "mask": c.mask}
-        if not one:
+        if not one and "n_dev" in c.lay:
+            # device-N: the sums belong to the loss launch pair of ``_backward`` (after the stats all-reduce); their outputs exist from here
+            # on, so that ``last`` names the tensors a replayed graph writes
+            n = c.lay["Ncap"]
+            c.popdense = popdense
+            c.pc_sorted = torch.empty(n, device=self.device, dtype=torch.float32)
+            self.last.update(popcount=torch.empty(n, device=self.device, dtype=torch.float32), slot=c.slot, unit_n=c.lay["n_dev"])
+        elif not one:
             c.pc_sorted = ops.unit_popcount(popdense, c.slot, c.lay["N"], c.lay["unit_off"])
             self.last.update(popcount=c.pc_sorted.index_select(0, c.lay["to_caller"]), slot=c.slot)
 
@@ -634,7 +657,7 @@ class FusedTrainStep:
         (pt, pl), (B, H, W) = c.pads, c.shape
         g_pc = g_pd = admin = census = None
         if c.lay is not None:
-            g_pd = self._unit_loss(s, c)
+            g_pd = self._unit_loss_dev(c) if "n_dev" in c.lay else self._unit_loss(s, c)
         else:
             admin, census = s["admin_mask"], s["census_idx"]
             g_pc = torch.empty(B, device=self.device, dtype=torch.float32)
@@ -674,6 +697,51 @@ class FusedTrainStep:
         ops.loss_fwd_bwd(c.pc_sorted, y_sorted, self.stats, self.lam4, self.sreg, self.lam_weak, 1.0 / N, self.loss_out, g_pc,
                          self.g_scale_const)
         return ops.unit_paint(g_pc, c.slot)
+
+    def _device_n(self, s):
+        """A multi-unit sample takes the device-N form: the trainer's switch, and ``census_n`` already on the device (``step`` /
+        ``_graph_step`` put it there after the host's validation)."""
+        return self.device_units and torch.is_tensor(s.get("census_n")) and s["census_n"].is_cuda
+
+    def _layout_dev(self, s):
+        """The device-N layout (ops.unit_layout_dev): capacity B * K, the counts read from the device tensor ``census_n``, the local N
+        left in stats[2] for the stats all-reduce."""
+        cidx, y = s["census_idx"], s["y"]
+        if tuple(y.shape) != tuple(cidx.shape):
+            raise ValueError(f"y must be (B, K) like census_idx {tuple(cidx.shape)}, got {tuple(y.shape)}")
+        return ops.unit_layout_dev(cidx, y.float(), s["census_n"], stats=self.stats)
+
+    def _unit_loss_dev(self, c):
+        """``_unit_loss`` at capacity: sums, finish, scatter and loss in two launches with N and 1 / N (global, after the stats
+        all-reduce) read on the device; g_popcount's tail is 0, so the paint runs with N := Ncap."""
+        g_pc = torch.empty(c.lay["Ncap"], device=self.device, dtype=torch.float32)
+        ops.unit_popcount_loss_dev(c.popdense, c.slot, c.lay, self.stats, self.lam4, self.sreg, self.lam_weak, self.loss_out, g_pc,
+                                   self.g_scale_const, out=(c.pc_sorted, self.last["popcount"]))
+        return ops.unit_paint(g_pc, c.slot)
+
+    def _counts_to_device(self, counts, dst=None):
+        """The host's valid counts -> a device int32 [B] tensor through a ring of pinned slots (``_sel_to_device``'s scheme: no pageable
+        copy, no host synchronisation)."""
+        n = len(counts)
+        if not self._cn_ring or self._cn_ring[0][0].numel() < n:
+            self._cn_ring = [(torch.empty(max(n, L.PC_UNIT_LAYOUT_MAX_B), dtype=torch.int32).pin_memory(), torch.cuda.Event())
+                             for _ in range(8)]
+            self._cn_next = 0
+            for _, ev in self._cn_ring:
+                ev.record()
+        buf, ev = self._cn_ring[self._cn_next]
+        self._cn_next = (self._cn_next + 1) % len(self._cn_ring)
+        ev.synchronize()
+        buf[:n].copy_(torch.tensor(counts, dtype=torch.int32))
+        if dst is None:
+            dst = torch.empty(n, dtype=torch.int32, device=self.device)
+        dst.copy_(buf[:n], non_blocking=True)
+        ev.record()
+        return dst
+
+    @staticmethod
+    def _units_capped(B, K):
+        return K > L.PC_UNIT_LAYOUT_MAX_K or B > L.PC_UNIT_LAYOUT_MAX_B
 
     def _sections(self, st, sel, enc_ng, unet_ng, collectives=True):
         """The step: forward -> [all-reduce {Nsel, sum scale}] -> backward -> [all-reduce the flat gradient] -> update.  The reducer's calls
@@ -739,19 +807,40 @@ class FusedTrainStep:
         eagerly through the per-launch engine (``native_steps`` does not count it) or, with ``native_units=True``, through
         pc_train_step_units (counted in ``native_unit_steps``; what that entry declines -- K or B beyond its caps -- falls back to the
         per-launch engine within the step).  Out of scope, and refused: ``use_graph=True`` raises ValueError, an active data-parallel
-        reducer raises NotImplementedError."""
+        reducer raises NotImplementedError.
+
+        With ``device_units=True`` a multi-unit sample takes the device-N step instead -- eagerly, under ``use_graph=True`` (one capture per
+        (B, K, H, W) serves every N, id list and y) and with an active reducer (the global N rides in the stats all-reduce; each rank's
+        loss_out[0] is its part of the global mean plus the regulariser).  ``census_n`` stays host data and is validated here (a count
+        outside [1, K] raises ValueError before anything is enqueued); it reaches the device through a pinned ring and sizes nothing:
+        ``last["popcount"]`` has B * K elements, the first N in (b, k) order, the rest 0, and ``last["unit_n"]`` is N as a device int32.
+        K or B beyond pc_unit_layout's caps: ValueError under a graph or a reducer (no fallback there), the host-N step otherwise."""
         dkey = data_keys(sample)[0]
         B, _, H, W = sample[dkey].shape
+        counts = None
         if _is_multi_unit(sample):
-            if self.use_graph:
-                raise ValueError("multi-unit samples (2-D census_idx) run eagerly: build the FusedTrainStep with use_graph=False")
-            if self.reducer.active:
-                raise NotImplementedError("multi-unit samples (2-D census_idx) are not supported with a data-parallel reducer")
+            K = sample["census_idx"].shape[1]
+            dev_n = self.device_units
+            if dev_n and self._units_capped(B, K):
+                if self.use_graph or self.reducer.active:
+                    raise ValueError(f"device_units: (B, K) = {(B, K)} is beyond the layout kernel's caps ({L.PC_UNIT_LAYOUT_MAX_B}, "
+                                     f"{L.PC_UNIT_LAYOUT_MAX_K}); a captured or data-parallel step has no fallback")
+                dev_n = False                                      # eager, single process: the host-N step takes any K
+            if not dev_n:
+                if self.use_graph:
+                    raise ValueError("multi-unit samples (2-D census_idx) run eagerly: build the FusedTrainStep with use_graph=False")
+                if self.reducer.active:
+                    raise NotImplementedError("multi-unit samples (2-D census_idx) are not supported with a data-parallel reducer")
+            elif not (self.use_graph and self._static_counts(sample)):
+                counts = ops._unit_counts(sample.get("census_n"), B, K)      # (raises before anything is enqueued)
         sel_host = self._draw_selection(H, W)
         if self.use_graph:
-            return self._graph_step(sample, sel_host, encoder_no_grad, unet_no_grad)
+            return self._graph_step(sample, sel_host, encoder_no_grad, unet_no_grad, counts)
         s = {k: (v.contiguous() if torch.is_tensor(v) else v) for k, v in sample.items() if not k.startswith("_")}
         s["admin_mask"] = s["admin_mask"].float()
+        if counts is not None:
+            s["census_n"] = self._counts_to_device(counts)         # from here on the step reads the counts on the device only
+            self.device_unit_steps += 1
         with L.precision(self.model.precision), L.stream_scope():      # (one stream lookup for the step's ~40 launches)
             done = False
             if self._native_ok(s):
@@ -765,20 +854,30 @@ class FusedTrainStep:
                 self._sections(s, self._sel_to_device(sel_host), encoder_no_grad, unet_no_grad)
         return self.loss_out
 
-    def _graph_step(self, sample, sel_host, encoder_no_grad, unet_no_grad):
+    def _static_counts(self, sample):
+        """``census_n`` of the sample IS the device tensor of one of the loader's static sets (``static_buffers(units=K)``), filled in
+        place: nothing to validate on the host (the layout kernel clamps), nothing to copy."""
+        cn = sample.get("census_n")
+        return torch.is_tensor(cn) and cn.is_cuda and any(d.get("census_n") is cn for d in (self._static or {}).values())
+
+    def _graph_step(self, sample, sel_host, encoder_no_grad, unet_no_grad, counts=None):
         dks = data_keys(sample)
         dkey = dks[0]
         # "_slot": which of the loader's static sets this is (static_buffers(slot=...)): every set has its own captured graph, so
-        # a double-buffering loader replays graph A on set A while the copy stream fills set B -- no device-to-device copies
+        # a double-buffering loader replays graph A on set A while the copy stream fills set B -- no device-to-device copies.
+        # K: the units per crop of a device-N multi-unit step (0: one unit per sample) -- the capacity B * K shapes the launches
+        multi = _is_multi_unit(sample)
         key = (dkey, tuple(sample[dkey].shape), encoder_no_grad, unet_no_grad, self.model.precision, sample.get("_slot", 0),
+               sample["census_idx"].shape[1] if multi else 0,
                (not self.model.sentinelbuildings) and sample.get("building_counts") is not None)
         if self._graphs is None or self._graphs[0] != key:
             if key in self._graph_cache:
                 self._graphs, self.last = self._graph_cache.pop(key)      # (re-inserted below: most recently used last)
             else:
-                with L.precision(self.model.precision):      # the mode is read when a launch is enqueued = captured
+                guard = self.capture_guard() if self.capture_guard is not None else contextlib.nullcontext()
+                with guard, L.precision(self.model.precision):      # the mode is read when a launch is enqueued = captured
                     try:
-                        self._capture(sample, sel_host, key)
+                        self._capture(sample, sel_host, key, counts)
                     except RuntimeError as e:
                         if not _is_oom(e):
                             raise
@@ -788,7 +887,7 @@ class FusedTrainStep:
                         self._graph_cache.clear()
                         torch.cuda.synchronize()
                         torch.cuda.empty_cache()
-                        self._capture(sample, sel_host, key)
+                        self._capture(sample, sel_host, key, counts)
             self._graph_cache[key] = (self._graphs, self.last)
             while len(self._graph_cache) > self._graph_cache_max:
                 self._graph_cache.pop(next(iter(self._graph_cache)))
@@ -797,6 +896,10 @@ class FusedTrainStep:
         for k in dks + ("admin_mask", "census_idx", "y") + extra:
             if sample[k] is not st[k]:            # a loader that fills static_buffers() in place skips the copy
                 st[k].copy_(sample[k], non_blocking=True)
+        if multi:
+            if counts is not None:                # (None: the loader filled the static set's census_n in place)
+                self._counts_to_device(counts, st["census_n"])
+            self.device_unit_steps += 1
         self._sel_to_device(sel_host, sel)
         graphs[0].replay()
         if len(graphs) > 1:                       # (one graph: single process, or both collectives captured inside it (RCCL))
@@ -806,25 +909,65 @@ class FusedTrainStep:
             graphs[2].replay()
         return self.loss_out
 
-    def static_buffers(self, B, H, W, C=6, raw_channels=None, slot=0, split=False, building=False):
+    @staticmethod
+    def packed_layout(B, H, W, units=0):
+        """The ``_packed`` byte buffer of ``static_buffers``: ({name: (byte offset, dtype, shape)}, total bytes).  units = 0: admin_mask
+        f32 (B, H, W) | y f32 [B] | census_idx i64 [B], each 16-byte aligned -- the layout of every one-unit set so far.  units = K >= 1
+        (multi-unit, device-N): y f32 (B, K) and census_idx i64 (B, K) in their places, then census_n i32 [B] behind them."""
+        K = int(units)
+        if K < 0:
+            raise ValueError("units >= 0")
+        al = lambda n: -(-n // 16) * 16                            # noqa: E731
+        per = max(K, 1)
+        shape = (B, K) if K else (B,)
+        o_y = al(B * H * W * 4) if K else B * H * W * 4            # (units = 0: byte for byte the layout ``pack_small`` has always written)
+        o_ci = o_y + al(B * per * 4)
+        lay = {"admin_mask": (0, torch.float32, (B, H, W)), "y": (o_y, torch.float32, shape), "census_idx": (o_ci, torch.int64, shape)}
+        total = o_ci + B * per * 8
+        if K:
+            o_cn = o_ci + al(B * K * 8)
+            lay["census_n"] = (o_cn, torch.int32, (B,))
+            total = o_cn + B * 4
+        return lay, total
+
+    @staticmethod
+    def _packed_views(packed, lay):
+        out = {}
+        for name, (off, dt, shape) in lay.items():
+            n = 1
+            for d in shape:
+                n *= d
+            out[name] = packed[off:off + n * torch.empty((), dtype=dt).element_size()].view(dt).view(shape)
+        return out
+
+    def static_buffers(self, B, H, W, C=6, raw_channels=None, slot=0, split=False, building=False, units=0):
         """The device tensors the captured graph reads {input, admin_mask (float ids), census_idx, y}.  A data pipeline
         that writes its batch straight into them (e.g. ``ops.select_normalize(raw, ..., out=buf["input"])``) and passes
         this very dict to ``step`` saves the per-step input copies.  raw_channels: the data tensor is the RAW tile
         {raw (B, raw_channels, H, W)} instead of the normalised input (the graph then starts with the one-pass ingest).
         slot: independent sets for a double-buffering loader (each is captured into its own graph: H2D copies go straight into the
-        idle set on a copy stream, guarded by two events, and `step(set)` replays that set's graph)."""
+        idle set on a copy stream, guarded by two events, and `step(set)` replays that set's graph).
+        units = K >= 1: the set of a multi-unit step (``device_units=True``): census_idx (B, K) int64, y (B, K) and census_n int32 [B]
+        (1 everywhere until the loader writes it), all in the packed buffer (``packed_layout``).  K or B beyond the layout kernel's caps
+        raises ValueError (a graph has no fallback)."""
+        if units and self._units_capped(B, int(units)):
+            raise ValueError(f"static_buffers: (B, units) = {(B, units)} is beyond the layout kernel's caps ({L.PC_UNIT_LAYOUT_MAX_B}, "
+                             f"{L.PC_UNIT_LAYOUT_MAX_K})")
         dkey = "raw_s2" if split else ("input" if raw_channels is None else "raw")      # split: {raw_s2 uint16 (B,4,H,W), raw_s1 (B,2,H,W)}
         C = 4 if split else (C if raw_channels is None else raw_channels)
         if self._static is None:
             self._static = {}
-        skey = (dkey, C, slot, bool(building))     # (a new B / H / W replaces the set of that kind: bounded memory with varying tile sizes)
+        skey = (dkey, C, slot, bool(building)) + ((int(units),) if units else ())     # (a new B / H / W replaces the set of that kind: bounded memory with varying tile sizes)
         cur = self._static.get(skey)
         if cur is None or tuple(cur[dkey].shape) != (B, C, H, W):
             dev = self.device
-            # the three small tensors are views of ONE packed byte buffer ("_packed": admin_mask f32 | y f32 | census_idx i64, each
-            # 16-byte aligned): a loader that stages a batch elsewhere moves them with a single device copy
-            n_am, n_y = B * H * W * 4, -(-B * 4 // 16) * 16
-            packed = torch.zeros(n_am + n_y + B * 8, dtype=torch.uint8, device=dev)
+            # the small tensors are views of ONE packed byte buffer ("_packed": admin_mask f32 | y f32 | census_idx i64 [| census_n i32],
+            # each 16-byte aligned): a loader that stages a batch elsewhere moves them with a single device copy
+            lay, total = self.packed_layout(B, H, W, units)
+            packed = torch.zeros(total, dtype=torch.uint8, device=dev)
+            small = self._packed_views(packed, lay)
+            if units:
+                small["census_n"].fill_(1)
             if split:
                 # both tensors are views of ONE byte buffer ("_rawpacked": uint16 S2 | fp32 S1, 16-byte aligned): one H2D copy per batch
                 n2 = -(-B * 4 * H * W * 2 // 16) * 16
@@ -835,10 +978,7 @@ class FusedTrainStep:
                 data = {dkey: torch.zeros(B, C, H, W, device=dev)}
             if building:
                 data["building_counts"] = torch.zeros(B, 1, H, W, device=dev)
-            cur = self._static[skey] = {**data, "_slot": slot,
-                                        "admin_mask": packed[:n_am].view(torch.float32).view(B, H, W),
-                                        "y": packed[n_am:n_am + B * 4].view(torch.float32),
-                                        "census_idx": packed[n_am + n_y:].view(torch.int64), "_packed": packed}
+            cur = self._static[skey] = {**data, "_slot": slot, **small, "_packed": packed}
         return cur
 
     @staticmethod
@@ -851,8 +991,19 @@ class FusedTrainStep:
         return out
 
     @staticmethod
-    def pack_small(admin_mask, y, census_idx):
-        """Host-side counterpart of the ``_packed`` layout of ``static_buffers`` (one byte tensor)."""
+    def pack_small(admin_mask, y, census_idx, census_n=None):
+        """Host-side counterpart of the ``_packed`` layout of ``static_buffers`` (one byte tensor).  A 2-D census_idx (B, K) with
+        ``census_n`` (B counts): the ``units=K`` layout."""
+        if census_idx.dim() == 2:
+            B, K = census_idx.shape
+            lay, total = FusedTrainStep.packed_layout(B, admin_mask.shape[-2], admin_mask.shape[-1], K)
+            out = torch.zeros(total, dtype=torch.uint8)
+            v = FusedTrainStep._packed_views(out, lay)
+            v["admin_mask"].copy_(admin_mask.float().reshape(v["admin_mask"].shape))
+            v["y"].copy_(y.float().reshape(B, K))
+            v["census_idx"].copy_(census_idx.to(torch.int64))
+            v["census_n"].copy_(torch.as_tensor([K] * B if census_n is None else census_n, dtype=torch.int32).reshape(B))
+            return out
         B = y.numel()
         n_am, n_y = admin_mask.numel() * 4, -(-B * 4 // 16) * 16
         out = torch.zeros(n_am + n_y + B * 8, dtype=torch.uint8)
@@ -861,14 +1012,25 @@ class FusedTrainStep:
         out[n_am + n_y:].view(torch.int64).copy_(census_idx.to(torch.int64).reshape(-1))
         return out
 
-    def _capture(self, sample, sel_host, key):
+    def _capture(self, sample, sel_host, key, counts=None):
         dkey, _, enc_ng, unet_ng = key[:4]
-        mine = [d for d in (self._static or {}).values() if all(sample.get(k) is d[k] for k in d)]
+        # (census_n: host data in the public interface -- a loader may fill a static set in place and still pass its counts as a list)
+        mine = [d for d in (self._static or {}).values() if all(sample.get(k) is d[k] for k in d if k != "census_n")]
         if mine:
             st = dict(mine[0])
         else:
             st = {k: sample[k].detach().clone().contiguous() for k in data_keys(sample) + ("admin_mask", "census_idx", "y")}
             st["admin_mask"] = st["admin_mask"].float()
+        if _is_multi_unit(sample):
+            # the device-N step: y as fp32 (B, K); the counts in a static int32 [B] tensor that ``_graph_step`` rewrites before every replay
+            st["y"] = st["y"].float()
+            if tuple(st["y"].shape) != tuple(st["census_idx"].shape) or st["census_idx"].dtype != torch.int64:
+                raise ValueError(f"census_idx must be int64 (B, K) and y (B, K) alike, got {st['census_idx'].dtype} "
+                                 f"{tuple(st['census_idx'].shape)} and {tuple(st['y'].shape)}")
+            if st.get("census_n") is None or not (torch.is_tensor(st["census_n"]) and st["census_n"].is_cuda):
+                st["census_n"] = torch.ones(st["census_idx"].shape[0], dtype=torch.int32, device=self.device)
+            if counts is not None:
+                self._counts_to_device(counts, st["census_n"])
         if key[-1] and "building_counts" not in st:
             # a sample that brings its own building layer (sentinelbuildings = False models, popcorn.py:113-114; key[-1]) -- also with a
             # static set built without ``building=True``: the layer is an INPUT of the captured step -- it gets its own static tensor, which
@@ -927,3 +1089,4 @@ class FusedTrainStep:
                 self._update(enc_ng, unet_ng)
             graphs = [g0, g1, g2]
         self._graphs = (key, st, sel, graphs)
+        self.captures += 1
