@@ -865,6 +865,33 @@ typedef struct pc_step_units {
 } pc_step_units;
 int pc_train_step_units(void* handle, pc_step_io* io, pc_step_units* u, int phases, void* stream);
 
+/* ---- region-resident training data (csrc/region.hip) ----
+ * The reference's weaksup items are crops of a country's rasters around one census unit (data/PopulationDataset.py:403-458,624-649) and its
+ * preprocessing makes the units' bounding boxes and pixel counts with one pass per unit (utils/02_preprocess_rwa_shapefile.py:142-161).
+ *
+ * pc_region_units: boundary = DEVICE int32 (h, w), h * w < 2^31.  table = DEVICE int32 [num_ids][5] = {xmin, xmax, ymin, ymax, count} in the
+ * reference's convention -- x indexes rows, y indexes columns, xmax / ymax exclusive, five zeros for a unit without pixels.  Ids outside
+ * [0, num_ids), negative ones included, contribute nothing; *stray (DEVICE int64) receives their pixel count.  Every element of table and
+ * *stray is written.  ONE pass over the raster between an init and a finish launch over the table; integer min / max / add only, so the
+ * table holds the same bits for any launch geometry.  16-byte loads when w % 4 == 0 and the raster is 16-byte aligned, scalar loads
+ * otherwise.  max_blocks <= 0: the library's launch geometry; > 0: at most that many workgroups (tests of the geometry). */
+int pc_region_units(const int32_t* boundary, int h, int w, int num_ids, int32_t* table, int64_t* stray, int max_blocks, void* stream);
+/* pc_region_gather: the batch of B crops of the resident rasters, as the reference's collate would assemble it (PopulationDataset.py:885-958).
+ *   s2        DEVICE (S, C2, h, w), fp32 or (s2_u16 != 0) uint16 digital numbers        s1  DEVICE fp32 (S, C1, h, w)
+ *   boundary  DEVICE int32 (h, w)
+ *   band_sel  HOST int32 [6]: the source band (0-based) of S2 output channels 0 .. 3 and of S1 output channels 0 .. 1
+ *   crops     HOST int32 [B][5] = {x0, x1, y0, y1, season}: rows [x0, x1), columns [y0, y1) of season `season`
+ *   s2_out (B, 4, Hm, Wm), s1_out (B, 2, Hm, Wm), admin_out (B, Hm, Wm) = (float)id: DEVICE fp32; data_hw DEVICE int32 (B, 2) = {x1 - x0, y1 - y0}
+ * Every element of every output is written; outside a crop's extent (bottom, right) the padding is 0 / 0 / -1.  fp32 sources are copied
+ * bit for bit (a NaN keeps its payload); uint16 converts exactly.  A crop that is empty, leaves the raster, exceeds (Hm, Wm) or names a season
+ * >= S, a band outside its source, h * w or Hm * Wm >= 2^31: PC_EINVAL before anything is enqueued.  The crops travel in the kernel
+ * arguments (no copy, no synchronisation): one launch per PC_REGION_GATHER_MAX_B crops.  16-byte stores when Wm % 4 == 0 and the outputs are
+ * 16-byte aligned (loads at the sources' natural 4- / 2-byte alignment: crop origins are arbitrary), element by element otherwise. */
+#define PC_REGION_GATHER_MAX_B 128
+int pc_region_gather(const void* s2, int s2_u16, const float* s1, const int32_t* boundary, int S, int C2, int C1, int h, int w,
+                     const int32_t* band_sel, const int32_t* crops, int B, int Hm, int Wm, float* s2_out, float* s1_out, float* admin_out,
+                     int32_t* data_hw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -161,6 +161,7 @@ class PcStepUnits(C.Structure):
 
 
 PC_UNIT_LAYOUT_MAX_K, PC_UNIT_LAYOUT_MAX_B = 1024, 256
+PC_REGION_GATHER_MAX_B = 128          # crops per pc_region_gather launch (the crop list travels in the kernel arguments)
 
 
 class PopcornHipError(RuntimeError):
@@ -223,6 +224,9 @@ def lib():
         _lib.pc_unit_popcount_loss_dev.argtypes = ([C.c_void_p] * 10 + [C.POINTER(C.c_float), C.c_float, C.c_float] + [C.c_int] * 4 +
                                                    [C.c_void_p] * 4)
         _lib.pc_train_step_units.argtypes = [C.c_void_p, C.POINTER(PcStepIo), C.POINTER(PcStepUnits), C.c_int, C.c_void_p]
+        _lib.pc_region_units.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        _lib.pc_region_gather.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
+                                          [C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_int] * 3 + [C.c_void_p] * 5)
     return _lib
 
 

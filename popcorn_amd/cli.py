@@ -98,6 +98,15 @@ def train_parser():
     p.add_argument("--device_units", action="store_true",
                    help="--units_per_crop steps in the device-N form (counts, N and 1 / N read from device memory): allowed with --fixed_hw "
                         "(replayed HIP graph) and under data parallelism; implies nothing without --units_per_crop")
+    p.add_argument("--resident_region", type=int, nargs=2, default=None, metavar=("H", "W"),
+                   help="region-resident training: a synthetic H x W raw raster stays on the device and every batch of census-unit crops "
+                        "is one gather launch (data/region.py); one unit per crop, or --units_per_crop K complete units per crop")
+    p.add_argument("--resident_units", type=int, default=400, help="--resident_region: census units of the synthetic raster")
+    p.add_argument("--max_weak_pix", type=int, default=10_000_000,
+                   help="--resident_region: census units with at least this many pixels are dropped (the reference's max_pix)")
+    p.add_argument("--max_pix_box", type=int, default=12_000_000,
+                   help="--resident_region: units whose bounding box has at least this many pixels are dropped; the pixel budget of a "
+                        "multi-unit crop (the reference's max_pix_box)")
     return p
 
 
@@ -248,6 +257,9 @@ class Trainer:
                              "data-parallel runs use the fused step (drop the flag)")
         seed_all(args.seed)
         collate = Population_Dataset_collate_fn
+        self._resident_feed = None
+        if args.resident_region is not None:
+            self._init_resident_region()
         if args.units_per_crop > 0:
             if args.torch_optimizer or (self.world > 1 and not args.device_units):
                 raise SystemExit("--units_per_crop trains with the fused eager step in a single process (no --torch_optimizer, no data "
@@ -305,6 +317,31 @@ class Trainer:
                                         device_units=args.device_units and args.units_per_crop > 0)
         if args.resume:
             self.resume(args.resume)
+
+    def _init_resident_region(self):
+        """--resident_region: the training data is a synthetic raw raster kept on the device, planned into census-unit crops and fed by one
+        gather launch per batch (data/region.py) in place of loader -> collate -> pinned staging -> copy stream."""
+        a = self.args
+        if a.torch_optimizer:
+            raise SystemExit("--resident_region feeds device batches to the fused step: the --torch_optimizer recipe keeps the host loader")
+        if a.fixed_hw is not None:
+            raise SystemExit("--resident_region cuts census-unit crops of variable size: it cannot be combined with --fixed_hw")
+        if self.world > 1:
+            raise SystemExit("--resident_region runs in a single process: sharding a crop plan over data-parallel ranks is not part of it")
+        from .data.region import ResidentRegion, ResidentRegionFeed, plan_multi_unit, plan_one_unit
+        data = SyntheticTestRaster(a.resident_region[0], a.resident_region[1], seasons=1, n_regions=a.resident_units, seed=a.seed + 20,
+                                   device=self.device, raw=True, nan_clouds=a.nan_clouds)
+        self.region = ResidentRegion.from_synthetic(data)
+        kw = dict(max_pix=a.max_weak_pix, max_pix_box=a.max_pix_box)
+        if a.units_per_crop > 0:
+            self.region_plan = plan_multi_unit(self.region.table, self.region.census_idx, self.region.census_pop, self.region.shape,
+                                               units_per_crop=a.units_per_crop, **kw)
+        else:
+            self.region_plan = plan_one_unit(self.region.table, self.region.census_idx, self.region.census_pop, self.region.shape, **kw)
+        if len(self.region_plan) < a.weak_batch_size:
+            raise SystemExit(f"--resident_region: the plan holds {len(self.region_plan)} crops, fewer than one batch of {a.weak_batch_size}")
+        self._resident_feed = ResidentRegionFeed(self.region, self.region_plan, a.weak_batch_size,
+                                                 generator=torch.Generator().manual_seed(a.seed), drop_last=True)
 
     # ---- checkpoint (run_train.py:445-476) --------------------------------------------------------------------------
     def save_model(self, prefix="last"):
@@ -482,7 +519,10 @@ class Trainer:
             losses = []
             # the fused step is fed one batch ahead through pinned memory and a copy stream (data/feed.py: RegionFeed); the torch-optimizer
             # recipe keeps the reference's synchronous loop
-            feed = RegionFeed(self.loader, self.device) if self.fused is not None else self.loader
+            if self._resident_feed is not None:
+                feed = self._resident_feed                 # --resident_region: one gather launch per batch, no producer thread
+            else:
+                feed = RegionFeed(self.loader, self.device) if self.fused is not None else self.loader
             if self.fused is not None:
                 self.fused.capture_guard = feed.pause              # (the feed's producer thread keeps still while a step is captured)
             for i, sample in enumerate(feed):

@@ -8,6 +8,7 @@ from __future__ import annotations
 import collections
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -975,6 +976,90 @@ def census_paint(boundary, tables, out=None):
     op = (C.c_void_p * K)(*[p.data_ptr() for p in planes])
     L.check(L.lib().pc_census_paint(L.ptr(boundary), C.c_int64(boundary.numel()), tables[0].numel(), K, tp, op, L.stream_ptr()),
             "pc_census_paint")
+    return out
+
+
+def region_units(boundary, num_ids, max_blocks=0):
+    """The census bookkeeping of a boundary raster in one device pass (csrc/region.hip, pc_region_units; the reference: one Python pass per
+    unit, utils/02_preprocess_rwa_shapefile.py:142-161).  boundary: contiguous int32 device map (h, w), h * w < 2^31.  Returns (table int32
+    (num_ids, 5) = {xmin, xmax, ymin, ymax, count} -- x indexes rows, y columns, maxima exclusive, zeros for a unit without pixels --, stray
+    int64 (): the pixels whose id lies outside [0, num_ids), which contribute nothing).  Bit-reproducible for any launch geometry;
+    max_blocks > 0 caps the workgroups of the pass (tests)."""
+    L.require_device(boundary)
+    if boundary.dim() != 2 or boundary.dtype != torch.int32 or not boundary.is_contiguous() or boundary.numel() == 0:
+        raise ValueError(f"region_units: a non-empty contiguous int32 (h, w) boundary, got {boundary.dtype} {tuple(boundary.shape)}")
+    h, w = boundary.shape
+    num_ids = int(num_ids)
+    if num_ids < 1 or 5 * num_ids >= 1 << 31 or h * w >= 1 << 31:
+        raise ValueError(f"region_units: num_ids >= 1 and h * w < 2^31, got num_ids {num_ids}, raster {h} x {w}")
+    table = torch.empty(num_ids, 5, dtype=torch.int32, device=boundary.device)
+    stray = torch.empty((), dtype=torch.int64, device=boundary.device)
+    L.check(L.lib().pc_region_units(L.ptr(boundary), h, w, num_ids, L.ptr(table), L.ptr(stray), int(max_blocks), L.stream_ptr()),
+            "pc_region_units")
+    return table, stray
+
+
+def region_gather(s2, s1, boundary, band_sel, crops, out=None):
+    """One batch of crops of resident rasters in ONE launch (csrc/region.hip, pc_region_gather): what the reference's weaksup items
+    (data/PopulationDataset.py:403-458,566-568,624-649) and ``Population_Dataset_collate_fn`` (:885-958) assemble on the host.
+    s2: device (S, C2, h, w) fp32 or uint16; s1: device fp32 (S, C1, h, w); boundary: device int32 (h, w); band_sel: six 0-based source
+    bands, four of S2 then two of S1 (the reference's file bands (3, 2, 1, 4) / (1, 2) are (2, 1, 0, 3, 0, 1)); crops: HOST integers (B, 5)
+    = {x0, x1, y0, y1, season}, rows [x0, x1) and columns [y0, y1).  Returns {"S2" (B, 4, Hm, Wm), "S1" (B, 2, Hm, Wm), "admin_mask" (B, Hm, Wm)
+    = (float)id, "data_hw" int32 (B, 2)} at the batch maximum (Hm, Wm), padded 0 / 0 / -1 at the bottom and right; every element is written
+    and fp32 sources are copied bit for bit.  out: such a dict to write into (its (Hm, Wm) may exceed the batch maximum).  An empty crop, one
+    that leaves the raster and a season >= S raise before anything is enqueued."""
+    L.require_device(s2, s1, boundary)
+    if s2.dim() != 4 or s2.dtype not in (torch.float32, torch.uint16) or not s2.is_contiguous():
+        raise ValueError(f"region_gather: s2 must be a contiguous fp32 or uint16 (S, C, h, w) tensor, got {s2.dtype} {tuple(s2.shape)}")
+    S, C2, h, w = s2.shape
+    if s1.dim() != 4 or s1.dtype != torch.float32 or not s1.is_contiguous() or s1.shape[0] != S or tuple(s1.shape[2:]) != (h, w):
+        raise ValueError(f"region_gather: s1 must be a contiguous fp32 ({S}, C, {h}, {w}) tensor, got {s1.dtype} {tuple(s1.shape)}")
+    if boundary.dtype != torch.int32 or tuple(boundary.shape) != (h, w) or not boundary.is_contiguous():
+        raise ValueError(f"region_gather: boundary must be a contiguous int32 ({h}, {w}) map, got {boundary.dtype} {tuple(boundary.shape)}")
+    if h * w == 0 or h * w >= 1 << 31:
+        raise ValueError(f"region_gather: 0 < h * w < 2^31, got {h} x {w}")
+    C1 = s1.shape[1]
+    band = [int(v) for v in band_sel]
+    if len(band) != 6 or any(not 0 <= v < C2 for v in band[:4]) or any(not 0 <= v < C1 for v in band[4:]):
+        raise ValueError(f"region_gather: band_sel names four of {C2} S2 bands and two of {C1} S1 bands (0-based), got {band}")
+    if torch.is_tensor(crops):
+        if crops.is_cuda:
+            raise ValueError("region_gather: crops is host data (it travels in the kernel arguments)")
+        crops = crops.numpy()
+    # (numpy: a handful of vectorised checks -- this wrapper runs once per training batch, next to a kernel of a few microseconds)
+    cr = np.ascontiguousarray(np.asarray(crops, dtype=np.int64).reshape(-1, 5))
+    B = cr.shape[0]
+    if B < 1:
+        raise ValueError("region_gather: at least one crop")
+    hb, wb = cr[:, 1] - cr[:, 0], cr[:, 3] - cr[:, 2]
+    bad = (cr[:, 0] < 0) | (hb <= 0) | (cr[:, 1] > h) | (cr[:, 2] < 0) | (wb <= 0) | (cr[:, 3] > w) | (cr[:, 4] < 0) | (cr[:, 4] >= S)
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"region_gather: crop {i} = {cr[i].tolist()} is empty, leaves the {h} x {w} raster or names a season outside "
+                         f"[0, {S})")
+    Hm, Wm = int(hb.max()), int(wb.max())
+    cr32 = cr.astype(np.int32)
+    dev = s1.device
+    if out is None:
+        out = {"S2": torch.empty(B, 4, Hm, Wm, dtype=torch.float32, device=dev),
+               "S1": torch.empty(B, 2, Hm, Wm, dtype=torch.float32, device=dev),
+               "admin_mask": torch.empty(B, Hm, Wm, dtype=torch.float32, device=dev),
+               "data_hw": torch.empty(B, 2, dtype=torch.int32, device=dev)}
+    else:
+        L.require_device(out["S2"], out["S1"], out["admin_mask"], out["data_hw"])
+        Ho, Wo = out["admin_mask"].shape[-2:]
+        if (tuple(out["S2"].shape) != (B, 4, Ho, Wo) or tuple(out["S1"].shape) != (B, 2, Ho, Wo) or
+                tuple(out["admin_mask"].shape) != (B, Ho, Wo) or tuple(out["data_hw"].shape) != (B, 2) or Ho < Hm or Wo < Wm or
+                any(out[k].dtype != torch.float32 or not out[k].is_contiguous() for k in ("S2", "S1", "admin_mask")) or
+                out["data_hw"].dtype != torch.int32 or not out["data_hw"].is_contiguous()):
+            raise ValueError(f"region_gather: out must hold contiguous fp32 S2 ({B}, 4, H, W), S1 ({B}, 2, H, W), admin_mask ({B}, H, W) with "
+                             f"(H, W) >= ({Hm}, {Wm}) and int32 data_hw ({B}, 2)")
+        Hm, Wm = int(Ho), int(Wo)
+    if Hm * Wm >= 1 << 31:
+        raise ValueError(f"region_gather: Hm * Wm < 2^31, got {Hm} x {Wm}")
+    L.check(L.lib().pc_region_gather(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(boundary), S, C2, C1, h, w,
+                                     (C.c_int32 * 6)(*band), cr32.ctypes.data_as(C.POINTER(C.c_int32)), B, Hm, Wm, L.ptr(out["S2"]),
+                                     L.ptr(out["S1"]), L.ptr(out["admin_mask"]), L.ptr(out["data_hw"]), L.stream_ptr()), "pc_region_gather")
     return out
 
 
