@@ -891,6 +891,31 @@ int pc_region_units(const int32_t* boundary, int h, int w, int num_ids, int32_t*
 int pc_region_gather(const void* s2, int s2_u16, const float* s1, const int32_t* boundary, int S, int C2, int C1, int h, int w,
                      const int32_t* band_sel, const int32_t* crops, int B, int Hm, int Wm, float* s2_out, float* s1_out, float* admin_out,
                      int32_t* data_hw, void* stream);
+/* pc_region_batch (csrc/region_batch.hip): the batch a fused step takes, assembled from the resident rasters in ONE launch per
+ * PC_REGION_GATHER_MAX_B crops.  By definition, bit for bit (fp32 compared as integers, NaN payloads included):
+ *   raw, admin_out  ==  pc_augment_raw( pc_region_gather(crops; Hm, Wm), vflip, hflip, rot, bright, beta, gam, gamma )
+ * Sources, band_sel and crops as pc_region_gather takes them; (Hm, Wm) is the gathered tile and may exceed the batch maximum.  raw DEVICE
+ * fp32 (B, 6, Ho, Wo), admin_out DEVICE fp32 (B, Ho, Wo) with (Ho, Wo) = (Hm, Wm) for even rot and (Wm, Hm) for odd rot.  The padding is
+ * 0 / 0 / -1 in the gathered tile's coordinates (bottom, right) and sits wherever the flips and the rotation put it; the S2 value transform is
+ * applied to it as pc_augment_raw applies it.  Every element of both outputs is written; every address is formed from a row and a column
+ * clamped to the crop.  Even rot: a thread moves four consecutive pixels of an output row (aligned 16-byte stores when Wm % 4 == 0 and the
+ * outputs are 16-byte aligned, loads at the sources' natural alignment, element by element across the crop's edge and otherwise); odd rot:
+ * 32 x 32 tiles through LDS.  Crops, coins, band selection and items travel in the kernel arguments: no copy, no synchronisation.
+ * labels (NULL: none) assembles the step's labels in the same launch:
+ *   census_idx_out[b][k] = plan_cidx[items[b]][k],  y_out[b][k] = plan_y[items[b]][k]      for k < K,  1 <= K <= Kp
+ * PC_EINVAL before anything is enqueued: everything pc_region_gather refuses, rot outside 0 .. 3, (Ho, Wo) other than stated above, an item
+ * outside [0, n), K outside [1, Kp]. */
+typedef struct pc_region_labels {
+    const int64_t* plan_cidx;                       /* DEVICE int64 (n, Kp), uploaded once */
+    const float* plan_y;                            /* DEVICE fp32 (n, Kp) */
+    const int32_t* items;                           /* HOST [B]: the plan row of crop b */
+    int64_t* census_idx_out;                        /* DEVICE int64 (B, K) */
+    float* y_out;                                   /* DEVICE fp32 (B, K) */
+    int32_t n, Kp, K, _pad;
+} pc_region_labels;
+int pc_region_batch(const void* s2, int s2_u16, const float* s1, const int32_t* boundary, int S, int C2, int C1, int h, int w,
+                    const int32_t* band_sel, const int32_t* crops, int B, int Hm, int Wm, int vflip, int hflip, int rot, int bright, float beta,
+                    int gam, float gamma, float* raw, float* admin_out, int Ho, int Wo, const pc_region_labels* labels, void* stream);
 
 #ifdef __cplusplus
 }

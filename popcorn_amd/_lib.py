@@ -164,6 +164,12 @@ PC_UNIT_LAYOUT_MAX_K, PC_UNIT_LAYOUT_MAX_B = 1024, 256
 PC_REGION_GATHER_MAX_B = 128          # crops per pc_region_gather launch (the crop list travels in the kernel arguments)
 
 
+class PcRegionLabels(C.Structure):
+    """pc_region_labels: the label assembly of pc_region_batch (items: HOST int32 [B])."""
+    _fields_ = [("plan_cidx", C.c_void_p), ("plan_y", C.c_void_p), ("items", C.POINTER(C.c_int32)), ("census_idx_out", C.c_void_p),
+                ("y_out", C.c_void_p), ("n", C.c_int32), ("Kp", C.c_int32), ("K", C.c_int32), ("_pad", C.c_int32)]
+
+
 class PopcornHipError(RuntimeError):
     pass
 
@@ -227,6 +233,9 @@ def lib():
         _lib.pc_region_units.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.pc_region_gather.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
                                           [C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_int] * 3 + [C.c_void_p] * 5)
+        _lib.pc_region_batch.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
+                                         [C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_int] * 7 + [C.c_float, C.c_int, C.c_float] +
+                                         [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(PcRegionLabels), C.c_void_p])
     return _lib
 
 

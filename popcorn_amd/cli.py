@@ -107,6 +107,15 @@ def train_parser():
     p.add_argument("--max_pix_box", type=int, default=12_000_000,
                    help="--resident_region: units whose bounding box has at least this many pixels are dropped; the pixel budget of a "
                         "multi-unit crop (the reference's max_pix_box)")
+    p.add_argument("--resident_assemble", action="store_true",
+                   help="--resident_region: gather, augmentation, raw tile and labels of a batch in ONE launch (data/region.py: "
+                        "ResidentBatchFeed) instead of gather + augment_raw + torch indexing; the same batches and bits")
+    p.add_argument("--resident_pixel_budget", type=int, default=0, metavar="P",
+                   help="--resident_region: implies --resident_assemble and composes batches by crop size so that B * Hm * Wm <= P "
+                        "(plan_batches) instead of cutting them at -wb; variable batch size, NOT the reference recipe (0 = off)")
+    p.add_argument("--resident_max_batch", type=int, default=128, help="--resident_pixel_budget: at most this many crops per batch")
+    p.add_argument("--resident_min_fill", type=float, default=0.6,
+                   help="--resident_pixel_budget: a batch of more than one crop keeps real pixels / padded pixels at or above this")
     return p
 
 
@@ -258,6 +267,9 @@ class Trainer:
         seed_all(args.seed)
         collate = Population_Dataset_collate_fn
         self._resident_feed = None
+        if (args.resident_assemble or args.resident_pixel_budget > 0) and args.resident_region is None:
+            raise SystemExit("--resident_assemble / --resident_pixel_budget assemble batches from resident rasters: they need "
+                             "--resident_region")
         if args.resident_region is not None:
             self._init_resident_region()
         if args.units_per_crop > 0:
@@ -291,6 +303,8 @@ class Trainer:
         # get_sparsity_mask): every rank gets its own stream, rank 0 keeps the single-process one
         seed_all(args.seed + 2 + 1000 * self.rank)
         self.data_transform = default_train_transform()                    # run_train.py:386-402
+        if hasattr(self._resident_feed, "transform"):
+            self._resident_feed.transform = self.data_transform            # --resident_assemble: the feed draws the coins of this set
         self.reducer = FlatReducer()
         self.info = {"epoch": 0, "iter": 0, "sampleitr": 0}
         self._r2buf = collections.deque()
@@ -328,7 +342,13 @@ class Trainer:
             raise SystemExit("--resident_region cuts census-unit crops of variable size: it cannot be combined with --fixed_hw")
         if self.world > 1:
             raise SystemExit("--resident_region runs in a single process: sharding a crop plan over data-parallel ranks is not part of it")
-        from .data.region import ResidentRegion, ResidentRegionFeed, plan_multi_unit, plan_one_unit
+        assemble = a.resident_assemble or a.resident_pixel_budget > 0
+        if assemble and a.nan_fill:
+            raise SystemExit("--resident_assemble / --resident_pixel_budget cannot be combined with --nan_fill: the fill sits between the "
+                             "gather and the augmentation, which the one-launch assembly fuses; the unfused --resident_region feed takes it")
+        if a.resident_pixel_budget < 0 or a.resident_max_batch < 1 or not 0.0 <= a.resident_min_fill <= 1.0:
+            raise SystemExit("--resident_pixel_budget >= 0, --resident_max_batch >= 1 and --resident_min_fill in [0, 1]")
+        from .data.region import ResidentBatchFeed, ResidentRegion, ResidentRegionFeed, plan_multi_unit, plan_one_unit
         data = SyntheticTestRaster(a.resident_region[0], a.resident_region[1], seasons=1, n_regions=a.resident_units, seed=a.seed + 20,
                                    device=self.device, raw=True, nan_clouds=a.nan_clouds)
         self.region = ResidentRegion.from_synthetic(data)
@@ -340,8 +360,15 @@ class Trainer:
             self.region_plan = plan_one_unit(self.region.table, self.region.census_idx, self.region.census_pop, self.region.shape, **kw)
         if len(self.region_plan) < a.weak_batch_size:
             raise SystemExit(f"--resident_region: the plan holds {len(self.region_plan)} crops, fewer than one batch of {a.weak_batch_size}")
-        self._resident_feed = ResidentRegionFeed(self.region, self.region_plan, a.weak_batch_size,
-                                                 generator=torch.Generator().manual_seed(a.seed), drop_last=True)
+        gen = torch.Generator().manual_seed(a.seed)
+        if assemble:
+            # the coins are the feed's to draw (once per batch, right before the step).  The feed validates its transform at construction;
+            # Trainer.__init__ hands it the trainer's own data_transform, the same set, once that exists
+            self._resident_feed = ResidentBatchFeed(self.region, self.region_plan, a.weak_batch_size, transform=default_train_transform(),
+                                                    generator=gen, drop_last=True, pixel_budget=a.resident_pixel_budget,
+                                                    max_batch=a.resident_max_batch, min_fill=a.resident_min_fill)
+        else:
+            self._resident_feed = ResidentRegionFeed(self.region, self.region_plan, a.weak_batch_size, generator=gen, drop_last=True)
 
     # ---- checkpoint (run_train.py:445-476) --------------------------------------------------------------------------
     def save_model(self, prefix="last"):
@@ -397,7 +424,10 @@ class Trainer:
     def train_step(self, sample):
         a = self.args
         s = None
-        if self.fused is not None and torch.is_tensor(sample.get("S2")) and sample["S2"].is_cuda:
+        if self.fused is not None and torch.is_tensor(sample.get("raw")) and sample["raw"].is_cuda:
+            # a batch assembled by ResidentBatchFeed: augmented raw tile and labels are there already, the coins drawn by the feed
+            s = {k: sample[k] for k in ("raw", "admin_mask", "census_idx", "y")}
+        elif self.fused is not None and torch.is_tensor(sample.get("S2")) and sample["S2"].is_cuda:
             # a batch staged by the feed: augmentation + assembly in one launch, normalisation inside the step (raw input form)
             s = prepare_sample_fused(sample, self.data_transform, nan_fill=a.nan_fill)
         if s is None:
@@ -531,7 +561,7 @@ class Trainer:
                     losses.append(loss)
                     recent.append(loss)
                 self.info["iter"] += 1
-                self.info["sampleitr"] += a.weak_batch_size
+                self.info["sampleitr"] += len(sample["admin_mask"])       # (weak_batch_size, but for pixel-budget batches)
                 if (i + 1) % a.val_every_i_steps == 0 and a.weak_validation:          # run_train.py:255-259
                     self.validate_weak()
                     self.model.train()

@@ -28,6 +28,7 @@
 // PC_REGION_GATHER_MAX_B crops per launch; longer batches are split): no host-to-device copy, no synchronisation.  The host wrapper
 // validates every crop before anything is enqueued; the kernel never forms an address outside the sources.
 #include "common.h"
+#include "region_load.h"
 
 namespace {
 
@@ -42,8 +43,6 @@ static_assert((RU_BINS & (RU_BINS - 1)) == 0, "the slot of an id is id & (RU_BIN
 static_assert(RU_ROWS % RU_R == 0, "a tile is whole groups of rows");
 
 typedef unsigned long long rg_u64;
-typedef int i32x4u __attribute__((ext_vector_type(4), aligned(4)));                 // 16-byte access at 4-byte alignment
-typedef unsigned short u16x4u __attribute__((ext_vector_type(4), aligned(2)));      // 8-byte access at 2-byte alignment
 
 // ---- the unit table --------------------------------------------------------------------------------------------------------------------
 struct RegionUnitsArgs {
@@ -165,14 +164,6 @@ struct RegionGatherArgs {
     int Hm, Wm;
     int32_t crop[PC_REGION_GATHER_MAX_B][5];                     // {x0, x1, y0, y1, season}, validated by the host: 2,560 bytes of arguments
 };
-
-__device__ __forceinline__ float rg_val(const float* p) { return *p; }
-__device__ __forceinline__ float rg_val(const uint16_t* p) { return (float)*p; }
-__device__ __forceinline__ f32x4 rg_ld4(const float* p) { return *reinterpret_cast<const f32x4u*>(p); }
-__device__ __forceinline__ f32x4 rg_ld4(const uint16_t* p) {
-    const u16x4u q = *reinterpret_cast<const u16x4u*>(p);
-    return f32x4{(float)q[0], (float)q[1], (float)q[2], (float)q[3]};
-}
 
 // V = 4: Wm % 4 == 0 and 16-byte aligned outputs; V = 1: anything
 template <typename T2, int V>

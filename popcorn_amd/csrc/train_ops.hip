@@ -5,6 +5,7 @@
 // torch.nn.utils.clip_grad_norm_ + optim.Adam (run_train.py:82-90,233-238); utils/utils.py:105-127 (apply_normalize)
 // + the band selection of data/PopulationDataset.py:566-568.
 #include "common.h"
+#include "aug_value.h"
 
 namespace {
 
@@ -278,10 +279,8 @@ __global__ __launch_bounds__(256) void augment_raw_kernel(const AugArgs a) {
         const int64_t src = (int64_t)y * a.W + x;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
-            float v = a.s2[((int64_t)b * 4 + c) * hw + src];
-            if (a.bright) v = fminf(fmaxf(__fmul_rn(__fdiv_rn(v, 10000.f), a.beta), 0.f), 1.f) * 10000.f;
-            if (a.gam) v = fminf(fmaxf(powf(__fdiv_rn(fmaxf(v, 0.f), 10000.f), a.gamma), 0.f), 1.f) * 10000.f;
-            a.raw[((int64_t)b * 6 + c) * npx + r] = v;
+            const float v = a.s2[((int64_t)b * 4 + c) * hw + src];
+            a.raw[((int64_t)b * 6 + c) * npx + r] = pc_aug_s2_value(v, a.bright, a.beta, a.gam, a.gamma);
         }
 #pragma unroll
         for (int c = 0; c < 2; ++c) a.raw[((int64_t)b * 6 + 4 + c) * npx + r] = a.s1[((int64_t)b * 2 + c) * hw + src];
@@ -313,10 +312,8 @@ __global__ __launch_bounds__(256) void augment_raw_transposed_kernel(const AugAr
                 const int64_t src = (int64_t)y * a.W + x;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    float v = a.s2[((int64_t)b * 4 + c) * hw + src];
-                    if (a.bright) v = fminf(fmaxf(__fmul_rn(__fdiv_rn(v, 10000.f), a.beta), 0.f), 1.f) * 10000.f;
-                    if (a.gam) v = fminf(fmaxf(powf(__fdiv_rn(fmaxf(v, 0.f), 10000.f), a.gamma), 0.f), 1.f) * 10000.f;
-                    tile[c][dj][di] = v;
+                    const float v = a.s2[((int64_t)b * 4 + c) * hw + src];
+                    tile[c][dj][di] = pc_aug_s2_value(v, a.bright, a.beta, a.gam, a.gamma);
                 }
 #pragma unroll
                 for (int c = 0; c < 2; ++c) tile[4 + c][dj][di] = a.s1[((int64_t)b * 2 + c) * hw + src];

@@ -10,8 +10,10 @@ and pixel counts are made at preprocessing time with one pass per unit (utils/02
   ``plan_multi_unit``     crops that list up to K complete units each (multi-unit census supervision, data/units.py), greedy and deterministic
   ``ResidentRegionFeed``  iterates like ``feed.RegionFeed``: per batch one ``ops.region_gather`` launch, no loader / collate / pinned
                           staging / copy stream and no producer thread
+  ``ResidentBatchFeed``   the same batches in the form the fused step takes -- gather, augmentation, raw tile and labels in ONE
+                          ``ops.region_batch`` launch --, cut at a fixed count or composed by size under a pixel budget (``plan_batches``)
 
-Host glue, plain torch; the kernels are csrc/region.hip.  Deviations from the reference, all named where they happen: units without pixels
+Host glue, plain torch; the kernels are csrc/region.hip and csrc/region_batch.hip.  Deviations from the reference, all named where they happen: units without pixels
 are dropped (``plan_one_unit``); the per-epoch order and the season per item come from a torch generator, not Python's ``random`` stream
 (``ResidentRegionFeed``); the resident S1 is the orbit already chosen per season (no switch by NaN fraction: ``--nan_fill`` fills what is
 left).  Sharding a plan over data-parallel ranks and graph capture of the gather are not part of this module."""
@@ -254,4 +256,135 @@ class ResidentRegionFeed:
             out["img_coords"] = [(b[0], b[2]) for b in boxes]
             out["valid_coords"] = [tuple(b) for b in boxes]
             out["season"] = season_dev[k * B:(k + 1) * B]
+            yield out
+
+
+def plan_batches(hw_list, order, pixel_budget, max_batch, min_fill, generator):
+    """The batches of one epoch under a pixel budget (pure host code): ``hw_list[i]`` = (h, w) of plan item i, ``order`` = the epoch's
+    permutation of the items.  Returns a list of lists of item indices.
+    Rule: the permuted items are sorted by the size class floor(8 * log2(h * w)), ties by their position in the permutation (so batches of
+    similar items differ from epoch to epoch); a sweep over the sorted list lets an item join the open batch of B items while B + 1 <=
+    max_batch, (B + 1) * Hm' * Wm' <= pixel_budget and the real pixels are >= min_fill * the padded ones -- (Hm', Wm') the maximum with
+    the item included --, and otherwise opens a new batch with it; one ``torch.randperm`` from ``generator`` then shuffles the batches.
+    Invariants: (a) every item is in exactly one batch, nothing is dropped; (b) a batch with B > 1 has B * Hm * Wm <= pixel_budget (an
+    item that alone exceeds the budget is a batch of one); (c) B <= max_batch; (d) a batch with B > 1 has fill >= min_fill; (e) the
+    result is a function of the arguments and the generator's state alone; (f) two epochs (two permutations) give different
+    compositions when a size class holds at least two items that do not share a batch."""
+    import math
+    if int(max_batch) < 1 or int(pixel_budget) < 1 or not 0.0 <= float(min_fill) <= 1.0:
+        raise ValueError(f"plan_batches: pixel_budget >= 1, max_batch >= 1 and min_fill in [0, 1], got {pixel_budget}, {max_batch}, {min_fill}")
+    order = [int(i) for i in (order.tolist() if torch.is_tensor(order) else order)]
+    hw = [(int(h), int(w)) for h, w in hw_list]
+    if sorted(order) != list(range(len(hw))) or any(h < 1 or w < 1 for h, w in hw):
+        raise ValueError("plan_batches: order is a permutation of the items of hw_list, every item non-empty")
+    keyed = sorted(range(len(order)), key=lambda p: (math.floor(8.0 * math.log2(hw[order[p]][0] * hw[order[p]][1])), p))
+    batches, cur, Hm, Wm, real = [], [], 0, 0, 0
+    for p in keyed:
+        i = order[p]
+        h, w = hw[i]
+        if cur:
+            H2, W2, n2 = max(Hm, h), max(Wm, w), len(cur) + 1
+            padded = n2 * H2 * W2
+            if n2 <= max_batch and padded <= pixel_budget and real + h * w >= min_fill * padded:
+                cur.append(i)
+                Hm, Wm, real = H2, W2, real + h * w
+                continue
+            batches.append(cur)
+        cur, Hm, Wm, real = [i], h, w, h * w
+    if cur:
+        batches.append(cur)
+    shuffle = torch.randperm(len(batches), generator=generator).tolist()
+    return [batches[k] for k in shuffle]
+
+
+class ResidentBatchFeed:
+    """``ResidentRegionFeed`` with the whole batch assembled in ONE launch: per batch one ``ops.region_batch`` call -- gather, augmentation,
+    raw-tile assembly and the y / census_idx rows of the plan tables -- and no other device work.  Yields what the fused step takes:
+    {"raw" (B, 6, Ho, Wo), "admin_mask" (B, Ho, Wo), "census_idx", "y", ["census_n"], "img_coords", "valid_coords", "season"}; census_idx / y
+    are (B,) for a one-unit plan and (B, K) padded with -1 / 0 (K = the batch maximum) plus host ``census_n`` for a multi-unit plan.
+    Order: the epoch's ``randperm`` / ``randint`` come from ``generator`` as in ``ResidentRegionFeed``; the augmentation coins are drawn with
+    ``draw_fused_params(transform)`` once per batch, immediately before the batch is yielded, so the global generators see the sequence
+    ``Trainer.train_step`` consumes with the unfused feed: coins, then the step's selection draw.  A transform that ``draw_fused_params``
+    cannot express raises ValueError here (the global generators are left as they were).
+    pixel_budget > 0: batches are composed by size with ``plan_batches`` (one more ``randperm`` per epoch, after the two above) instead of
+    cut at ``batch_size``; nothing is dropped.  Variable batch sizes change the optimisation schedule: this is not the reference recipe."""
+
+    def __init__(self, region, plan, batch_size, transform=None, generator=None, drop_last=True, seasons=1, pixel_budget=0, max_batch=128,
+                 min_fill=0.6):
+        import random
+        from ..utils.transform import draw_fused_params
+        if len(plan) < 1 or int(batch_size) < 1:
+            raise ValueError("ResidentBatchFeed: a plan with at least one crop and batch_size >= 1")
+        if not 1 <= int(seasons) <= region.seasons:
+            raise ValueError(f"ResidentBatchFeed: seasons in [1, {region.seasons}] (what the region holds), got {seasons}")
+        if int(pixel_budget) < 0 or int(max_batch) < 1 or not 0.0 <= float(min_fill) <= 1.0:
+            raise ValueError(f"ResidentBatchFeed: pixel_budget >= 0, max_batch >= 1, min_fill in [0, 1]; got {pixel_budget}, {max_batch}, "
+                             f"{min_fill}")
+        state = torch.get_rng_state(), random.getstate()
+        expressible = draw_fused_params(transform) is not None
+        torch.set_rng_state(state[0])
+        random.setstate(state[1])
+        if not expressible:
+            raise ValueError("ResidentBatchFeed: the transform is not one draw_fused_params can express (one coin per batch, the reference "
+                             "trainer's brightness / gamma / flips / quarter turns); use ResidentRegionFeed with it")
+        self._draw = draw_fused_params
+        self.region, self.plan, self.batch_size, self.drop_last, self.seasons = region, plan, int(batch_size), bool(drop_last), int(seasons)
+        self.transform = transform
+        self.pixel_budget, self.max_batch, self.min_fill = int(pixel_budget), int(max_batch), float(min_fill)
+        self.generator = generator if generator is not None else torch.Generator().manual_seed(0)
+        self.device = region.device
+        self._cidx = plan.census_idx.to(self.device).contiguous()       # the plan tables, uploaded once
+        self._y = plan.y.to(self.device).float().contiguous()
+        self._crops = plan.crops.numpy()
+        self._hw = [(int(c[1] - c[0]), int(c[3] - c[2])) for c in self._crops]
+        self._bbox = plan.bbox.tolist()
+        self.last_order = self.last_season = self.last_batches = None
+
+    def pause(self):
+        return contextlib.nullcontext()
+
+    def __len__(self):
+        if self.pixel_budget > 0:
+            if self.last_batches is None:
+                raise TypeError("ResidentBatchFeed: under a pixel budget the number of batches is known once an epoch is planned")
+            return len(self.last_batches)
+        n, B = len(self.plan), self.batch_size
+        return n // B if self.drop_last else -(-n // B)
+
+    def __iter__(self):
+        plan, B, n = self.plan, self.batch_size, len(self.plan)
+        order = torch.randperm(n, generator=self.generator)
+        season = (torch.randint(0, self.seasons, (n,), generator=self.generator) if self.seasons > 1
+                  else torch.zeros(n, dtype=torch.int64))
+        self.last_order, self.last_season = order, season
+        order_np, season_np = order.numpy(), season.numpy()
+        if self.pixel_budget > 0:
+            pos = np.empty(n, dtype=np.int64)
+            pos[order_np] = np.arange(n)                               # the season of an item is drawn at its place in the permutation
+            batches = [np.asarray(b, dtype=np.int64) for b in
+                       plan_batches(self._hw, order_np, self.pixel_budget, self.max_batch, self.min_fill, self.generator)]
+            seasons = [season_np[pos[b]] for b in batches]
+        else:
+            batches = [order_np[k * B:(k + 1) * B] for k in range(len(self))]
+            seasons = [season_np[k * B:(k + 1) * B] for k in range(len(self))]
+        self.last_batches = [b.tolist() for b in batches]
+        season_dev = torch.from_numpy(np.concatenate(seasons)).to(self.device) if batches else None      # one upload per epoch
+        at = 0
+        for idx, sea in zip(batches, seasons):
+            crops = np.empty((idx.size, 5), dtype=np.int64)
+            crops[:, :4] = self._crops[idx]
+            crops[:, 4] = sea
+            cn = [plan.census_n[i] for i in idx] if plan.multi else None
+            params = self._draw(self.transform)                        # the coins, immediately before the batch goes out
+            out = ops.region_batch(self.region.s2, self.region.s1, self.region.boundary, self.region.band_sel, crops, params,
+                                   labels=(self._cidx, self._y, idx, max(cn) if plan.multi else 1))
+            if plan.multi:
+                out["census_n"] = cn
+            else:
+                out["census_idx"], out["y"] = out["census_idx"].view(-1), out["y"].view(-1)
+            boxes = [self._bbox[i] for i in idx]
+            out["img_coords"] = [(b[0], b[2]) for b in boxes]
+            out["valid_coords"] = [tuple(b) for b in boxes]
+            out["season"] = season_dev[at:at + idx.size]
+            at += idx.size
             yield out

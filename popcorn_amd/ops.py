@@ -999,6 +999,43 @@ def region_units(boundary, num_ids, max_blocks=0):
     return table, stray
 
 
+def _region_inputs(what, s2, s1, boundary, band_sel, crops):
+    """The validations ``region_gather`` and ``region_batch`` share: the resident rasters, the band selection and the host crop list.
+    Returns (S, C2, C1, h, w, band, crops as int32 (B, 5), the batch maximum (Hm, Wm)); raises before anything is enqueued."""
+    L.require_device(s2, s1, boundary)
+    if s2.dim() != 4 or s2.dtype not in (torch.float32, torch.uint16) or not s2.is_contiguous():
+        raise ValueError(f"{what}: s2 must be a contiguous fp32 or uint16 (S, C, h, w) tensor, got {s2.dtype} {tuple(s2.shape)}")
+    S, C2, h, w = s2.shape
+    if s1.dim() != 4 or s1.dtype != torch.float32 or not s1.is_contiguous() or s1.shape[0] != S or tuple(s1.shape[2:]) != (h, w):
+        raise ValueError(f"{what}: s1 must be a contiguous fp32 ({S}, C, {h}, {w}) tensor, got {s1.dtype} {tuple(s1.shape)}")
+    if boundary.dtype != torch.int32 or tuple(boundary.shape) != (h, w) or not boundary.is_contiguous():
+        raise ValueError(f"{what}: boundary must be a contiguous int32 ({h}, {w}) map, got {boundary.dtype} {tuple(boundary.shape)}")
+    if h * w == 0 or h * w >= 1 << 31:
+        raise ValueError(f"{what}: 0 < h * w < 2^31, got {h} x {w}")
+    C1 = s1.shape[1]
+    band = [int(v) for v in band_sel]
+    if len(band) != 6 or any(not 0 <= v < C2 for v in band[:4]) or any(not 0 <= v < C1 for v in band[4:]):
+        raise ValueError(f"{what}: band_sel names four of {C2} S2 bands and two of {C1} S1 bands (0-based), got {band}")
+    if torch.is_tensor(crops):
+        if crops.is_cuda:
+            raise ValueError(f"{what}: crops is host data (it travels in the kernel arguments)")
+        crops = crops.numpy()
+    # (numpy: a handful of vectorised checks -- this wrapper runs once per training batch, next to a kernel of a few microseconds)
+    cr = np.ascontiguousarray(np.asarray(crops, dtype=np.int64).reshape(-1, 5))
+    B = cr.shape[0]
+    if B < 1:
+        raise ValueError(f"{what}: at least one crop")
+    hb, wb = cr[:, 1] - cr[:, 0], cr[:, 3] - cr[:, 2]
+    bad = (cr[:, 0] < 0) | (hb <= 0) | (cr[:, 1] > h) | (cr[:, 2] < 0) | (wb <= 0) | (cr[:, 3] > w) | (cr[:, 4] < 0) | (cr[:, 4] >= S)
+    if bad.any():
+        i = int(np.flatnonzero(bad)[0])
+        raise ValueError(f"{what}: crop {i} = {cr[i].tolist()} is empty, leaves the {h} x {w} raster or names a season outside "
+                         f"[0, {S})")
+    Hm, Wm = int(hb.max()), int(wb.max())
+    cr32 = cr.astype(np.int32)
+    return S, C2, C1, h, w, band, cr32, Hm, Wm
+
+
 def region_gather(s2, s1, boundary, band_sel, crops, out=None):
     """One batch of crops of resident rasters in ONE launch (csrc/region.hip, pc_region_gather): what the reference's weaksup items
     (data/PopulationDataset.py:403-458,566-568,624-649) and ``Population_Dataset_collate_fn`` (:885-958) assemble on the host.
@@ -1008,37 +1045,8 @@ def region_gather(s2, s1, boundary, band_sel, crops, out=None):
     = (float)id, "data_hw" int32 (B, 2)} at the batch maximum (Hm, Wm), padded 0 / 0 / -1 at the bottom and right; every element is written
     and fp32 sources are copied bit for bit.  out: such a dict to write into (its (Hm, Wm) may exceed the batch maximum).  An empty crop, one
     that leaves the raster and a season >= S raise before anything is enqueued."""
-    L.require_device(s2, s1, boundary)
-    if s2.dim() != 4 or s2.dtype not in (torch.float32, torch.uint16) or not s2.is_contiguous():
-        raise ValueError(f"region_gather: s2 must be a contiguous fp32 or uint16 (S, C, h, w) tensor, got {s2.dtype} {tuple(s2.shape)}")
-    S, C2, h, w = s2.shape
-    if s1.dim() != 4 or s1.dtype != torch.float32 or not s1.is_contiguous() or s1.shape[0] != S or tuple(s1.shape[2:]) != (h, w):
-        raise ValueError(f"region_gather: s1 must be a contiguous fp32 ({S}, C, {h}, {w}) tensor, got {s1.dtype} {tuple(s1.shape)}")
-    if boundary.dtype != torch.int32 or tuple(boundary.shape) != (h, w) or not boundary.is_contiguous():
-        raise ValueError(f"region_gather: boundary must be a contiguous int32 ({h}, {w}) map, got {boundary.dtype} {tuple(boundary.shape)}")
-    if h * w == 0 or h * w >= 1 << 31:
-        raise ValueError(f"region_gather: 0 < h * w < 2^31, got {h} x {w}")
-    C1 = s1.shape[1]
-    band = [int(v) for v in band_sel]
-    if len(band) != 6 or any(not 0 <= v < C2 for v in band[:4]) or any(not 0 <= v < C1 for v in band[4:]):
-        raise ValueError(f"region_gather: band_sel names four of {C2} S2 bands and two of {C1} S1 bands (0-based), got {band}")
-    if torch.is_tensor(crops):
-        if crops.is_cuda:
-            raise ValueError("region_gather: crops is host data (it travels in the kernel arguments)")
-        crops = crops.numpy()
-    # (numpy: a handful of vectorised checks -- this wrapper runs once per training batch, next to a kernel of a few microseconds)
-    cr = np.ascontiguousarray(np.asarray(crops, dtype=np.int64).reshape(-1, 5))
-    B = cr.shape[0]
-    if B < 1:
-        raise ValueError("region_gather: at least one crop")
-    hb, wb = cr[:, 1] - cr[:, 0], cr[:, 3] - cr[:, 2]
-    bad = (cr[:, 0] < 0) | (hb <= 0) | (cr[:, 1] > h) | (cr[:, 2] < 0) | (wb <= 0) | (cr[:, 3] > w) | (cr[:, 4] < 0) | (cr[:, 4] >= S)
-    if bad.any():
-        i = int(np.flatnonzero(bad)[0])
-        raise ValueError(f"region_gather: crop {i} = {cr[i].tolist()} is empty, leaves the {h} x {w} raster or names a season outside "
-                         f"[0, {S})")
-    Hm, Wm = int(hb.max()), int(wb.max())
-    cr32 = cr.astype(np.int32)
+    S, C2, C1, h, w, band, cr32, Hm, Wm = _region_inputs("region_gather", s2, s1, boundary, band_sel, crops)
+    B = cr32.shape[0]
     dev = s1.device
     if out is None:
         out = {"S2": torch.empty(B, 4, Hm, Wm, dtype=torch.float32, device=dev),
@@ -1060,6 +1068,73 @@ def region_gather(s2, s1, boundary, band_sel, crops, out=None):
     L.check(L.lib().pc_region_gather(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(boundary), S, C2, C1, h, w,
                                      (C.c_int32 * 6)(*band), cr32.ctypes.data_as(C.POINTER(C.c_int32)), B, Hm, Wm, L.ptr(out["S2"]),
                                      L.ptr(out["S1"]), L.ptr(out["admin_mask"]), L.ptr(out["data_hw"]), L.stream_ptr()), "pc_region_gather")
+    return out
+
+
+def region_batch(s2, s1, boundary, band_sel, crops, params=None, hw=None, labels=None, out=None):
+    """The batch a fused step takes, assembled from resident rasters in ONE launch (csrc/region_batch.hip, pc_region_batch).  By definition,
+    bit for bit: ``augment_raw(*region_gather(...; tile (Hm, Wm)), params)`` -- without the intermediate S2 / S1 / admin_mask.
+    s2, s1, boundary, band_sel, crops: as ``region_gather``.  params: ``draw_fused_params``' dict (None = no augmentation).  hw: the gathered
+    tile (Hm, Wm), default and at least the batch maximum.  labels = (plan_cidx int64 (n, Kp), plan_y fp32 (n, Kp) -- device tables uploaded
+    once --, items: B host integers, K): the same launch also writes census_idx[b] = plan_cidx[items[b], :K] and y likewise.
+    Returns {"raw" (B, 6, Ho, Wo), "admin_mask" (B, Ho, Wo), ["census_idx" int64 (B, K), "y" fp32 (B, K)]} with (Ho, Wo) = (Wm, Hm) for an odd
+    rotation; out: such a dict to write into.  Everything ``region_gather`` refuses, a rotation outside 0 .. 3, an item outside [0, n), a K
+    outside [1, Kp] and an ``out`` of another shape raise ValueError before anything is enqueued."""
+    S, C2, C1, h, w, band, cr32, Hm, Wm = _region_inputs("region_batch", s2, s1, boundary, band_sel, crops)
+    B = cr32.shape[0]
+    if hw is not None:
+        th, tw = int(hw[0]), int(hw[1])
+        if th < Hm or tw < Wm:
+            raise ValueError(f"region_batch: the tile hw = ({th}, {tw}) is smaller than the batch maximum ({Hm}, {Wm})")
+        Hm, Wm = th, tw
+    if Hm * Wm >= 1 << 31:
+        raise ValueError(f"region_batch: Hm * Wm < 2^31, got {Hm} x {Wm}")
+    pr = params or {}
+    k = int(pr.get("rot", 0))
+    if not 0 <= k <= 3:
+        raise ValueError(f"region_batch: rot is a number of quarter turns in 0 .. 3, got {k}")
+    Ho, Wo = (Wm, Hm) if k & 1 else (Hm, Wm)
+    dev = s1.device
+    lab = None
+    if labels is not None:
+        plan_cidx, plan_y, items, K = labels
+        L.require_device(plan_cidx, plan_y)
+        K = int(K)
+        if (plan_cidx.dim() != 2 or plan_cidx.dtype != torch.int64 or plan_y.dtype != torch.float32 or plan_y.shape != plan_cidx.shape or
+                not plan_cidx.is_contiguous() or not plan_y.is_contiguous() or plan_cidx.shape[0] < 1):
+            raise ValueError("region_batch: labels are contiguous device tables plan_cidx int64 (n, Kp) and plan_y fp32 (n, Kp)")
+        n, Kp = plan_cidx.shape
+        it = np.ascontiguousarray(np.asarray(items, dtype=np.int64).reshape(-1))
+        if it.size != B or (it < 0).any() or (it >= n).any():
+            raise ValueError(f"region_batch: items names one plan row in [0, {n}) per crop ({B}), got {it.tolist()}")
+        if not 1 <= K <= Kp:
+            raise ValueError(f"region_batch: K in [1, {Kp}], got {K}")
+        it32 = it.astype(np.int32)
+    if out is None:
+        out = {"raw": torch.empty(B, 6, Ho, Wo, dtype=torch.float32, device=dev),
+               "admin_mask": torch.empty(B, Ho, Wo, dtype=torch.float32, device=dev)}
+        if labels is not None:
+            out["census_idx"] = torch.empty(B, K, dtype=torch.int64, device=dev)
+            out["y"] = torch.empty(B, K, dtype=torch.float32, device=dev)
+    else:
+        want = {"raw": ((B, 6, Ho, Wo), torch.float32), "admin_mask": ((B, Ho, Wo), torch.float32)}
+        if labels is not None:
+            want.update({"census_idx": ((B, K), torch.int64), "y": ((B, K), torch.float32)})
+        for key, (shape, dt) in want.items():
+            t = out.get(key)
+            if t is None or not t.is_cuda or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+                raise ValueError(f"region_batch: out[{key!r}] must be a contiguous device {dt} tensor of shape {shape}, got "
+                                 f"{None if t is None else (t.dtype, tuple(t.shape))}")
+    if labels is not None:
+        lab = L.PcRegionLabels(plan_cidx.data_ptr(), plan_y.data_ptr(), it32.ctypes.data_as(C.POINTER(C.c_int32)),
+                               out["census_idx"].data_ptr(), out["y"].data_ptr(), n, Kp, K, 0)
+    beta, gamma = pr.get("beta"), pr.get("gamma")
+    L.check(L.lib().pc_region_batch(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(boundary), S, C2, C1, h, w,
+                                    (C.c_int32 * 6)(*band), cr32.ctypes.data_as(C.POINTER(C.c_int32)), B, Hm, Wm,
+                                    int(bool(pr.get("vflip"))), int(bool(pr.get("hflip"))), k, int(beta is not None),
+                                    C.c_float(beta if beta is not None else 1.0), int(gamma is not None),
+                                    C.c_float(gamma if gamma is not None else 1.0), L.ptr(out["raw"]), L.ptr(out["admin_mask"]), Ho, Wo,
+                                    C.byref(lab) if lab is not None else None, L.stream_ptr()), "pc_region_batch")
     return out
 
 
