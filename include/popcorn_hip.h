@@ -917,6 +917,57 @@ int pc_region_batch(const void* s2, int s2_u16, const float* s1, const int32_t* 
                     const int32_t* band_sel, const int32_t* crops, int B, int Hm, int Wm, int vflip, int hflip, int rot, int bright, float beta,
                     int gam, float gamma, float* raw, float* admin_out, int Ho, int Wo, const pc_region_labels* labels, void* stream);
 
+/* ---- NaN repair of a resident plan, planned once (csrc/region_repair.hip; data/PopulationDataset.py:419-441) ----
+ * pc_region_gather_orbit / pc_region_batch_orbit: pc_region_gather / pc_region_batch with the S1 source chosen per crop.  s1_asc DEVICE fp32
+ * (S, C1, h, w) or NULL; orbit HOST uint8 [B] or NULL (= all zero): crop b reads its two S1 bands from s1_asc where orbit[b] == 1 and from s1
+ * where it is 0.  The choice travels as a 128-bit mask per launch in the kernel arguments.  pc_region_gather and pc_region_batch ARE the calls
+ * with s1_asc = orbit = NULL.  PC_EINVAL before anything is enqueued: everything the plain entry points refuse, orbit[b] > 1, orbit[b] == 1
+ * without s1_asc. */
+int pc_region_gather_orbit(const void* s2, int s2_u16, const float* s1, const float* s1_asc, const uint8_t* orbit, const int32_t* boundary,
+                           int S, int C2, int C1, int h, int w, const int32_t* band_sel, const int32_t* crops, int B, int Hm, int Wm,
+                           float* s2_out, float* s1_out, float* admin_out, int32_t* data_hw, void* stream);
+int pc_region_batch_orbit(const void* s2, int s2_u16, const float* s1, const float* s1_asc, const uint8_t* orbit, const int32_t* boundary,
+                          int S, int C2, int C1, int h, int w, const int32_t* band_sel, const int32_t* crops, int B, int Hm, int Wm, int vflip,
+                          int hflip, int rot, int bright, float beta, int gam, float gamma, float* raw, float* admin_out, int Ho, int Wo,
+                          const pc_region_labels* labels, void* stream);
+/* pc_region_nan_census: counts[k] = {NaN entries of S2 over its four selected bands (a band listed twice counts twice; 0 for uint16 S2), of
+ * s1 over its two selected bands, of s1_asc likewise (0 when s1_asc is NULL)} of box k.  boxes DEVICE int32 [n][5] = {x0, x1, y0, y1, season},
+ * uploaded once by the caller (n runs to thousands: it does not travel in the kernel arguments); rows_max = the largest x1 - x0 of the list
+ * (1 .. h; it sizes the launch: rows of a box beyond it are not counted).  counts DEVICE int64 [n][3], every element written (an init launch,
+ * then one 64-bit atomic add of three lanes per workgroup).  The kernel clamps every box to the rasters and every season to [0, S): the list
+ * is the caller's to validate, a bad one never makes an address outside the sources.  Integer adds only: the same bits for any launch
+ * geometry; max_blocks as pc_region_units takes it.  Sources and band_sel as pc_region_gather; w < 2^29.  PC_EINVAL before anything is
+ * enqueued for whatever pc_region_gather refuses of them. */
+int pc_region_nan_census(const void* s2, int s2_u16, const float* s1, const float* s1_asc, int S, int C2, int C1, int h, int w,
+                         const int32_t* band_sel, const int32_t* boxes, int n, int rows_max, int64_t* counts, int max_blocks, void* stream);
+/* The patch table of a gathered batch and its filled copy (pc_nan_fill): the entries whose 32-bit pattern differs, inside each item's extent
+ * data_hw[b] = {h_b, w_b} (DEVICE int32, what pc_region_gather wrote), as idx = (c * h_b + i) * w_b + j in the item's own (6, h_b, w_b) space
+ * (c = 0 .. 3: S2, 4 .. 5: S1; 6 * Hm * Wm < 2^31) and val = the filled tile's bits.  g2 / f2 DEVICE fp32 (B, 4, Hm, Wm), g1 / f1 (B, 2, Hm, Wm).
+ *   pc_region_patch_count   counts[b][k] (DEVICE int32 [B][nchunk]) = differing entries of chunk k (PC_REGION_PATCH_CHUNK entries of the index
+ *                           space) of item b; nchunk = ceil(6 * Hm * Wm / PC_REGION_PATCH_CHUNK); every element written
+ *   pc_region_patch_write   chunk_off[b][k] (DEVICE int64: the exclusive prefix of the counts, taken by the caller, + the item's base in the
+ *                           table): the entries of chunk k go to idx / val [chunk_off[b][k] ...) in ascending order of idx, so the entries of an
+ *                           item ascend.  Nothing is written at or beyond cap (the table's length).
+ * Deterministic: an entry's place is a function of the data alone (wave ballots, no atomics). */
+#define PC_REGION_PATCH_CHUNK 4096
+int pc_region_patch_count(const float* g2, const float* f2, const float* g1, const float* f1, const int32_t* data_hw, int B, int Hm, int Wm,
+                          int32_t* counts, int nchunk, void* stream);
+int pc_region_patch_write(const float* g2, const float* f2, const float* g1, const float* f1, const int32_t* data_hw, int B, int Hm, int Wm,
+                          const int64_t* chunk_off, int nchunk, int32_t* idx, float* val, int64_t cap, void* stream);
+/* pc_region_patch_apply: lays the patches of B batch items over an assembled batch.  idx / val DEVICE tables of cap entries; per item b, HOST:
+ * off[b] (int64) and count[b] (int32) = its range in the table, item_hw[b] = {h_b, w_b}.  Entry (c, i, j, val) is stored at the image of tile
+ * position (i, j) under vflip, then hflip, then rot quarter turns of the (Hm, Wm) tile -- (Ho, Wo) as pc_region_batch --, as
+ * pc_aug_s2_value(val, bright, beta, gam, gamma) for c < 4 and as val for c >= 4:
+ *   s2 + b * s2_stride + c * Ho * Wo + i' * Wo + j'        s1 + b * s1_stride + (c - 4) * Ho * Wo + i' * Wo + j'        (strides in elements)
+ * which serves raw (B, 6, Ho, Wo) (s1 = raw + 4 * Ho * Wo, both strides 6 * Ho * Wo) and separate S2 / S1 tensors alike.  By definition, bit
+ * for bit:  patch_apply(pc_region_batch_orbit(crops, orbit, coins)) == pc_augment_raw(pc_nan_fill(pc_region_gather_orbit(crops, orbit)), coins).
+ * Plain 4-byte stores on `stream`, no synchronisation; a launch takes up to PC_REGION_GATHER_MAX_B items (their ranges travel in the kernel
+ * arguments), none is made for items without entries.  PC_EINVAL before anything is enqueued: a range outside [0, cap], an item with entries
+ * whose extent is empty or exceeds (Hm, Wm), (Ho, Wo) other than stated, rot outside 0 .. 3, a stride smaller than the planes it spans. */
+int pc_region_patch_apply(const int32_t* idx, const float* val, int64_t cap, const int64_t* off, const int32_t* count, const int32_t* item_hw,
+                          int B, float* s2, int64_t s2_stride, float* s1, int64_t s1_stride, int Hm, int Wm, int Ho, int Wo, int vflip,
+                          int hflip, int rot, int bright, float beta, int gam, float gamma, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

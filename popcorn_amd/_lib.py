@@ -162,6 +162,7 @@ class PcStepUnits(C.Structure):
 
 PC_UNIT_LAYOUT_MAX_K, PC_UNIT_LAYOUT_MAX_B = 1024, 256
 PC_REGION_GATHER_MAX_B = 128          # crops per pc_region_gather launch (the crop list travels in the kernel arguments)
+PC_REGION_PATCH_CHUNK = 4096          # entries of an item's index space per workgroup of pc_region_patch_count / _write
 
 
 class PcRegionLabels(C.Structure):
@@ -236,6 +237,22 @@ def lib():
         _lib.pc_region_batch.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
                                          [C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_int] * 7 + [C.c_float, C.c_int, C.c_float] +
                                          [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(PcRegionLabels), C.c_void_p])
+        # the resident repair (csrc/region_repair.hip): the orbit forms take s1_asc and a HOST uint8 orbit list after s1
+        _lib.pc_region_gather_orbit.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), C.c_void_p] +
+                                                [C.c_int] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_int] * 3 +
+                                                [C.c_void_p] * 5)
+        _lib.pc_region_batch_orbit.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), C.c_void_p] +
+                                               [C.c_int] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_int] * 7 +
+                                               [C.c_float, C.c_int, C.c_float] +
+                                               [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(PcRegionLabels), C.c_void_p])
+        _lib.pc_region_nan_census.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
+                                              [C.POINTER(C.c_int32), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p])
+        _lib.pc_region_patch_count.argtypes = [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p]
+        _lib.pc_region_patch_write.argtypes = ([C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64,
+                                               C.c_void_p])
+        _lib.pc_region_patch_apply.argtypes = ([C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                                C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] +
+                                               [C.c_int] * 8 + [C.c_float, C.c_int, C.c_float, C.c_void_p])
     return _lib
 
 

@@ -116,6 +116,13 @@ def train_parser():
     p.add_argument("--resident_max_batch", type=int, default=128, help="--resident_pixel_budget: at most this many crops per batch")
     p.add_argument("--resident_min_fill", type=float, default=0.6,
                    help="--resident_pixel_budget: a batch of more than one crop keeps real pixels / padded pixels at or above this")
+    p.add_argument("--resident_repair", action="store_true",
+                   help="--resident_region: the reference's per-item NaN repair planned ONCE (data/region.py: plan_repair) -- the S1 orbit of "
+                        "every crop from one census pass (--ascfill as the reference's), the repaired sites as a patch table on the device, "
+                        "one small launch per batch and no per-step fill; works with every resident feed (pair with --nan_clouds / "
+                        "--resident_s1_gap)")
+    p.add_argument("--resident_s1_gap", type=float, default=0.0, metavar="F",
+                   help="--resident_repair: orbit-gap rows over this fraction of the synthetic raster's descending S1")
     return p
 
 
@@ -249,9 +256,22 @@ def limit_regime(num_pix, limit1, limit2, limit3):
     return enc_ng, unet_ng, skip
 
 
+def check_repair_args(args):
+    """The refusals of --resident_repair and its companions that need no device: raised before anything else is set up."""
+    if args.resident_repair and args.resident_region is None:
+        raise SystemExit("--resident_repair plans the NaN repair of a resident crop plan (orbit column and patch table on the device): it "
+                         "needs --resident_region")
+    if args.resident_s1_gap and not args.resident_repair:
+        raise SystemExit("--resident_s1_gap cuts orbit gaps that only the orbit choice of --resident_repair answers: it needs "
+                         "--resident_repair")
+    if not 0.0 <= args.resident_s1_gap <= 1.0:
+        raise SystemExit("--resident_s1_gap is a fraction of the raster's rows in [0, 1]")
+
+
 class Trainer:
     def __init__(self, args):
         self.args = args
+        check_repair_args(args)
         self.rank, self.local_rank, self.world = init_from_env()
         if not torch.cuda.is_available():
             raise SystemExit("popcorn_amd training needs a HIP device (no CPU path)")
@@ -267,6 +287,7 @@ class Trainer:
         seed_all(args.seed)
         collate = Population_Dataset_collate_fn
         self._resident_feed = None
+        self._step_nan_fill = args.nan_fill                              # --resident_repair: the repair is in the batch already
         if (args.resident_assemble or args.resident_pixel_budget > 0) and args.resident_region is None:
             raise SystemExit("--resident_assemble / --resident_pixel_budget assemble batches from resident rasters: they need "
                              "--resident_region")
@@ -343,21 +364,30 @@ class Trainer:
         if self.world > 1:
             raise SystemExit("--resident_region runs in a single process: sharding a crop plan over data-parallel ranks is not part of it")
         assemble = a.resident_assemble or a.resident_pixel_budget > 0
-        if assemble and a.nan_fill:
+        if assemble and a.nan_fill and not a.resident_repair:
             raise SystemExit("--resident_assemble / --resident_pixel_budget cannot be combined with --nan_fill: the fill sits between the "
                              "gather and the augmentation, which the one-launch assembly fuses; the unfused --resident_region feed takes it")
         if a.resident_pixel_budget < 0 or a.resident_max_batch < 1 or not 0.0 <= a.resident_min_fill <= 1.0:
             raise SystemExit("--resident_pixel_budget >= 0, --resident_max_batch >= 1 and --resident_min_fill in [0, 1]")
-        from .data.region import ResidentBatchFeed, ResidentRegion, ResidentRegionFeed, plan_multi_unit, plan_one_unit
+        from .data.region import ResidentBatchFeed, ResidentRegion, ResidentRegionFeed, plan_multi_unit, plan_one_unit, plan_repair
         data = SyntheticTestRaster(a.resident_region[0], a.resident_region[1], seasons=1, n_regions=a.resident_units, seed=a.seed + 20,
-                                   device=self.device, raw=True, nan_clouds=a.nan_clouds)
-        self.region = ResidentRegion.from_synthetic(data)
+                                   device=self.device, raw=True, nan_clouds=a.nan_clouds, s1_gap=a.resident_s1_gap)
+        self.region = ResidentRegion.from_synthetic(data, with_asc=a.resident_repair)
         kw = dict(max_pix=a.max_weak_pix, max_pix_box=a.max_pix_box)
         if a.units_per_crop > 0:
             self.region_plan = plan_multi_unit(self.region.table, self.region.census_idx, self.region.census_pop, self.region.shape,
                                                units_per_crop=a.units_per_crop, **kw)
         else:
             self.region_plan = plan_one_unit(self.region.table, self.region.census_idx, self.region.census_pop, self.region.shape, **kw)
+        self.region_repair = None
+        if a.resident_repair:
+            n0 = len(self.region_plan)
+            self.region_plan, self.region_repair = plan_repair(self.region, self.region_plan, seasons=1, ascfill=a.ascfill)
+            self._step_nan_fill = False
+            r = self.region_repair
+            if self.rank == 0:
+                print(f"resident repair: {n0} items, {len(r.dropped)} dropped, {r.ascending} ascending, {r.entries} table entries "
+                      f"({r.nbytes} bytes), built in {r.build_ms:.1f} ms", flush=True)
         if len(self.region_plan) < a.weak_batch_size:
             raise SystemExit(f"--resident_region: the plan holds {len(self.region_plan)} crops, fewer than one batch of {a.weak_batch_size}")
         gen = torch.Generator().manual_seed(a.seed)
@@ -366,9 +396,10 @@ class Trainer:
             # Trainer.__init__ hands it the trainer's own data_transform, the same set, once that exists
             self._resident_feed = ResidentBatchFeed(self.region, self.region_plan, a.weak_batch_size, transform=default_train_transform(),
                                                     generator=gen, drop_last=True, pixel_budget=a.resident_pixel_budget,
-                                                    max_batch=a.resident_max_batch, min_fill=a.resident_min_fill)
+                                                    max_batch=a.resident_max_batch, min_fill=a.resident_min_fill, repair=self.region_repair)
         else:
-            self._resident_feed = ResidentRegionFeed(self.region, self.region_plan, a.weak_batch_size, generator=gen, drop_last=True)
+            self._resident_feed = ResidentRegionFeed(self.region, self.region_plan, a.weak_batch_size, generator=gen, drop_last=True,
+                                                     repair=self.region_repair)
 
     # ---- checkpoint (run_train.py:445-476) --------------------------------------------------------------------------
     def save_model(self, prefix="last"):
@@ -429,9 +460,9 @@ class Trainer:
             s = {k: sample[k] for k in ("raw", "admin_mask", "census_idx", "y")}
         elif self.fused is not None and torch.is_tensor(sample.get("S2")) and sample["S2"].is_cuda:
             # a batch staged by the feed: augmentation + assembly in one launch, normalisation inside the step (raw input form)
-            s = prepare_sample_fused(sample, self.data_transform, nan_fill=a.nan_fill)
+            s = prepare_sample_fused(sample, self.data_transform, nan_fill=self._step_nan_fill)
         if s is None:
-            s = normalize_sample(sample, self.device, self.data_transform, nan_fill=a.nan_fill)
+            s = normalize_sample(sample, self.device, self.data_transform, nan_fill=self._step_nan_fill)
         if sample.get("census_n") is not None:             # multi-unit items (--units_per_crop): the valid units per row, host data
             s["census_n"] = sample["census_n"]
             K = s["census_idx"].shape[1]

@@ -27,6 +27,8 @@
 // element.  fp32 payloads pass through registers untouched: a NaN keeps its payload.  The crop list travels in the kernel arguments (up to
 // PC_REGION_GATHER_MAX_B crops per launch; longer batches are split): no host-to-device copy, no synchronisation.  The host wrapper
 // validates every crop before anything is enqueued; the kernel never forms an address outside the sources.
+// pc_region_gather_orbit is the same kernel with the S1 source chosen per crop: a second raster (the ascending orbit) and a 128-bit mask per
+// launch in the kernel arguments; pc_region_gather is its call without either (region_repair.hip plans the mask once per region).
 #include "common.h"
 #include "region_load.h"
 
@@ -157,9 +159,10 @@ __global__ __launch_bounds__(256) void region_units_finish_kernel(int32_t* table
 
 // ---- the gather ------------------------------------------------------------------------------------------------------------------------
 struct RegionGatherArgs {
-    const void* s2; const float* s1; const int32_t* boundary;
+    const void* s2; const float* s1; const float* s1_asc; const int32_t* boundary;
     int C2, C1, h, w;
     int band2[4], band1[2];                                     // source band of output channel c
+    uint32_t orbit[PC_REGION_GATHER_MAX_B / 32];                // bit b: crop b reads its S1 from s1_asc (16 bytes; zero: every crop from s1)
     float* o2; float* o1; float* adm; int32_t* data_hw;          // already offset to the launch's first crop
     int Hm, Wm;
     int32_t crop[PC_REGION_GATHER_MAX_B][5];                     // {x0, x1, y0, y1, season}, validated by the host: 2,560 bytes of arguments
@@ -174,7 +177,7 @@ __global__ __launch_bounds__(RG_THREADS) void region_gather_kernel(const RegionG
     if (blockIdx.x == 0 && t == 0) { a.data_hw[2 * b] = hb; a.data_hw[2 * b + 1] = wb; }
     const int64_t plane = (int64_t)a.h * a.w, oplane = (int64_t)a.Hm * a.Wm;
     const T2* s2 = reinterpret_cast<const T2*>(a.s2) + (int64_t)a.crop[b][4] * a.C2 * plane;
-    const float* s1 = a.s1 + (int64_t)a.crop[b][4] * a.C1 * plane;
+    const float* s1 = (((a.orbit[b >> 5] >> (b & 31)) & 1u) ? a.s1_asc : a.s1) + (int64_t)a.crop[b][4] * a.C1 * plane;
     float* o2 = a.o2 + (int64_t)b * 4 * oplane;
     float* o1 = a.o1 + (int64_t)b * 2 * oplane;
     float* adm = a.adm + (int64_t)b * oplane;
@@ -264,10 +267,15 @@ extern "C" int pc_region_units(const int32_t* boundary, int h, int w, int num_id
     return 0;
 }
 
-extern "C" int pc_region_gather(const void* s2, int s2_u16, const float* s1, const int32_t* boundary, int S, int C2, int C1, int h, int w,
-                                const int32_t* band_sel, const int32_t* crops, int B, int Hm, int Wm, float* s2_out, float* s1_out,
-                                float* admin_out, int32_t* data_hw, void* stream) {
+extern "C" int pc_region_gather_orbit(const void* s2, int s2_u16, const float* s1, const float* s1_asc, const uint8_t* orbit,
+                                      const int32_t* boundary, int S, int C2, int C1, int h, int w, const int32_t* band_sel,
+                                      const int32_t* crops, int B, int Hm, int Wm, float* s2_out, float* s1_out, float* admin_out,
+                                      int32_t* data_hw, void* stream) {
     if (!s2 || !s1 || !boundary || !band_sel || !crops || !s2_out || !s1_out || !admin_out || !data_hw) return PC_EINVAL;
+    if (reinterpret_cast<uintptr_t>(s1_asc) & 3) return PC_EINVAL;
+    if (orbit && B >= 1)
+        for (int b = 0; b < B; ++b)
+            if (orbit[b] > 1 || (orbit[b] && !s1_asc)) return PC_EINVAL;      // an ascending crop needs the ascending raster
     if (S < 1 || C2 < 1 || C1 < 1 || h < 1 || w < 1 || B < 1 || Hm < 1 || Wm < 1) return PC_EINVAL;
     if ((int64_t)h * w >= ((int64_t)1 << 31) || (int64_t)Hm * Wm >= ((int64_t)1 << 31)) return PC_EINVAL;
     if ((reinterpret_cast<uintptr_t>(s1) | reinterpret_cast<uintptr_t>(boundary) | reinterpret_cast<uintptr_t>(s2_out) |
@@ -286,7 +294,7 @@ extern "C" int pc_region_gather(const void* s2, int s2_u16, const float* s1, con
                                         reinterpret_cast<uintptr_t>(admin_out)) & 15) == 0;
     const int64_t oplane = (int64_t)Hm * Wm;
     RegionGatherArgs a{};
-    a.s2 = s2; a.s1 = s1; a.boundary = boundary; a.C2 = C2; a.C1 = C1; a.h = h; a.w = w; a.Hm = Hm; a.Wm = Wm;
+    a.s2 = s2; a.s1 = s1; a.s1_asc = s1_asc; a.boundary = boundary; a.C2 = C2; a.C1 = C1; a.h = h; a.w = w; a.Hm = Hm; a.Wm = Wm;
     for (int c = 0; c < 4; ++c) a.band2[c] = band_sel[c];
     for (int c = 0; c < 2; ++c) a.band1[c] = band_sel[4 + c];
     for (int b0 = 0; b0 < B; b0 += PC_REGION_GATHER_MAX_B) {
@@ -295,9 +303,21 @@ extern "C" int pc_region_gather(const void* s2, int s2_u16, const float* s1, con
         a.data_hw = data_hw + 2 * (int64_t)b0;
         for (int b = 0; b < Bc; ++b)
             for (int k = 0; k < 5; ++k) a.crop[b][k] = crops[5 * (int64_t)(b0 + b) + k];
+        for (int k = 0; k < PC_REGION_GATHER_MAX_B / 32; ++k) a.orbit[k] = 0;
+        if (orbit)
+            for (int b = 0; b < Bc; ++b)
+                if (orbit[b0 + b]) a.orbit[b >> 5] |= 1u << (b & 31);
         if (s2_u16) rg_launch<uint16_t>(a, Bc, vec, (hipStream_t)stream);
         else rg_launch<float>(a, Bc, vec, (hipStream_t)stream);
         PC_CHECK_LAUNCH();
     }
     return 0;
+}
+
+// the mask-zero call of the same code
+extern "C" int pc_region_gather(const void* s2, int s2_u16, const float* s1, const int32_t* boundary, int S, int C2, int C1, int h, int w,
+                                const int32_t* band_sel, const int32_t* crops, int B, int Hm, int Wm, float* s2_out, float* s1_out,
+                                float* admin_out, int32_t* data_hw, void* stream) {
+    return pc_region_gather_orbit(s2, s2_u16, s1, nullptr, nullptr, boundary, S, C2, C1, h, w, band_sel, crops, B, Hm, Wm, s2_out, s1_out,
+                                  admin_out, data_hw, stream);
 }

@@ -22,8 +22,12 @@
 // plan_y fp32, (n, Kp), uploaded once) into census_idx_out / y_out (B, K).  Crops, items, coins and the band selection travel by value in
 // the kernel arguments (the idiom of RegionGatherArgs): no device descriptor, no copy, no synchronisation.  The host wrapper validates
 // everything before anything is enqueued.
+// pc_region_batch_orbit is the same code with the S1 source chosen per crop (s1_asc and a 128-bit mask per launch in the kernel arguments);
+// pc_region_batch is its call without either.  The map between output and tile positions is region_index.h's, which the patch launch of
+// region_repair.hip uses in the other direction.
 #include "common.h"
 #include "aug_value.h"
+#include "region_index.h"
 #include "region_load.h"
 
 namespace {
@@ -32,9 +36,10 @@ constexpr int RB_THREADS = 256;
 constexpr int RB_MAX_BLOCKS = 2048;      // workgroups of a launch
 
 struct RegionBatchArgs {
-    const void* s2; const float* s1; const int32_t* boundary;
+    const void* s2; const float* s1; const float* s1_asc; const int32_t* boundary;
     int C2, C1, h, w;
     int band2[4], band1[2];                                     // source band of output channel c
+    uint32_t orbit[PC_REGION_GATHER_MAX_B / 32];                // bit b: crop b reads its S1 from s1_asc (16 bytes; zero: every crop from s1)
     float* raw; float* adm;                                     // already offset to the launch's first crop
     int Hm, Wm, Ho, Wo;                                         // the gathered tile and the output: (Ho, Wo) = (Wm, Hm) for odd rot
     int vflip, hflip, rot;
@@ -69,11 +74,11 @@ __global__ __launch_bounds__(RB_THREADS) void region_batch_kernel(const RegionBa
     const int hb = a.crop[b][1] - x0, wb = a.crop[b][3] - y0;     // 1 <= hb <= Hm, 1 <= wb <= Wm (host)
     const int64_t plane = (int64_t)a.h * a.w, oplane = (int64_t)a.Hm * a.Wm;
     const T2* s2 = reinterpret_cast<const T2*>(a.s2) + (int64_t)a.crop[b][4] * a.C2 * plane;
-    const float* s1 = a.s1 + (int64_t)a.crop[b][4] * a.C1 * plane;
+    const float* s1 = (((a.orbit[b >> 5] >> (b & 31)) & 1u) ? a.s1_asc : a.s1) + (int64_t)a.crop[b][4] * a.C1 * plane;
     float* raw = a.raw + (int64_t)b * 6 * oplane;
     float* adm = a.adm + (int64_t)b * oplane;
     // out = rot90^k(hflip(vflip(T))), k in {0, 2}: a half turn mirrors both axes, a flip mirrors one
-    const bool yrev = ((a.rot & 2) != 0) != (a.vflip != 0), xrev = ((a.rot & 2) != 0) != (a.hflip != 0);
+    const bool yrev = pc_region_yrev(a.vflip, a.rot), xrev = pc_region_xrev(a.hflip, a.rot);
     const bool value = a.bright || a.gam;
     const float pad2 = pc_aug_s2_value(0.f, a.bright, a.beta, a.gam, a.gamma);     // what the composite makes of the S2 padding
     const int wg = a.Wm / V, groups = a.Hm * wg;                   // (Hm * Wm < 2^31: host)
@@ -150,7 +155,7 @@ __global__ __launch_bounds__(RB_THREADS) void region_batch_transposed_kernel(con
     const int hb = a.crop[b][1] - x0, wb = a.crop[b][3] - y0;
     const int64_t plane = (int64_t)a.h * a.w, oplane = (int64_t)a.Ho * a.Wo;
     const T2* s2 = reinterpret_cast<const T2*>(a.s2) + (int64_t)a.crop[b][4] * a.C2 * plane;
-    const float* s1 = a.s1 + (int64_t)a.crop[b][4] * a.C1 * plane;
+    const float* s1 = (((a.orbit[b >> 5] >> (b & 31)) & 1u) ? a.s1_asc : a.s1) + (int64_t)a.crop[b][4] * a.C1 * plane;
     float* raw = a.raw + (int64_t)b * 6 * oplane;
     float* adm = a.adm + (int64_t)b * oplane;
     const float pad2 = pc_aug_s2_value(0.f, a.bright, a.beta, a.gam, a.gamma);
@@ -167,9 +172,7 @@ __global__ __launch_bounds__(RB_THREADS) void region_batch_transposed_kernel(con
             const int i = i0 + di, j = j0 + dj;
             if (i < a.Ho && j < a.Wo) {
                 int y, x;
-                if ((a.rot & 3) == 1) { y = j; x = a.Wm - 1 - i; } else { y = a.Hm - 1 - j; x = i; }
-                if (a.hflip) x = a.Wm - 1 - x;
-                if (a.vflip) y = a.Hm - 1 - y;
+                pc_region_out_to_tile(i, j, a.Hm, a.Wm, a.vflip, a.hflip, a.rot, y, x);
                 const bool in = y < hb && x < wb;
                 const int64_t s = (int64_t)(x0 + min(y, hb - 1)) * a.w + y0 + min(x, wb - 1);      // inside the crop whatever `in` says
 #pragma unroll
@@ -218,11 +221,16 @@ inline void rb_launch(const RegionBatchArgs& a, int Bc, bool vec, hipStream_t st
 
 }  // namespace
 
-extern "C" int pc_region_batch(const void* s2, int s2_u16, const float* s1, const int32_t* boundary, int S, int C2, int C1, int h, int w,
-                               const int32_t* band_sel, const int32_t* crops, int B, int Hm, int Wm, int vflip, int hflip, int rot,
-                               int bright, float beta, int gam, float gamma, float* raw, float* admin_out, int Ho, int Wo,
-                               const pc_region_labels* labels, void* stream) {
+extern "C" int pc_region_batch_orbit(const void* s2, int s2_u16, const float* s1, const float* s1_asc, const uint8_t* orbit,
+                                     const int32_t* boundary, int S, int C2, int C1, int h, int w, const int32_t* band_sel,
+                                     const int32_t* crops, int B, int Hm, int Wm, int vflip, int hflip, int rot, int bright, float beta,
+                                     int gam, float gamma, float* raw, float* admin_out, int Ho, int Wo, const pc_region_labels* labels,
+                                     void* stream) {
     if (!s2 || !s1 || !boundary || !band_sel || !crops || !raw || !admin_out) return PC_EINVAL;
+    if (reinterpret_cast<uintptr_t>(s1_asc) & 3) return PC_EINVAL;
+    if (orbit && B >= 1)
+        for (int b = 0; b < B; ++b)
+            if (orbit[b] > 1 || (orbit[b] && !s1_asc)) return PC_EINVAL;      // an ascending crop needs the ascending raster
     if (S < 1 || C2 < 1 || C1 < 1 || h < 1 || w < 1 || B < 1 || Hm < 1 || Wm < 1 || rot < 0 || rot > 3) return PC_EINVAL;
     if (Ho != ((rot & 1) ? Wm : Hm) || Wo != ((rot & 1) ? Hm : Wm)) return PC_EINVAL;
     if ((int64_t)h * w >= ((int64_t)1 << 31) || (int64_t)Hm * Wm >= ((int64_t)1 << 31)) return PC_EINVAL;
@@ -249,7 +257,7 @@ extern "C" int pc_region_batch(const void* s2, int s2_u16, const float* s1, cons
     const bool vec = (Wm & 3) == 0 && ((reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(admin_out)) & 15) == 0;
     const int64_t oplane = (int64_t)Hm * Wm;
     RegionBatchArgs a{};
-    a.s2 = s2; a.s1 = s1; a.boundary = boundary; a.C2 = C2; a.C1 = C1; a.h = h; a.w = w; a.Hm = Hm; a.Wm = Wm; a.Ho = Ho; a.Wo = Wo;
+    a.s2 = s2; a.s1 = s1; a.s1_asc = s1_asc; a.boundary = boundary; a.C2 = C2; a.C1 = C1; a.h = h; a.w = w; a.Hm = Hm; a.Wm = Wm; a.Ho = Ho; a.Wo = Wo;
     a.vflip = vflip != 0; a.hflip = hflip != 0; a.rot = rot; a.bright = bright != 0; a.gam = gam != 0; a.beta = beta; a.gamma = gamma;
     for (int c = 0; c < 4; ++c) a.band2[c] = band_sel[c];
     for (int c = 0; c < 2; ++c) a.band1[c] = band_sel[4 + c];
@@ -259,6 +267,10 @@ extern "C" int pc_region_batch(const void* s2, int s2_u16, const float* s1, cons
         a.raw = raw + (int64_t)b0 * 6 * oplane; a.adm = admin_out + (int64_t)b0 * oplane;
         for (int b = 0; b < Bc; ++b)
             for (int k = 0; k < 5; ++k) a.crop[b][k] = crops[5 * (int64_t)(b0 + b) + k];
+        for (int k = 0; k < PC_REGION_GATHER_MAX_B / 32; ++k) a.orbit[k] = 0;
+        if (orbit)
+            for (int b = 0; b < Bc; ++b)
+                if (orbit[b0 + b]) a.orbit[b >> 5] |= 1u << (b & 31);
         if (labels) {
             a.cidx_out = labels->census_idx_out + (int64_t)b0 * labels->K; a.y_out = labels->y_out + (int64_t)b0 * labels->K;
             for (int b = 0; b < Bc; ++b) a.item[b] = labels->items[b0 + b];
@@ -268,4 +280,13 @@ extern "C" int pc_region_batch(const void* s2, int s2_u16, const float* s1, cons
         PC_CHECK_LAUNCH();
     }
     return 0;
+}
+
+// the mask-zero call of the same code
+extern "C" int pc_region_batch(const void* s2, int s2_u16, const float* s1, const int32_t* boundary, int S, int C2, int C1, int h, int w,
+                               const int32_t* band_sel, const int32_t* crops, int B, int Hm, int Wm, int vflip, int hflip, int rot,
+                               int bright, float beta, int gam, float gamma, float* raw, float* admin_out, int Ho, int Wo,
+                               const pc_region_labels* labels, void* stream) {
+    return pc_region_batch_orbit(s2, s2_u16, s1, nullptr, nullptr, boundary, S, C2, C1, h, w, band_sel, crops, B, Hm, Wm, vflip, hflip, rot,
+                                 bright, beta, gam, gamma, raw, admin_out, Ho, Wo, labels, stream);
 }

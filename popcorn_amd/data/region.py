@@ -12,11 +12,14 @@ and pixel counts are made at preprocessing time with one pass per unit (utils/02
                           staging / copy stream and no producer thread
   ``ResidentBatchFeed``   the same batches in the form the fused step takes -- gather, augmentation, raw tile and labels in ONE
                           ``ops.region_batch`` launch --, cut at a fixed count or composed by size under a pixel budget (``plan_batches``)
+  ``plan_repair``         the reference's per-item NaN repair (:419-441), decided ONCE for a plan: the S1 orbit of every (item, season) from
+                          one census pass, the repaired sites as a sparse patch table in HBM (``RegionRepair``); a feed built with
+                          ``repair=`` gathers with orbits and lays each batch's patches over it with one small launch
 
-Host glue, plain torch; the kernels are csrc/region.hip and csrc/region_batch.hip.  Deviations from the reference, all named where they happen: units without pixels
+Host glue, plain torch; the kernels are csrc/region.hip, csrc/region_batch.hip and csrc/region_repair.hip.  Deviations from the reference, all named where they happen: units without pixels
 are dropped (``plan_one_unit``); the per-epoch order and the season per item come from a torch generator, not Python's ``random`` stream
-(``ResidentRegionFeed``); the resident S1 is the orbit already chosen per season (no switch by NaN fraction: ``--nan_fill`` fills what is
-left).  Sharding a plan over data-parallel ranks and graph capture of the gather are not part of this module."""
+(``ResidentRegionFeed``); without ``plan_repair`` the resident S1 is the orbit already chosen per season (``--nan_fill`` fills what is
+left), with it an item the reference would end on ("No data here!") is dropped from the plan.  Sharding a plan over data-parallel ranks and graph capture of the gather are not part of this module."""
 from __future__ import annotations
 
 import contextlib
@@ -29,22 +32,25 @@ from .. import ops
 REFERENCE_BANDS = (2, 1, 0, 3, 0, 1)      # file bands (3, 2, 1, 4) of S2 and (1, 2) of S1, 1-based (PopulationDataset.py:566-568), 0-based
 MODEL_ORDER_BANDS = (0, 1, 2, 3, 0, 1)    # rasters whose bands are stored in the model's order already (SyntheticTestRaster)
 MAX_PIX, MAX_PIX_BOX = 10_000_000, 12_000_000      # the reference's defaults (PopulationDataset.py:124-131)
+PC_GATHER_MAX_B = 128                               # crops of one gather launch (popcorn_hip.h: PC_REGION_GATHER_MAX_B)
 
 
 class ResidentRegion:
     """The rasters of one region on the device: s2 (S, C2, h, w) fp32 or uint16 digital numbers, s1 fp32 (S, C1, h, w), boundary int32
-    (h, w) of census-unit ids, and the census table (census_idx (n,) ids, census_pop (n,) counts; host).  ``table`` (host int32
+    (h, w) of census-unit ids, optionally s1_asc (the ascending-orbit S1, shaped and checked like s1), and the census table (census_idx (n,) ids, census_pop (n,) counts; host).  ``table`` (host int32
     (num_ids, 5) = {xmin, xmax, ymin, ymax, count}, the reference's convention) is computed once on the device.  Raises when the boundary
     holds ids outside [0, num_ids) (num_ids defaults to the largest census id + 1) and when the tensors that still have to move do not
     fit the device's free memory."""
 
-    def __init__(self, s2, s1, boundary, census_idx, census_pop, band_sel=REFERENCE_BANDS, device=None, num_ids=None):
+    def __init__(self, s2, s1, boundary, census_idx, census_pop, band_sel=REFERENCE_BANDS, device=None, num_ids=None, s1_asc=None):
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if dev.type != "cuda":
             raise ValueError(f"ResidentRegion: the region lives on a HIP device, got {dev}")
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
-        need = sum(t.numel() * t.element_size() for t in (s2, s1, boundary) if t.device != dev)
+        if s1_asc is not None and tuple(s1_asc.shape) != tuple(s1.shape):
+            raise ValueError(f"ResidentRegion: s1_asc is shaped like s1 {tuple(s1.shape)}, got {tuple(s1_asc.shape)}")
+        need = sum(t.numel() * t.element_size() for t in (s2, s1, boundary, s1_asc) if t is not None and t.device != dev)
         if need:
             free, total = torch.cuda.mem_get_info(dev)
             if need > free:
@@ -52,6 +58,7 @@ class ResidentRegion:
                                   f"of {total / 2 ** 30:.2f}: keep fewer seasons resident or store S2 as uint16")
         self.s2 = s2.to(dev).contiguous()
         self.s1 = s1.to(dev).float().contiguous()
+        self.s1_asc = None if s1_asc is None else s1_asc.to(dev).float().contiguous()
         self.boundary = boundary.to(dev).to(torch.int32).contiguous()
         if self.s2.dtype not in (torch.float32, torch.uint16):
             raise ValueError(f"ResidentRegion: S2 as fp32 or uint16, got {self.s2.dtype}")
@@ -72,16 +79,20 @@ class ResidentRegion:
         self.table = table.cpu()
 
     @classmethod
-    def from_synthetic(cls, data, device=None):
-        """From a ``SyntheticTestRaster(raw=True, ...)``: its S2 / S1 / boundary / census table, bands in the model's order."""
+    def from_synthetic(cls, data, device=None, with_asc=False):
+        """From a ``SyntheticTestRaster(raw=True, ...)``: its S2 / S1 / boundary / census table, bands in the model's order.  with_asc: its
+        ascending-orbit S1 stays resident as well (a third more S1 memory; off by default)."""
         if not getattr(data, "raw", False):
             raise ValueError("ResidentRegion.from_synthetic: a SyntheticTestRaster(raw=True)")
         return cls(data.s2, data.s1, data.boundary, data.census_idx, data.census_pop, band_sel=MODEL_ORDER_BANDS,
-                   device=data.s2.device if data.s2.is_cuda and device is None else device)
+                   device=data.s2.device if data.s2.is_cuda and device is None else device, s1_asc=data.s1_asc if with_asc else None)
 
-    def gather(self, crops, out=None):
-        """``ops.region_gather`` of host crops (B, 5) = {x0, x1, y0, y1, season} on this region."""
-        return ops.region_gather(self.s2, self.s1, self.boundary, self.band_sel, crops, out=out)
+    def gather(self, crops, out=None, orbit=None):
+        """``ops.region_gather`` of host crops (B, 5) = {x0, x1, y0, y1, season} on this region; orbit: per crop 0 = descending S1,
+        1 = ascending (None: the plain gather)."""
+        if orbit is None:
+            return ops.region_gather(self.s2, self.s1, self.boundary, self.band_sel, crops, out=out)
+        return ops.region_gather(self.s2, self.s1, self.boundary, self.band_sel, crops, out=out, s1_asc=self.s1_asc, orbit=orbit)
 
 
 class RegionPlan:
@@ -94,6 +105,11 @@ class RegionPlan:
 
     def __len__(self):
         return int(self.crops.shape[0])
+
+    def subset(self, rows):
+        """The plan of the listed rows, in the listed order: every table keeps its row."""
+        sel = torch.as_tensor(list(rows), dtype=torch.int64)
+        return RegionPlan(self.crops[sel], self.census_idx[sel], self.y[sel], [self.census_n[int(i)] for i in sel], self.bbox[sel], self.multi)
 
     def __eq__(self, other):
         return (isinstance(other, RegionPlan) and self.multi == other.multi and self.census_n == other.census_n and
@@ -191,6 +207,160 @@ def plan_multi_unit(table, census_idx, census_pop, shape, units_per_crop=4, admi
     return RegionPlan(_grow(union, shape, admin_overlap), cidx, y, [len(mem) for mem in lists], union, multi=True)
 
 
+class RegionRepair:
+    """What ``plan_repair`` decided for a plan of n items over S seasons, all of it fixed before the first step:
+    orbit int8 (n, S): 0 = the descending S1, 1 = the ascending one; dropped: the rows of the ORIGINAL plan that were taken out, kept: the
+    rows that stayed (row k of the new plan is row kept[k] of the original); counts int64 (n, S, 3): the census of every kept (item,
+    season) = NaN entries of {S2, descending S1, ascending S1}; the patch table idx int32 / val fp32 (device) with off int64 (n * S + 1)
+    on the host and the device (``off_dev``): the entries of (item i, season s) are [off[i * S + s], off[i * S + s + 1]), ascending, idx =
+    (c * h + i) * w + j in the item's own (6, h, w) space; hw: the items' extents; entries, nbytes (table bytes on the device),
+    ascending (how many (item, season) pairs switched orbit), build_ms."""
+
+    def __init__(self, orbit, dropped, kept, counts, idx, val, off, hw, build_ms=0.0):
+        self.orbit, self.dropped, self.kept, self.counts, self.idx, self.val, self.off = orbit, list(dropped), list(kept), counts, idx, val, off
+        self.hw = [(int(h), int(w)) for h, w in hw]
+        self.n, self.seasons = int(orbit.shape[0]), int(orbit.shape[1])
+        self.off_dev = off.to(idx.device)
+        self.entries = int(off[-1])
+        self.nbytes = 8 * self.entries + 8 * off.numel()
+        self.ascending = int(orbit.sum())
+        self.build_ms = float(build_ms)
+        self._orbit = orbit.numpy()
+        self._off = off.numpy()
+        self._hw = np.asarray(self.hw, dtype=np.int64).reshape(-1, 2)
+
+    def orbit_of(self, items, seasons):
+        """The orbit of every (item, season) of a batch: a host uint8 array."""
+        return self._orbit[np.asarray(items, dtype=np.int64), np.asarray(seasons, dtype=np.int64)].astype(np.uint8)
+
+    def ranges(self, items, seasons):
+        """(off, count, item_hw) of a batch's items: host arrays for ``ops.region_patch_apply``."""
+        k = np.asarray(items, dtype=np.int64) * self.seasons + np.asarray(seasons, dtype=np.int64)
+        return self._off[k], self._off[k + 1] - self._off[k], self._hw[np.asarray(items, dtype=np.int64)]
+
+    def apply(self, items, seasons, s2, s1, hw, params=None):
+        """Lay the batch's patches over s2 / s1 (``ops.region_patch_apply``); no launch when the host table shows no entry for the batch."""
+        off, count, item_hw = self.ranges(items, seasons)
+        if not count.any():
+            return 0
+        return ops.region_patch_apply(self.idx, self.val, off, count, item_hw, s2, s1, hw, params)
+
+
+def item_orbit(n_desc, n_asc, numel, ascfill=False, has_asc=True):
+    """The orbit of one (item, season) from its census: (0 | 1, ok).  With an ascending raster the rule is ``nanfill.s1_orbit`` /
+    ``nanfill.asc_fill`` unchanged (numel = 2 * h * w of the item); ok False where the reference raises "No data here!".  Without one the
+    descending orbit is kept and filled at any fraction."""
+    from . import nanfill
+    if not has_asc or nanfill.s1_orbit(n_desc, numel, ascfill)[0] == "desc":
+        return 0, True
+    try:
+        nanfill.asc_fill(n_asc, numel)
+    except Exception as e:                                             # the reference's exception type: told apart by its words
+        if str(e) != "No data here!":
+            raise
+        return 1, False
+    return 1, True
+
+
+def _check_repair(what, repair, plan, seasons):
+    if repair is None:
+        return
+    if repair.n != len(plan) or repair.seasons < int(seasons) or repair.hw != [(int(c[1] - c[0]), int(c[3] - c[2])) for c in plan.crops.tolist()]:
+        raise ValueError(f"{what}: repair was planned for another plan (it holds {repair.n} items over {repair.seasons} seasons; the plan "
+                         f"has {len(plan)}, the feed draws from {seasons} seasons): pass the plan plan_repair returned")
+
+
+def plan_repair(region, plan, seasons=1, ascfill=False, pixel_budget=1 << 22):
+    """The reference's repair of every weaksup item (data/PopulationDataset.py:419-441), decided once for ``plan`` over seasons [0, seasons):
+    returns (plan', RegionRepair).
+
+    Orbit column: ONE census call over all items x seasons (``ops.region_nan_census``) and one synchronisation.  A region with ``s1_asc``
+    follows ``nanfill.s1_orbit`` / ``nanfill.asc_fill`` unchanged -- the descending S1 is kept (and filled) below 5 % NaN, in the
+    reference's float32 quotient count / numel < 0.05 with numel = 2 * h * w of the item, otherwise (or always where it holds NaN, with
+    ``ascfill``) the ascending orbit replaces it under the same rule.  A region without ``s1_asc`` keeps the descending orbit and fills it at
+    any fraction, which is what ``--nan_fill`` does on the resident feed; ``ascfill`` then raises ValueError.
+    Named deviation: an item for which the reference would raise "No data here!" in ANY of the seasons is dropped -- the reference's run
+    would end on that exception; its row of ``plan`` is recorded in ``RegionRepair.dropped``.  plan' keeps the order and the rows of crops,
+    census_idx, y, census_n and bbox of the surviving items.
+
+    Patch table: the (item, season) pairs whose census shows a NaN in S2 or in the chosen S1 are grouped by size (``plan_batches`` under
+    ``pixel_budget`` pixels per group, a generator of its own), gathered with their orbits, filled on a clone (what ``fill_sample_`` does to
+    a batch) and reduced to the entries whose bit pattern changed (``ops.region_patch_extract``: one synchronisation per group, build time
+    only).  Items without NaN never reach that pass.  MemoryError, with the byte count, before a table that does not fit is allocated."""
+    import time
+    S = int(seasons)
+    if not 1 <= S <= region.seasons:
+        raise ValueError(f"plan_repair: seasons in [1, {region.seasons}] (what the region holds), got {seasons}")
+    if len(plan) < 1:
+        raise ValueError("plan_repair: a plan with at least one crop")
+    has_asc = region.s1_asc is not None
+    if ascfill and not has_asc:
+        raise ValueError("plan_repair: ascfill takes the ascending orbit wherever the descending one holds NaN: the region holds no s1_asc")
+    t0 = time.perf_counter()
+    n = len(plan)
+    crops = plan.crops.numpy()
+    boxes = np.empty((n, S, 5), dtype=np.int64)
+    boxes[:, :, :4] = crops[:, None, :]
+    boxes[:, :, 4] = np.arange(S)[None, :]
+    counts = ops.region_nan_census(region.s2, region.s1, region.boundary, region.band_sel, boxes.reshape(-1, 5),
+                                   s1_asc=region.s1_asc).cpu().reshape(n, S, 3)         # the one synchronisation of the orbit column
+    orbit = torch.zeros(n, S, dtype=torch.int8)
+    alive = [True] * n
+    cl = counts.tolist()
+    for i in range(n):
+        numel = 2 * int(crops[i, 1] - crops[i, 0]) * int(crops[i, 3] - crops[i, 2])
+        for s in range(S):
+            orbit[i, s], ok = item_orbit(cl[i][s][1], cl[i][s][2], numel, ascfill, has_asc)
+            alive[i] = alive[i] and ok
+    kept = [i for i in range(n) if alive[i]]
+    dropped = [i for i in range(n) if not alive[i]]
+    if not kept:
+        raise ValueError("plan_repair: every item of the plan lacks S1 data in some season (the reference's \"No data here!\")")
+    new = plan.subset(kept)
+    sel = torch.tensor(kept, dtype=torch.int64)
+    orbit, counts = orbit[sel].contiguous(), counts[sel].contiguous()
+    m = len(kept)
+    kc = new.crops.numpy()
+    hw = [(int(c[1] - c[0]), int(c[3] - c[2])) for c in kc]
+    # the (item, season) pairs that need patches: a NaN in S2 or in the chosen S1
+    chosen = torch.where(orbit == 1, counts[:, :, 2], counts[:, :, 1])
+    pairs = torch.nonzero((counts[:, :, 0] > 0) | (chosen > 0)).tolist()
+    pieces = {}
+    dev = region.device
+    if pairs:
+        groups = plan_batches([hw[i] for i, _ in pairs], list(range(len(pairs))), int(pixel_budget), PC_GATHER_MAX_B, 0.6,
+                              torch.Generator().manual_seed(0))
+        for grp in groups:
+            gc = np.array([list(kc[pairs[p][0]]) + [pairs[p][1]] for p in grp], dtype=np.int64)
+            go = np.array([int(orbit[pairs[p][0], pairs[p][1]]) for p in grp], dtype=np.uint8)
+            gathered = region.gather(gc, orbit=go) if has_asc else region.gather(gc)
+            filled = {"S2": gathered["S2"].clone(), "S1": gathered["S1"].clone()}
+            ops.nan_fill_(filled["S2"], gathered["data_hw"])           # cli.fill_sample_ on the clone
+            ops.nan_fill_(filled["S1"], gathered["data_hw"])
+            idx, val, per_item = ops.region_patch_extract(gathered, filled)
+            sizes = per_item.tolist()
+            for p, pi, pv in zip(grp, idx.split(sizes), val.split(sizes)):
+                pieces[tuple(pairs[p])] = (pi, pv)
+    off = torch.zeros(m * S + 1, dtype=torch.int64)
+    order = sorted(pieces)
+    for i, s in order:
+        off[i * S + s + 1] = pieces[(i, s)][0].numel()
+    off = torch.cumsum(off, 0)
+    total = int(off[-1])
+    if total:
+        free, _ = torch.cuda.mem_get_info(dev)
+        if 8 * total > free:
+            raise MemoryError(f"plan_repair: the patch table takes {8 * total} bytes ({total} entries), device {dev} has {free} free: plan "
+                              "fewer seasons")
+        idx = torch.cat([pieces[k][0] for k in order])
+        val = torch.cat([pieces[k][1] for k in order])
+    else:
+        idx = torch.empty(0, dtype=torch.int32, device=dev)
+        val = torch.empty(0, dtype=torch.float32, device=dev)
+    torch.cuda.synchronize(dev)
+    return new, RegionRepair(orbit, dropped, kept, counts, idx, val, off, hw, build_ms=(time.perf_counter() - t0) * 1e3)
+
+
 class ResidentRegionFeed:
     """Batches of a ``RegionPlan`` over a ``ResidentRegion``, iterated like ``feed.RegionFeed``:
 
@@ -207,11 +377,13 @@ class ResidentRegionFeed:
     and its Python ``random.choice`` of the season (PopulationDataset.py:409) is not claimed.
     There is no producer thread: ``pause()`` returns a null context, so ``FusedTrainStep.capture_guard`` keeps working."""
 
-    def __init__(self, region, plan, batch_size, generator=None, drop_last=True, seasons=1):
+    def __init__(self, region, plan, batch_size, generator=None, drop_last=True, seasons=1, repair=None):
         if len(plan) < 1 or int(batch_size) < 1:
             raise ValueError("ResidentRegionFeed: a plan with at least one crop and batch_size >= 1")
         if not 1 <= int(seasons) <= region.seasons:
             raise ValueError(f"ResidentRegionFeed: seasons in [1, {region.seasons}] (what the region holds), got {seasons}")
+        _check_repair("ResidentRegionFeed", repair, plan, seasons)
+        self.repair = repair
         self.region, self.plan, self.batch_size, self.drop_last, self.seasons = region, plan, int(batch_size), bool(drop_last), int(seasons)
         self.generator = generator if generator is not None else torch.Generator().manual_seed(0)
         self.device = region.device
@@ -242,7 +414,14 @@ class ResidentRegionFeed:
             crops = np.empty((idx.size, 5), dtype=np.int64)
             crops[:, :4] = self._crops[idx]
             crops[:, 4] = season_np[k * B:(k + 1) * B]
-            out = self.region.gather(crops)
+            if self.repair is None:
+                out = self.region.gather(crops)
+            else:
+                # the plan's orbit column, then the batch's patches: one small launch behind the gather, none for a batch without entries
+                orbit = self.repair.orbit_of(idx, crops[:, 4])
+                out = self.region.gather(crops, orbit=orbit)
+                self.repair.apply(idx, crops[:, 4], out["S2"], out["S1"], tuple(out["admin_mask"].shape[1:]))
+                out["orbit"] = orbit.tolist()
             if plan.multi:
                 cn = [plan.census_n[i] for i in idx]
                 K = max(cn)
@@ -310,7 +489,7 @@ class ResidentBatchFeed:
     cut at ``batch_size``; nothing is dropped.  Variable batch sizes change the optimisation schedule: this is not the reference recipe."""
 
     def __init__(self, region, plan, batch_size, transform=None, generator=None, drop_last=True, seasons=1, pixel_budget=0, max_batch=128,
-                 min_fill=0.6):
+                 min_fill=0.6, repair=None):
         import random
         from ..utils.transform import draw_fused_params
         if len(plan) < 1 or int(batch_size) < 1:
@@ -320,6 +499,8 @@ class ResidentBatchFeed:
         if int(pixel_budget) < 0 or int(max_batch) < 1 or not 0.0 <= float(min_fill) <= 1.0:
             raise ValueError(f"ResidentBatchFeed: pixel_budget >= 0, max_batch >= 1, min_fill in [0, 1]; got {pixel_budget}, {max_batch}, "
                              f"{min_fill}")
+        _check_repair("ResidentBatchFeed", repair, plan, seasons)
+        self.repair = repair
         state = torch.get_rng_state(), random.getstate()
         expressible = draw_fused_params(transform) is not None
         torch.set_rng_state(state[0])
@@ -376,8 +557,18 @@ class ResidentBatchFeed:
             crops[:, 4] = sea
             cn = [plan.census_n[i] for i in idx] if plan.multi else None
             params = self._draw(self.transform)                        # the coins, immediately before the batch goes out
-            out = ops.region_batch(self.region.s2, self.region.s1, self.region.boundary, self.region.band_sel, crops, params,
-                                   labels=(self._cidx, self._y, idx, max(cn) if plan.multi else 1))
+            labels = (self._cidx, self._y, idx, max(cn) if plan.multi else 1)
+            if self.repair is None:
+                out = ops.region_batch(self.region.s2, self.region.s1, self.region.boundary, self.region.band_sel, crops, params,
+                                       labels=labels)
+            else:
+                # the plan's orbit column, then the batch's patches through the same coins: one small launch behind the assembly
+                orbit = self.repair.orbit_of(idx, sea)
+                out = ops.region_batch(self.region.s2, self.region.s1, self.region.boundary, self.region.band_sel, crops, params,
+                                       labels=labels, s1_asc=self.region.s1_asc, orbit=orbit)
+                tile = (max(self._hw[i][0] for i in idx), max(self._hw[i][1] for i in idx))
+                self.repair.apply(idx, sea, out["raw"][:, :4], out["raw"][:, 4:], tile, params)
+                out["orbit"] = orbit.tolist()
             if plan.multi:
                 out["census_n"] = cn
             else:

@@ -1036,7 +1036,26 @@ def _region_inputs(what, s2, s1, boundary, band_sel, crops):
     return S, C2, C1, h, w, band, cr32, Hm, Wm
 
 
-def region_gather(s2, s1, boundary, band_sel, crops, out=None):
+def _region_orbit(what, s1, s1_asc, orbit, B):
+    """The orbit arguments ``region_gather`` and ``region_batch`` share: s1_asc shaped like s1 on its device, orbit = B host values in
+    {0, 1}, an ascending crop only with s1_asc.  Returns the list as a ctypes uint8 pointer (None: all descending)."""
+    if s1_asc is not None:
+        L.require_device(s1_asc)
+        if s1_asc.dtype != torch.float32 or s1_asc.shape != s1.shape or not s1_asc.is_contiguous() or s1_asc.device != s1.device:
+            raise ValueError(f"{what}: s1_asc must be a contiguous fp32 tensor shaped like s1 {tuple(s1.shape)} on its device, got "
+                             f"{s1_asc.dtype} {tuple(s1_asc.shape)}")
+    if orbit is None:
+        return None
+    ob = np.ascontiguousarray(np.asarray(orbit.cpu() if torch.is_tensor(orbit) else orbit, dtype=np.int64).reshape(-1))
+    if ob.size != B or ((ob != 0) & (ob != 1)).any() or (ob.any() and s1_asc is None):
+        raise ValueError(f"{what}: orbit holds one value in {{0, 1}} per crop ({B}), and 1 (ascending) needs s1_asc; got {ob.tolist()}")
+    ob8 = ob.astype(np.uint8)
+    ptr = ob8.ctypes.data_as(C.POINTER(C.c_uint8))
+    ptr._keep = ob8
+    return ptr
+
+
+def region_gather(s2, s1, boundary, band_sel, crops, out=None, s1_asc=None, orbit=None):
     """One batch of crops of resident rasters in ONE launch (csrc/region.hip, pc_region_gather): what the reference's weaksup items
     (data/PopulationDataset.py:403-458,566-568,624-649) and ``Population_Dataset_collate_fn`` (:885-958) assemble on the host.
     s2: device (S, C2, h, w) fp32 or uint16; s1: device fp32 (S, C1, h, w); boundary: device int32 (h, w); band_sel: six 0-based source
@@ -1044,9 +1063,12 @@ def region_gather(s2, s1, boundary, band_sel, crops, out=None):
     = {x0, x1, y0, y1, season}, rows [x0, x1) and columns [y0, y1).  Returns {"S2" (B, 4, Hm, Wm), "S1" (B, 2, Hm, Wm), "admin_mask" (B, Hm, Wm)
     = (float)id, "data_hw" int32 (B, 2)} at the batch maximum (Hm, Wm), padded 0 / 0 / -1 at the bottom and right; every element is written
     and fp32 sources are copied bit for bit.  out: such a dict to write into (its (Hm, Wm) may exceed the batch maximum).  An empty crop, one
-    that leaves the raster and a season >= S raise before anything is enqueued."""
+    that leaves the raster and a season >= S raise before anything is enqueued.
+    s1_asc / orbit (pc_region_gather_orbit): the ascending-orbit S1, shaped like s1, and B host values in {0, 1}: crop b takes its S1 from
+    s1_asc where orbit[b] == 1.  Without them this is the plain entry point."""
     S, C2, C1, h, w, band, cr32, Hm, Wm = _region_inputs("region_gather", s2, s1, boundary, band_sel, crops)
     B = cr32.shape[0]
+    orb = _region_orbit("region_gather", s1, s1_asc, orbit, B)
     dev = s1.device
     if out is None:
         out = {"S2": torch.empty(B, 4, Hm, Wm, dtype=torch.float32, device=dev),
@@ -1065,13 +1087,17 @@ def region_gather(s2, s1, boundary, band_sel, crops, out=None):
         Hm, Wm = int(Ho), int(Wo)
     if Hm * Wm >= 1 << 31:
         raise ValueError(f"region_gather: Hm * Wm < 2^31, got {Hm} x {Wm}")
-    L.check(L.lib().pc_region_gather(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(boundary), S, C2, C1, h, w,
-                                     (C.c_int32 * 6)(*band), cr32.ctypes.data_as(C.POINTER(C.c_int32)), B, Hm, Wm, L.ptr(out["S2"]),
-                                     L.ptr(out["S1"]), L.ptr(out["admin_mask"]), L.ptr(out["data_hw"]), L.stream_ptr()), "pc_region_gather")
+    tail = (S, C2, C1, h, w, (C.c_int32 * 6)(*band), cr32.ctypes.data_as(C.POINTER(C.c_int32)), B, Hm, Wm, L.ptr(out["S2"]),
+            L.ptr(out["S1"]), L.ptr(out["admin_mask"]), L.ptr(out["data_hw"]), L.stream_ptr())
+    if s1_asc is None and orbit is None:
+        L.check(L.lib().pc_region_gather(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(boundary), *tail), "pc_region_gather")
+    else:
+        L.check(L.lib().pc_region_gather_orbit(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orb, L.ptr(boundary),
+                                               *tail), "pc_region_gather_orbit")
     return out
 
 
-def region_batch(s2, s1, boundary, band_sel, crops, params=None, hw=None, labels=None, out=None):
+def region_batch(s2, s1, boundary, band_sel, crops, params=None, hw=None, labels=None, out=None, s1_asc=None, orbit=None):
     """The batch a fused step takes, assembled from resident rasters in ONE launch (csrc/region_batch.hip, pc_region_batch).  By definition,
     bit for bit: ``augment_raw(*region_gather(...; tile (Hm, Wm)), params)`` -- without the intermediate S2 / S1 / admin_mask.
     s2, s1, boundary, band_sel, crops: as ``region_gather``.  params: ``draw_fused_params``' dict (None = no augmentation).  hw: the gathered
@@ -1079,9 +1105,11 @@ def region_batch(s2, s1, boundary, band_sel, crops, params=None, hw=None, labels
     once --, items: B host integers, K): the same launch also writes census_idx[b] = plan_cidx[items[b], :K] and y likewise.
     Returns {"raw" (B, 6, Ho, Wo), "admin_mask" (B, Ho, Wo), ["census_idx" int64 (B, K), "y" fp32 (B, K)]} with (Ho, Wo) = (Wm, Hm) for an odd
     rotation; out: such a dict to write into.  Everything ``region_gather`` refuses, a rotation outside 0 .. 3, an item outside [0, n), a K
-    outside [1, Kp] and an ``out`` of another shape raise ValueError before anything is enqueued."""
+    outside [1, Kp] and an ``out`` of another shape raise ValueError before anything is enqueued.
+    s1_asc / orbit: as ``region_gather`` takes them (pc_region_batch_orbit); without them this is the plain entry point."""
     S, C2, C1, h, w, band, cr32, Hm, Wm = _region_inputs("region_batch", s2, s1, boundary, band_sel, crops)
     B = cr32.shape[0]
+    orb = _region_orbit("region_batch", s1, s1_asc, orbit, B)
     if hw is not None:
         th, tw = int(hw[0]), int(hw[1])
         if th < Hm or tw < Wm:
@@ -1129,13 +1157,124 @@ def region_batch(s2, s1, boundary, band_sel, crops, params=None, hw=None, labels
         lab = L.PcRegionLabels(plan_cidx.data_ptr(), plan_y.data_ptr(), it32.ctypes.data_as(C.POINTER(C.c_int32)),
                                out["census_idx"].data_ptr(), out["y"].data_ptr(), n, Kp, K, 0)
     beta, gamma = pr.get("beta"), pr.get("gamma")
-    L.check(L.lib().pc_region_batch(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(boundary), S, C2, C1, h, w,
-                                    (C.c_int32 * 6)(*band), cr32.ctypes.data_as(C.POINTER(C.c_int32)), B, Hm, Wm,
-                                    int(bool(pr.get("vflip"))), int(bool(pr.get("hflip"))), k, int(beta is not None),
-                                    C.c_float(beta if beta is not None else 1.0), int(gamma is not None),
-                                    C.c_float(gamma if gamma is not None else 1.0), L.ptr(out["raw"]), L.ptr(out["admin_mask"]), Ho, Wo,
-                                    C.byref(lab) if lab is not None else None, L.stream_ptr()), "pc_region_batch")
+    tail = (S, C2, C1, h, w, (C.c_int32 * 6)(*band), cr32.ctypes.data_as(C.POINTER(C.c_int32)), B, Hm, Wm,
+            int(bool(pr.get("vflip"))), int(bool(pr.get("hflip"))), k, int(beta is not None),
+            C.c_float(beta if beta is not None else 1.0), int(gamma is not None),
+            C.c_float(gamma if gamma is not None else 1.0), L.ptr(out["raw"]), L.ptr(out["admin_mask"]), Ho, Wo,
+            C.byref(lab) if lab is not None else None, L.stream_ptr())
+    if s1_asc is None and orbit is None:
+        L.check(L.lib().pc_region_batch(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(boundary), *tail), "pc_region_batch")
+    else:
+        L.check(L.lib().pc_region_batch_orbit(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orb, L.ptr(boundary),
+                                              *tail), "pc_region_batch_orbit")
     return out
+
+
+def region_nan_census(s2, s1, boundary, band_sel, boxes, s1_asc=None, max_blocks=0):
+    """The NaN entries of many boxes of the resident rasters in ONE pass (csrc/region_repair.hip, pc_region_nan_census): what decides an
+    item's S1 orbit (data/PopulationDataset.py:419-441), for a whole plan at once.  Sources and band_sel as ``region_gather``; boxes: HOST
+    integers (n, 5) = {x0, x1, y0, y1, season}, validated here and uploaded once.  Returns a device int64 (n, 3) = {S2 over its four
+    selected bands (a band listed twice counts twice; 0 for uint16 S2), descending S1 over its two, ascending S1 likewise (0 without
+    s1_asc)}.  Integer adds only: the same bits for any launch geometry; max_blocks > 0 caps the workgroups of the pass (tests)."""
+    S, C2, C1, h, w, band, bx32, Hm, _ = _region_inputs("region_nan_census", s2, s1, boundary, band_sel, boxes)
+    _region_orbit("region_nan_census", s1, s1_asc, None, bx32.shape[0])
+    n = bx32.shape[0]
+    if 5 * n >= 1 << 31 or w >= 1 << 29:
+        raise ValueError(f"region_nan_census: 5 * n < 2^31 and w < 2^29, got n {n}, w {w}")
+    dev = s1.device
+    boxes_dev = torch.from_numpy(bx32).to(dev)                       # the one upload
+    counts = torch.empty(n, 3, dtype=torch.int64, device=dev)
+    L.check(L.lib().pc_region_nan_census(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), S, C2, C1, h, w,
+                                         (C.c_int32 * 6)(*band), L.ptr(boxes_dev), n, Hm, L.ptr(counts), int(max_blocks), L.stream_ptr()),
+            "pc_region_nan_census")
+    return counts
+
+
+def region_patch_extract(gathered, filled):
+    """The sparse difference of a gathered batch and its filled copy (pc_region_patch_count / pc_region_patch_write): gathered = what
+    ``region_gather`` returned, filled = {"S2", "S1"} of the same shapes after ``nan_fill_`` over ``gathered["data_hw"]``.  Returns (idx
+    int32 device (N,), val fp32 device (N,), counts: host int64 (B,)): per item b, in order, the entries (c * h_b + i) * w_b + j of its own
+    (6, h_b, w_b) space (c = 0 .. 3: S2, 4 .. 5: S1) whose 32-bit pattern differs, ascending, with the filled tile's bits.  Comparing bit
+    patterns covers the fill's "fewer than 4 known entries -> zeros" case without a rule of its own.  ONE synchronisation (the counts come to
+    the host for the exclusive prefix): this is build-time work.  Raises MemoryError with the byte count before it allocates a table that
+    does not fit the device's free memory."""
+    g2, g1, hw = gathered["S2"], gathered["S1"], gathered["data_hw"]
+    f2, f1 = filled["S2"], filled["S1"]
+    L.require_device(g2, g1, f2, f1, hw)
+    B, _, Hm, Wm = g2.shape
+    if (tuple(g2.shape) != (B, 4, Hm, Wm) or tuple(g1.shape) != (B, 2, Hm, Wm) or f2.shape != g2.shape or f1.shape != g1.shape or
+            tuple(hw.shape) != (B, 2) or hw.dtype != torch.int32 or not hw.is_contiguous() or
+            any(t.dtype != torch.float32 or not t.is_contiguous() for t in (g2, g1, f2, f1))):
+        raise ValueError("region_patch_extract: contiguous fp32 S2 (B, 4, H, W) / S1 (B, 2, H, W) pairs of equal shapes and int32 data_hw (B, 2)")
+    if B < 1 or B > 65535 or 6 * Hm * Wm >= 1 << 31:
+        raise ValueError(f"region_patch_extract: 1 <= B <= 65535 and 6 * Hm * Wm < 2^31, got B {B}, tile {Hm} x {Wm}")
+    dev = g2.device
+    nchunk = -(-6 * Hm * Wm // L.PC_REGION_PATCH_CHUNK)
+    counts = torch.empty(B, nchunk, dtype=torch.int32, device=dev)
+    L.check(L.lib().pc_region_patch_count(L.ptr(g2), L.ptr(f2), L.ptr(g1), L.ptr(f1), L.ptr(hw), B, Hm, Wm, L.ptr(counts), nchunk,
+                                          L.stream_ptr()), "pc_region_patch_count")
+    host = counts.cpu().to(torch.int64)                              # the one synchronisation
+    per_item = host.sum(1)
+    total = int(per_item.sum())
+    if total == 0:
+        return (torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.float32, device=dev), per_item)
+    free, _ = torch.cuda.mem_get_info(dev)
+    if 8 * total > free:
+        raise MemoryError(f"region_patch_extract: the patch table takes {8 * total} bytes ({total} entries), device {dev} has {free} free")
+    flat = host.reshape(-1)
+    chunk_off = (torch.cumsum(flat, 0) - flat).to(dev)               # the exclusive prefix
+    idx = torch.empty(total, dtype=torch.int32, device=dev)
+    val = torch.empty(total, dtype=torch.float32, device=dev)
+    L.check(L.lib().pc_region_patch_write(L.ptr(g2), L.ptr(f2), L.ptr(g1), L.ptr(f1), L.ptr(hw), B, Hm, Wm, L.ptr(chunk_off), nchunk,
+                                          L.ptr(idx), L.ptr(val), C.c_int64(total), L.stream_ptr()), "pc_region_patch_write")
+    return idx, val, per_item
+
+
+def region_patch_apply(idx, val, off, count, item_hw, s2, s1, hw, params=None):
+    """Lay the patches of a batch over it (pc_region_patch_apply), on the current stream, without synchronisation.  idx / val: the device
+    tables; off / count / item_hw: HOST, per batch item its range in the tables and its extent (h_b, w_b).  Targets: s2 = the batch's S2
+    planes and s1 = its S1 planes -- two views of one raw tile (``raw[:, :4]``, ``raw[:, 4:]``) or the separate contiguous S2 / S1 of the
+    unfused feed -- whose item stride may exceed the planes they span.  hw = the gathered tile (Hm, Wm) the batch was assembled at; params:
+    the coins it was assembled with (None = none): an entry lands at the image of its tile position under the flips and quarter turns and
+    S2 values pass through the same brightness / gamma as the pixels they replace.  Returns the number of entries applied (0: no launch)."""
+    B = len(count)
+    total = int(sum(int(c) for c in count))
+    if total == 0:
+        return 0
+    L.require_device(idx, val, s2, s1)
+    Hm, Wm = int(hw[0]), int(hw[1])
+    pr = params or {}
+    k = int(pr.get("rot", 0))
+    if not 0 <= k <= 3:
+        raise ValueError(f"region_patch_apply: rot is a number of quarter turns in 0 .. 3, got {k}")
+    Ho, Wo = (Wm, Hm) if k & 1 else (Hm, Wm)
+    if (idx.dtype != torch.int32 or val.dtype != torch.float32 or idx.dim() != 1 or idx.shape != val.shape or not idx.is_contiguous() or
+            not val.is_contiguous()):
+        raise ValueError("region_patch_apply: idx int32 (N,) and val fp32 (N,), contiguous")
+    for t, ch, name in ((s2, 4, "s2"), (s1, 2, "s1")):
+        if (t.dtype != torch.float32 or tuple(t.shape) != (B, ch, Ho, Wo) or t.stride()[1:] != (Ho * Wo, Wo, 1) or
+                (B > 1 and t.stride(0) < ch * Ho * Wo)):
+            raise ValueError(f"region_patch_apply: {name} must be fp32 ({B}, {ch}, {Ho}, {Wo}) with dense planes, got {t.dtype} "
+                             f"{tuple(t.shape)} strides {t.stride()}")
+    offs = np.ascontiguousarray(np.asarray(off, dtype=np.int64).reshape(-1))
+    cnt = np.ascontiguousarray(np.asarray(count, dtype=np.int64).reshape(-1))
+    ihw = np.ascontiguousarray(np.asarray(item_hw, dtype=np.int64).reshape(-1, 2))
+    N = idx.numel()
+    live = cnt > 0
+    if (offs.size != B or ihw.shape[0] != B or (cnt < 0).any() or (offs < 0).any() or (offs + cnt > N).any() or
+            (live & ((ihw[:, 0] < 1) | (ihw[:, 1] < 1) | (ihw[:, 0] > Hm) | (ihw[:, 1] > Wm))).any()):
+        raise ValueError(f"region_patch_apply: every item's range inside the table of {N} entries and its extent inside the {Hm} x {Wm} tile")
+    cnt32, ihw32 = cnt.astype(np.int32), ihw.astype(np.int32)
+    beta, gamma = pr.get("beta"), pr.get("gamma")
+    st2 = s2.stride(0) if B > 1 else 4 * Ho * Wo
+    st1 = s1.stride(0) if B > 1 else 2 * Ho * Wo
+    L.check(L.lib().pc_region_patch_apply(L.ptr(idx), L.ptr(val), C.c_int64(N), offs.ctypes.data_as(C.POINTER(C.c_int64)),
+                                          cnt32.ctypes.data_as(C.POINTER(C.c_int32)), ihw32.ctypes.data_as(C.POINTER(C.c_int32)), B,
+                                          L.ptr(s2), C.c_int64(st2), L.ptr(s1), C.c_int64(st1), Hm, Wm, Ho, Wo,
+                                          int(bool(pr.get("vflip"))), int(bool(pr.get("hflip"))), k, int(beta is not None),
+                                          C.c_float(beta if beta is not None else 1.0), int(gamma is not None),
+                                          C.c_float(gamma if gamma is not None else 1.0), L.stream_ptr()), "pc_region_patch_apply")
+    return total
 
 
 def nan_fill_(x, hw=None, count_only=False):
