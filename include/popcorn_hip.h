@@ -967,6 +967,24 @@ int pc_region_patch_write(const float* g2, const float* f2, const float* g1, con
 int pc_region_patch_apply(const int32_t* idx, const float* val, int64_t cap, const int64_t* off, const int32_t* count, const int32_t* item_hw,
                           int B, float* s2, int64_t s2_stride, float* s1, int64_t s1_stride, int Hm, int Wm, int Ho, int Wo, int vflip,
                           int hflip, int rot, int bright, float beta, int gam, float gamma, void* stream);
+/* pc_region_window (csrc/region_window.hip): the normalised model input of ONE evaluation window of the resident rasters in ONE launch.
+ * out DEVICE fp32 (6, ps, ps), channels [S2 R G B NIR | S1 VV VH]:  out[c][i][j] = (v - mean6[c]) / std6[c]  (the fp32 division of
+ * pc_select_normalize), v = the value of the patch table where its slice [start, start + count) holds an entry for the site, otherwise the
+ * raster's value at (season, band_sel[c], x + i, y + j); orbit 1 reads the two S1 channels from s1_asc.  Sources and band_sel as
+ * pc_region_gather.  idx / val DEVICE tables of cap entries as pc_region_patch_write makes them: the slice ascends, idx = (c * ps + i) * ps + j
+ * in the window's own (6, ps, ps) space, val = the raw, un-normalised repaired value; both may be NULL with count = 0.  By definition, on
+ * every non-NaN element and with NaN at the same sites:
+ *   pc_region_window(window, orbit; no table) == pc_select_normalize(cat(S2, S1 of pc_region_gather_orbit(window, orbit)), 0 .. 5, mean6, std6)
+ * Every element of out is stored exactly once, the patch value before the normalisation; nothing outside out is written.  16-byte accesses
+ * when ps % 4 == 0 and out is 16-byte aligned, element by element otherwise.  A workgroup owns pc_region_window_rows(ps) rows of one
+ * channel (0 for a ps the launch refuses).  PC_EINVAL before anything is enqueued: a NULL pointer, ps < 1 or > PC_REGION_WINDOW_MAX_PS, a
+ * window that leaves the raster, a season outside [0, S), a band outside its source, an orbit outside {0, 1} or 1 without s1_asc, count > 0
+ * without tables, a slice outside [0, cap] or longer than 6 * ps * ps. */
+#define PC_REGION_WINDOW_MAX_PS 8192
+int pc_region_window_rows(int ps);
+int pc_region_window(const void* s2, int s2_u16, const float* s1, const float* s1_asc, int orbit, int S, int C2, int C1, int h, int w,
+                     const int32_t* band_sel, int x, int y, int season, int ps, const float* mean6, const float* std6, const int32_t* idx,
+                     const float* val, int64_t cap, int64_t start, int64_t count, float* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -163,6 +163,7 @@ class PcStepUnits(C.Structure):
 PC_UNIT_LAYOUT_MAX_K, PC_UNIT_LAYOUT_MAX_B = 1024, 256
 PC_REGION_GATHER_MAX_B = 128          # crops per pc_region_gather launch (the crop list travels in the kernel arguments)
 PC_REGION_PATCH_CHUNK = 4096          # entries of an item's index space per workgroup of pc_region_patch_count / _write
+PC_REGION_WINDOW_MAX_PS = 8192        # the widest window of pc_region_window (one row = a 32 KB tile; 6 * ps * ps < 2^31)
 
 
 class PcRegionLabels(C.Structure):
@@ -253,6 +254,12 @@ def lib():
         _lib.pc_region_patch_apply.argtypes = ([C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                                 C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] +
                                                [C.c_int] * 8 + [C.c_float, C.c_int, C.c_float, C.c_void_p])
+        # resident evaluation (csrc/region_window.hip): s2, s2_u16, s1, s1_asc, orbit, S, C2, C1, h, w, band_sel, x, y, season, ps, mean6,
+        # std6, idx, val, cap, start, count, out, stream
+        _lib.pc_region_window_rows.argtypes = [C.c_int]
+        _lib.pc_region_window.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_int32)] +
+                                          [C.c_int] * 4 + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p] +
+                                          [C.c_int64] * 3 + [C.c_void_p, C.c_void_p])
     return _lib
 
 

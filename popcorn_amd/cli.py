@@ -123,6 +123,11 @@ def train_parser():
                         "--resident_s1_gap)")
     p.add_argument("--resident_s1_gap", type=float, default=0.0, metavar="F",
                    help="--resident_repair: orbit-gap rows over this fraction of the synthetic raster's descending S1")
+    p.add_argument("--resident_test", action="store_true",
+                   help="--resident_region: the in-training target test evaluates the resident region itself (--test_patchsize / "
+                        "--test_overlap) through data/region.py: ResidentWindows -- orbit and NaN repair of every window planned at the "
+                        "first test and reused by every later one, one launch per window, no per-window fill; keeps the ascending S1 "
+                        "resident as --resident_repair does")
     return p
 
 
@@ -152,6 +157,11 @@ def eval_parser():
     p.add_argument("--nan_clouds", type=float, default=0.0, help="--raw_input: NaN cloud discs over about this fraction of S2")
     p.add_argument("--s1_gap", type=float, default=0.0, help="--raw_input: orbit-gap rows over this fraction of the descending S1")
     p.add_argument("--ascfill", action="store_true", help="always take the ascending S1 where the descending one holds NaNs")
+    p.add_argument("--resident_windows", action="store_true",
+                   help="the raw raster stays on the device as a resident region and the sliding windows are planned once "
+                        "(data/region.py: ResidentWindows): orbit choice and NaN repair of every window from one census pass and a patch "
+                        "table, then one launch per window with no fill and no synchronisation; the same maps and metrics as --raw_input "
+                        "(takes --nan_clouds / --s1_gap / --ascfill / --fourseasons; not together with --raw_input)")
     p.add_argument("--product_cell", type=int, default=0,
                    help="side in pixels of the product grid the 10 m maps are aggregated to on the device (0 = off; 10 = the hectare grid "
                         "the reference recommends for the final product and for evaluation)")
@@ -266,6 +276,16 @@ def check_repair_args(args):
                          "--resident_repair")
     if not 0.0 <= args.resident_s1_gap <= 1.0:
         raise SystemExit("--resident_s1_gap is a fraction of the raster's rows in [0, 1]")
+    if args.resident_test and args.resident_region is None:
+        raise SystemExit("--resident_test evaluates the resident region itself in the in-training target test (windows planned once on "
+                         "the device): it needs --resident_region")
+
+
+def check_eval_args(args):
+    """The refusals of run_eval that need no device: raised before anything else is set up."""
+    if args.resident_windows and args.raw_input:
+        raise SystemExit("--resident_windows and --raw_input name two paths for the same raw raster (windows planned once on the device / "
+                         "filled one by one): give one of them")
 
 
 class Trainer:
@@ -318,6 +338,7 @@ class Trainer:
                                     seed=args.seed + 77, fixed_hw=args.fixed_hw, nan_clouds=args.nan_clouds, ascfill=args.ascfill),
             batch_size=args.weak_val_batch_size, shuffle=False, collate_fn=Population_Dataset_collate_fn, drop_last=False)
         self._test_raster = None
+        self._resident_windows = None                                    # --resident_test: planned at the first test, reused afterwards
         self.model = model_dict[args.model](**get_model_kwargs(args, args.model)).to(self.device)   # same seed: same init on every rank
         self.model.set_precision(args.precision)
         # from here on the CPU generators feed per-rank randomness (augmentation coins, the 60x60 sparsity grid of
@@ -372,7 +393,8 @@ class Trainer:
         from .data.region import ResidentBatchFeed, ResidentRegion, ResidentRegionFeed, plan_multi_unit, plan_one_unit, plan_repair
         data = SyntheticTestRaster(a.resident_region[0], a.resident_region[1], seasons=1, n_regions=a.resident_units, seed=a.seed + 20,
                                    device=self.device, raw=True, nan_clouds=a.nan_clouds, s1_gap=a.resident_s1_gap)
-        self.region = ResidentRegion.from_synthetic(data, with_asc=a.resident_repair)
+        self.region = ResidentRegion.from_synthetic(data, with_asc=a.resident_repair or a.resident_test)
+        self.region_data = data                                          # (the raster callable of evaluate_raster(raw=True) over the same data)
         kw = dict(max_pix=a.max_weak_pix, max_pix_box=a.max_pix_box)
         if a.units_per_crop > 0:
             self.region_plan = plan_multi_unit(self.region.table, self.region.census_idx, self.region.census_pop, self.region.shape,
@@ -544,6 +566,8 @@ class Trainer:
         from . import eval as E
         from .utils.metrics import get_test_metrics
         a = self.args
+        if a.resident_test:
+            return self._test_resident(save)
         if self._test_raster is None:
             self._test_raster = SyntheticTestRaster(a.test_raster_hw[0], a.test_raster_hw[1], seasons=1, n_regions=64,
                                                     seed=a.seed + 10, device=self.device)
@@ -553,6 +577,29 @@ class Trainer:
                                              FlatReducer(), 0) if self.world == 1 else \
             E.evaluate_raster([self.model], data.raster, a.test_patchsize, a.test_overlap, False, self.reducer, self.rank)
         cp, cg = E.convert_popmap_to_census(out, data.boundary, data.census_idx, data.census_pop)
+        stats = get_test_metrics(cp, cg, tag="MainCensus_synthetic_fine")
+        self.target_test_stats = {k + "/targettest": float(v) for k, v in stats.items()}
+        if save and self.rank == 0:
+            torch.save({"popdensemap": out.cpu(), "scale": None if scale is None else scale.cpu()},
+                       os.path.join(self.exp, "synthetic_predictions.pt"))
+        self._log(self.target_test_stats)
+        return self.target_test_stats
+
+    def _test_resident(self, save=False):
+        """--resident_test: the target test over the region the run trains on (the reference's `-treg rwa -tregtrain rwa`), its windows
+        planned once (data/region.py: ResidentWindows) -- every later test is one launch per window in front of the model."""
+        from . import eval as E
+        from .data.region import ResidentWindows
+        from .utils.metrics import get_test_metrics
+        a, region = self.args, self.region
+        if self._resident_windows is None:
+            f = self._resident_windows = ResidentWindows(region, a.test_patchsize, a.test_overlap, fourseasons=False, ascfill=a.ascfill)
+            if self.rank == 0:
+                print(f"resident windows: {len(f.idx)} windows, {f.ascending} ascending, {f.entries} table entries ({f.nbytes} bytes), "
+                      f"built in {f.build_ms:.1f} ms", flush=True)
+        self.model.eval()
+        out, _, scale, _ = E.evaluate_raster([self.model], self._resident_windows, a.test_patchsize, a.test_overlap, False, FlatReducer(), 0)
+        cp, cg = E.convert_popmap_to_census(out, region.boundary, region.census_idx, region.census_pop)
         stats = get_test_metrics(cp, cg, tag="MainCensus_synthetic_fine")
         self.target_test_stats = {k + "/targettest": float(v) for k, v in stats.items()}
         if save and self.rank == 0:
@@ -655,6 +702,7 @@ def run_eval(argv=None):
     from . import eval as E
     from .utils.metrics import get_test_metrics
     args = eval_parser().parse_args(argv)
+    check_eval_args(args)
     rank, local_rank, world = init_from_env()
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
@@ -667,13 +715,21 @@ def run_eval(argv=None):
             m.load_state_dict(torch.load(args.resume[j], map_location="cpu", weights_only=False)["model"])   # run_eval.py:243-257
         models.append(m.eval().set_precision(args.precision))
     data = SyntheticTestRaster(args.raster_hw[0], args.raster_hw[1], seasons=4 if args.fourseasons else 1, device=dev,
-                               raw=args.raw_input, nan_clouds=args.nan_clouds, s1_gap=args.s1_gap)
+                               raw=args.raw_input or args.resident_windows, nan_clouds=args.nan_clouds, s1_gap=args.s1_gap)
     reducer = FlatReducer()
+    raster = data.raster
+    if args.resident_windows:
+        from .data.region import ResidentRegion, ResidentWindows
+        raster = ResidentWindows(ResidentRegion.from_synthetic(data, with_asc=True), args.patchsize, args.overlap,
+                                 fourseasons=args.fourseasons, ascfill=args.ascfill, rank=rank, world=reducer.world)
+        if rank == 0:
+            print(f"resident windows: {len(raster.idx)} windows, {raster.ascending} ascending, {raster.entries} table entries "
+                  f"({raster.nbytes} bytes), built in {raster.build_ms:.1f} ms", flush=True)
     product = E.ProductGrid(args.raster_hw[0], args.raster_hw[1], args.product_cell, n, dev) if args.product_cell > 0 else None
     num_ids = int(data.census_idx.max()) + 1
     census = E.CensusTable(args.raster_hw[0], args.raster_hw[1], [data.boundary], [num_ids], n, dev) if args.census_table else None
     t0 = time.time()
-    out, out_std, scale, scale_std = E.evaluate_raster(models, data.raster, args.patchsize, args.overlap, args.fourseasons,
+    out, out_std, scale, scale_std = E.evaluate_raster(models, raster, args.patchsize, args.overlap, args.fourseasons,
                                                        reducer, rank, raw=args.raw_input, ascfill=args.ascfill, product=product,
                                                        census=census)
     res = {}

@@ -15,8 +15,12 @@ and pixel counts are made at preprocessing time with one pass per unit (utils/02
   ``plan_repair``         the reference's per-item NaN repair (:419-441), decided ONCE for a plan: the S1 orbit of every (item, season) from
                           one census pass, the repaired sites as a sparse patch table in HBM (``RegionRepair``); a feed built with
                           ``repair=`` gathers with orbits and lays each batch's patches over it with one small launch
+  ``ResidentWindows``     the same region EVALUATED: the sliding windows of ``eval.evaluate_raster`` planned once -- orbit per window from
+                          one census pass, repaired sites as a patch table (``repair_core``, shared with ``plan_repair``), sharded over
+                          ranks like the windows --, each window's normalised model input then ONE ``ops.region_window`` launch with no
+                          fill and no synchronisation; it is the raster callable ``evaluate_raster`` already takes
 
-Host glue, plain torch; the kernels are csrc/region.hip, csrc/region_batch.hip and csrc/region_repair.hip.  Deviations from the reference, all named where they happen: units without pixels
+Host glue, plain torch; the kernels are csrc/region.hip, csrc/region_batch.hip, csrc/region_repair.hip and csrc/region_window.hip.  Deviations from the reference, all named where they happen: units without pixels
 are dropped (``plan_one_unit``); the per-epoch order and the season per item come from a torch generator, not Python's ``random`` stream
 (``ResidentRegionFeed``); without ``plan_repair`` the resident S1 is the orbit already chosen per season (``--nan_fill`` fills what is
 left), with it an item the reference would end on ("No data here!") is dropped from the plan.  Sharding a plan over data-parallel ranks and graph capture of the gather are not part of this module."""
@@ -28,6 +32,7 @@ import numpy as np
 import torch
 
 from .. import ops
+from . import stats
 
 REFERENCE_BANDS = (2, 1, 0, 3, 0, 1)      # file bands (3, 2, 1, 4) of S2 and (1, 2) of S1, 1-based (PopulationDataset.py:566-568), 0-based
 MODEL_ORDER_BANDS = (0, 1, 2, 3, 0, 1)    # rasters whose bands are stored in the model's order already (SyntheticTestRaster)
@@ -298,20 +303,8 @@ def plan_repair(region, plan, seasons=1, ascfill=False, pixel_budget=1 << 22):
         raise ValueError("plan_repair: ascfill takes the ascending orbit wherever the descending one holds NaN: the region holds no s1_asc")
     t0 = time.perf_counter()
     n = len(plan)
-    crops = plan.crops.numpy()
-    boxes = np.empty((n, S, 5), dtype=np.int64)
-    boxes[:, :, :4] = crops[:, None, :]
-    boxes[:, :, 4] = np.arange(S)[None, :]
-    counts = ops.region_nan_census(region.s2, region.s1, region.boundary, region.band_sel, boxes.reshape(-1, 5),
-                                   s1_asc=region.s1_asc).cpu().reshape(n, S, 3)         # the one synchronisation of the orbit column
-    orbit = torch.zeros(n, S, dtype=torch.int8)
-    alive = [True] * n
-    cl = counts.tolist()
-    for i in range(n):
-        numel = 2 * int(crops[i, 1] - crops[i, 0]) * int(crops[i, 3] - crops[i, 2])
-        for s in range(S):
-            orbit[i, s], ok = item_orbit(cl[i][s][1], cl[i][s][2], numel, ascfill, has_asc)
-            alive[i] = alive[i] and ok
+    orbit, counts, ok, pieces = repair_core(region, plan.crops.numpy(), S, ascfill, pixel_budget)
+    alive = ok.all(1).tolist()
     kept = [i for i in range(n) if alive[i]]
     dropped = [i for i in range(n) if not alive[i]]
     if not kept:
@@ -320,18 +313,60 @@ def plan_repair(region, plan, seasons=1, ascfill=False, pixel_budget=1 << 22):
     sel = torch.tensor(kept, dtype=torch.int64)
     orbit, counts = orbit[sel].contiguous(), counts[sel].contiguous()
     m = len(kept)
-    kc = new.crops.numpy()
-    hw = [(int(c[1] - c[0]), int(c[3] - c[2])) for c in kc]
+    hw = [(int(c[1] - c[0]), int(c[3] - c[2])) for c in new.crops.numpy()]
+    row = {i: k for k, i in enumerate(kept)}                           # row of the original plan -> row of plan'
+    off, idx, val = _assemble_table({row[i] * S + s: pc for (i, s), pc in pieces.items()}, m * S, region.device, "plan_repair",
+                                    "plan fewer seasons")
+    torch.cuda.synchronize(region.device)
+    return new, RegionRepair(orbit, dropped, kept, counts, idx, val, off, hw, build_ms=(time.perf_counter() - t0) * 1e3)
+
+
+def orbit_column(counts, numel, ascfill=False, has_asc=True):
+    """The orbit rule over a census (pure host code): counts = n rows of S triples {S2, descending S1, ascending S1} NaN entries (nested
+    lists or a tensor (n, S, 3)), numel = n values 2 * h * w.  Returns (orbit int8 (n, S), ok bool (n, S)): ``item_orbit`` of every pair."""
+    cl = counts.tolist() if torch.is_tensor(counts) else counts
+    n, S = len(cl), len(cl[0]) if len(cl) else 0
+    orbit, ok = torch.zeros(n, S, dtype=torch.int8), torch.ones(n, S, dtype=torch.bool)
+    for i in range(n):
+        for s in range(S):
+            o, good = item_orbit(cl[i][s][1], cl[i][s][2], int(numel[i]), ascfill, has_asc)
+            orbit[i, s], ok[i, s] = o, good
+    return orbit, ok
+
+
+def repair_core(region, crops, seasons, ascfill=False, pixel_budget=1 << 22, select=None, no_data=None):
+    """What ``plan_repair`` and ``ResidentWindows`` share: over items crops (n, 4) = {x0, x1, y0, y1} (host integers) x seasons [0, seasons)
+    ONE census call and one synchronisation, the orbit rule (``orbit_column``), and the patch-table pieces of the pairs that need them.
+    Returns (orbit int8 (n, S), counts int64 (n, S, 3), ok bool (n, S), pieces {(i, s): (idx, val)}).
+    ok is False where the reference raises "No data here!"; ``no_data`` (a callable) is handed the list of those (i, s) and the counts
+    before any table work -- what it raises ends the call --, and an item with such a season gets no pieces.  Pieces: the (i, s) whose census shows a NaN in S2
+    or in the chosen S1, and for which ``select(i, s)`` holds where it is given, are grouped by size (``plan_batches`` under ``pixel_budget``
+    pixels per group, a generator of its own; an item at or above the budget is a group of one), gathered with their orbits, filled on a
+    clone and reduced to the entries whose bit pattern changed (``ops.region_patch_extract``: one synchronisation per group)."""
+    S = int(seasons)
+    has_asc = region.s1_asc is not None
+    crops = np.asarray(crops, dtype=np.int64).reshape(-1, 4)
+    n = crops.shape[0]
+    boxes = np.empty((n, S, 5), dtype=np.int64)
+    boxes[:, :, :4] = crops[:, None, :]
+    boxes[:, :, 4] = np.arange(S)[None, :]
+    counts = ops.region_nan_census(region.s2, region.s1, region.boundary, region.band_sel, boxes.reshape(-1, 5),
+                                   s1_asc=region.s1_asc).cpu().reshape(n, S, 3)         # the one synchronisation of the orbit column
+    hw = [(int(c[1] - c[0]), int(c[3] - c[2])) for c in crops]
+    orbit, ok = orbit_column(counts, [2 * h * w for h, w in hw], ascfill, has_asc)
+    if no_data is not None and not bool(ok.all()):
+        no_data([(int(i), int(s)) for i, s in torch.nonzero(~ok).tolist()], counts)
+    alive = ok.all(1)
     # the (item, season) pairs that need patches: a NaN in S2 or in the chosen S1
     chosen = torch.where(orbit == 1, counts[:, :, 2], counts[:, :, 1])
-    pairs = torch.nonzero((counts[:, :, 0] > 0) | (chosen > 0)).tolist()
+    pairs = [(i, s) for i, s in torch.nonzero(((counts[:, :, 0] > 0) | (chosen > 0)) & alive[:, None]).tolist()
+             if select is None or select(i, s)]
     pieces = {}
-    dev = region.device
     if pairs:
         groups = plan_batches([hw[i] for i, _ in pairs], list(range(len(pairs))), int(pixel_budget), PC_GATHER_MAX_B, 0.6,
                               torch.Generator().manual_seed(0))
         for grp in groups:
-            gc = np.array([list(kc[pairs[p][0]]) + [pairs[p][1]] for p in grp], dtype=np.int64)
+            gc = np.array([list(crops[pairs[p][0]]) + [pairs[p][1]] for p in grp], dtype=np.int64)
             go = np.array([int(orbit[pairs[p][0], pairs[p][1]]) for p in grp], dtype=np.uint8)
             gathered = region.gather(gc, orbit=go) if has_asc else region.gather(gc)
             filled = {"S2": gathered["S2"].clone(), "S1": gathered["S1"].clone()}
@@ -341,24 +376,143 @@ def plan_repair(region, plan, seasons=1, ascfill=False, pixel_budget=1 << 22):
             sizes = per_item.tolist()
             for p, pi, pv in zip(grp, idx.split(sizes), val.split(sizes)):
                 pieces[tuple(pairs[p])] = (pi, pv)
-    off = torch.zeros(m * S + 1, dtype=torch.int64)
+    return orbit, counts, ok, pieces
+
+
+def _assemble_table(pieces, slots, dev, who, hint):
+    """pieces {slot: (idx, val)} -> (off int64 (slots + 1) on the host, idx int32, val fp32 on the device): the pieces in slot order.
+    MemoryError, with the byte count, before a table that does not fit is allocated."""
+    off = torch.zeros(slots + 1, dtype=torch.int64)
     order = sorted(pieces)
-    for i, s in order:
-        off[i * S + s + 1] = pieces[(i, s)][0].numel()
+    for k in order:
+        off[k + 1] = pieces[k][0].numel()
     off = torch.cumsum(off, 0)
     total = int(off[-1])
     if total:
         free, _ = torch.cuda.mem_get_info(dev)
         if 8 * total > free:
-            raise MemoryError(f"plan_repair: the patch table takes {8 * total} bytes ({total} entries), device {dev} has {free} free: plan "
-                              "fewer seasons")
+            raise MemoryError(f"{who}: the patch table takes {8 * total} bytes ({total} entries), device {dev} has {free} free: {hint}")
         idx = torch.cat([pieces[k][0] for k in order])
         val = torch.cat([pieces[k][1] for k in order])
     else:
         idx = torch.empty(0, dtype=torch.int32, device=dev)
         val = torch.empty(0, dtype=torch.float32, device=dev)
-    torch.cuda.synchronize(dev)
-    return new, RegionRepair(orbit, dropped, kept, counts, idx, val, off, hw, build_ms=(time.perf_counter() - t0) * 1e3)
+    return off, idx, val
+
+
+def window_orbits(counts, windows, ps, ascfill=False, has_asc=True):
+    """The orbit column of an evaluation's window list from its census (pure host code): counts = per window its triple {S2, descending
+    S1, ascending S1} NaN entries, windows = rows (x, y, season), ps the window side.  Returns int8 (n,): ``item_orbit`` with numel =
+    2 * ps * ps.  A window for which the reference raises "No data here!" (PopulationDataset.py:498-500) raises ValueError naming it."""
+    cl = counts.tolist() if torch.is_tensor(counts) else list(counts)
+    wl = windows.tolist() if torch.is_tensor(windows) else [list(v) for v in windows]
+    if len(cl) != len(wl):
+        raise ValueError(f"window_orbits: one census triple per window, got {len(cl)} for {len(wl)} windows")
+    orbit, ok = orbit_column([[c] for c in cl], [2 * int(ps) * int(ps)] * len(cl), ascfill, has_asc)
+    bad = torch.nonzero(~ok[:, 0]).reshape(-1).tolist() if len(cl) else []
+    if bad:
+        raise _no_data_error(wl[bad[0]], cl[bad[0]], ps, len(bad))
+    return orbit[:, 0].contiguous() if len(cl) else torch.zeros(0, dtype=torch.int8)
+
+
+def _no_data_error(window, triple, ps, how_many):
+    x, y, s = (int(v) for v in window)
+    return ValueError(f"ResidentWindows: no S1 data in window (x, y, season) = ({x}, {y}, {s}) of side {ps}: {int(triple[1])} NaN entries in "
+                      f"the descending and {int(triple[2])} in the ascending orbit of {2 * int(ps) * int(ps)}, both at or above 5 % (the "
+                      f"reference's \"No data here!\"; {how_many} such window(s))")
+
+
+class ResidentWindows:
+    """The sliding windows of an evaluation over a ``ResidentRegion``, planned ONCE: the raster callable ``eval.evaluate_raster`` takes
+    (``.shape`` = (h, w), ``self(x, y, season, ps)`` -> the normalised model input (1, 6, ps, ps) on the device), so that
+    ``evaluate_raster(models, ResidentWindows(region, ps, overlap, ...), ps, overlap, fourseasons, ...)`` returns the bits of
+    ``evaluate_raster(models, raster, ..., raw=True, ascfill=...)`` without a per-window fill, clone, concatenation or synchronisation.
+
+    Construction: the window list is ``eval.get_patch_indices(h, w, patchsize, overlap, fourseasons)``; ONE ``region_nan_census`` over all
+    windows on every rank (the one synchronisation of the orbit column) decides each window's S1 orbit by the reference's rule for test
+    windows (PopulationDataset.py:479-500 = ``nanfill.fill_item_``; ``window_orbits``).  A window for which the reference raises "No data
+    here!" raises ValueError naming (x, y, season) -- on every rank alike, since every rank sees the same census, so no rank enters a
+    collective another never reaches.  A region without ``s1_asc`` keeps the descending orbit and fills it at any fraction; ``ascfill`` then
+    raises.  The patch table (``repair_core``) is built only for the windows of ``shard_indices(n, rank, world)``; MemoryError with the byte
+    count before a table that does not fit is allocated.
+    Attributes: idx int64 (n, 3) the window list, orbit int8 (n,) (0 descending, 1 ascending), counts int64 (n, 3) the census, mine (the
+    window numbers of this rank), off int64 (n + 1) / table_idx int32 / table_val fp32 the patch table (window k: [off[k], off[k + 1])),
+    entries, nbytes (table bytes on the device), ascending (windows on the ascending orbit), build_ms.
+    ``__call__``: one ``ops.region_window`` launch, no synchronisation; a window that is not planned, another ps or a window of another
+    rank raises ValueError."""
+
+    def __init__(self, region, patchsize, overlap, fourseasons=False, ascfill=False, rank=0, world=1, mean6=stats.MEAN6, std6=stats.STD6):
+        import time
+        from .. import eval as E
+        from ..distributed import shard_indices
+        self.region, self.patchsize, self.overlap = region, int(patchsize), int(overlap)
+        self.fourseasons, self.ascfill, self.rank, self.world = bool(fourseasons), bool(ascfill), int(rank), max(1, int(world))
+        self.mean6, self.std6 = tuple(float(v) for v in mean6), tuple(float(v) for v in std6)
+        self.shape = tuple(region.shape)
+        h, w = self.shape
+        ps = self.patchsize
+        S = 4 if self.fourseasons else 1
+        if not 1 <= ps <= min(h, w) or not 0 <= self.overlap or 2 * self.overlap >= ps:
+            raise ValueError(f"ResidentWindows: 1 <= patchsize <= min(h, w) = {min(h, w)} and 0 <= 2 * overlap < patchsize, got patchsize "
+                             f"{patchsize}, overlap {overlap}")
+        if region.seasons < S:
+            raise ValueError(f"ResidentWindows: fourseasons evaluates seasons 0 .. 3, the region holds {region.seasons}")
+        if not 0 <= self.rank < self.world:
+            raise ValueError(f"ResidentWindows: rank in [0, {self.world}), got {rank}")
+        has_asc = region.s1_asc is not None
+        if self.ascfill and not has_asc:
+            raise ValueError("ResidentWindows: ascfill takes the ascending orbit wherever the descending one holds NaN: the region holds no "
+                             "s1_asc")
+        t0 = time.perf_counter()
+        self.idx = E.get_patch_indices(h, w, ps, self.overlap, self.fourseasons)
+        wl = self.idx.tolist()
+        n = len(wl)
+        # the list is origins x seasons: the census runs over the distinct origins and all S seasons at once
+        item = {}
+        for x, y, _ in wl:
+            item.setdefault((x, y), len(item))
+        crops = np.array([[x, x + ps, y, y + ps] for x, y in item], dtype=np.int64).reshape(-1, 4)
+        self._at = {}
+        for k, (x, y, s) in enumerate(wl):
+            self._at.setdefault((x, y, s), k)
+        self.mine = list(shard_indices(n, self.rank, self.world))
+        rows = [(item[(x, y)], s) for x, y, s in wl]                      # window k -> (origin, season) of the census
+        mine = {rows[k] for k in self.mine}
+
+        def no_data(bad, counts):
+            lacking = set(bad)
+            first = min(k for k in range(n) if rows[k] in lacking)
+            raise _no_data_error(wl[first], counts[rows[first][0], rows[first][1]].tolist(), ps, len(bad))
+
+        orbit, counts, ok, pieces = repair_core(region, crops, S, self.ascfill, select=lambda i, s: (i, s) in mine, no_data=no_data)
+        self.orbit = torch.tensor([int(orbit[i, s]) for i, s in rows], dtype=torch.int8)
+        self.counts = torch.stack([counts[i, s] for i, s in rows]) if n else torch.zeros(0, 3, dtype=torch.int64)
+        slot = {}
+        for k in self.mine:
+            slot.setdefault(rows[k], k)
+        self.off, self.table_idx, self.table_val = _assemble_table({slot[key]: pc for key, pc in pieces.items()}, n, region.device,
+                                                                   "ResidentWindows", "evaluate fewer seasons or shard over more ranks")
+        torch.cuda.synchronize(region.device)
+        self._off = self.off.tolist()
+        self._orbit = self.orbit.tolist()
+        self._mine = set(self.mine)
+        self.entries = int(self.off[-1])
+        self.nbytes = 8 * self.entries
+        self.ascending = int(self.orbit.sum())
+        self.build_ms = (time.perf_counter() - t0) * 1e3
+
+    def __call__(self, x, y, season, ps):
+        k = self._at.get((int(x), int(y), int(season)))
+        if int(ps) != self.patchsize or k is None:
+            raise ValueError(f"ResidentWindows: window (x, y, season) = ({x}, {y}, {season}) of side {ps} is not planned: the plan holds "
+                             f"{len(self._at)} windows of side {self.patchsize}, overlap {self.overlap}")
+        if k not in self._mine:
+            raise ValueError(f"ResidentWindows: window {k} = ({x}, {y}, {season}) belongs to rank {k % self.world}, this feed was planned "
+                             f"for rank {self.rank} of {self.world} and holds no patches for it")
+        r = self.region
+        start = self._off[k]
+        return ops.region_window(r.s2, r.s1, r.band_sel, (x, y, season), self.patchsize, self.mean6, self.std6, s1_asc=r.s1_asc,
+                                 orbit=self._orbit[k], table=(self.table_idx, self.table_val, start, self._off[k + 1] - start))
 
 
 class ResidentRegionFeed:

@@ -1277,6 +1277,81 @@ def region_patch_apply(idx, val, off, count, item_hw, s2, s1, hw, params=None):
     return total
 
 
+def region_window_rows(ps):
+    """Rows of one channel a workgroup of ``region_window`` owns at window side ps (pc_region_window_rows; 0 for a ps it refuses)."""
+    return int(L.lib().pc_region_window_rows(int(ps)))
+
+
+def region_window(s2, s1, band_sel, window, ps, mean6, std6, out=None, s1_asc=None, orbit=0, table=None):
+    """The normalised model input (1, 6, ps, ps) of ONE evaluation window of resident rasters in ONE launch (csrc/region_window.hip,
+    pc_region_window), channels [S2 R G B NIR | S1 VV VH]: out = (v - mean6[c]) / std6[c] with ``select_normalize``'s fp32 division.
+    s2, s1, band_sel: as ``region_gather``; window: HOST integers (x, y, season) = row origin, column origin, season; orbit: 0 = s1,
+    1 = s1_asc (shaped like s1).  table = (idx int32 (N,), val fp32 (N,), start, count): the slice [start, start + count) of a patch table as
+    ``region_patch_extract`` writes it -- ascending, idx = (c * ps + i) * ps + j in the window's own (6, ps, ps) space, val the raw repaired
+    value, which replaces the raster's value BEFORE the normalisation.  Every element of out is stored exactly once; no synchronisation.
+    out: a contiguous fp32 device (1, 6, ps, ps) or (6, ps, ps) tensor to write into.  A window that leaves the raster, a season >= S, a ps
+    outside [1, PC_REGION_WINDOW_MAX_PS], a band outside its source, an orbit outside {0, 1} or 1 without s1_asc and a slice outside the
+    tables raise ValueError before anything is enqueued."""
+    what = "region_window"
+    L.require_device(s2, s1)
+    if s2.dim() != 4 or s2.dtype not in (torch.float32, torch.uint16) or not s2.is_contiguous():
+        raise ValueError(f"{what}: s2 must be a contiguous fp32 or uint16 (S, C, h, w) tensor, got {s2.dtype} {tuple(s2.shape)}")
+    S, C2, h, w = s2.shape
+    if s1.dim() != 4 or s1.dtype != torch.float32 or not s1.is_contiguous() or s1.shape[0] != S or tuple(s1.shape[2:]) != (h, w):
+        raise ValueError(f"{what}: s1 must be a contiguous fp32 ({S}, C, {h}, {w}) tensor, got {s1.dtype} {tuple(s1.shape)}")
+    if h * w == 0 or h * w >= 1 << 31:
+        raise ValueError(f"{what}: 0 < h * w < 2^31, got {h} x {w}")
+    C1 = s1.shape[1]
+    band = [int(v) for v in band_sel]
+    if len(band) != 6 or any(not 0 <= v < C2 for v in band[:4]) or any(not 0 <= v < C1 for v in band[4:]):
+        raise ValueError(f"{what}: band_sel names four of {C2} S2 bands and two of {C1} S1 bands (0-based), got {band}")
+    _region_orbit(what, s1, s1_asc, None, 1)
+    if isinstance(orbit, bool) or orbit not in (0, 1) or (orbit == 1 and s1_asc is None):
+        raise ValueError(f"{what}: orbit is 0 (s1) or 1 (s1_asc, which must then be given), got {orbit!r}")
+    ps = int(ps)
+    if not 1 <= ps <= L.PC_REGION_WINDOW_MAX_PS:
+        raise ValueError(f"{what}: ps in [1, {L.PC_REGION_WINDOW_MAX_PS}], got {ps}")
+    win = [int(v) for v in (window.tolist() if torch.is_tensor(window) else window)]
+    if len(win) != 3:
+        raise ValueError(f"{what}: window = (x, y, season), got {win}")
+    x, y, season = win
+    if x < 0 or y < 0 or x + ps > h or y + ps > w or not 0 <= season < S:
+        raise ValueError(f"{what}: window {tuple(win)} of side {ps} leaves the {h} x {w} raster or names a season outside [0, {S})")
+    mean = [float(v) for v in mean6]
+    std = [float(v) for v in std6]
+    if len(mean) != 6 or len(std) != 6:
+        raise ValueError(f"{what}: mean6 and std6 hold six values each, got {len(mean)} and {len(std)}")
+    idx = val = None
+    cap = start = count = 0
+    if table is not None:
+        idx, val, start, count = table
+        start, count = int(start), int(count)
+        if count > 0 or idx is not None:
+            if idx is None or val is None:
+                raise ValueError(f"{what}: a slice of {count} entries needs the tables idx and val")
+            L.require_device(idx, val)
+            if (idx.dtype != torch.int32 or val.dtype != torch.float32 or idx.dim() != 1 or idx.shape != val.shape or
+                    not idx.is_contiguous() or not val.is_contiguous() or idx.device != s1.device or val.device != s1.device):
+                raise ValueError(f"{what}: idx int32 (N,) and val fp32 (N,), contiguous, on the rasters' device")
+            cap = idx.numel()
+        if start < 0 or count < 0 or start + count > cap or count > 6 * ps * ps:
+            raise ValueError(f"{what}: the slice [{start}, {start} + {count}) lies outside the table of {cap} entries or exceeds the "
+                             f"window's {6 * ps * ps} sites")
+    if out is None:
+        out = torch.empty(1, 6, ps, ps, dtype=torch.float32, device=s1.device)
+    else:
+        L.require_device(out)
+        if (out.dtype != torch.float32 or tuple(out.shape) not in ((1, 6, ps, ps), (6, ps, ps)) or not out.is_contiguous() or
+                out.device != s1.device):
+            raise ValueError(f"{what}: out must be a contiguous fp32 (1, 6, {ps}, {ps}) tensor on the rasters' device, got {out.dtype} "
+                             f"{tuple(out.shape)}")
+    L.check(L.lib().pc_region_window(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), int(orbit), S, C2, C1, h, w,
+                                     (C.c_int32 * 6)(*band), x, y, season, ps, (C.c_float * 6)(*mean), (C.c_float * 6)(*std),
+                                     L.ptr(idx if count > 0 else None), L.ptr(val if count > 0 else None), C.c_int64(cap),
+                                     C.c_int64(start), C.c_int64(count), L.ptr(out), L.stream_ptr()), "pc_region_window")
+    return out
+
+
 def nan_fill_(x, hw=None, count_only=False):
     """Nearest-value NaN fill in place (data/PopulationDataset.py:526-551 interpolate_nan, pc_nan_fill): x = contiguous fp32 device tensor
     (B, C, H, W) or (C, H, W), each sample's (C, h, w) array filled on its own -- every NaN takes the value of the nearest known entry in
