@@ -226,10 +226,21 @@ __global__ __launch_bounds__(256) void conv3x3_mfma_kernel(const ConvArgs p) {
             I = I < 0 ? 0 : (I >= Hh ? Hh - 1 : I);                            // clamped: masked when it is written to LDS
             const int c0 = (x0 >> 1) - 1 + 9 * z_half;                          // first of the lane's 9 columns (>= -1)
             const float* rowp = q.z + b * q.z_bs + (int64_t)(zc * 8 + z_ch) * q.z_cs + (int64_t)I * q.z_rs;
-            Rz[0] = rowp[c0 < 0 ? 0 : c0];
+            if (c0 + 7 < Wh) {                                                  // columns 1..7 inside the row: immediate offsets
+                Rz[0] = rowp[c0 < 0 ? 0 : c0];
 #pragma unroll
-            for (int k = 1; k < 8; ++k) Rz[k] = rowp[c0 + k];
-            Rz[8] = rowp[c0 + 8 < Wh ? c0 + 8 : Wh - 1];
+                for (int k = 1; k < 8; ++k) Rz[k] = rowp[c0 + k];
+                Rz[8] = rowp[c0 + 8 < Wh ? c0 + 8 : Wh - 1];                    // (the halo column of the image's last tile)
+            } else {
+                // the piece ends beyond the row (a map narrower than 18 columns, the ragged last tile): clamped like the rows, masked
+                // when it is written to LDS -- unclamped these loads ran into the next row and, in the last row of the last channel
+                // of the last image, up to 16 floats past the end of z
+#pragma unroll
+                for (int k = 0; k < 9; ++k) {
+                    const int c = c0 + k;
+                    Rz[k] = rowp[c < 0 ? 0 : (c < Wh ? c : Wh - 1)];
+                }
+            }
         }
     };
     auto commit_z = [&](int y0, int x0) {        // the coordinates of the strip whose piece is pending

@@ -309,7 +309,8 @@ __global__ __launch_bounds__(256) void conv3x3_cl_kernel(const ConvArgs p) {
                             const u32x2 sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(m), __float_as_uint(m), false, false);
                             v[r] = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1]));
                         }
-                        if ((li & 1) == 0 && e_s == 0)
+                        // (`ok`: a strip below the image -- H % 16 != 0 -- has no pooled rows: its store landed in the next image)
+                        if ((li & 1) == 0 && e_s == 0 && ok)
                             pc_st4(reinterpret_cast<pc_bf16_t*>(q.pool_out.ptr) + eb * q.pool_out.bstride +
                                        (int64_t)((ey0 >> 1) + (u >> 1)) * q.pool_out.rstride +
                                        (int64_t)((ex0 >> 1) + (u & 1) * 8 + (li >> 1)) * q.pool_out.xstride + nb * 8 + c4, v);

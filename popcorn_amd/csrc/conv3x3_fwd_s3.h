@@ -438,7 +438,9 @@ __global__ __launch_bounds__(256, (FS3Cfg<CI, CO, ZC>::WAVES_PER_SIMD)) void con
                         float m0 = fmaxf(v[0], v[1]), m1 = fmaxf(v[2], v[3]);
                         m0 = fmaxf(m0, pc_lane_xor8(m0));
                         m1 = fmaxf(m1, pc_lane_xor8(m1));
-                        if (s_row == 0)
+                        // (`in`: a strip below the image -- H % 16 != 0, the waves past the last row of a ragged last tile -- has no pooled
+                        //  rows; its store landed in the next channel's first rows and, for the last channel, past the end of pool_out)
+                        if (s_row == 0 && in)
                             *(pc_gst2)(po_base + (size_t)(((unsigned)eb * po_bs + (unsigned)(nb * 8 + col) * po_cs + (unsigned)(y >> 1) * po_rs +
                                                              (unsigned)(x >> 1)) * 4u)) = f32x2{m0, m1};
                     }
