@@ -985,6 +985,28 @@ int pc_region_window_rows(int ps);
 int pc_region_window(const void* s2, int s2_u16, const float* s1, const float* s1_asc, int orbit, int S, int C2, int C1, int h, int w,
                      const int32_t* band_sel, int x, int y, int season, int ps, const float* mean6, const float* std6, const int32_t* idx,
                      const float* val, int64_t cap, int64_t start, int64_t count, float* out, void* stream);
+/* pc_region_item (csrc/region_item.hip): the normalised model input AND the admin mask of ONE rectangular crop {x0, x1, y0, y1, season} of
+ * the resident rasters (rows [x0, x1), columns [y0, y1); hc = x1 - x0, wc = y1 - y0) in ONE launch -- a validation item.
+ * out DEVICE fp32 (6, hc, wc), channels [S2 R G B NIR | S1 VV VH]:  out[c][i][j] = (v - mean6[c]) / std6[c]  (the fp32 division of
+ * pc_select_normalize), v = the value of the patch table where its slice [start, start + count) holds an entry for the site, otherwise the
+ * raster's value at (season, band_sel[c], x0 + i, y0 + j); orbit 1 reads the two S1 channels from s1_asc; uint16 S2 converts exactly.
+ * admin_out DEVICE fp32 (hc, wc) = (float)boundary[x0 + i][y0 + j].  Sources and band_sel as pc_region_gather.  idx / val DEVICE tables of
+ * cap entries as pc_region_patch_write makes them: the slice ascends, idx = (c * hc + i) * wc + j in the item's own (6, hc, wc) space, val =
+ * the raw, un-normalised repaired value; both may be NULL with count = 0.  By definition, bit for bit on every non-NaN element and with NaN
+ * at the same sites:
+ *   out       == pc_select_normalize(cat(S2, S1 of patch_apply(pc_region_gather_orbit({crop}, orbit))), 0 .. 5, mean6, std6)
+ *   admin_out == admin_mask of that gather (B = 1: no padding)
+ * Every element of both outputs is stored exactly once, the patch value before the normalisation; nothing outside them is written.  There
+ * is no cap on a side: a workgroup owns a contiguous range of PC_REGION_ITEM_TILE elements of one plane's hc * wc index space, which need
+ * not end on a row boundary (an entry's place is checked against that range whatever the table holds).  16-byte accesses when wc % 4 == 0
+ * and both outputs are 16-byte aligned, element by element otherwise.  PC_EINVAL before anything is enqueued: a NULL pointer, an empty crop
+ * or one that leaves the raster, 6 * hc * wc >= 2^31, a season outside [0, S), a band outside its source, an orbit outside {0, 1} or 1
+ * without s1_asc, count > 0 without tables, a slice outside [0, cap] or longer than 6 * hc * wc, misaligned pointers. */
+#define PC_REGION_ITEM_TILE 4096
+int pc_region_item(const void* s2, int s2_u16, const float* s1, const float* s1_asc, int orbit, const int32_t* boundary, int S, int C2, int C1,
+                   int h, int w, const int32_t* band_sel, int x0, int x1, int y0, int y1, int season, const float* mean6, const float* std6,
+                   const int32_t* idx, const float* val, int64_t cap, int64_t start, int64_t count, float* out, float* admin_out,
+                   void* stream);
 
 #ifdef __cplusplus
 }

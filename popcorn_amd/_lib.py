@@ -164,6 +164,7 @@ PC_UNIT_LAYOUT_MAX_K, PC_UNIT_LAYOUT_MAX_B = 1024, 256
 PC_REGION_GATHER_MAX_B = 128          # crops per pc_region_gather launch (the crop list travels in the kernel arguments)
 PC_REGION_PATCH_CHUNK = 4096          # entries of an item's index space per workgroup of pc_region_patch_count / _write
 PC_REGION_WINDOW_MAX_PS = 8192        # the widest window of pc_region_window (one row = a 32 KB tile; 6 * ps * ps < 2^31)
+PC_REGION_ITEM_TILE = 4096            # elements of one plane's hc * wc index space a workgroup of pc_region_item owns
 
 
 class PcRegionLabels(C.Structure):
@@ -260,6 +261,12 @@ def lib():
         _lib.pc_region_window.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_int32)] +
                                           [C.c_int] * 4 + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p] +
                                           [C.c_int64] * 3 + [C.c_void_p, C.c_void_p])
+        # resident validation (csrc/region_item.hip): s2, s2_u16, s1, s1_asc, orbit, boundary, S, C2, C1, h, w, band_sel, x0, x1, y0, y1,
+        # season, mean6, std6, idx, val, cap, start, count, out, admin_out, stream
+        _lib.pc_region_item.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 5 +
+                                        [C.POINTER(C.c_int32)] + [C.c_int] * 5 +
+                                        [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p] + [C.c_int64] * 3 +
+                                        [C.c_void_p] * 3)
     return _lib
 
 

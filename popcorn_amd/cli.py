@@ -128,6 +128,15 @@ def train_parser():
                         "--test_overlap) through data/region.py: ResidentWindows -- orbit and NaN repair of every window planned at the "
                         "first test and reused by every later one, one launch per window, no per-window fill; keeps the ascending S1 "
                         "resident as --resident_repair does")
+    p.add_argument("--resident_seasons", type=int, default=1, metavar="S",
+                   help="--resident_region: the synthetic raster holds S seasons and the resident feeds, --resident_repair and "
+                        "--resident_val draw every item's season from them (the reference trains and validates across four); "
+                        "--resident_test keeps evaluating season 0")
+    p.add_argument("--resident_val", action="store_true",
+                   help="--resident_region: the reference's -wv split on the resident raster -- the census rows are shuffled once "
+                        "(random_state 1610), the run trains on the first 80 %% and validate_weak runs over the other 20 %% through "
+                        "data/region.py: ResidentItems (season, orbit and NaN repair of every item planned once, one launch per item, no "
+                        "per-item fill or synchronisation); needs -wvb 1; keeps the ascending S1 resident as --resident_repair does")
     return p
 
 
@@ -279,6 +288,17 @@ def check_repair_args(args):
     if args.resident_test and args.resident_region is None:
         raise SystemExit("--resident_test evaluates the resident region itself in the in-training target test (windows planned once on "
                          "the device): it needs --resident_region")
+    if args.resident_seasons != 1 and args.resident_region is None:
+        raise SystemExit("--resident_seasons sets how many seasons the resident raster holds and its feeds draw from: it needs "
+                         "--resident_region")
+    if args.resident_seasons < 1:
+        raise SystemExit("--resident_seasons is a number of seasons >= 1")
+    if args.resident_val and args.resident_region is None:
+        raise SystemExit("--resident_val splits the census rows of the resident raster into a training and a validation plan (items "
+                         "planned once on the device): it needs --resident_region")
+    if args.resident_val and args.weak_val_batch_size != 1:
+        raise SystemExit(f"--resident_val validates item by item (padding makes an item's result depend on its batch): -wvb must be 1, got "
+                         f"{args.weak_val_batch_size}")
 
 
 def check_eval_args(args):
@@ -390,21 +410,41 @@ class Trainer:
                              "gather and the augmentation, which the one-launch assembly fuses; the unfused --resident_region feed takes it")
         if a.resident_pixel_budget < 0 or a.resident_max_batch < 1 or not 0.0 <= a.resident_min_fill <= 1.0:
             raise SystemExit("--resident_pixel_budget >= 0, --resident_max_batch >= 1 and --resident_min_fill in [0, 1]")
-        from .data.region import ResidentBatchFeed, ResidentRegion, ResidentRegionFeed, plan_multi_unit, plan_one_unit, plan_repair
-        data = SyntheticTestRaster(a.resident_region[0], a.resident_region[1], seasons=1, n_regions=a.resident_units, seed=a.seed + 20,
+        from .data.region import (ResidentBatchFeed, ResidentItems, ResidentRegion, ResidentRegionFeed, plan_multi_unit, plan_one_unit,
+                                  plan_repair, split_census)
+        S = a.resident_seasons
+        data = SyntheticTestRaster(a.resident_region[0], a.resident_region[1], seasons=S, n_regions=a.resident_units, seed=a.seed + 20,
                                    device=self.device, raw=True, nan_clouds=a.nan_clouds, s1_gap=a.resident_s1_gap)
-        self.region = ResidentRegion.from_synthetic(data, with_asc=a.resident_repair or a.resident_test)
+        self.region = ResidentRegion.from_synthetic(data, with_asc=a.resident_repair or a.resident_test or a.resident_val)
         self.region_data = data                                          # (the raster callable of evaluate_raster(raw=True) over the same data)
         kw = dict(max_pix=a.max_weak_pix, max_pix_box=a.max_pix_box)
-        if a.units_per_crop > 0:
-            self.region_plan = plan_multi_unit(self.region.table, self.region.census_idx, self.region.census_pop, self.region.shape,
-                                               units_per_crop=a.units_per_crop, **kw)
-        else:
-            self.region_plan = plan_one_unit(self.region.table, self.region.census_idx, self.region.census_pop, self.region.shape, **kw)
+
+        def plan_of(split):
+            # the reference's order: the split, then the two size filters (inside the planner)
+            n = self.region.census_idx.numel()
+            ids, pop = split_census(self.region.census_idx, self.region.census_pop, split)
+            if ids.numel() < 1:
+                raise SystemExit(f"--resident_val: the {split} split of {n} census rows is empty (int({n} * 0.8) = {int(n * 0.8)} rows train)")
+            if a.units_per_crop > 0:
+                return plan_multi_unit(self.region.table, ids, pop, self.region.shape, units_per_crop=a.units_per_crop, **kw)
+            return plan_one_unit(self.region.table, ids, pop, self.region.shape, **kw)
+
+        self.region_plan = plan_of("train" if a.resident_val else "all")
+        self.val_items = None
+        if a.resident_val:
+            # the held-out 20 %: season, orbit and repaired sites of every item planned once; its own generator, seeded from --seed
+            val_plan = plan_of("val")
+            if len(val_plan) < 1:
+                raise SystemExit("--resident_val: no unit of the validation split survives the size filters")
+            v = self.val_items = ResidentItems(self.region, val_plan, seasons=S, generator=torch.Generator().manual_seed(a.seed),
+                                               ascfill=a.ascfill)
+            if self.rank == 0:
+                print(f"resident validation: {len(val_plan)} items, {len(v.dropped)} dropped, {v.ascending} ascending, {v.entries} table "
+                      f"entries ({v.nbytes} bytes), built in {v.build_ms:.1f} ms", flush=True)
         self.region_repair = None
         if a.resident_repair:
             n0 = len(self.region_plan)
-            self.region_plan, self.region_repair = plan_repair(self.region, self.region_plan, seasons=1, ascfill=a.ascfill)
+            self.region_plan, self.region_repair = plan_repair(self.region, self.region_plan, seasons=S, ascfill=a.ascfill)
             self._step_nan_fill = False
             r = self.region_repair
             if self.rank == 0:
@@ -418,10 +458,11 @@ class Trainer:
             # Trainer.__init__ hands it the trainer's own data_transform, the same set, once that exists
             self._resident_feed = ResidentBatchFeed(self.region, self.region_plan, a.weak_batch_size, transform=default_train_transform(),
                                                     generator=gen, drop_last=True, pixel_budget=a.resident_pixel_budget,
-                                                    max_batch=a.resident_max_batch, min_fill=a.resident_min_fill, repair=self.region_repair)
+                                                    max_batch=a.resident_max_batch, min_fill=a.resident_min_fill, repair=self.region_repair,
+                                                    seasons=S)
         else:
             self._resident_feed = ResidentRegionFeed(self.region, self.region_plan, a.weak_batch_size, generator=gen, drop_last=True,
-                                                     repair=self.region_repair)
+                                                     repair=self.region_repair, seasons=S)
 
     # ---- checkpoint (run_train.py:445-476) --------------------------------------------------------------------------
     def save_model(self, prefix="last"):
@@ -544,16 +585,24 @@ class Trainer:
 
     # ---- validation / in-training target test (run_train.py:289-370) ---------------------------------------------------
     def validate_weak(self):
-        """Weak validation: census-level metrics of model(sample, padding=False) over the validation regions."""
+        """Weak validation: census-level metrics of model(sample, padding=False) over the validation regions.  --resident_val: over the
+        held-out units of the resident raster (data/region.py: ResidentItems), one launch per item in front of the model."""
         from .utils.metrics import get_test_metrics
         self.model.eval()
         pred, gt = [], []
         with torch.no_grad():
-            for sample in self.val_loader:
-                s = normalize_sample(sample, self.device, None, nan_fill=self.args.nan_fill)
-                out = self.model(s, padding=False)
-                pred.append(out["popcount"])
-                gt.append(s["y"])
+            if self.args.resident_val:
+                from .data.units import flat_valid
+                for s in self.val_items:
+                    out = self.model(s, padding=False)
+                    pred.append(out["popcount"])
+                    gt.append(flat_valid(s["y"], s["census_n"]) if s.get("census_n") is not None else s["y"])
+            else:
+                for sample in self.val_loader:
+                    s = normalize_sample(sample, self.device, None, nan_fill=self.args.nan_fill)
+                    out = self.model(s, padding=False)
+                    pred.append(out["popcount"])
+                    gt.append(s["y"])
         stats = get_test_metrics(torch.cat(pred), torch.cat(gt).float(), tag="MainCensus_synthetic_fine")
         self.valweak_stats = {k + "/val": float(v) for k, v in stats.items()}
         self._log(self.valweak_stats)

@@ -19,8 +19,12 @@ and pixel counts are made at preprocessing time with one pass per unit (utils/02
                           one census pass, repaired sites as a patch table (``repair_core``, shared with ``plan_repair``), sharded over
                           ranks like the windows --, each window's normalised model input then ONE ``ops.region_window`` launch with no
                           fill and no synchronisation; it is the raster callable ``evaluate_raster`` already takes
+  ``split_census``        the reference's 80 / 20 split of the census rows (one shuffle with random_state 1610), before the size filters
+  ``ResidentItems``       the same region VALIDATED: the items of a (validation) plan with season, orbit and repaired sites planned once,
+                          each item's normalised input and admin mask then ONE ``ops.region_item`` launch
 
-Host glue, plain torch; the kernels are csrc/region.hip, csrc/region_batch.hip, csrc/region_repair.hip and csrc/region_window.hip.  Deviations from the reference, all named where they happen: units without pixels
+Host glue, plain torch; the kernels are csrc/region.hip, csrc/region_batch.hip, csrc/region_repair.hip, csrc/region_window.hip and
+csrc/region_item.hip.  Deviations from the reference, all named where they happen: units without pixels
 are dropped (``plan_one_unit``); the per-epoch order and the season per item come from a torch generator, not Python's ``random`` stream
 (``ResidentRegionFeed``); without ``plan_repair`` the resident S1 is the orbit already chosen per season (``--nan_fill`` fills what is
 left), with it an item the reference would end on ("No data here!") is dropped from the plan.  Sharding a plan over data-parallel ranks and graph capture of the gather are not part of this module."""
@@ -148,6 +152,35 @@ def _eligible(table, census_idx, census_pop, max_pix, max_pix_box):
     keep &= area < max_pix_box                                                  # :128-131
     keep &= count > 0
     return ids[keep], pop[keep], bbox[keep], count[keep]
+
+
+SPLIT_SEED = 1610                                   # the reference's random_state (PopulationDataset.py:112, :117)
+
+
+def split_census(census_idx, census_pop, split, frac=0.8, seed=SPLIT_SEED):
+    """The reference's 80 / 20 split of a census table (data/PopulationDataset.py:105-121; run_train.py:425-440 builds the training set
+    with split="train" and the validation set with split="val" under ``-wv``): returns (census_idx', census_pop').
+    Rule: the n rows are permuted as ``DataFrame.sample(frac=1, random_state=1610)`` permutes them, which is
+    ``numpy.random.RandomState(1610).permutation(n)`` (pinned by tests/golden/g14_split.npz, written with pandas itself); "train" is the
+    first int(n * frac) rows of that order, "val" the rest, and both KEEP the permuted order, as the reference's items do after its
+    ``reset_index``.  "all" returns the rows untouched.  Both cuts come from one permutation, so they are disjoint and cover the table.
+    Placement: before the two size filters, as in the reference -- hand the result to ``plan_one_unit`` / ``plan_multi_unit`` as it is.
+    Multi-unit plans: the units are split first and a crop is composed from one split's units only; a validation unit may still lie inside
+    a training crop, where it shows up in ``admin_mask`` as an unlisted neighbour, which the step ignores (its pixels reach no loss term).
+    int(n * frac) == 0 (n = 1) gives an empty training split: the caller refuses it, naming n.  Pure host code; no pandas."""
+    ids = torch.as_tensor(census_idx, dtype=torch.int64).cpu().reshape(-1)
+    pop = torch.as_tensor(census_pop, dtype=torch.float32).cpu().reshape(-1)
+    if ids.numel() != pop.numel():
+        raise ValueError("split_census: census_idx and census_pop differ in length")
+    if split == "all":
+        return ids, pop
+    if split not in ("train", "val"):
+        raise ValueError(f"split_census: split is \"all\", \"train\" or \"val\", got {split!r}")
+    n = ids.numel()
+    order = torch.from_numpy(np.random.RandomState(int(seed)).permutation(n).astype(np.int64))
+    cut = int(n * frac)
+    rows = order[:cut] if split == "train" else order[cut:]
+    return ids[rows], pop[rows]
 
 
 def plan_one_unit(table, census_idx, census_pop, shape, admin_overlap=32, max_pix=MAX_PIX, max_pix_box=MAX_PIX_BOX):
@@ -339,7 +372,7 @@ def repair_core(region, crops, seasons, ascfill=False, pixel_budget=1 << 22, sel
     ONE census call and one synchronisation, the orbit rule (``orbit_column``), and the patch-table pieces of the pairs that need them.
     Returns (orbit int8 (n, S), counts int64 (n, S, 3), ok bool (n, S), pieces {(i, s): (idx, val)}).
     ok is False where the reference raises "No data here!"; ``no_data`` (a callable) is handed the list of those (i, s) and the counts
-    before any table work -- what it raises ends the call --, and an item with such a season gets no pieces.  Pieces: the (i, s) whose census shows a NaN in S2
+    before any table work -- what it raises ends the call --, and an item with such a season gets no pieces (under ``select``: a pair without data gets none, the item's other seasons keep theirs).  Pieces: the (i, s) whose census shows a NaN in S2
     or in the chosen S1, and for which ``select(i, s)`` holds where it is given, are grouped by size (``plan_batches`` under ``pixel_budget``
     pixels per group, a generator of its own; an item at or above the budget is a group of one), gathered with their orbits, filled on a
     clone and reduced to the entries whose bit pattern changed (``ops.region_patch_extract``: one synchronisation per group)."""
@@ -356,10 +389,11 @@ def repair_core(region, crops, seasons, ascfill=False, pixel_budget=1 << 22, sel
     orbit, ok = orbit_column(counts, [2 * h * w for h, w in hw], ascfill, has_asc)
     if no_data is not None and not bool(ok.all()):
         no_data([(int(i), int(s)) for i, s in torch.nonzero(~ok).tolist()], counts)
-    alive = ok.all(1)
+    # an item lacking data in ANY season gets no pieces; under ``select`` only the selected pairs count, each on its own season
+    alive = ok.all(1)[:, None] if select is None else ok
     # the (item, season) pairs that need patches: a NaN in S2 or in the chosen S1
     chosen = torch.where(orbit == 1, counts[:, :, 2], counts[:, :, 1])
-    pairs = [(i, s) for i, s in torch.nonzero(((counts[:, :, 0] > 0) | (chosen > 0)) & alive[:, None]).tolist()
+    pairs = [(i, s) for i, s in torch.nonzero(((counts[:, :, 0] > 0) | (chosen > 0)) & alive).tolist()
              if select is None or select(i, s)]
     pieces = {}
     if pairs:
@@ -513,6 +547,86 @@ class ResidentWindows:
         start = self._off[k]
         return ops.region_window(r.s2, r.s1, r.band_sel, (x, y, season), self.patchsize, self.mean6, self.std6, s1_asc=r.s1_asc,
                                  orbit=self._orbit[k], table=(self.table_idx, self.table_val, start, self._off[k + 1] - start))
+
+
+class ResidentItems:
+    """The validation set of a ``RegionPlan`` over a ``ResidentRegion``, planned ONCE: iterating yields one item at a time in the form
+    ``model(sample, padding=False)`` takes -- {"input" (1, 6, hc, wc), "admin_mask" (1, hc, wc), "census_idx", "y"} ((1,) each for a one-unit
+    plan; (1, K) plus the host list ``census_n`` = [K] for a multi-unit plan, K = the item's listed units) --, each item ONE
+    ``ops.region_item`` launch: no clone, no concatenation, no fill and no synchronisation after construction.  By definition, bit for bit:
+
+        item == normalize_sample(region.gather([crop + season], orbit=[orbit]), transform=None, nan_fill=True)
+
+    Construction: the season of every item is drawn ONCE -- ``torch.randint(0, seasons, (n,))`` from ``generator``, all zero for seasons ==
+    1.  Named deviation: the reference draws a fresh season from Python's ``random`` at every validation (PopulationDataset.py:409), so its
+    validation sets differ from epoch to epoch; here every validation sees the same (item, season) list and its metrics are comparable.
+    ``repair_core`` over the plan's crops, restricted to each item's own season, gives the orbit (one census call, one synchronisation; the
+    rule of ``plan_repair``) and the patch pieces.  An item whose own season would make the reference raise "No data here!" is dropped and
+    its row of the ORIGINAL plan recorded in ``dropped`` -- the named deviation of ``plan_repair``.  MemoryError with the byte count before a
+    table that does not fit is allocated.
+    Attributes: plan (the surviving items, in order), season int64 (m,) and orbit int8 (m,) of the surviving items, counts int64 (m, 3)
+    their census, off int64 (m + 1) / table_idx int32 / table_val fp32 the patch table (item k: [off[k], off[k + 1])), entries, nbytes
+    (table bytes on the device), ascending (items on the ascending orbit), build_ms, dropped."""
+
+    def __init__(self, region, plan, seasons=1, generator=None, ascfill=False, mean6=stats.MEAN6, std6=stats.STD6):
+        import time
+        S = int(seasons)
+        if not 1 <= S <= region.seasons:
+            raise ValueError(f"ResidentItems: seasons in [1, {region.seasons}] (what the region holds), got {seasons}")
+        if len(plan) < 1:
+            raise ValueError("ResidentItems: a plan with at least one crop")
+        if ascfill and region.s1_asc is None:
+            raise ValueError("ResidentItems: ascfill takes the ascending orbit wherever the descending one holds NaN: the region holds no "
+                             "s1_asc")
+        t0 = time.perf_counter()
+        self.region, self.seasons, self.ascfill = region, S, bool(ascfill)
+        self.mean6, self.std6 = tuple(float(v) for v in mean6), tuple(float(v) for v in std6)
+        n = len(plan)
+        gen = generator if generator is not None else torch.Generator().manual_seed(0)
+        drawn = torch.randint(0, S, (n,), generator=gen) if S > 1 else torch.zeros(n, dtype=torch.int64)
+        own = drawn.tolist()
+        orbit, counts, ok, pieces = repair_core(region, plan.crops.numpy(), S, self.ascfill, select=lambda i, s: s == own[i])
+        kept = [i for i in range(n) if bool(ok[i, own[i]])]
+        self.dropped = [i for i in range(n) if not bool(ok[i, own[i]])]
+        if not kept:
+            raise ValueError("ResidentItems: every item of the plan lacks S1 data in its season (the reference's \"No data here!\")")
+        self.plan = plan.subset(kept)
+        m = len(kept)
+        self.season = drawn[torch.tensor(kept, dtype=torch.int64)].contiguous()
+        self.orbit = torch.tensor([int(orbit[i, own[i]]) for i in kept], dtype=torch.int8)
+        self.counts = torch.stack([counts[i, own[i]] for i in kept])
+        row = {i: k for k, i in enumerate(kept)}
+        self.off, self.table_idx, self.table_val = _assemble_table({row[i]: pc for (i, s), pc in pieces.items() if i in row}, m,
+                                                                   region.device, "ResidentItems", "validate fewer items")
+        # the plan tables, uploaded once: an item's labels are views of them
+        self._cidx = self.plan.census_idx.to(region.device).contiguous()
+        self._y = self.plan.y.to(region.device).float().contiguous()
+        torch.cuda.synchronize(region.device)
+        self._crops = [tuple(int(v) for v in c) + (int(s),) for c, s in zip(self.plan.crops.tolist(), self.season.tolist())]
+        self._off = self.off.tolist()
+        self._orbit = self.orbit.tolist()
+        self.entries = int(self.off[-1])
+        self.nbytes = 8 * self.entries
+        self.ascending = int(self.orbit.sum())
+        self.build_ms = (time.perf_counter() - t0) * 1e3
+
+    def __len__(self):
+        return len(self.plan)
+
+    def item(self, k):
+        """Item k: one ``ops.region_item`` launch."""
+        r, plan = self.region, self.plan
+        start = self._off[k]
+        x, admin = ops.region_item(r.s2, r.s1, r.boundary, r.band_sel, self._crops[k], self.mean6, self.std6, s1_asc=r.s1_asc,
+                                   orbit=self._orbit[k], table=(self.table_idx, self.table_val, start, self._off[k + 1] - start))
+        if plan.multi:
+            K = plan.census_n[k]
+            return {"input": x, "admin_mask": admin, "census_idx": self._cidx[k:k + 1, :K], "y": self._y[k:k + 1, :K], "census_n": [K]}
+        return {"input": x, "admin_mask": admin, "census_idx": self._cidx[k, :1], "y": self._y[k, :1]}
+
+    def __iter__(self):
+        for k in range(len(self.plan)):
+            yield self.item(k)
 
 
 class ResidentRegionFeed:

@@ -1352,6 +1352,66 @@ def region_window(s2, s1, band_sel, window, ps, mean6, std6, out=None, s1_asc=No
     return out
 
 
+def region_item(s2, s1, boundary, band_sel, crop, mean6, std6, out=None, admin_out=None, s1_asc=None, orbit=0, table=None):
+    """The normalised model input (1, 6, hc, wc) AND the admin mask (1, hc, wc) of ONE rectangular crop of resident rasters in ONE launch
+    (csrc/region_item.hip, pc_region_item) -- a validation item: input = (v - mean6[c]) / std6[c] with ``select_normalize``'s fp32
+    division, channels [S2 R G B NIR | S1 VV VH]; admin_mask = (float)boundary over the crop.
+    s2, s1, boundary, band_sel: as ``region_gather``; crop: HOST integers (x0, x1, y0, y1, season), rows [x0, x1) and columns [y0, y1);
+    orbit: 0 = s1, 1 = s1_asc (shaped like s1).  table = (idx int32 (N,), val fp32 (N,), start, count): the slice [start, start + count) of
+    a patch table as ``region_patch_extract`` writes it -- ascending, idx = (c * hc + i) * wc + j in the item's own (6, hc, wc) space, val the
+    raw repaired value, which replaces the raster's value BEFORE the normalisation.  Every element of both outputs is stored exactly once;
+    no synchronisation; no cap on a side (6 * hc * wc < 2^31).  out / admin_out: contiguous fp32 device tensors (1, 6, hc, wc) or
+    (6, hc, wc) / (1, hc, wc) or (hc, wc) to write into.  Returns (input, admin_mask).  An empty crop, one that leaves the raster, a season
+    >= S, a band outside its source, an orbit outside {0, 1} or 1 without s1_asc and a slice outside the tables raise ValueError before
+    anything is enqueued."""
+    what = "region_item"
+    cr = [int(v) for v in (crop.tolist() if torch.is_tensor(crop) or isinstance(crop, np.ndarray) else crop)]
+    if len(cr) != 5:
+        raise ValueError(f"{what}: crop = (x0, x1, y0, y1, season), got {cr}")
+    S, C2, C1, h, w, band, _, hc, wc = _region_inputs(what, s2, s1, boundary, band_sel, [cr])
+    _region_orbit(what, s1, s1_asc, None, 1)
+    if isinstance(orbit, bool) or orbit not in (0, 1) or (orbit == 1 and s1_asc is None):
+        raise ValueError(f"{what}: orbit is 0 (s1) or 1 (s1_asc, which must then be given), got {orbit!r}")
+    if 6 * hc * wc >= 1 << 31:
+        raise ValueError(f"{what}: 6 * hc * wc < 2^31, got a crop of {hc} x {wc}")
+    mean = [float(v) for v in mean6]
+    std = [float(v) for v in std6]
+    if len(mean) != 6 or len(std) != 6:
+        raise ValueError(f"{what}: mean6 and std6 hold six values each, got {len(mean)} and {len(std)}")
+    idx = val = None
+    cap = start = count = 0
+    if table is not None:
+        idx, val, start, count = table
+        start, count = int(start), int(count)
+        if count > 0 or idx is not None:
+            if idx is None or val is None:
+                raise ValueError(f"{what}: a slice of {count} entries needs the tables idx and val")
+            L.require_device(idx, val)
+            if (idx.dtype != torch.int32 or val.dtype != torch.float32 or idx.dim() != 1 or idx.shape != val.shape or
+                    not idx.is_contiguous() or not val.is_contiguous() or idx.device != s1.device or val.device != s1.device):
+                raise ValueError(f"{what}: idx int32 (N,) and val fp32 (N,), contiguous, on the rasters' device")
+            cap = idx.numel()
+        if start < 0 or count < 0 or start + count > cap or count > 6 * hc * wc:
+            raise ValueError(f"{what}: the slice [{start}, {start} + {count}) lies outside the table of {cap} entries or exceeds the "
+                             f"item's {6 * hc * wc} sites")
+    dev = s1.device
+    if out is None:
+        out = torch.empty(1, 6, hc, wc, dtype=torch.float32, device=dev)
+    if admin_out is None:
+        admin_out = torch.empty(1, hc, wc, dtype=torch.float32, device=dev)
+    L.require_device(out, admin_out)
+    for t, shapes, name in ((out, ((1, 6, hc, wc), (6, hc, wc)), "out"), (admin_out, ((1, hc, wc), (hc, wc)), "admin_out")):
+        if t.dtype != torch.float32 or tuple(t.shape) not in shapes or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{what}: {name} must be a contiguous fp32 {shapes[0]} tensor on the rasters' device, got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    L.check(L.lib().pc_region_item(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), int(orbit), L.ptr(boundary), S, C2,
+                                   C1, h, w, (C.c_int32 * 6)(*band), cr[0], cr[1], cr[2], cr[3], cr[4], (C.c_float * 6)(*mean),
+                                   (C.c_float * 6)(*std), L.ptr(idx if count > 0 else None), L.ptr(val if count > 0 else None),
+                                   C.c_int64(cap), C.c_int64(start), C.c_int64(count), L.ptr(out), L.ptr(admin_out), L.stream_ptr()),
+            "pc_region_item")
+    return out if out.dim() == 4 else out.view(1, 6, hc, wc), admin_out if admin_out.dim() == 3 else admin_out.view(1, hc, wc)
+
+
 def nan_fill_(x, hw=None, count_only=False):
     """Nearest-value NaN fill in place (data/PopulationDataset.py:526-551 interpolate_nan, pc_nan_fill): x = contiguous fp32 device tensor
     (B, C, H, W) or (C, H, W), each sample's (C, h, w) array filled on its own -- every NaN takes the value of the nearest known entry in
