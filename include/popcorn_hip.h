@@ -967,7 +967,8 @@ int pc_region_patch_write(const float* g2, const float* f2, const float* g1, con
 int pc_region_patch_apply(const int32_t* idx, const float* val, int64_t cap, const int64_t* off, const int32_t* count, const int32_t* item_hw,
                           int B, float* s2, int64_t s2_stride, float* s1, int64_t s1_stride, int Hm, int Wm, int Ho, int Wo, int vflip,
                           int hflip, int rot, int bright, float beta, int gam, float gamma, void* stream);
-/* pc_region_window (csrc/region_window.hip): the normalised model input of ONE evaluation window of the resident rasters in ONE launch.
+/* pc_region_window (csrc/region_crop.hip; the kernel of pc_region_item below: a window is a square item without the admin plane whose
+ * workgroup ranges are blocks of whole rows): the normalised model input of ONE evaluation window of the resident rasters in ONE launch.
  * out DEVICE fp32 (6, ps, ps), channels [S2 R G B NIR | S1 VV VH]:  out[c][i][j] = (v - mean6[c]) / std6[c]  (the fp32 division of
  * pc_select_normalize), v = the value of the patch table where its slice [start, start + count) holds an entry for the site, otherwise the
  * raster's value at (season, band_sel[c], x + i, y + j); orbit 1 reads the two S1 channels from s1_asc.  Sources and band_sel as
@@ -985,7 +986,7 @@ int pc_region_window_rows(int ps);
 int pc_region_window(const void* s2, int s2_u16, const float* s1, const float* s1_asc, int orbit, int S, int C2, int C1, int h, int w,
                      const int32_t* band_sel, int x, int y, int season, int ps, const float* mean6, const float* std6, const int32_t* idx,
                      const float* val, int64_t cap, int64_t start, int64_t count, float* out, void* stream);
-/* pc_region_item (csrc/region_item.hip): the normalised model input AND the admin mask of ONE rectangular crop {x0, x1, y0, y1, season} of
+/* pc_region_item (csrc/region_crop.hip): the normalised model input AND the admin mask of ONE rectangular crop {x0, x1, y0, y1, season} of
  * the resident rasters (rows [x0, x1), columns [y0, y1); hc = x1 - x0, wc = y1 - y0) in ONE launch -- a validation item.
  * out DEVICE fp32 (6, hc, wc), channels [S2 R G B NIR | S1 VV VH]:  out[c][i][j] = (v - mean6[c]) / std6[c]  (the fp32 division of
  * pc_select_normalize), v = the value of the patch table where its slice [start, start + count) holds an entry for the site, otherwise the

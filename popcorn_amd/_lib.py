@@ -255,13 +255,13 @@ def lib():
         _lib.pc_region_patch_apply.argtypes = ([C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                                 C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] +
                                                [C.c_int] * 8 + [C.c_float, C.c_int, C.c_float, C.c_void_p])
-        # resident evaluation (csrc/region_window.hip): s2, s2_u16, s1, s1_asc, orbit, S, C2, C1, h, w, band_sel, x, y, season, ps, mean6,
+        # resident evaluation (csrc/region_crop.hip): s2, s2_u16, s1, s1_asc, orbit, S, C2, C1, h, w, band_sel, x, y, season, ps, mean6,
         # std6, idx, val, cap, start, count, out, stream
         _lib.pc_region_window_rows.argtypes = [C.c_int]
         _lib.pc_region_window.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.POINTER(C.c_int32)] +
                                           [C.c_int] * 4 + [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p] +
                                           [C.c_int64] * 3 + [C.c_void_p, C.c_void_p])
-        # resident validation (csrc/region_item.hip): s2, s2_u16, s1, s1_asc, orbit, boundary, S, C2, C1, h, w, band_sel, x0, x1, y0, y1,
+        # resident validation (csrc/region_crop.hip): s2, s2_u16, s1, s1_asc, orbit, boundary, S, C2, C1, h, w, band_sel, x0, x1, y0, y1,
         # season, mean6, std6, idx, val, cap, start, count, out, admin_out, stream
         _lib.pc_region_item.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 5 +
                                         [C.POINTER(C.c_int32)] + [C.c_int] * 5 +

@@ -30,6 +30,7 @@
 // pc_region_gather_orbit is the same kernel with the S1 source chosen per crop: a second raster (the ascending orbit) and a 128-bit mask per
 // launch in the kernel arguments; pc_region_gather is its call without either (region_repair.hip plans the mask once per region).
 #include "common.h"
+#include "region_args.h"
 #include "region_load.h"
 
 namespace {
@@ -159,9 +160,7 @@ __global__ __launch_bounds__(256) void region_units_finish_kernel(int32_t* table
 
 // ---- the gather ------------------------------------------------------------------------------------------------------------------------
 struct RegionGatherArgs {
-    const void* s2; const float* s1; const float* s1_asc; const int32_t* boundary;
-    int C2, C1, h, w;
-    int band2[4], band1[2];                                     // source band of output channel c
+    RegionSources src;
     uint32_t orbit[PC_REGION_GATHER_MAX_B / 32];                // bit b: crop b reads its S1 from s1_asc (16 bytes; zero: every crop from s1)
     float* o2; float* o1; float* adm; int32_t* data_hw;          // already offset to the launch's first crop
     int Hm, Wm;
@@ -172,12 +171,12 @@ struct RegionGatherArgs {
 template <typename T2, int V>
 __global__ __launch_bounds__(RG_THREADS) void region_gather_kernel(const RegionGatherArgs a) {
     const int t = threadIdx.x, b = blockIdx.y;
-    const int x0 = a.crop[b][0], y0 = a.crop[b][2];
-    const int hb = a.crop[b][1] - x0, wb = a.crop[b][3] - y0;     // 1 <= hb <= Hm, 1 <= wb <= Wm (host)
+    const RegionSources& r = a.src;
+    const T2* s2; const float* s1;
+    const RegionCrop cr = rg_crop(r, a.orbit, a.crop, b, s2, s1);
+    const int x0 = cr.x0, y0 = cr.y0, hb = cr.hb, wb = cr.wb;
     if (blockIdx.x == 0 && t == 0) { a.data_hw[2 * b] = hb; a.data_hw[2 * b + 1] = wb; }
-    const int64_t plane = (int64_t)a.h * a.w, oplane = (int64_t)a.Hm * a.Wm;
-    const T2* s2 = reinterpret_cast<const T2*>(a.s2) + (int64_t)a.crop[b][4] * a.C2 * plane;
-    const float* s1 = (((a.orbit[b >> 5] >> (b & 31)) & 1u) ? a.s1_asc : a.s1) + (int64_t)a.crop[b][4] * a.C1 * plane;
+    const int64_t plane = (int64_t)r.h * r.w, oplane = (int64_t)a.Hm * a.Wm;
     float* o2 = a.o2 + (int64_t)b * 4 * oplane;
     float* o1 = a.o1 + (int64_t)b * 2 * oplane;
     float* adm = a.adm + (int64_t)b * oplane;
@@ -185,15 +184,15 @@ __global__ __launch_bounds__(RG_THREADS) void region_gather_kernel(const RegionG
     for (int g = blockIdx.x * RG_THREADS + t; g < groups; g += gridDim.x * RG_THREADS) {
         const int y = g / wg, x = (g - y * wg) * V;
         const int64_t o = (int64_t)y * a.Wm + x;
-        const int64_t src = (int64_t)(x0 + min(y, hb - 1)) * a.w + y0;      // the crop's row (a padding row: its last row, not read)
+        const int64_t src = (int64_t)(x0 + min(y, hb - 1)) * r.w + y0;      // the crop's row (a padding row: its last row, not read)
         if constexpr (V == 4) {
             if (y < hb && x + 4 <= wb) {
                 // four pixels inside the crop
 #pragma unroll
-                for (int c = 0; c < 4; ++c) pc_st4(o2 + c * oplane + o, rg_ld4(s2 + a.band2[c] * plane + src + x));
+                for (int c = 0; c < 4; ++c) pc_st4(o2 + c * oplane + o, rg_ld4(s2 + r.band2[c] * plane + src + x));
 #pragma unroll
-                for (int c = 0; c < 2; ++c) pc_st4(o1 + c * oplane + o, rg_ld4(s1 + a.band1[c] * plane + src + x));
-                const i32x4u id = *reinterpret_cast<const i32x4u*>(a.boundary + src + x);
+                for (int c = 0; c < 2; ++c) pc_st4(o1 + c * oplane + o, rg_ld4(s1 + r.band1[c] * plane + src + x));
+                const i32x4u id = *reinterpret_cast<const i32x4u*>(r.boundary + src + x);
                 pc_st4(adm + o, f32x4{(float)id[0], (float)id[1], (float)id[2], (float)id[3]});
                 continue;
             }
@@ -215,15 +214,15 @@ __global__ __launch_bounds__(RG_THREADS) void region_gather_kernel(const RegionG
             const int64_t s = src + min(x + e, wb - 1);            // inside the crop whatever `in` says
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                const float v = rg_val(s2 + a.band2[c] * plane + s);
+                const float v = rg_val(s2 + r.band2[c] * plane + s);
                 o2[c * oplane + o + e] = in ? v : 0.f;
             }
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                const float v = s1[a.band1[c] * plane + s];
+                const float v = s1[r.band1[c] * plane + s];
                 o1[c * oplane + o + e] = in ? v : 0.f;
             }
-            adm[o + e] = in ? (float)a.boundary[s] : -1.f;
+            adm[o + e] = in ? (float)r.boundary[s] : -1.f;
         }
     }
 }
@@ -271,42 +270,30 @@ extern "C" int pc_region_gather_orbit(const void* s2, int s2_u16, const float* s
                                       const int32_t* boundary, int S, int C2, int C1, int h, int w, const int32_t* band_sel,
                                       const int32_t* crops, int B, int Hm, int Wm, float* s2_out, float* s1_out, float* admin_out,
                                       int32_t* data_hw, void* stream) {
-    if (!s2 || !s1 || !boundary || !band_sel || !crops || !s2_out || !s1_out || !admin_out || !data_hw) return PC_EINVAL;
-    if (reinterpret_cast<uintptr_t>(s1_asc) & 3) return PC_EINVAL;
-    if (orbit && B >= 1)
-        for (int b = 0; b < B; ++b)
-            if (orbit[b] > 1 || (orbit[b] && !s1_asc)) return PC_EINVAL;      // an ascending crop needs the ascending raster
-    if (S < 1 || C2 < 1 || C1 < 1 || h < 1 || w < 1 || B < 1 || Hm < 1 || Wm < 1) return PC_EINVAL;
-    if ((int64_t)h * w >= ((int64_t)1 << 31) || (int64_t)Hm * Wm >= ((int64_t)1 << 31)) return PC_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(s1) | reinterpret_cast<uintptr_t>(boundary) | reinterpret_cast<uintptr_t>(s2_out) |
-         reinterpret_cast<uintptr_t>(s1_out) | reinterpret_cast<uintptr_t>(admin_out) | reinterpret_cast<uintptr_t>(data_hw)) & 3)
+    RegionGatherArgs a{};
+    if (rg_sources(a.src, s2, s2_u16, s1, s1_asc, boundary, true, S, C2, C1, h, w, band_sel)) return PC_EINVAL;
+    if (!crops || !s2_out || !s1_out || !admin_out || !data_hw || B < 1 || Hm < 1 || Wm < 1) return PC_EINVAL;
+    if ((int64_t)Hm * Wm >= ((int64_t)1 << 31)) return PC_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(s2_out) | reinterpret_cast<uintptr_t>(s1_out) | reinterpret_cast<uintptr_t>(admin_out) |
+         reinterpret_cast<uintptr_t>(data_hw)) & 3)
         return PC_EINVAL;
-    if (reinterpret_cast<uintptr_t>(s2) & (s2_u16 ? 1 : 3)) return PC_EINVAL;
-    for (int c = 0; c < 6; ++c)
-        if (band_sel[c] < 0 || band_sel[c] >= (c < 4 ? C2 : C1)) return PC_EINVAL;
-    // every crop non-empty, inside the raster, inside the outputs, of an existing season: nothing is enqueued otherwise
-    for (int b = 0; b < B; ++b) {
-        const int32_t* c = crops + 5 * (int64_t)b;
-        if (c[0] < 0 || c[1] <= c[0] || c[1] > h || c[2] < 0 || c[3] <= c[2] || c[3] > w) return PC_EINVAL;
-        if (c[1] - c[0] > Hm || c[3] - c[2] > Wm || c[4] < 0 || c[4] >= S) return PC_EINVAL;
-    }
+    // every crop valid and every orbit byte good: nothing is enqueued otherwise
+    for (int b = 0; b < B; ++b)
+        if (!rg_crop_ok(crops + 5 * (int64_t)b, h, w, S, Hm, Wm)) return PC_EINVAL;
+    for (int b0 = 0; b0 < B; b0 += PC_REGION_GATHER_MAX_B)
+        if (rg_orbit_mask(a.orbit, orbit ? orbit + b0 : nullptr, B - b0 < PC_REGION_GATHER_MAX_B ? B - b0 : PC_REGION_GATHER_MAX_B, s1_asc))
+            return PC_EINVAL;
     const bool vec = (Wm & 3) == 0 && ((reinterpret_cast<uintptr_t>(s2_out) | reinterpret_cast<uintptr_t>(s1_out) |
                                         reinterpret_cast<uintptr_t>(admin_out)) & 15) == 0;
     const int64_t oplane = (int64_t)Hm * Wm;
-    RegionGatherArgs a{};
-    a.s2 = s2; a.s1 = s1; a.s1_asc = s1_asc; a.boundary = boundary; a.C2 = C2; a.C1 = C1; a.h = h; a.w = w; a.Hm = Hm; a.Wm = Wm;
-    for (int c = 0; c < 4; ++c) a.band2[c] = band_sel[c];
-    for (int c = 0; c < 2; ++c) a.band1[c] = band_sel[4 + c];
+    a.Hm = Hm; a.Wm = Wm;
     for (int b0 = 0; b0 < B; b0 += PC_REGION_GATHER_MAX_B) {
         const int Bc = B - b0 < PC_REGION_GATHER_MAX_B ? B - b0 : PC_REGION_GATHER_MAX_B;
         a.o2 = s2_out + (int64_t)b0 * 4 * oplane; a.o1 = s1_out + (int64_t)b0 * 2 * oplane; a.adm = admin_out + (int64_t)b0 * oplane;
         a.data_hw = data_hw + 2 * (int64_t)b0;
         for (int b = 0; b < Bc; ++b)
             for (int k = 0; k < 5; ++k) a.crop[b][k] = crops[5 * (int64_t)(b0 + b) + k];
-        for (int k = 0; k < PC_REGION_GATHER_MAX_B / 32; ++k) a.orbit[k] = 0;
-        if (orbit)
-            for (int b = 0; b < Bc; ++b)
-                if (orbit[b0 + b]) a.orbit[b >> 5] |= 1u << (b & 31);
+        rg_orbit_mask(a.orbit, orbit ? orbit + b0 : nullptr, Bc, s1_asc);
         if (s2_u16) rg_launch<uint16_t>(a, Bc, vec, (hipStream_t)stream);
         else rg_launch<float>(a, Bc, vec, (hipStream_t)stream);
         PC_CHECK_LAUNCH();

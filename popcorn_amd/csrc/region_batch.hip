@@ -27,6 +27,7 @@
 // region_repair.hip uses in the other direction.
 #include "common.h"
 #include "aug_value.h"
+#include "region_args.h"
 #include "region_index.h"
 #include "region_load.h"
 
@@ -36,9 +37,7 @@ constexpr int RB_THREADS = 256;
 constexpr int RB_MAX_BLOCKS = 2048;      // workgroups of a launch
 
 struct RegionBatchArgs {
-    const void* s2; const float* s1; const float* s1_asc; const int32_t* boundary;
-    int C2, C1, h, w;
-    int band2[4], band1[2];                                     // source band of output channel c
+    RegionSources src;
     uint32_t orbit[PC_REGION_GATHER_MAX_B / 32];                // bit b: crop b reads its S1 from s1_asc (16 bytes; zero: every crop from s1)
     float* raw; float* adm;                                     // already offset to the launch's first crop
     int Hm, Wm, Ho, Wo;                                         // the gathered tile and the output: (Ho, Wo) = (Wm, Hm) for odd rot
@@ -70,11 +69,11 @@ template <typename T2, int V>
 __global__ __launch_bounds__(RB_THREADS) void region_batch_kernel(const RegionBatchArgs a) {
     const int t = threadIdx.x, b = blockIdx.y;
     rb_labels(a, b, t);
-    const int x0 = a.crop[b][0], y0 = a.crop[b][2];
-    const int hb = a.crop[b][1] - x0, wb = a.crop[b][3] - y0;     // 1 <= hb <= Hm, 1 <= wb <= Wm (host)
-    const int64_t plane = (int64_t)a.h * a.w, oplane = (int64_t)a.Hm * a.Wm;
-    const T2* s2 = reinterpret_cast<const T2*>(a.s2) + (int64_t)a.crop[b][4] * a.C2 * plane;
-    const float* s1 = (((a.orbit[b >> 5] >> (b & 31)) & 1u) ? a.s1_asc : a.s1) + (int64_t)a.crop[b][4] * a.C1 * plane;
+    const RegionSources& r = a.src;
+    const T2* s2; const float* s1;
+    const RegionCrop cr = rg_crop(r, a.orbit, a.crop, b, s2, s1);
+    const int x0 = cr.x0, y0 = cr.y0, hb = cr.hb, wb = cr.wb;
+    const int64_t plane = (int64_t)r.h * r.w, oplane = (int64_t)a.Hm * a.Wm;
     float* raw = a.raw + (int64_t)b * 6 * oplane;
     float* adm = a.adm + (int64_t)b * oplane;
     // out = rot90^k(hflip(vflip(T))), k in {0, 2}: a half turn mirrors both axes, a flip mirrors one
@@ -87,13 +86,13 @@ __global__ __launch_bounds__(RB_THREADS) void region_batch_kernel(const RegionBa
         const int y = yrev ? a.Hm - 1 - i : i;                     // tile row
         const int xl = xrev ? a.Wm - V - j : j;                    // lowest tile column of the group (>= 0: Wm % V == 0)
         const int64_t o = (int64_t)i * a.Wm + j;
-        const int64_t src = (int64_t)(x0 + min(y, hb - 1)) * a.w + y0;      // the crop's row (a padding row: its last row, not used)
+        const int64_t src = (int64_t)(x0 + min(y, hb - 1)) * r.w + y0;      // the crop's row (a padding row: its last row, not used)
         if constexpr (V == 4) {
             if (y < hb && xl + 4 <= wb) {
                 // four pixels inside the crop
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    f32x4 v = rg_ld4(s2 + a.band2[c] * plane + src + xl);
+                    f32x4 v = rg_ld4(s2 + r.band2[c] * plane + src + xl);
                     if (xrev) v = rb_rev(v);
                     if (value) {
 #pragma unroll
@@ -103,11 +102,11 @@ __global__ __launch_bounds__(RB_THREADS) void region_batch_kernel(const RegionBa
                 }
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
-                    f32x4 v = rg_ld4(s1 + a.band1[c] * plane + src + xl);
+                    f32x4 v = rg_ld4(s1 + r.band1[c] * plane + src + xl);
                     if (xrev) v = rb_rev(v);
                     pc_st4(raw + (4 + c) * oplane + o, v);
                 }
-                const i32x4u id = *reinterpret_cast<const i32x4u*>(a.boundary + src + xl);
+                const i32x4u id = *reinterpret_cast<const i32x4u*>(r.boundary + src + xl);
                 f32x4 m = f32x4{(float)id[0], (float)id[1], (float)id[2], (float)id[3]};
                 if (xrev) m = rb_rev(m);
                 pc_st4(adm + o, m);
@@ -131,15 +130,15 @@ __global__ __launch_bounds__(RB_THREADS) void region_batch_kernel(const RegionBa
             const int64_t s = src + min(x, wb - 1);                // inside the crop whatever `in` says
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
-                const float v = rg_val(s2 + a.band2[c] * plane + s);
+                const float v = rg_val(s2 + r.band2[c] * plane + s);
                 raw[c * oplane + o + e] = in ? pc_aug_s2_value(v, a.bright, a.beta, a.gam, a.gamma) : pad2;
             }
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
-                const float v = s1[a.band1[c] * plane + s];
+                const float v = s1[r.band1[c] * plane + s];
                 raw[(4 + c) * oplane + o + e] = in ? v : 0.f;
             }
-            adm[o + e] = in ? (float)a.boundary[s] : -1.f;
+            adm[o + e] = in ? (float)r.boundary[s] : -1.f;
         }
     }
 }
@@ -151,11 +150,11 @@ __global__ __launch_bounds__(RB_THREADS) void region_batch_transposed_kernel(con
     __shared__ float tile[7][32][33];
     const int t = threadIdx.x, b = blockIdx.y;
     rb_labels(a, b, t);
-    const int x0 = a.crop[b][0], y0 = a.crop[b][2];
-    const int hb = a.crop[b][1] - x0, wb = a.crop[b][3] - y0;
-    const int64_t plane = (int64_t)a.h * a.w, oplane = (int64_t)a.Ho * a.Wo;
-    const T2* s2 = reinterpret_cast<const T2*>(a.s2) + (int64_t)a.crop[b][4] * a.C2 * plane;
-    const float* s1 = (((a.orbit[b >> 5] >> (b & 31)) & 1u) ? a.s1_asc : a.s1) + (int64_t)a.crop[b][4] * a.C1 * plane;
+    const RegionSources& r = a.src;
+    const T2* s2; const float* s1;
+    const RegionCrop cr = rg_crop(r, a.orbit, a.crop, b, s2, s1);
+    const int x0 = cr.x0, y0 = cr.y0, hb = cr.hb, wb = cr.wb;
+    const int64_t plane = (int64_t)r.h * r.w, oplane = (int64_t)a.Ho * a.Wo;
     float* raw = a.raw + (int64_t)b * 6 * oplane;
     float* adm = a.adm + (int64_t)b * oplane;
     const float pad2 = pc_aug_s2_value(0.f, a.bright, a.beta, a.gam, a.gamma);
@@ -174,18 +173,18 @@ __global__ __launch_bounds__(RB_THREADS) void region_batch_transposed_kernel(con
                 int y, x;
                 pc_region_out_to_tile(i, j, a.Hm, a.Wm, a.vflip, a.hflip, a.rot, y, x);
                 const bool in = y < hb && x < wb;
-                const int64_t s = (int64_t)(x0 + min(y, hb - 1)) * a.w + y0 + min(x, wb - 1);      // inside the crop whatever `in` says
+                const int64_t s = (int64_t)(x0 + min(y, hb - 1)) * r.w + y0 + min(x, wb - 1);      // inside the crop whatever `in` says
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    const float v = rg_val(s2 + a.band2[c] * plane + s);
+                    const float v = rg_val(s2 + r.band2[c] * plane + s);
                     tile[c][dj][di] = in ? pc_aug_s2_value(v, a.bright, a.beta, a.gam, a.gamma) : pad2;
                 }
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
-                    const float v = s1[a.band1[c] * plane + s];
+                    const float v = s1[r.band1[c] * plane + s];
                     tile[4 + c][dj][di] = in ? v : 0.f;
                 }
-                tile[6][dj][di] = in ? (float)a.boundary[s] : -1.f;
+                tile[6][dj][di] = in ? (float)r.boundary[s] : -1.f;
             }
         }
         __syncthreads();
@@ -226,26 +225,18 @@ extern "C" int pc_region_batch_orbit(const void* s2, int s2_u16, const float* s1
                                      const int32_t* crops, int B, int Hm, int Wm, int vflip, int hflip, int rot, int bright, float beta,
                                      int gam, float gamma, float* raw, float* admin_out, int Ho, int Wo, const pc_region_labels* labels,
                                      void* stream) {
-    if (!s2 || !s1 || !boundary || !band_sel || !crops || !raw || !admin_out) return PC_EINVAL;
-    if (reinterpret_cast<uintptr_t>(s1_asc) & 3) return PC_EINVAL;
-    if (orbit && B >= 1)
-        for (int b = 0; b < B; ++b)
-            if (orbit[b] > 1 || (orbit[b] && !s1_asc)) return PC_EINVAL;      // an ascending crop needs the ascending raster
-    if (S < 1 || C2 < 1 || C1 < 1 || h < 1 || w < 1 || B < 1 || Hm < 1 || Wm < 1 || rot < 0 || rot > 3) return PC_EINVAL;
+    RegionBatchArgs a{};
+    if (rg_sources(a.src, s2, s2_u16, s1, s1_asc, boundary, true, S, C2, C1, h, w, band_sel)) return PC_EINVAL;
+    if (!crops || !raw || !admin_out || B < 1 || Hm < 1 || Wm < 1 || rot < 0 || rot > 3) return PC_EINVAL;
     if (Ho != ((rot & 1) ? Wm : Hm) || Wo != ((rot & 1) ? Hm : Wm)) return PC_EINVAL;
-    if ((int64_t)h * w >= ((int64_t)1 << 31) || (int64_t)Hm * Wm >= ((int64_t)1 << 31)) return PC_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(s1) | reinterpret_cast<uintptr_t>(boundary) | reinterpret_cast<uintptr_t>(raw) |
-         reinterpret_cast<uintptr_t>(admin_out)) & 3)
-        return PC_EINVAL;
-    if (reinterpret_cast<uintptr_t>(s2) & (s2_u16 ? 1 : 3)) return PC_EINVAL;
-    for (int c = 0; c < 6; ++c)
-        if (band_sel[c] < 0 || band_sel[c] >= (c < 4 ? C2 : C1)) return PC_EINVAL;
-    // every crop non-empty, inside the raster, inside the tile, of an existing season: nothing is enqueued otherwise
-    for (int b = 0; b < B; ++b) {
-        const int32_t* c = crops + 5 * (int64_t)b;
-        if (c[0] < 0 || c[1] <= c[0] || c[1] > h || c[2] < 0 || c[3] <= c[2] || c[3] > w) return PC_EINVAL;
-        if (c[1] - c[0] > Hm || c[3] - c[2] > Wm || c[4] < 0 || c[4] >= S) return PC_EINVAL;
-    }
+    if ((int64_t)Hm * Wm >= ((int64_t)1 << 31)) return PC_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(admin_out)) & 3) return PC_EINVAL;
+    // every crop valid and every orbit byte good: nothing is enqueued otherwise
+    for (int b = 0; b < B; ++b)
+        if (!rg_crop_ok(crops + 5 * (int64_t)b, h, w, S, Hm, Wm)) return PC_EINVAL;
+    for (int b0 = 0; b0 < B; b0 += PC_REGION_GATHER_MAX_B)
+        if (rg_orbit_mask(a.orbit, orbit ? orbit + b0 : nullptr, B - b0 < PC_REGION_GATHER_MAX_B ? B - b0 : PC_REGION_GATHER_MAX_B, s1_asc))
+            return PC_EINVAL;
     if (labels) {
         if (!labels->plan_cidx || !labels->plan_y || !labels->items || !labels->census_idx_out || !labels->y_out) return PC_EINVAL;
         if (labels->n < 1 || labels->Kp < 1 || labels->K < 1 || labels->K > labels->Kp) return PC_EINVAL;
@@ -256,21 +247,15 @@ extern "C" int pc_region_batch_orbit(const void* s2, int s2_u16, const float* s1
     }
     const bool vec = (Wm & 3) == 0 && ((reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(admin_out)) & 15) == 0;
     const int64_t oplane = (int64_t)Hm * Wm;
-    RegionBatchArgs a{};
-    a.s2 = s2; a.s1 = s1; a.s1_asc = s1_asc; a.boundary = boundary; a.C2 = C2; a.C1 = C1; a.h = h; a.w = w; a.Hm = Hm; a.Wm = Wm; a.Ho = Ho; a.Wo = Wo;
+    a.Hm = Hm; a.Wm = Wm; a.Ho = Ho; a.Wo = Wo;
     a.vflip = vflip != 0; a.hflip = hflip != 0; a.rot = rot; a.bright = bright != 0; a.gam = gam != 0; a.beta = beta; a.gamma = gamma;
-    for (int c = 0; c < 4; ++c) a.band2[c] = band_sel[c];
-    for (int c = 0; c < 2; ++c) a.band1[c] = band_sel[4 + c];
     if (labels) { a.plan_cidx = labels->plan_cidx; a.plan_y = labels->plan_y; a.Kp = labels->Kp; a.K = labels->K; }
     for (int b0 = 0; b0 < B; b0 += PC_REGION_GATHER_MAX_B) {
         const int Bc = B - b0 < PC_REGION_GATHER_MAX_B ? B - b0 : PC_REGION_GATHER_MAX_B;
         a.raw = raw + (int64_t)b0 * 6 * oplane; a.adm = admin_out + (int64_t)b0 * oplane;
         for (int b = 0; b < Bc; ++b)
             for (int k = 0; k < 5; ++k) a.crop[b][k] = crops[5 * (int64_t)(b0 + b) + k];
-        for (int k = 0; k < PC_REGION_GATHER_MAX_B / 32; ++k) a.orbit[k] = 0;
-        if (orbit)
-            for (int b = 0; b < Bc; ++b)
-                if (orbit[b0 + b]) a.orbit[b >> 5] |= 1u << (b & 31);
+        rg_orbit_mask(a.orbit, orbit ? orbit + b0 : nullptr, Bc, s1_asc);
         if (labels) {
             a.cidx_out = labels->census_idx_out + (int64_t)b0 * labels->K; a.y_out = labels->y_out + (int64_t)b0 * labels->K;
             for (int b = 0; b < Bc; ++b) a.item[b] = labels->items[b0 + b];

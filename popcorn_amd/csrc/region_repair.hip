@@ -24,6 +24,7 @@
 // No loop's trip count depends on another lane's, wave's or workgroup's progress.
 #include "common.h"
 #include "aug_value.h"
+#include "region_args.h"
 #include "region_index.h"
 #include "region_load.h"
 
@@ -40,9 +41,9 @@ typedef unsigned long long rr_u64;
 
 // ---- the census ------------------------------------------------------------------------------------------------------------------------
 struct RegionCensusArgs {
-    const void* s2; const float* s1; const float* s1_asc; const int32_t* boxes;
-    int S, C2, C1, h, w, n;
-    int band2[4], band1[2];
+    RegionSources src;                      // (no boundary: the census reads none)
+    const int32_t* boxes;
+    int S, n;
     int nrb;                                // row blocks per box: ceil(rows_max / CN_ROWS)
     int64_t items;                          // n * nrb
     rr_u64* counts;                         // [n][3]
@@ -59,48 +60,49 @@ template <typename T2>
 __global__ __launch_bounds__(RR_THREADS) void region_census_kernel(const RegionCensusArgs a) {
     __shared__ int part[RR_WAVES][3];
     const int t = threadIdx.x;
-    const int64_t plane = (int64_t)a.h * a.w;
+    const RegionSources& rs = a.src;
+    const int64_t plane = (int64_t)rs.h * rs.w;
     for (int64_t it = blockIdx.x; it < a.items; it += gridDim.x) {      // (the same trip count for every thread of the workgroup)
         const int k = (int)(it / a.nrb), rb = (int)(it - (int64_t)k * a.nrb);
         const int32_t* box = a.boxes + 5 * (int64_t)k;
         // the box, clamped to the raster whatever the list holds: no address outside the sources is ever formed
-        const int x0 = min(max(box[0], 0), a.h), x1 = min(max(box[1], x0), a.h);
-        const int y0 = min(max(box[2], 0), a.w), y1 = min(max(box[3], y0), a.w);
+        const int x0 = min(max(box[0], 0), rs.h), x1 = min(max(box[1], x0), rs.h);
+        const int y0 = min(max(box[2], 0), rs.w), y1 = min(max(box[3], y0), rs.w);
         const int season = min(max(box[4], 0), a.S - 1);
         const int hb = x1 - x0, wb = y1 - y0;
         const int r0 = rb * CN_ROWS;
         if (r0 >= hb || wb == 0) continue;                               // (uniform over the workgroup: no barrier is skipped by a part of it)
         const int rows = min(CN_ROWS, hb - r0);
-        const T2* s2 = reinterpret_cast<const T2*>(a.s2) + (int64_t)season * a.C2 * plane;
-        const float* s1 = a.s1 + (int64_t)season * a.C1 * plane;
-        const float* sa = a.s1_asc ? a.s1_asc + (int64_t)season * a.C1 * plane : nullptr;
+        const T2* s2 = reinterpret_cast<const T2*>(rs.s2) + (int64_t)season * rs.C2 * plane;
+        const float* s1 = rs.s1 + (int64_t)season * rs.C1 * plane;
+        const float* sa = rs.s1_asc ? rs.s1_asc + (int64_t)season * rs.C1 * plane : nullptr;
         const int wg = (wb + 3) >> 2, groups = rows * wg;                // (rows * wg <= 16 * 2^29)
         int n2 = 0, n1 = 0, na = 0;
         for (int g = t; g < groups; g += RR_THREADS) {
             const int r = g / wg, x = (g - r * wg) << 2;
-            const int64_t src = (int64_t)(x0 + r0 + r) * a.w + y0 + x;
+            const int64_t src = (int64_t)(x0 + r0 + r) * rs.w + y0 + x;
             if (x + 4 <= wb) {
                 if constexpr (sizeof(T2) == 4) {
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) n2 += rr_nan4(rg_ld4(s2 + a.band2[c] * plane + src));
+                    for (int c = 0; c < 4; ++c) n2 += rr_nan4(rg_ld4(s2 + rs.band2[c] * plane + src));
                 }
 #pragma unroll
-                for (int c = 0; c < 2; ++c) n1 += rr_nan4(rg_ld4(s1 + a.band1[c] * plane + src));
+                for (int c = 0; c < 2; ++c) n1 += rr_nan4(rg_ld4(s1 + rs.band1[c] * plane + src));
                 if (sa) {
 #pragma unroll
-                    for (int c = 0; c < 2; ++c) na += rr_nan4(rg_ld4(sa + a.band1[c] * plane + src));
+                    for (int c = 0; c < 2; ++c) na += rr_nan4(rg_ld4(sa + rs.band1[c] * plane + src));
                 }
             } else {
                 for (int e = 0; x + e < wb; ++e) {                       // the group across the box's right edge: element by element
                     if constexpr (sizeof(T2) == 4) {
 #pragma unroll
-                        for (int c = 0; c < 4; ++c) { const float v = rg_val(s2 + a.band2[c] * plane + src + e); n2 += v != v; }
+                        for (int c = 0; c < 4; ++c) { const float v = rg_val(s2 + rs.band2[c] * plane + src + e); n2 += v != v; }
                     }
 #pragma unroll
-                    for (int c = 0; c < 2; ++c) { const float v = s1[a.band1[c] * plane + src + e]; n1 += v != v; }
+                    for (int c = 0; c < 2; ++c) { const float v = s1[rs.band1[c] * plane + src + e]; n1 += v != v; }
                     if (sa) {
 #pragma unroll
-                        for (int c = 0; c < 2; ++c) { const float v = sa[a.band1[c] * plane + src + e]; na += v != v; }
+                        for (int c = 0; c < 2; ++c) { const float v = sa[rs.band1[c] * plane + src + e]; na += v != v; }
                     }
                 }
             }
@@ -221,23 +223,17 @@ __global__ __launch_bounds__(RR_THREADS) void region_patch_apply_kernel(const Re
 extern "C" int pc_region_nan_census(const void* s2, int s2_u16, const float* s1, const float* s1_asc, int S, int C2, int C1, int h, int w,
                                     const int32_t* band_sel, const int32_t* boxes, int n, int rows_max, int64_t* counts, int max_blocks,
                                     void* stream) {
-    if (!s2 || !s1 || !band_sel || !boxes || !counts) return PC_EINVAL;
-    if (S < 1 || C2 < 1 || C1 < 1 || h < 1 || w < 1 || n < 1 || rows_max < 1 || rows_max > h) return PC_EINVAL;
-    if ((int64_t)h * w >= ((int64_t)1 << 31) || (int64_t)n * 5 >= ((int64_t)1 << 31) || w >= (1 << 29)) return PC_EINVAL;
-    if ((reinterpret_cast<uintptr_t>(s1) | reinterpret_cast<uintptr_t>(s1_asc) | reinterpret_cast<uintptr_t>(boxes)) & 3) return PC_EINVAL;
-    if (reinterpret_cast<uintptr_t>(s2) & (s2_u16 ? 1 : 3)) return PC_EINVAL;
-    if (reinterpret_cast<uintptr_t>(counts) & 7) return PC_EINVAL;
-    for (int c = 0; c < 6; ++c)
-        if (band_sel[c] < 0 || band_sel[c] >= (c < 4 ? C2 : C1)) return PC_EINVAL;
+    RegionCensusArgs a{};
+    if (rg_sources(a.src, s2, s2_u16, s1, s1_asc, nullptr, false, S, C2, C1, h, w, band_sel)) return PC_EINVAL;
+    if (!boxes || !counts || n < 1 || rows_max < 1 || rows_max > h) return PC_EINVAL;
+    if ((int64_t)n * 5 >= ((int64_t)1 << 31) || w >= (1 << 29)) return PC_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(boxes) & 3) || (reinterpret_cast<uintptr_t>(counts) & 7)) return PC_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const int64_t n3 = 3 * (int64_t)n;
     const int gi = (int)((n3 + 255) / 256 < 256 ? (n3 + 255) / 256 : 256);
     hipLaunchKernelGGL(region_census_init_kernel, dim3(gi), dim3(256), 0, st, reinterpret_cast<rr_u64*>(counts), n3);
     PC_CHECK_LAUNCH();
-    RegionCensusArgs a{};
-    a.s2 = s2; a.s1 = s1; a.s1_asc = s1_asc; a.boxes = boxes; a.S = S; a.C2 = C2; a.C1 = C1; a.h = h; a.w = w; a.n = n;
-    for (int c = 0; c < 4; ++c) a.band2[c] = band_sel[c];
-    for (int c = 0; c < 2; ++c) a.band1[c] = band_sel[4 + c];
+    a.boxes = boxes; a.S = S; a.n = n;
     a.nrb = (rows_max + CN_ROWS - 1) / CN_ROWS;
     a.items = (int64_t)n * a.nrb;
     a.counts = reinterpret_cast<rr_u64*>(counts);

@@ -23,9 +23,8 @@ and pixel counts are made at preprocessing time with one pass per unit (utils/02
   ``ResidentItems``       the same region VALIDATED: the items of a (validation) plan with season, orbit and repaired sites planned once,
                           each item's normalised input and admin mask then ONE ``ops.region_item`` launch
 
-Host glue, plain torch; the kernels are csrc/region.hip, csrc/region_batch.hip, csrc/region_repair.hip, csrc/region_window.hip and
-csrc/region_item.hip.  Deviations from the reference, all named where they happen: units without pixels
-are dropped (``plan_one_unit``); the per-epoch order and the season per item come from a torch generator, not Python's ``random`` stream
+Host glue, plain torch; the kernels are csrc/region.hip, csrc/region_batch.hip, csrc/region_repair.hip and csrc/region_crop.hip.
+Deviations from the reference, all named where they happen: units without pixels are dropped (``plan_one_unit``); the per-epoch order and the season per item come from a torch generator, not Python's ``random`` stream
 (``ResidentRegionFeed``); without ``plan_repair`` the resident S1 is the orbit already chosen per season (``--nan_fill`` fills what is
 left), with it an item the reference would end on ("No data here!") is dropped from the plan.  Sharding a plan over data-parallel ranks and graph capture of the gather are not part of this module."""
 from __future__ import annotations
@@ -456,6 +455,19 @@ def _no_data_error(window, triple, ps, how_many):
                       f"reference's \"No data here!\"; {how_many} such window(s))")
 
 
+def _finish_plan(plan, pieces, n, what, hint):
+    """The tail of ``ResidentWindows``' and ``ResidentItems``' constructors, once ``plan.orbit`` stands: the patch table of its n crops
+    from the pieces (``_assemble_table``), the host copies ``_off`` / ``_orbit`` its launches index, and the figures it reports."""
+    dev = plan.region.device
+    plan.off, plan.table_idx, plan.table_val = _assemble_table(pieces, n, dev, what, hint)
+    torch.cuda.synchronize(dev)
+    plan._off = plan.off.tolist()
+    plan._orbit = plan.orbit.tolist()
+    plan.entries = int(plan.off[-1])
+    plan.nbytes = 8 * plan.entries
+    plan.ascending = int(plan.orbit.sum())
+
+
 class ResidentWindows:
     """The sliding windows of an evaluation over a ``ResidentRegion``, planned ONCE: the raster callable ``eval.evaluate_raster`` takes
     (``.shape`` = (h, w), ``self(x, y, season, ps)`` -> the normalised model input (1, 6, ps, ps) on the device), so that
@@ -524,15 +536,9 @@ class ResidentWindows:
         slot = {}
         for k in self.mine:
             slot.setdefault(rows[k], k)
-        self.off, self.table_idx, self.table_val = _assemble_table({slot[key]: pc for key, pc in pieces.items()}, n, region.device,
-                                                                   "ResidentWindows", "evaluate fewer seasons or shard over more ranks")
-        torch.cuda.synchronize(region.device)
-        self._off = self.off.tolist()
-        self._orbit = self.orbit.tolist()
         self._mine = set(self.mine)
-        self.entries = int(self.off[-1])
-        self.nbytes = 8 * self.entries
-        self.ascending = int(self.orbit.sum())
+        _finish_plan(self, {slot[key]: pc for key, pc in pieces.items()}, n, "ResidentWindows",
+                     "evaluate fewer seasons or shard over more ranks")
         self.build_ms = (time.perf_counter() - t0) * 1e3
 
     def __call__(self, x, y, season, ps):
@@ -596,18 +602,11 @@ class ResidentItems:
         self.orbit = torch.tensor([int(orbit[i, own[i]]) for i in kept], dtype=torch.int8)
         self.counts = torch.stack([counts[i, own[i]] for i in kept])
         row = {i: k for k, i in enumerate(kept)}
-        self.off, self.table_idx, self.table_val = _assemble_table({row[i]: pc for (i, s), pc in pieces.items() if i in row}, m,
-                                                                   region.device, "ResidentItems", "validate fewer items")
         # the plan tables, uploaded once: an item's labels are views of them
         self._cidx = self.plan.census_idx.to(region.device).contiguous()
         self._y = self.plan.y.to(region.device).float().contiguous()
-        torch.cuda.synchronize(region.device)
         self._crops = [tuple(int(v) for v in c) + (int(s),) for c, s in zip(self.plan.crops.tolist(), self.season.tolist())]
-        self._off = self.off.tolist()
-        self._orbit = self.orbit.tolist()
-        self.entries = int(self.off[-1])
-        self.nbytes = 8 * self.entries
-        self.ascending = int(self.orbit.sum())
+        _finish_plan(self, {row[i]: pc for (i, s), pc in pieces.items() if i in row}, m, "ResidentItems", "validate fewer items")
         self.build_ms = (time.perf_counter() - t0) * 1e3
 
     def __len__(self):

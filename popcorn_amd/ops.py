@@ -999,31 +999,38 @@ def region_units(boundary, num_ids, max_blocks=0):
     return table, stray
 
 
-def _region_inputs(what, s2, s1, boundary, band_sel, crops):
-    """The validations ``region_gather`` and ``region_batch`` share: the resident rasters, the band selection and the host crop list.
-    Returns (S, C2, C1, h, w, band, crops as int32 (B, 5), the batch maximum (Hm, Wm)); raises before anything is enqueued."""
-    L.require_device(s2, s1, boundary)
+def _region_sources(what, s2, s1, boundary, band_sel):
+    """The resident rasters and the band selection every ``region_*`` wrapper takes (boundary None: the entry point reads none).
+    Returns (S, C2, C1, h, w, band); raises before anything is enqueued."""
+    L.require_device(s2, s1)
     if s2.dim() != 4 or s2.dtype not in (torch.float32, torch.uint16) or not s2.is_contiguous():
         raise ValueError(f"{what}: s2 must be a contiguous fp32 or uint16 (S, C, h, w) tensor, got {s2.dtype} {tuple(s2.shape)}")
     S, C2, h, w = s2.shape
     if s1.dim() != 4 or s1.dtype != torch.float32 or not s1.is_contiguous() or s1.shape[0] != S or tuple(s1.shape[2:]) != (h, w):
         raise ValueError(f"{what}: s1 must be a contiguous fp32 ({S}, C, {h}, {w}) tensor, got {s1.dtype} {tuple(s1.shape)}")
-    if boundary.dtype != torch.int32 or tuple(boundary.shape) != (h, w) or not boundary.is_contiguous():
-        raise ValueError(f"{what}: boundary must be a contiguous int32 ({h}, {w}) map, got {boundary.dtype} {tuple(boundary.shape)}")
+    if boundary is not None:
+        L.require_device(boundary)
+        if boundary.dtype != torch.int32 or tuple(boundary.shape) != (h, w) or not boundary.is_contiguous():
+            raise ValueError(f"{what}: boundary must be a contiguous int32 ({h}, {w}) map, got {boundary.dtype} {tuple(boundary.shape)}")
     if h * w == 0 or h * w >= 1 << 31:
         raise ValueError(f"{what}: 0 < h * w < 2^31, got {h} x {w}")
     C1 = s1.shape[1]
     band = [int(v) for v in band_sel]
     if len(band) != 6 or any(not 0 <= v < C2 for v in band[:4]) or any(not 0 <= v < C1 for v in band[4:]):
         raise ValueError(f"{what}: band_sel names four of {C2} S2 bands and two of {C1} S1 bands (0-based), got {band}")
+    return S, C2, C1, h, w, band
+
+
+def _region_crops(what, crops, S, h, w):
+    """The host crop list {x0, x1, y0, y1, season} of a ``region_*`` wrapper over an (h, w) raster of S seasons.  Returns (crops as int32
+    (B, 5), the batch maximum (Hm, Wm)); raises before anything is enqueued."""
     if torch.is_tensor(crops):
         if crops.is_cuda:
             raise ValueError(f"{what}: crops is host data (it travels in the kernel arguments)")
         crops = crops.numpy()
     # (numpy: a handful of vectorised checks -- this wrapper runs once per training batch, next to a kernel of a few microseconds)
     cr = np.ascontiguousarray(np.asarray(crops, dtype=np.int64).reshape(-1, 5))
-    B = cr.shape[0]
-    if B < 1:
+    if cr.shape[0] < 1:
         raise ValueError(f"{what}: at least one crop")
     hb, wb = cr[:, 1] - cr[:, 0], cr[:, 3] - cr[:, 2]
     bad = (cr[:, 0] < 0) | (hb <= 0) | (cr[:, 1] > h) | (cr[:, 2] < 0) | (wb <= 0) | (cr[:, 3] > w) | (cr[:, 4] < 0) | (cr[:, 4] >= S)
@@ -1031,9 +1038,13 @@ def _region_inputs(what, s2, s1, boundary, band_sel, crops):
         i = int(np.flatnonzero(bad)[0])
         raise ValueError(f"{what}: crop {i} = {cr[i].tolist()} is empty, leaves the {h} x {w} raster or names a season outside "
                          f"[0, {S})")
-    Hm, Wm = int(hb.max()), int(wb.max())
-    cr32 = cr.astype(np.int32)
-    return S, C2, C1, h, w, band, cr32, Hm, Wm
+    return cr.astype(np.int32), int(hb.max()), int(wb.max())
+
+
+def _region_inputs(what, s2, s1, boundary, band_sel, crops):
+    """``_region_sources`` and ``_region_crops``: (S, C2, C1, h, w, band, crops as int32 (B, 5), the batch maximum (Hm, Wm))."""
+    S, C2, C1, h, w, band = _region_sources(what, s2, s1, boundary, band_sel)
+    return (S, C2, C1, h, w, band) + _region_crops(what, crops, S, h, w)
 
 
 def _region_orbit(what, s1, s1_asc, orbit, B):
@@ -1055,6 +1066,47 @@ def _region_orbit(what, s1, s1_asc, orbit, B):
     return ptr
 
 
+def _region_crop_orbit(what, s1, s1_asc, orbit):
+    """The orbit of ONE crop (``region_window``, ``region_item``): 0 = s1, 1 = s1_asc, which is shaped like s1 on its device."""
+    _region_orbit(what, s1, s1_asc, None, 1)
+    if isinstance(orbit, bool) or orbit not in (0, 1) or (orbit == 1 and s1_asc is None):
+        raise ValueError(f"{what}: orbit is 0 (s1) or 1 (s1_asc, which must then be given), got {orbit!r}")
+    return int(orbit)
+
+
+def _region_norm(what, mean6, std6):
+    """The six means and standard deviations of ``region_window`` / ``region_item`` as ctypes float[6] arrays."""
+    mean = [float(v) for v in mean6]
+    std = [float(v) for v in std6]
+    if len(mean) != 6 or len(std) != 6:
+        raise ValueError(f"{what}: mean6 and std6 hold six values each, got {len(mean)} and {len(std)}")
+    return (C.c_float * 6)(*mean), (C.c_float * 6)(*std)
+
+
+def _region_table(what, table, sites, device):
+    """The slice of a patch table ``region_window`` / ``region_item`` take: table = (idx int32 (N,), val fp32 (N,), start, count) or None,
+    sites = the crop's 6 * hc * wc.  Returns (idx, val, cap, start, count), idx and val None for a slice without entries."""
+    idx = val = None
+    cap = start = count = 0
+    if table is not None:
+        idx, val, start, count = table
+        start, count = int(start), int(count)
+        if count > 0 or idx is not None:
+            if idx is None or val is None:
+                raise ValueError(f"{what}: a slice of {count} entries needs the tables idx and val")
+            L.require_device(idx, val)
+            if (idx.dtype != torch.int32 or val.dtype != torch.float32 or idx.dim() != 1 or idx.shape != val.shape or
+                    not idx.is_contiguous() or not val.is_contiguous() or idx.device != device or val.device != device):
+                raise ValueError(f"{what}: idx int32 (N,) and val fp32 (N,), contiguous, on the rasters' device")
+            cap = idx.numel()
+        if start < 0 or count < 0 or start + count > cap or count > sites:
+            raise ValueError(f"{what}: the slice [{start}, {start} + {count}) lies outside the table of {cap} entries or exceeds the "
+                             f"{what.rsplit('_', 1)[-1]}'s {sites} sites")
+    if count == 0:
+        idx = val = None
+    return idx, val, cap, start, count
+
+
 def region_gather(s2, s1, boundary, band_sel, crops, out=None, s1_asc=None, orbit=None):
     """One batch of crops of resident rasters in ONE launch (csrc/region.hip, pc_region_gather): what the reference's weaksup items
     (data/PopulationDataset.py:403-458,566-568,624-649) and ``Population_Dataset_collate_fn`` (:885-958) assemble on the host.
@@ -1065,7 +1117,7 @@ def region_gather(s2, s1, boundary, band_sel, crops, out=None, s1_asc=None, orbi
     and fp32 sources are copied bit for bit.  out: such a dict to write into (its (Hm, Wm) may exceed the batch maximum).  An empty crop, one
     that leaves the raster and a season >= S raise before anything is enqueued.
     s1_asc / orbit (pc_region_gather_orbit): the ascending-orbit S1, shaped like s1, and B host values in {0, 1}: crop b takes its S1 from
-    s1_asc where orbit[b] == 1.  Without them this is the plain entry point."""
+    s1_asc where orbit[b] == 1.  Without them the same entry point is called with NULL for both, which IS pc_region_gather."""
     S, C2, C1, h, w, band, cr32, Hm, Wm = _region_inputs("region_gather", s2, s1, boundary, band_sel, crops)
     B = cr32.shape[0]
     orb = _region_orbit("region_gather", s1, s1_asc, orbit, B)
@@ -1089,11 +1141,8 @@ def region_gather(s2, s1, boundary, band_sel, crops, out=None, s1_asc=None, orbi
         raise ValueError(f"region_gather: Hm * Wm < 2^31, got {Hm} x {Wm}")
     tail = (S, C2, C1, h, w, (C.c_int32 * 6)(*band), cr32.ctypes.data_as(C.POINTER(C.c_int32)), B, Hm, Wm, L.ptr(out["S2"]),
             L.ptr(out["S1"]), L.ptr(out["admin_mask"]), L.ptr(out["data_hw"]), L.stream_ptr())
-    if s1_asc is None and orbit is None:
-        L.check(L.lib().pc_region_gather(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(boundary), *tail), "pc_region_gather")
-    else:
-        L.check(L.lib().pc_region_gather_orbit(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orb, L.ptr(boundary),
-                                               *tail), "pc_region_gather_orbit")
+    L.check(L.lib().pc_region_gather_orbit(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orb, L.ptr(boundary),
+                                           *tail), "pc_region_gather_orbit")
     return out
 
 
@@ -1106,7 +1155,7 @@ def region_batch(s2, s1, boundary, band_sel, crops, params=None, hw=None, labels
     Returns {"raw" (B, 6, Ho, Wo), "admin_mask" (B, Ho, Wo), ["census_idx" int64 (B, K), "y" fp32 (B, K)]} with (Ho, Wo) = (Wm, Hm) for an odd
     rotation; out: such a dict to write into.  Everything ``region_gather`` refuses, a rotation outside 0 .. 3, an item outside [0, n), a K
     outside [1, Kp] and an ``out`` of another shape raise ValueError before anything is enqueued.
-    s1_asc / orbit: as ``region_gather`` takes them (pc_region_batch_orbit); without them this is the plain entry point."""
+    s1_asc / orbit: as ``region_gather`` takes them (pc_region_batch_orbit; NULL for both IS pc_region_batch)."""
     S, C2, C1, h, w, band, cr32, Hm, Wm = _region_inputs("region_batch", s2, s1, boundary, band_sel, crops)
     B = cr32.shape[0]
     orb = _region_orbit("region_batch", s1, s1_asc, orbit, B)
@@ -1162,11 +1211,8 @@ def region_batch(s2, s1, boundary, band_sel, crops, params=None, hw=None, labels
             C.c_float(beta if beta is not None else 1.0), int(gamma is not None),
             C.c_float(gamma if gamma is not None else 1.0), L.ptr(out["raw"]), L.ptr(out["admin_mask"]), Ho, Wo,
             C.byref(lab) if lab is not None else None, L.stream_ptr())
-    if s1_asc is None and orbit is None:
-        L.check(L.lib().pc_region_batch(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(boundary), *tail), "pc_region_batch")
-    else:
-        L.check(L.lib().pc_region_batch_orbit(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orb, L.ptr(boundary),
-                                              *tail), "pc_region_batch_orbit")
+    L.check(L.lib().pc_region_batch_orbit(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orb, L.ptr(boundary),
+                                          *tail), "pc_region_batch_orbit")
     return out
 
 
@@ -1283,7 +1329,7 @@ def region_window_rows(ps):
 
 
 def region_window(s2, s1, band_sel, window, ps, mean6, std6, out=None, s1_asc=None, orbit=0, table=None):
-    """The normalised model input (1, 6, ps, ps) of ONE evaluation window of resident rasters in ONE launch (csrc/region_window.hip,
+    """The normalised model input (1, 6, ps, ps) of ONE evaluation window of resident rasters in ONE launch (csrc/region_crop.hip,
     pc_region_window), channels [S2 R G B NIR | S1 VV VH]: out = (v - mean6[c]) / std6[c] with ``select_normalize``'s fp32 division.
     s2, s1, band_sel: as ``region_gather``; window: HOST integers (x, y, season) = row origin, column origin, season; orbit: 0 = s1,
     1 = s1_asc (shaped like s1).  table = (idx int32 (N,), val fp32 (N,), start, count): the slice [start, start + count) of a patch table as
@@ -1293,21 +1339,8 @@ def region_window(s2, s1, band_sel, window, ps, mean6, std6, out=None, s1_asc=No
     outside [1, PC_REGION_WINDOW_MAX_PS], a band outside its source, an orbit outside {0, 1} or 1 without s1_asc and a slice outside the
     tables raise ValueError before anything is enqueued."""
     what = "region_window"
-    L.require_device(s2, s1)
-    if s2.dim() != 4 or s2.dtype not in (torch.float32, torch.uint16) or not s2.is_contiguous():
-        raise ValueError(f"{what}: s2 must be a contiguous fp32 or uint16 (S, C, h, w) tensor, got {s2.dtype} {tuple(s2.shape)}")
-    S, C2, h, w = s2.shape
-    if s1.dim() != 4 or s1.dtype != torch.float32 or not s1.is_contiguous() or s1.shape[0] != S or tuple(s1.shape[2:]) != (h, w):
-        raise ValueError(f"{what}: s1 must be a contiguous fp32 ({S}, C, {h}, {w}) tensor, got {s1.dtype} {tuple(s1.shape)}")
-    if h * w == 0 or h * w >= 1 << 31:
-        raise ValueError(f"{what}: 0 < h * w < 2^31, got {h} x {w}")
-    C1 = s1.shape[1]
-    band = [int(v) for v in band_sel]
-    if len(band) != 6 or any(not 0 <= v < C2 for v in band[:4]) or any(not 0 <= v < C1 for v in band[4:]):
-        raise ValueError(f"{what}: band_sel names four of {C2} S2 bands and two of {C1} S1 bands (0-based), got {band}")
-    _region_orbit(what, s1, s1_asc, None, 1)
-    if isinstance(orbit, bool) or orbit not in (0, 1) or (orbit == 1 and s1_asc is None):
-        raise ValueError(f"{what}: orbit is 0 (s1) or 1 (s1_asc, which must then be given), got {orbit!r}")
+    S, C2, C1, h, w, band = _region_sources(what, s2, s1, None, band_sel)
+    orbit = _region_crop_orbit(what, s1, s1_asc, orbit)
     ps = int(ps)
     if not 1 <= ps <= L.PC_REGION_WINDOW_MAX_PS:
         raise ValueError(f"{what}: ps in [1, {L.PC_REGION_WINDOW_MAX_PS}], got {ps}")
@@ -1317,26 +1350,8 @@ def region_window(s2, s1, band_sel, window, ps, mean6, std6, out=None, s1_asc=No
     x, y, season = win
     if x < 0 or y < 0 or x + ps > h or y + ps > w or not 0 <= season < S:
         raise ValueError(f"{what}: window {tuple(win)} of side {ps} leaves the {h} x {w} raster or names a season outside [0, {S})")
-    mean = [float(v) for v in mean6]
-    std = [float(v) for v in std6]
-    if len(mean) != 6 or len(std) != 6:
-        raise ValueError(f"{what}: mean6 and std6 hold six values each, got {len(mean)} and {len(std)}")
-    idx = val = None
-    cap = start = count = 0
-    if table is not None:
-        idx, val, start, count = table
-        start, count = int(start), int(count)
-        if count > 0 or idx is not None:
-            if idx is None or val is None:
-                raise ValueError(f"{what}: a slice of {count} entries needs the tables idx and val")
-            L.require_device(idx, val)
-            if (idx.dtype != torch.int32 or val.dtype != torch.float32 or idx.dim() != 1 or idx.shape != val.shape or
-                    not idx.is_contiguous() or not val.is_contiguous() or idx.device != s1.device or val.device != s1.device):
-                raise ValueError(f"{what}: idx int32 (N,) and val fp32 (N,), contiguous, on the rasters' device")
-            cap = idx.numel()
-        if start < 0 or count < 0 or start + count > cap or count > 6 * ps * ps:
-            raise ValueError(f"{what}: the slice [{start}, {start} + {count}) lies outside the table of {cap} entries or exceeds the "
-                             f"window's {6 * ps * ps} sites")
+    mean, std = _region_norm(what, mean6, std6)
+    idx, val, cap, start, count = _region_table(what, table, 6 * ps * ps, s1.device)
     if out is None:
         out = torch.empty(1, 6, ps, ps, dtype=torch.float32, device=s1.device)
     else:
@@ -1345,16 +1360,15 @@ def region_window(s2, s1, band_sel, window, ps, mean6, std6, out=None, s1_asc=No
                 out.device != s1.device):
             raise ValueError(f"{what}: out must be a contiguous fp32 (1, 6, {ps}, {ps}) tensor on the rasters' device, got {out.dtype} "
                              f"{tuple(out.shape)}")
-    L.check(L.lib().pc_region_window(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), int(orbit), S, C2, C1, h, w,
-                                     (C.c_int32 * 6)(*band), x, y, season, ps, (C.c_float * 6)(*mean), (C.c_float * 6)(*std),
-                                     L.ptr(idx if count > 0 else None), L.ptr(val if count > 0 else None), C.c_int64(cap),
+    L.check(L.lib().pc_region_window(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orbit, S, C2, C1, h, w,
+                                     (C.c_int32 * 6)(*band), x, y, season, ps, mean, std, L.ptr(idx), L.ptr(val), C.c_int64(cap),
                                      C.c_int64(start), C.c_int64(count), L.ptr(out), L.stream_ptr()), "pc_region_window")
     return out
 
 
 def region_item(s2, s1, boundary, band_sel, crop, mean6, std6, out=None, admin_out=None, s1_asc=None, orbit=0, table=None):
     """The normalised model input (1, 6, hc, wc) AND the admin mask (1, hc, wc) of ONE rectangular crop of resident rasters in ONE launch
-    (csrc/region_item.hip, pc_region_item) -- a validation item: input = (v - mean6[c]) / std6[c] with ``select_normalize``'s fp32
+    (csrc/region_crop.hip, pc_region_item) -- a validation item: input = (v - mean6[c]) / std6[c] with ``select_normalize``'s fp32
     division, channels [S2 R G B NIR | S1 VV VH]; admin_mask = (float)boundary over the crop.
     s2, s1, boundary, band_sel: as ``region_gather``; crop: HOST integers (x0, x1, y0, y1, season), rows [x0, x1) and columns [y0, y1);
     orbit: 0 = s1, 1 = s1_asc (shaped like s1).  table = (idx int32 (N,), val fp32 (N,), start, count): the slice [start, start + count) of
@@ -1369,31 +1383,11 @@ def region_item(s2, s1, boundary, band_sel, crop, mean6, std6, out=None, admin_o
     if len(cr) != 5:
         raise ValueError(f"{what}: crop = (x0, x1, y0, y1, season), got {cr}")
     S, C2, C1, h, w, band, _, hc, wc = _region_inputs(what, s2, s1, boundary, band_sel, [cr])
-    _region_orbit(what, s1, s1_asc, None, 1)
-    if isinstance(orbit, bool) or orbit not in (0, 1) or (orbit == 1 and s1_asc is None):
-        raise ValueError(f"{what}: orbit is 0 (s1) or 1 (s1_asc, which must then be given), got {orbit!r}")
+    orbit = _region_crop_orbit(what, s1, s1_asc, orbit)
     if 6 * hc * wc >= 1 << 31:
         raise ValueError(f"{what}: 6 * hc * wc < 2^31, got a crop of {hc} x {wc}")
-    mean = [float(v) for v in mean6]
-    std = [float(v) for v in std6]
-    if len(mean) != 6 or len(std) != 6:
-        raise ValueError(f"{what}: mean6 and std6 hold six values each, got {len(mean)} and {len(std)}")
-    idx = val = None
-    cap = start = count = 0
-    if table is not None:
-        idx, val, start, count = table
-        start, count = int(start), int(count)
-        if count > 0 or idx is not None:
-            if idx is None or val is None:
-                raise ValueError(f"{what}: a slice of {count} entries needs the tables idx and val")
-            L.require_device(idx, val)
-            if (idx.dtype != torch.int32 or val.dtype != torch.float32 or idx.dim() != 1 or idx.shape != val.shape or
-                    not idx.is_contiguous() or not val.is_contiguous() or idx.device != s1.device or val.device != s1.device):
-                raise ValueError(f"{what}: idx int32 (N,) and val fp32 (N,), contiguous, on the rasters' device")
-            cap = idx.numel()
-        if start < 0 or count < 0 or start + count > cap or count > 6 * hc * wc:
-            raise ValueError(f"{what}: the slice [{start}, {start} + {count}) lies outside the table of {cap} entries or exceeds the "
-                             f"item's {6 * hc * wc} sites")
+    mean, std = _region_norm(what, mean6, std6)
+    idx, val, cap, start, count = _region_table(what, table, 6 * hc * wc, s1.device)
     dev = s1.device
     if out is None:
         out = torch.empty(1, 6, hc, wc, dtype=torch.float32, device=dev)
@@ -1404,9 +1398,8 @@ def region_item(s2, s1, boundary, band_sel, crop, mean6, std6, out=None, admin_o
         if t.dtype != torch.float32 or tuple(t.shape) not in shapes or not t.is_contiguous() or t.device != dev:
             raise ValueError(f"{what}: {name} must be a contiguous fp32 {shapes[0]} tensor on the rasters' device, got {t.dtype} "
                              f"{tuple(t.shape)}")
-    L.check(L.lib().pc_region_item(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), int(orbit), L.ptr(boundary), S, C2,
-                                   C1, h, w, (C.c_int32 * 6)(*band), cr[0], cr[1], cr[2], cr[3], cr[4], (C.c_float * 6)(*mean),
-                                   (C.c_float * 6)(*std), L.ptr(idx if count > 0 else None), L.ptr(val if count > 0 else None),
+    L.check(L.lib().pc_region_item(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orbit, L.ptr(boundary), S, C2, C1,
+                                   h, w, (C.c_int32 * 6)(*band), cr[0], cr[1], cr[2], cr[3], cr[4], mean, std, L.ptr(idx), L.ptr(val),
                                    C.c_int64(cap), C.c_int64(start), C.c_int64(count), L.ptr(out), L.ptr(admin_out), L.stream_ptr()),
             "pc_region_item")
     return out if out.dim() == 4 else out.view(1, 6, hc, wc), admin_out if admin_out.dim() == 3 else admin_out.view(1, hc, wc)

@@ -1,4 +1,4 @@
-"""pc_region_item (csrc/region_item.hip, ops.region_item): the normalised model input and the admin mask of ONE rectangular crop of the
+"""pc_region_item (csrc/region_crop.hip, ops.region_item): the normalised model input and the admin mask of ONE rectangular crop of the
 resident rasters in one launch, against the composition of the existing ops it replaces, fp32 compared as integers:
 
     out       == select_normalize(cat(S2, S1 of patch_apply(region_gather({crop}, orbit))), 0 .. 5, mean6, std6)
@@ -190,6 +190,47 @@ def test_hand_made_table_at_range_and_channel_boundaries(y0):
     plain, _ = _compose(*src, MODEL_BANDS, crop, 1)
     changed = (want.view(torch.int32) != plain.view(torch.int32)).reshape(-1).nonzero().reshape(-1).tolist()
     assert changed == sites                                              # the composition itself moved exactly the listed sites
+
+
+@pytest.mark.parametrize("with_table", [False, True])
+@pytest.mark.parametrize("orbit", [0, 1])
+@pytest.mark.parametrize("ps", [32, 33, 36])
+@pytest.mark.parametrize("kind", ["f32", "u16"])
+def test_a_window_is_a_square_item_bit_for_bit(kind, ps, orbit, with_table):
+    """``region_window`` and ``region_item`` are two launches of one kernel: a window of side ps is the item [x, x + ps) x [y, y + ps)
+    whose workgroup ranges are blocks of ``region_window_rows(ps)`` whole rows.  ps = 32: 16-byte accesses; 33: element by element; 36:
+    16-byte accesses and a short last range (R = 16 < ps).  The origin is odd (source rows are not 16-byte aligned), the season is 1.  The
+    hand-made table has entries at the first and the last site of channel 0, on both sides of a boundary between two of the window's
+    ranges and at the first site of channel 4, inside a longer table whose other entries would damage the output if they were read."""
+    from popcorn_amd import ops
+    s2, s1, asc, boundary = _sources(kind)
+    mean6, std6 = _stats()
+    x, y, season = 1, 5, 1
+    plane, T = ps * ps, ops.region_window_rows(ps) * ps
+    assert x + ps <= H and y + ps <= W and 0 < T < plane and (ps % 4 == 0) == (ps != 33) and (plane % T != 0) == (ps != 32)
+    table = None
+    if with_table:
+        sites = [0, T - 1, T, plane - 1, 4 * plane]
+        assert sites == sorted(set(sites))
+        idx = torch.tensor(sites, dtype=torch.int32, device="cuda")
+        val = torch.arange(len(sites), dtype=torch.float32, device="cuda") * 17.0 + 1000.5      # (no S2 digital number has a fraction)
+        stray = torch.tensor([6 * plane + 5], dtype=torch.int32, device="cuda")
+        junk_i = torch.tensor([0, 5], dtype=torch.int32, device="cuda")
+        junk_v = torch.full((2,), 1e30, device="cuda")
+        table = (torch.cat([junk_i, idx, stray, junk_i]), torch.cat([junk_v, val, torch.full((1,), -1e30, device="cuda"), junk_v]), 2,
+                 len(sites) + 1)
+    win = torch.full((1, 6, ps, ps), NAN, device="cuda")
+    item = torch.full((1, 6, ps, ps), NAN, device="cuda")
+    admin = torch.full((1, ps, ps), NAN, device="cuda")
+    ops.region_window(s2, s1, DUP_BANDS, (x, y, season), ps, mean6, std6, out=win, s1_asc=asc, orbit=orbit, table=table)
+    ops.region_item(s2, s1, boundary, DUP_BANDS, (x, x + ps, y, y + ps, season), mean6, std6, out=item, admin_out=admin, s1_asc=asc,
+                    orbit=orbit, table=table)
+    assert torch.equal(win.view(torch.int32), item.view(torch.int32)), (kind, ps, orbit, with_table)
+    assert not bool(torch.isnan(admin).any())
+    if with_table:
+        plain = ops.region_window(s2, s1, DUP_BANDS, (x, y, season), ps, mean6, std6, s1_asc=asc, orbit=orbit)
+        changed = (win.view(torch.int32) != plain.view(torch.int32)).reshape(-1).nonzero().reshape(-1).tolist()
+        assert changed == sites                                          # the table moved exactly the listed sites
 
 
 def test_refusals_enqueue_nothing():

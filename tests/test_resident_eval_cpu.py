@@ -32,6 +32,20 @@ def test_library_exports_the_window_kernel_at_abi_10():
     assert lib.pc_region_window_rows(36) < 36                         # the ps = 36 tests of the GPU file cross a row-block boundary
 
 
+def test_window_rows_make_ranges_the_crop_kernel_takes():
+    """A window is launched as a square item whose range argument is R * ps, R = pc_region_window_rows(ps).  For every side the launch
+    accepts: at least one row and no more than 16 or than the window has; a range of at most 4,096 elements unless it is a single row;
+    and a range that is a multiple of the vector width whenever the rows are -- the conditions under which the contiguous ranges of
+    region_crop.hip are blocks of whole rows and a group of four never leaves its row."""
+    from popcorn_amd import _lib as L
+    rows = L.lib().pc_region_window_rows
+    for ps in range(1, L.PC_REGION_WINDOW_MAX_PS + 1):
+        R = rows(ps)
+        assert 1 <= R <= min(16, ps), (ps, R)
+        assert R * ps <= 4096 or R == 1, (ps, R)
+        assert ps % 4 != 0 or (R * ps) % 4 == 0, (ps, R)
+
+
 @pytest.mark.parametrize("ascfill", [False, True])
 @pytest.mark.parametrize("ps", [10, 20, 36])
 def test_window_orbits_against_item_orbit_around_five_percent(ps, ascfill):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The resident evaluation (csrc/region_window.hip, popcorn_amd/data/region.py: ResidentWindows) against the per-window path it replaces
+"""The resident evaluation (csrc/region_crop.hip, popcorn_amd/data/region.py: ResidentWindows) against the per-window path it replaces
 (eval.raw_window_input: clone + cat + fill pair + orbit synchronisation + normalise).  Two legs, each in a child process of its own under
 ``timeout -k 10`` (a leg that faults or hangs ends the run; the leg behind it does not start), by the method of tools/bench_region_repair.py:
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The resident validation (csrc/region_item.hip, popcorn_amd/data/region.py: ResidentItems, split_census) against the per-item path it
+"""The resident validation (csrc/region_crop.hip, popcorn_amd/data/region.py: ResidentItems, split_census) against the per-item path it
 replaces (gather, orbit decision with its synchronisation, fill pair, concatenation, normalisation).  Two legs, each in a child process of
 its own under ``timeout -k 10`` (a leg that faults or hangs ends the run; the leg behind it does not start), by the method of
 tools/bench_resident_eval.py, over a 2304 x 2560 raster with 400 census units, 5 % clouds in S2 and 3 % gap rows in the descending S1:
