@@ -141,6 +141,8 @@ int pc_set_conv_split(int on);
 int pc_get_conv_split(void);
 /* does pc_conv3x3_bwd_group take these fp32 tensors (planar, aligned; Cg = 8 or 16 gradient channels, 8 x channels)?  1 / 0 */
 int pc_conv3x3_bwd_ok(const pc_src* g, const pc_src* x, const pc_dst* out, const pc_src* pool_act, int B, int H, int W);
+/* ... and with pc_conv_bwd_desc::pool_grad (the pool-add form)? */
+int pc_conv3x3_bwd_pool_add_ok(const pc_src* g, const pc_src* x, const pc_dst* out, const pc_src* pool_grad, int B, int H, int W);
 
 /* ---- conv3x3 (+BN +ReLU) forward: nn.Conv2d(3,pad 1) -> BatchNorm2d(eval) -> ReLU, networks.py:259-266.
  * Input channels = a.C + b.C (torch.cat([skip, up]) fused, networks.py:318); conv domain H x W, batch B.
@@ -264,6 +266,11 @@ typedef struct pc_conv_bwd_desc {
     const pc_src* pool_act;
     /* added to the call's c0 for THIS problem: the column blocks of a concat layer (same g, different x) can share one launch */
     int32_t c0_add; int32_t _pad;
+    /* optional (fp32, 8 gradient channels, x_bn set, no pool_act, no accumulate; W % 32 == 0, H % 4 == 0): x ALSO went through a
+     * MaxPool2d(2), and this is the raw data gradient of its pooled copy (planar fp32, 8 channels, H/2 x W/2, rows on 8-byte
+     * boundaries).  The epilogue adds its scatter -- first arg-max of every 2x2 window of x, times relu'(x) * bn_scale(x_bn) -- and
+     * writes out once: bit for bit what this launch without the operand, followed by a pool_act launch into the same out, leaves */
+    const pc_src* pool_grad;
 } pc_conv_bwd_desc;
 int pc_conv3x3_bwd_group(int n, const pc_conv_bwd_desc* d, int Cin_total, int c0, int accumulate, int B, int H, int W,
                          int* nwg_out, void* stream);
@@ -336,6 +343,10 @@ int pc_level2_fwd_group(int n, const pc_level2_fwd_desc* d, int B, void* stream)
 typedef struct pc_level2_bwd_desc {
     const pc_src* g2; const pc_src* c1; const pc_src* x; const float* w1; const float* w2; const pc_bn* bn1;
     const pc_src* act; const pc_bn* act_bn; const pc_dst* out; void* ws1; void* ws2;
+    /* optional (fp32): B x 16 x 32 x 32, planar, 16-byte rows.  conv^T(g1, w1) is written there raw, at the pooled resolution, INSTEAD
+     * of the scatter: `act` is not read and `out` not touched (both still describe valid tensors).  The launch that writes `out`
+     * adds the scatter (pc_conv_bwd_desc::pool_grad) */
+    const pc_dst* pool_grad_out;
 } pc_level2_bwd_desc;
 int64_t pc_level2_bwd_ws_bytes(int B);
 int pc_level2_bwd_ok(const pc_src* g2, const pc_src* c1, const pc_src* x, const pc_src* act, const pc_dst* out);

@@ -74,7 +74,7 @@ class PcWgradReduceDesc(C.Structure):
 class PcConvBwdDesc(C.Structure):
     _fields_ = [("g", C.POINTER(PcSrc)), ("x", C.POINTER(PcSrc)), ("w", C.c_void_p), ("x_bn", C.POINTER(PcBn)),
                 ("out", C.POINTER(PcDst)), ("ws", C.c_void_p), ("pool_act", C.POINTER(PcSrc)), ("c0_add", C.c_int32),
-                ("_pad", C.c_int32)]
+                ("_pad", C.c_int32), ("pool_grad", C.POINTER(PcSrc))]
 
 
 class PcLevel2FwdDesc(C.Structure):
@@ -96,7 +96,7 @@ class PcConvUpBwdDesc(C.Structure):
 class PcLevel2BwdDesc(C.Structure):
     _fields_ = [("g2", C.POINTER(PcSrc)), ("c1", C.POINTER(PcSrc)), ("x", C.POINTER(PcSrc)), ("w1", C.c_void_p), ("w2", C.c_void_p),
                 ("bn1", C.POINTER(PcBn)), ("act", C.POINTER(PcSrc)), ("act_bn", C.POINTER(PcBn)), ("out", C.POINTER(PcDst)),
-                ("ws1", C.c_void_p), ("ws2", C.c_void_p)]
+                ("ws1", C.c_void_p), ("ws2", C.c_void_p), ("pool_grad_out", C.POINTER(PcDst))]
 
 
 class PcInputGradDesc(C.Structure):

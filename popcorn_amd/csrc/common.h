@@ -98,6 +98,7 @@ typedef __attribute__((address_space(1))) char* pc_gptr;
 typedef __attribute__((address_space(1))) const f32x4* pc_gld4;
 typedef __attribute__((address_space(1))) f32x4* pc_gst4;
 typedef __attribute__((address_space(1))) f32x2* pc_gst2;
+typedef __attribute__((address_space(1))) const f32x2* pc_gld2;
 __device__ __forceinline__ pc_gptr pc_pin_global(const void* ptr) {
     uint64_t v = reinterpret_cast<uint64_t>(ptr);
     asm volatile("" : "+s"(v));

@@ -27,6 +27,7 @@ struct BwdProb {
     pc_bn bn;               // BN of the layer that produced x (mask = 1)
     pc_dst out;             // gx (POOL: the gradient map at twice the resolution, accumulated into)
     pc_src pool_act;        // POOL: the full-resolution activation the pooled x was taken from (arg-max + ReLU mask)
+                            // PADD (conv3x3_bwd_s3_kernel): the raw data gradient of x's pooled copy, at half the resolution (pool_grad)
     float* partial;         // [nwg][GC * XC * 9 + GC]
 };
 
@@ -615,8 +616,13 @@ struct S3Cfg {
     static constexpr int WAVES_PER_SIMD = (size_t)2 * LDS_B <= 160 * 1024 ? 2 : 1;
 };
 
-template <int GC, bool POOL>
+// PADD (pool-add, GC = 8, whole strips, masked): x also went through a MaxPool2d(2) whose consumer's raw data gradient is q.pool_act.
+// The epilogue adds that gradient's scatter (first arg-max of every 2x2 window of x, times relu'(x) * bn_scale) to the lane's own
+// pixels and writes the sum once -- the roundings of a plain launch followed by a <.., POOL> launch over the same map, in their order,
+// without the read-modify-write pass at full resolution.
+template <int GC, bool POOL, bool PADD = false>
 __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3_kernel(const BwdArgs p) {
+    static_assert(!PADD || (GC == 8 && !POOL), "the pool-add epilogue belongs to the 8-channel non-POOL geometry");
     using Cfg = S3Cfg<GC>;
     constexpr int NG = Cfg::NG, BSL = Cfg::BSL, IMG = Cfg::IMG, PLANE = Cfg::PLANE, NBLK = Cfg::NBLK, EC = Cfg::EC;
     constexpr int BW_CO = Cfg::BW_CO, BW_DYS = Cfg::BW_DYS;
@@ -643,9 +649,9 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
 #else
     constexpr int dbg = 0;
 #endif
-    const pc_gptr a_base = pc_pin_global(POOL ? q.pool_act.ptr : q.x.ptr);
-    const unsigned a_bs = pc_pinned((unsigned)(POOL ? q.pool_act.bstride : 0)), a_cs = pc_pinned((unsigned)(POOL ? q.pool_act.cstride : 0)),
-                   a_rs = pc_pinned((unsigned)(POOL ? q.pool_act.rstride : 0));
+    const pc_gptr a_base = pc_pin_global(POOL || PADD ? q.pool_act.ptr : q.x.ptr);
+    const unsigned a_bs = pc_pinned((unsigned)(POOL || PADD ? q.pool_act.bstride : 0)), a_cs = pc_pinned((unsigned)(POOL || PADD ? q.pool_act.cstride : 0)),
+                   a_rs = pc_pinned((unsigned)(POOL || PADD ? q.pool_act.rstride : 0));
 
     // ---- loader: lane = (row of the 6-row strip, 16-byte segment of the 40-float row x0 - 4 ..), both tensors.  Byte offsets inside a
     //      tensor are 32-bit (the launcher checks the extents): one scalar base per channel + one vector offset per lane
@@ -812,8 +818,8 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
         }
         BQ_CLOSE(bq2);
         // the mask operands of the epilogue, read ahead of the matrix phase
-        unsigned short xm[POOL ? 1 : 16];
-        if constexpr (!POOL) {
+        unsigned short xm[POOL || PADD ? 1 : 16];
+        if constexpr (!POOL && !PADD) {
             if (maskf) {
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
@@ -888,6 +894,49 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
                     for (int rr = 0; rr < 2; ++rr)
 #pragma unroll
                         for (int h = 0; h < 2; ++h) *(pc_gst4)(o0 + (size_t)((rr * o_rs + 4 * h) * 4u)) = O[rr][h];
+                }
+            }
+        } else if constexpr (PADD) {
+            // (the launcher admits whole strips only -- W % 32 == 0, H % 4 == 0 -- always masked, never accumulating; a tile is 16 rows: the
+            // strips of its waves below the image store nothing.)  The lane reads both rows of its pixels' windows from x (L2 hits: the strip
+            // was just loaded) and the pooled gradient of the two windows of each of its four pixel quads
+            if (__builtin_amdgcn_readfirstlane(y0 < H)) {
+                const unsigned xo = ((unsigned)b * x_bs + (unsigned)y0 * x_rs + (unsigned)(x0 + 4 * lk)) * 4u + (unsigned)col * x_cs;
+                const unsigned po = ((unsigned)b * a_bs + (unsigned)col * a_cs + (unsigned)(y0 >> 1) * a_rs + (unsigned)((x0 >> 1) + 2 * lk)) * 4u;
+                const unsigned ob = ((unsigned)b * o_bs + (unsigned)col * o_cs + (unsigned)(y0 + s_row) * o_rs + (unsigned)(x0 + 4 * lk)) * 4u;
+                f32x4 A[4][2];
+                f32x2 PG[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+#pragma unroll
+                    for (int rr = 0; rr < 2; ++rr) A[u][rr] = *(pc_gld4)(x_base + (size_t)(xo + (((u >> 1) * 2 + rr) * x_rs + (u & 1) * 16) * 4u));
+                    PG[u] = *(pc_gld2)(a_base + (size_t)(po + ((u >> 1) * a_rs + (u & 1) * 8) * 4u));
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const f32x4 own = s_row ? A[u][1] : A[u][0];
+                    f32x4 v;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        // the plain form's test of the x image's first split plane, rn_bf16(x), taken from the fp32 value: the same conversion
+                        const unsigned h = __float_as_uint(pc_bf16r(own[r])) >> 16;
+                        v[r] = (h != 0 && !(h & 0x8000u)) ? acc[u][r] * e_scale : 0.f;
+                    }
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        // first arg-max in the order w00, w01, w10, w11 (strict >), as <.., POOL> takes it
+                        const float w00 = A[u][0][2 * j], w01 = A[u][0][2 * j + 1], w10 = A[u][1][2 * j], w11 = A[u][1][2 * j + 1];
+                        int am = 0;
+                        float m = w00;
+                        if (w01 > m) { m = w01; am = 1; }
+                        if (w10 > m) { m = w10; am = 2; }
+                        if (w11 > m) { m = w11; am = 3; }
+                        const float gv = m > 0.f ? PG[u][j] * e_scale : 0.f;
+                        // (added at every pixel, with 0.f where it is not the arg-max: -0.f + 0.f is what the += pass gave)
+                        v[2 * j] += am == 2 * s_row ? gv : 0.f;
+                        v[2 * j + 1] += am == 2 * s_row + 1 ? gv : 0.f;
+                    }
+                    *(pc_gst4)(o_base + (size_t)(ob + ((u >> 1) * 2 * o_rs + (u & 1) * 16) * 4u)) = v;
                 }
             }
         } else {
@@ -1023,15 +1072,15 @@ __global__ __launch_bounds__(256, S3Cfg<GC>::WAVES_PER_SIMD) void conv3x3_bwd_s3
     }
 }
 
-template <int GC, bool POOL>
+template <int GC, bool POOL, bool PADD = false>
 int launch_bwd_s3(BwdArgs& p, int n, int* nwg_out, hipStream_t stream) {
     using Cfg = S3Cfg<GC>;
     static pc_launch_setup setup;
-    const hipError_t e = setup(reinterpret_cast<const void*>(&conv3x3_bwd_s3_kernel<GC, POOL>), Cfg::LDS_B, PC_SETUP_LDS | PC_SETUP_PROBE, __PRETTY_FUNCTION__);
+    const hipError_t e = setup(reinterpret_cast<const void*>(&conv3x3_bwd_s3_kernel<GC, POOL, PADD>), Cfg::LDS_B, PC_SETUP_LDS | PC_SETUP_PROBE, __PRETTY_FUNCTION__);
     if (e != hipSuccess) return (int)e;
     const int cap = setup.resident / n;
     const int nwg = pc_balanced_grid(p.ntiles, cap > 512 ? 512 : cap);
-    hipLaunchKernelGGL((conv3x3_bwd_s3_kernel<GC, POOL>), dim3(nwg, n), dim3(256), Cfg::LDS_B, stream, p);
+    hipLaunchKernelGGL((conv3x3_bwd_s3_kernel<GC, POOL, PADD>), dim3(nwg, n), dim3(256), Cfg::LDS_B, stream, p);
     PC_CHECK_LAUNCH();
     *nwg_out = nwg;
 #ifdef POPCORN_BWD_PROF
@@ -1057,6 +1106,16 @@ int launch_bwd_s3(BwdArgs& p, int n, int* nwg_out, hipStream_t stream) {
 
 static int g_bwd_dbg = 0;
 extern "C" void pc_debug_conv_bwd(int dbg) { g_bwd_dbg = dbg; }
+
+// The pool-add form's own conditions (fp32, on top of the plain 8-channel problem's): whole strips, so that no 2x2 window straddles two
+// lanes' strips; the split-operand kernel; the pooled gradient planar fp32 at (H / 2, W / 2), 8 channels, every row on an 8-byte boundary
+static bool pool_add_ok(const pc_src& g, const pc_src& pg, bool s3, int B, int H, int W) {
+    if (!s3 || g.C != 8 || W % 32 != 0 || H % 4 != 0) return false;
+    if (!pg.ptr || pg.dtype != PC_F32 || !pc_planar(pg) || pg.mode != PC_SRC_DIRECT || pg.oy || pg.ox || pg.C != 8 || pg.H < H / 2 || pg.W < W / 2)
+        return false;
+    if ((reinterpret_cast<uintptr_t>(pg.ptr) & 7) != 0 || pg.bstride % 2 != 0 || pg.cstride % 2 != 0 || pg.rstride % 2 != 0) return false;
+    return pg.bstride > 0 && (int64_t)B * pg.bstride < ((int64_t)1 << 30);
+}
 
 extern "C" int pc_conv3x3_bwd_group(int n, const pc_conv_bwd_desc* d, int Cin_total, int c0, int accumulate, int B, int H, int W,
                                     int* nwg_out, void* stream) {
@@ -1085,6 +1144,8 @@ extern "C" int pc_conv3x3_bwd_group(int n, const pc_conv_bwd_desc* d, int Cin_to
             bool s3 = pc_conv_split_on() != 0 && fits32(q.g.bstride) && fits32(q.x.bstride) && fits32(o.bstride) &&
                       (!d[i].pool_act || fits32(d[i].pool_act->bstride));
             use_s3 = use_s3 && s3;
+            if ((d[i].pool_grad != nullptr) != (d[0].pool_grad != nullptr)) return PC_EINVAL;
+            if (d[i].pool_grad && (d[i].pool_act || !d[i].x_bn || accumulate || !pool_add_ok(q.g, *d[i].pool_grad, s3, B, H, W))) return PC_EINVAL;
             if (!((GC == 8 && !d[i].pool_act) || (s3 && (GC == 8 || GC == 16))) || XC != 8 || W % 4 != 0 || q.g.dtype != PC_F32 ||
                 q.x.dtype != PC_F32 || o.dtype != PC_F32 ||
                 !pc_planar(q.g) || !pc_planar(q.x) || !pc_planar(o) || q.x.oy != 0 || q.x.ox != 0 || q.x.H != H || q.x.W != W ||
@@ -1106,6 +1167,10 @@ extern "C" int pc_conv3x3_bwd_group(int n, const pc_conv_bwd_desc* d, int Cin_to
         if (d[i].x_bn) q.bn = *d[i].x_bn;
         q.out = *d[i].out;
         if ((d[i].pool_act != nullptr) != (d[0].pool_act != nullptr)) return PC_EINVAL;
+        if (d[i].pool_grad) {
+            if (!f32) return PC_EINVAL;                     // (bf16 mode keeps the scatter launch)
+            q.pool_act = *d[i].pool_grad;
+        }
         if (d[i].pool_act) {
             // the scatter always accumulates and always applies the producer's ReLU / BN factor
             q.pool_act = *d[i].pool_act;
@@ -1126,6 +1191,7 @@ extern "C" int pc_conv3x3_bwd_group(int n, const pc_conv_bwd_desc* d, int Cin_to
     if (f32) {
         if (!use_s3) return launch_bwd_f32(p, n, nwg_out, st);
         if (d[0].pool_act) return GC == 8 ? launch_bwd_s3<8, true>(p, n, nwg_out, st) : launch_bwd_s3<16, true>(p, n, nwg_out, st);
+        if (d[0].pool_grad) return launch_bwd_s3<8, false, true>(p, n, nwg_out, st);
         return GC == 8 ? launch_bwd_s3<8, false>(p, n, nwg_out, st) : launch_bwd_s3<16, false>(p, n, nwg_out, st);
     }
     if (d[0].pool_act) {
@@ -1162,4 +1228,13 @@ extern "C" int pc_conv3x3_bwd_ok(const pc_src* g, const pc_src* x, const pc_dst*
             return 0;
     }
     return 1;
+}
+
+// fp32 mode: would pc_conv3x3_bwd_group take this problem WITH pool_grad (the pool-add form: out = masked data gradient + the max-pool
+// scatter of pool_grad, written once)?  The executors ask before they defer an Up block's skip launch behind the Down block's backward.
+extern "C" int pc_conv3x3_bwd_pool_add_ok(const pc_src* g, const pc_src* x, const pc_dst* out, const pc_src* pool_grad, int B, int H, int W) {
+    if (!pool_grad || !pc_conv3x3_bwd_ok(g, x, out, nullptr, B, H, W)) return 0;
+    auto fits32 = [](int64_t bs, int B) { return bs > 0 && (int64_t)B * bs < ((int64_t)1 << 30); };
+    const bool s3 = pc_conv_split_on() != 0 && fits32(g->bstride, B) && fits32(x->bstride, B) && fits32(out->bstride, B);
+    return pool_add_ok(*g, *pool_grad, s3, B, H, W) ? 1 : 0;
 }

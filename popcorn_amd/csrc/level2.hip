@@ -250,6 +250,7 @@ struct B2Prob {
     pc_bn act_bn;                                // BN of the layer that produced b2
     float* out; int64_t o_bs, o_cs; int o_rs;    // G_b2 (B,16,64,64), accumulated
     float* ws2; float* ws1;                      // partials: [B * B2_PARTIALS][B2_EC]
+    float* pg; int64_t pg_bs, pg_cs; int pg_rs;  // pool_grad_out (B,16,32,32) or null: Gp raw, INSTEAD of the scatter into out
 };
 struct B2Args { B2Prob pr[PC_MAX_GROUP]; long long* ts; };
 
@@ -446,7 +447,18 @@ __global__ __launch_bounds__(512) void level2_bwd_kernel(const B2Args args) {
     stamp(5);
     wgrad(img1, img0, q.ws1);                      // dW1, db1: G1 x pooled input
     stamp(6);
-    {
+    if (q.pg) {
+        // pool_grad_out: the gradient w.r.t. the pooled map leaves the kernel raw, at its own resolution; whoever writes G_b2 adds its
+        // scatter (conv3x3_bwd.hip: the pool-add form).  No load of act, no access to out.
+        f32x4 acc[5];
+        dgrad(img1, acc, uoff, std::integral_constant<int, 4>());
+        stamp(7);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int y = r0 + 2 * wave + (u >> 1), x = ucol[u] + 4 * lk;
+            *reinterpret_cast<f32x4*>(q.pg + b * q.pg_bs + li * q.pg_cs + (int64_t)y * q.pg_rs + x) = acc[u];
+        }
+    } else {
         // MaxPool2d(2) backward: the lane's four pooled pixels cover 2 rows x 8 full-resolution pixels.  Its loads (the pooled
         // activations and the gradient accumulated so far: 100 MB over the launch) are issued BEFORE the last data gradient
         float sc, sh;
@@ -565,7 +577,11 @@ extern "C" int pc_level2_bwd_ok(const pc_src* g2, const pc_src* c1, const pc_src
 
 extern "C" int pc_level2_bwd_group(int n, const pc_level2_bwd_desc* d, int B, int* nwg_out, void* stream) {
     if (n < 1 || n > PC_MAX_GROUP || B < 1 || !d || !nwg_out) return PC_EINVAL;
-    if (g_pc_precision == PC_PREC_BF16) return pc_level2_bwd_cl_launch(n, d, B, nwg_out, g_l2_ts, (hipStream_t)stream);
+    if (g_pc_precision == PC_PREC_BF16) {
+        for (int i = 0; i < n; ++i)
+            if (d[i].pool_grad_out) return PC_EINVAL;          // (bf16 mode keeps the scatter)
+        return pc_level2_bwd_cl_launch(n, d, B, nwg_out, g_l2_ts, (hipStream_t)stream);
+    }
     B2Args a;
     a.ts = g_l2_ts;
     for (int i = 0; i < n; ++i) {
@@ -579,6 +595,12 @@ extern "C" int pc_level2_bwd_group(int n, const pc_level2_bwd_desc* d, int B, in
         p.act = s.act->ptr; p.a_bs = s.act->bstride; p.a_cs = s.act->cstride; p.a_rs = s.act->rstride;
         p.out = s.out->ptr; p.o_bs = s.out->bstride; p.o_cs = s.out->cstride; p.o_rs = s.out->rstride;
         p.ws1 = (float*)s.ws1; p.ws2 = (float*)s.ws2;
+        p.pg = nullptr; p.pg_bs = p.pg_cs = 0; p.pg_rs = 0;
+        if (s.pool_grad_out) {
+            const pc_dst& g = *s.pool_grad_out;
+            if (!plane_ok(g.ptr, g.bstride, g.cstride, g.rstride, g.xstride, g.dtype)) return PC_EINVAL;
+            p.pg = reinterpret_cast<float*>(g.ptr); p.pg_bs = g.bstride; p.pg_cs = g.cstride; p.pg_rs = g.rstride;
+        }
     }
     static pc_launch_setup setup;
     const hipError_t e = setup(reinterpret_cast<const void*>(&level2_bwd_kernel), B2_LDS, PC_SETUP_LDS, __PRETTY_FUNCTION__);

@@ -21,6 +21,12 @@
 // It has the COMPOSED form of the two Up blocks only: the trainable U-Net works on the add_padding domain, whose sides are multiples of
 // 32 (pad_geometry), so both levels have exact 2x geometry, widths that are multiples of 16 and 16-byte rows -- everything the composed
 // forward and backward ask for.  forward_nets refuses (PC_ENOTSUP, in the sizing pass) a network that saves activations otherwise.
+// One launch leaves its block: inc2's output a2 feeds both up1a (skip) and, through the max-pool, d1a, so its gradient has two sources.
+// With the encoder trained, up(UP1) holds its skip launch back (pool_add_plan); down(DOWN1) runs d1a as a plain launch into a gradient at
+// the pooled resolution and issues the skip launch after it, with that gradient as pool_grad: the scatter is added in the epilogue and
+// a2's gradient is written once, not written and then read, added to and written again.  Under encoder_no_grad the order is the old one.
+// Level 2 likewise: up(UP2) holds its skip-halves launch back (pool_add_plan2), level2() runs the whole-level kernel with pool_grad_out
+// and issues the halves after it, each with its 8-channel slice of that gradient.
 #include "common.h"
 #include <chrono>
 
@@ -633,6 +639,10 @@ struct Backward {
     const hipStream_t main_st;
     const bool two;
     bool side_used = false;
+    bool deferred = false;      // up(UP1)'s skip launch waits for down(DOWN1) (pool_add_plan)
+    T2 deferred_g;              // ... its gradient operand
+    bool deferred2 = false;     // up(UP2)'s skip-halves launch waits for level2() (pool_add_plan2)
+    T2 deferred_g2;
     const int64_t slot_bytes = pc_conv3x3_wgrad_ws_bytes(32, 8);      // partials of one weight-gradient problem
 
     explicit Backward(Step& x)
@@ -663,9 +673,13 @@ struct Backward {
 
     // ---- launch helpers
     // data + weight gradient of an 8 -> 8 layer (or of an 8-channel column block of a wider one) in ONE launch, both streams
-    struct Blk { const Ten* g; const Ten* x; const pc_bn* x_bn; Ten* out; int L; int s; int c0_add; bool with_db; const Ten* pool_act = nullptr; };
+    // (x_bn nullptr: the raw data gradient; pool_grad: the pool-add form -- out also receives the max-pool scatter of that gradient)
+    struct Blk {
+        const Ten* g; const Ten* x; const pc_bn* x_bn; Ten* out; int L; int s; int c0_add; bool with_db; const Ten* pool_act = nullptr;
+        const Ten* pool_grad = nullptr;
+    };
     void bwd8(const Blk* blk, int n, int cin_total, int h, int w) {
-        pc_src sg[MAXK], sx[MAXK], spa[MAXK];
+        pc_src sg[MAXK], sx[MAXK], spa[MAXK], spg[MAXK];
         pc_dst dout[MAXK];
         pc_conv_bwd_desc d[MAXK];
         void* ws[MAXK];
@@ -676,6 +690,7 @@ struct Backward {
             d[i].g = &sg[i]; d[i].x = &sx[i]; d[i].w = ST[blk[i].s].w[blk[i].L]; d[i].x_bn = blk[i].x_bn; d[i].out = &dout[i]; d[i].ws = ws[i];
             d[i].c0_add = blk[i].c0_add;
             if (blk[i].pool_act) { spa[i] = S(*blk[i].pool_act); d[i].pool_act = &spa[i]; }     // Down block: scatter (+=) into the full-resolution gradient
+            if (blk[i].pool_grad) { spg[i] = S(*blk[i].pool_grad); d[i].pool_grad = &spg[i]; }
         }
         int nwg = 0;
         if (X.go()) X.rc(pc_conv3x3_bwd_group(n, d, cin_total, 0, blk[0].pool_act ? 1 : 0, B, h, w, &nwg, X.st));
@@ -685,14 +700,19 @@ struct Backward {
     }
     // a layer with a 16-channel input as ONE launch of bwd8: the two 8-channel halves of x (masked by half_bn[s][i]) are two problems per
     // stream over the same gradient, each writing its half of the data gradient and its column block of the weight gradient
-    void bwd_halves(int L, const T2& g, const T2& x, const pc_bn (*half_bn)[2], T2& out, int cin_total, int h, int w) {
+    // (pool_grad: the pool-add form, each half with its 8-channel slice of the pooled gradient)
+    void bwd_halves(int L, const T2& g, const T2& x, const pc_bn (*half_bn)[2], T2& out, int cin_total, int h, int w, const T2* pool_grad = nullptr) {
         Blk b[4];
-        Ten xh[2][2], oh[2][2];
+        Ten xh[2][2], oh[2][2], ph[2][2];
         for (int s = 0; s < 2; ++s)
             for (int i = 0; i < 2; ++i) {
                 xh[s][i] = chans(x[s], 8 * i, 8);
                 oh[s][i] = chans(out[s], 8 * i, 8);
                 b[2 * s + i] = Blk{&g[s], &xh[s][i], &half_bn[s][i], &oh[s][i], L, s, 8 * i, i == 0};
+                if (pool_grad) {
+                    ph[s][i] = chans((*pool_grad)[s], 8 * i, 8);
+                    b[2 * s + i].pool_grad = &ph[s][i];
+                }
             }
         bwd8(b, 4, cin_total, h, w);
     }
@@ -703,6 +723,46 @@ struct Backward {
         pc_src spa;
         if (pool_act) spa = S(*pool_act);
         return pc_conv3x3_bwd_ok(&sg, &sx, &dout, pool_act ? &spa : nullptr, B, h, w) != 0;
+    }
+    // Level 1, encoder trained (engine.py: _Backward.pool_add_plan, the same predicates): may the Up block's skip launch wait for the Down
+    // block that pooled the same map and add that block's max-pool scatter in its own epilogue?  Asked of tensors laid out as the pass
+    // will allocate them (the arena gives every tensor the same alignment); nothing stays allocated.
+    bool pool_add_plan(const T2& g, const T2& skip, const T2& g_skip, int h, int w) {
+        if (enc_ng) return false;
+        const int64_t mark = X.ar.off;
+        const T2 g_out = fresh(16, h / 2, w / 2), g_mid = fresh(16, h / 2, w / 2), g_pooled = fresh(DOWN1.cin, h / 2, w / 2);
+        const T2 mid = saved(DOWN1.mid), pooled = saved(DOWN1.pooled), full = saved(DOWN1.full);
+        bool ok = true;
+        for (int s = 0; s < 2 && ok; ++s) {
+            const pc_src sg = S(g[s]), sx = S(skip[s]), spg = S(g_pooled[s]);
+            const pc_dst dout = D(g_skip[s]);
+            ok = pooled[s].ok() && bwd_ok(g_mid[s], pooled[s], g_skip[s], &full[s], h / 2, w / 2) &&
+                 bwd_ok(g_out[s], chans(mid[s], 8, 8), chans(g_mid[s], 8, 8), nullptr, h / 2, w / 2) &&
+                 bwd_ok(g_mid[s], pooled[s], g_pooled[s], nullptr, h / 2, w / 2) &&
+                 pc_conv3x3_bwd_pool_add_ok(&sg, &sx, &dout, &spg, B, h, w) != 0;
+        }
+        X.ar.off = mark;
+        return ok;
+    }
+    // ... and one level down (engine.py: _Backward.pool_add_plan2): where the whole-level kernel will take the 32 x 32 level and the launcher
+    // takes both skip halves with their slices of the pooled gradient
+    bool pool_add_plan2(const T2& g, const T2& skip, const T2& g_skip, int h, int w) {
+        if (enc_ng || !sv[0].pb2.ok() || h != 64 || w != 64) return false;
+        const int64_t mark = X.ar.off;
+        const T2 gz = fresh(16, 32, 32), g_pooled = fresh(16, 32, 32);
+        bool ok = true;
+        for (int s = 0; s < 2 && ok; ++s) {
+            const pc_src sg2 = S(gz[s]), sc = S(sv[s].c1), sx = S(sv[s].pb2), sa = S(sv[s].b2);
+            const pc_dst dz = D(g_skip[s]);
+            ok = pc_level2_bwd_ok(&sg2, &sc, &sx, &sa, &dz) != 0;
+            for (int i = 0; i < 2 && ok; ++i) {
+                const pc_src sg = S(g[s]), sxh = S(chans(skip[s], 8 * i, 8)), spg = S(chans(g_pooled[s], 8 * i, 8));
+                const pc_dst dout = D(chans(g_skip[s], 8 * i, 8));
+                ok = pc_conv3x3_bwd_ok(&sg, &sxh, &dout, nullptr, B, h, w) != 0 && pc_conv3x3_bwd_pool_add_ok(&sg, &sxh, &dout, &spg, B, h, w) != 0;
+            }
+        }
+        X.ar.off = mark;
+        return ok;
     }
     // grouped weight gradient of layer L over both streams (side stream); cin_total: the layer's input channels where a is a column block
     void wgrad(int L, const T2& a, int mode, const T2& g, int h, int w, int cin_total = 0) {
@@ -775,12 +835,19 @@ struct Backward {
         const T2 skip = saved(lv.skip);
         if (lv.c == 8) {            // one problem per stream, whatever the regime
             g_skip = fresh(8, h, w);
-            Blk b[2];
-            for (int s = 0; s < 2; ++s) b[s] = Blk{&g[s], &skip[s], &X.bn_nobias[s][lv.skip_act], &g_skip[s], lv.conv, s, 0, true};
-            bwd8(b, 2, 16, h, w);
+            deferred = pool_add_plan(g, skip, g_skip, h, w);
+            if (deferred) {         // down(DOWN1) issues the launch, behind its own first layer
+                deferred_g = g;
+            } else {
+                Blk b[2];
+                for (int s = 0; s < 2; ++s) b[s] = Blk{&g[s], &skip[s], &X.bn_nobias[s][lv.skip_act], &g_skip[s], lv.conv, s, 0, true};
+                bwd8(b, 2, 16, h, w);
+            }
         } else if (!enc_ng) {       // the two 8-channel halves of the 16-channel skip tensor
             g_skip = fresh(16, h, w);
-            bwd_halves(lv.conv, g, skip, X.bn_half, g_skip, 32, h, w);
+            deferred2 = pool_add_plan2(g, skip, g_skip, h, w);
+            if (deferred2) deferred_g2 = g;             // level2() issues the launch, behind its own
+            else bwd_halves(lv.conv, g, skip, X.bn_half, g_skip, 32, h, w);
         } else {
             wgrad(lv.conv, skip, PC_SRC_DIRECT, g, h, w, 32);
         }
@@ -789,10 +856,12 @@ struct Backward {
     }
     // the 32 x 32 level: both weight gradients, the data gradient chain d2b -> d2a and the pooling scatter in one launch.  false: the
     // geometry does not qualify, nothing was enqueued
-    bool level2(const T2& g_out, const T2& g_in, int h, int w) {
+    bool level2(const T2& g_out, T2& g_in, int h, int w) {
         if (!sv[0].pb2.ok() || h != 32 || w != 32) return false;
         pc_src sg[2], sc[2], sx[2], sa[2];
-        pc_dst dout[2];
+        pc_dst dout[2], dpg[2];
+        T2 g_pooled;
+        if (deferred2) g_pooled = fresh(16, h, w);
         pc_level2_bwd_desc d[2];
         void* w1[2];
         void* w2[2];
@@ -803,15 +872,22 @@ struct Backward {
             d[s] = pc_level2_bwd_desc{&sg[s], &sc[s], &sx[s], ST[s].w[L_D2A], ST[s].w[L_D2B], &X.bn_nobias[s][L_D2A], &sa[s],
                                       &X.bn_nobias[s][L_D1B], &dout[s], w1[s], w2[s]};
             if (!pc_level2_bwd_ok(&sg[s], &sc[s], &sx[s], &sa[s], &dout[s])) {
+                if (deferred2) X.rc(PC_EINVAL);         // (pool_add_plan2 asked the same predicate of the same layout)
                 X.ar.off = mark;
                 return false;
             }
+            if (deferred2) { dpg[s] = D(g_pooled[s]); d[s].pool_grad_out = &dpg[s]; }
         }
         int nwg = 0;
         if (X.go()) X.rc(pc_level2_bwd_group(2, d, B, &nwg, X.st));
         for (int s = 0; s < 2; ++s) {
             R.add(w1[s], ST[s].dw[L_D2A], ST[s].db[L_D2A], nwg, 16, 16, 0);
             R.add(w2[s], ST[s].dw[L_D2B], ST[s].db[L_D2B], nwg, 16, 16, 0);
+        }
+        if (deferred2) {
+            // pool-add order (pool_add_plan2): the Up block's skip-halves launch scatters the level's raw data gradient while it writes g_in
+            deferred2 = false;
+            bwd_halves(UP2.conv, deferred_g2, saved(UP2.skip), X.bn_half, g_in, 32, 2 * h, 2 * w, &g_pooled);
         }
         return true;
     }
@@ -820,6 +896,20 @@ struct Backward {
     void down(const DownLv& lv, const T2& g_out, T2& g_in, int h, int w) {
         const T2 mid = saved(lv.mid), pooled = saved(lv.pooled), full = saved(lv.full);
         T2 g_mid = fresh(16, h, w);
+        if (deferred && lv.cin == 8) {
+            // pool-add order (pool_add_plan): the first layer's raw data gradient stays at the pooled resolution; the Up block's deferred skip
+            // launch scatters it into g_in while it writes that map -- once
+            deferred = false;
+            T2 g_pooled = fresh(lv.cin, h, w);
+            bwd_halves(lv.conv2, g_out, mid, X.bn_half_d1a, g_mid, 16, h, w);
+            Blk a[2], b[2];
+            for (int s = 0; s < 2; ++s) a[s] = Blk{&g_mid[s], &pooled[s], nullptr, &g_pooled[s], lv.conv1, s, 0, true};
+            bwd8(a, 2, lv.cin, h, w);
+            for (int s = 0; s < 2; ++s)
+                b[s] = Blk{&deferred_g[s], &full[s], &X.bn_nobias[s][lv.full_act], &g_in[s], UP1.conv, s, 0, true, nullptr, &g_pooled[s]};
+            bwd8(b, 2, 16, 2 * h, 2 * w);
+            return;
+        }
         // down1, round 6: data + weight gradient of each layer in ONE launch of the split-operand kernel -- the second conv as the two
         // 8-channel halves of its input over the same 16-channel gradient (two problems per stream), the first with the max-pool scatter
         // into inc2's gradient -- instead of four launches (weight gradient 16 -> 16, data gradient 16 -> 16, weight gradient 8 -> 16,

@@ -246,6 +246,8 @@ class _Backward:
         self.bf = L.act_dtype() == torch.bfloat16
         self.fuse_bf16 = FUSED_CONV_BWD and self.bf
         self.wb = ops.WgradBatch(self.dev, accumulate)
+        self.deferred = None                # up(UP1)'s skip launch, handed to down(DOWN1): (lv, gs, g_skip, g_mid, g_pooled) -- see pool_add_plan
+        self.deferred2 = None               # up(UP2)'s skip-halves launch, handed to level2(): (lv, gs, hv, g_pooled) -- see pool_add_plan2
         if head_reduce is not None:
             self.wb.head_reduce(head_reduce)
 
@@ -288,15 +290,19 @@ class _Backward:
         ops.conv3x3_dgrad_group(probs, c0, cn, pool=pool, accumulate=acc)
         return outs
 
-    def bwd8(self, tag, gs, x_key, act_tag, outs, cin_total=8, pool_key=None, accumulate=False):
+    def bwd8(self, tag, gs, x_key, act_tag, outs, cin_total=8, pool_key=None, accumulate=False, pool_grads=None):
         """data + weight gradient of layer `tag` in one launch.  pool_key: a Down block's first layer -- x is the saved pooled map,
-        outs the (accumulated) gradient of the full-resolution map it was pooled from"""
+        outs the (accumulated) gradient of the full-resolution map it was pooled from.  act_tag None: the raw data gradient (no ReLU / BN
+        factor).  pool_grads: the pool-add form -- x also went through a max-pool, outs receives the scatter of these raw gradients of
+        its pooled copy in the same pass"""
         probs = []
         for s in self.S:
             pr = {"g": gs[s], "x": self.A[s][x_key], "w": self.ly(s, tag).w, "out": outs[s], "dw": self.dw(s, tag), "db": self.db(s, tag),
-                  "x_bn": self.ly(s, act_tag).bn_nobias}
+                  "x_bn": None if act_tag is None else self.ly(s, act_tag).bn_nobias}
             if pool_key is not None:
                 pr["pool_act"] = self.A[s][pool_key]
+            if pool_grads is not None:
+                pr["pool_grad"] = pool_grads[s]
             probs.append(pr)
         self.wb.conv3x3_bwd_group(probs, cin_total, 0, accumulate=accumulate)
         return outs
@@ -307,15 +313,17 @@ class _Backward:
         hv = {s: [(self.A[s][x_key][:, c:c + 8], outs[s][:, c:c + 8]) for c in (0, 8)] for s in self.S}
         return hv if self.f32_ok(gs, {s: hv[s][1][0] for s in self.S}, {s: hv[s][1][1] for s in self.S}) else None
 
-    def bwd_halves(self, tag, gs, hv, act_tag, cin_total):
+    def bwd_halves(self, tag, gs, hv, act_tag, cin_total, pool_grads=None):
         """fp32: a layer with a 16-channel input as ONE launch of the fused 8-channel backward (round 4) -- the two halves are two
         problems per stream over the same gradient (it comes out of L2 once), each writing its half of the data gradient and its
-        column block of the weight gradient"""
+        column block of the weight gradient.  pool_grads: the pool-add form, each half with its 8-channel slice of the pooled gradient"""
         probs = []
         for s in self.S:
             for i, (x, out) in enumerate(hv[s]):
                 probs.append({"g": gs[s], "x": x, "w": self.ly(s, tag).w, "out": out, "dw": self.dw(s, tag),
                               "db": self.db(s, tag) if i == 0 else None, "x_bn": self.ly(s, act_tag).bn_slice(8 * i, 8), "c0_add": 8 * i})
+                if pool_grads is not None:
+                    probs[-1]["pool_grad"] = pool_grads[s][:, 8 * i:8 * i + 8]
         self.wb.conv3x3_bwd_group(probs, cin_total, 0)
 
     def bwd_cat(self, lv, gs, g_skip, g_up):
@@ -353,6 +361,43 @@ class _Backward:
                                "w": ly(s, lv.conv).w, "wt": ly(s, lv.convt).w, "bt": ly(s, lv.convt).b, "fwd_ws": self.A[s][lv.ws],
                                "dw": self.dw(s, lv.conv), "dwt": self.dw(s, lv.convt), "dbt": self.db(s, lv.convt)} for s in self.S])
 
+    def pool_add_plan(self, lv, gs, g_skip, h, w):
+        """fp32, level 1, encoder trained: may the skip launch of the Up block wait for the Down block that pooled the same map, and add
+        that block's max-pool scatter in its own epilogue (one write of the map's gradient instead of a write and a read-modify-write)?
+        Yes where today's fused pair of the Down block applies (asked of tensors allocated as the pass allocates them), its first layer
+        runs as a plain launch into a pooled-resolution gradient, and the launcher takes the skip launch with that operand.  Returns
+        (g_mid, g_pooled) -- the Down block's two gradient maps, allocated here -- or None.  csrc/step.hip: Backward::pool_add_plan asks
+        the same predicates."""
+        S, A, dn = self.S, self.A, DOWN1
+        if self.enc_ng or self.bf or lv is not UP1 or not all(A[s].get(dn.pooled) is not None for s in S):
+            return None
+        h1, w1 = h // 2, w // 2
+        g_out, g_mid, g_pooled = self.new(16, h1, w1), self.new(16, h1, w1), self.new(dn.cin, h1, w1)
+        pooled, fulls = {s: A[s][dn.pooled] for s in S}, {s: A[s][dn.full] for s in S}
+        if not (self.f32_ok(g_mid, pooled, g_skip, fulls) and self.halves(g_out, dn.mid, g_mid) and self.f32_ok(g_mid, pooled, g_pooled)):
+            return None
+        if not all(ops.conv3x3_bwd_pool_add_ok(gs[s], A[s][lv.skip], g_skip[s], g_pooled[s]) for s in S):
+            return None
+        return g_mid, g_pooled
+
+    def level2_ok(self, g_out, g_in):
+        S, A = self.S, self.A
+        return FUSED_LEVEL2 and FUSED_LEVEL2_BWD and all(
+            A[s].get("pb2") is not None and ops.level2_bwd_ok(g_out[s], A[s]["c1"], A[s]["pb2"], A[s]["b2"], g_in[s]) for s in S)
+
+    def pool_add_plan2(self, gs, hv, g_skip, gz):
+        """fp32, level 2, encoder trained: the same exchange one level down -- where the whole-level kernel will take the 32 x 32 level
+        (level2_ok, asked of the tensors it will get) and the launcher takes both skip halves with their slices of the pooled gradient,
+        that kernel writes its data gradient raw (pool_grad_out) and the skip-halves launch, issued after it, adds the scatter.
+        Returns the pooled gradient, or None.  csrc/step.hip: Backward::pool_add_plan2"""
+        if self.bf or gz is None or not self.level2_ok(gz, g_skip):
+            return None
+        g_pooled = self.new(16, 32, 32)
+        if not all(ops.conv3x3_bwd_pool_add_ok(gs[s], x, out, g_pooled[s][:, 8 * i:8 * i + 8])
+                   for s in self.S for i, (x, out) in enumerate(hv[s])):
+            return None
+        return g_pooled
+
     # ---- the blocks (csrc/step.hip: struct Backward has the same five, over its bwd8 / bwd_halves / wgrad / dgrad / up_bwd; it has no
     # non-composed Up block -- bwd_cat / convt_bwd -- because its trainable network always runs on a domain whose levels compose)
     def conv8(self, tag, gs, x_key, act_tag, h, w):
@@ -376,9 +421,17 @@ class _Backward:
         if composed:
             # the skip column block: weight gradient into the first c input columns, data gradient masked by its producer
             if c == 8:          # (one launch whatever the regime: the composed forward's geometry implies the fused backward's)
-                self.bwd8(lv.conv, gs, lv.skip, lv.skip_act, g_skip, cin_total=2 * c)
+                plan = self.pool_add_plan(lv, gs, g_skip, h, w)
+                if plan is not None:
+                    self.deferred = (lv, gs, g_skip) + plan           # down(DOWN1) issues it, behind its own first layer
+                else:
+                    self.bwd8(lv.conv, gs, lv.skip, lv.skip_act, g_skip, cin_total=2 * c)
             elif not enc_ng and (hv := self.halves(gs, lv.skip, g_skip)):
-                self.bwd_halves(lv.conv, gs, hv, lv.skip_act, 2 * c)
+                g_pooled = self.pool_add_plan2(gs, hv, g_skip, gz)
+                if g_pooled is not None:
+                    self.deferred2 = (lv, gs, hv, g_pooled)           # level2() issues it, behind its own launch
+                else:
+                    self.bwd_halves(lv.conv, gs, hv, lv.skip_act, 2 * c)
             else:
                 self.wgrad(lv.conv, lv.skip, gs, cin_total=2 * c)
                 if not enc_ng:
@@ -412,13 +465,21 @@ class _Backward:
         """the 32 x 32 level: both weight gradients, the data gradient chain d2b -> d2a and the pooling scatter in one launch (both
         arithmetic modes: level2.hip / level2_cl.hip).  False: the geometry does not qualify, nothing was enqueued"""
         S, A, ly = self.S, self.A, self.ly
-        if not (FUSED_LEVEL2 and FUSED_LEVEL2_BWD and all(
-                A[s].get("pb2") is not None and ops.level2_bwd_ok(g_out[s], A[s]["c1"], A[s]["pb2"], A[s]["b2"], g_in[s]) for s in S)):
+        deferred, self.deferred2 = self.deferred2, None
+        if not self.level2_ok(g_out, g_in):
+            if deferred is not None:
+                raise RuntimeError("pool-add backward: the whole-level kernel declines the level it was planned for")
             return False
+        g_pooled = None if deferred is None else deferred[3]
         self.wb.level2_bwd_group([{"g2": g_out[s], "c1": A[s]["c1"], "x": A[s]["pb2"], "w1": ly(s, "d2a").w, "w2": ly(s, "d2b").w,
                                    "bn1": ly(s, "d2a").bn_nobias, "act": A[s]["b2"], "act_bn": ly(s, "d1b").bn_nobias, "out": g_in[s],
-                                   "dw1": self.dw(s, "d2a"), "db1": self.db(s, "d2a"), "dw2": self.dw(s, "d2b"), "db2": self.db(s, "d2b")}
+                                   "dw1": self.dw(s, "d2a"), "db1": self.db(s, "d2a"), "dw2": self.dw(s, "d2b"), "db2": self.db(s, "d2b"),
+                                   "pool_grad_out": None if g_pooled is None else g_pooled[s]}
                                   for s in S])
+        if deferred is not None:
+            # pool-add order (pool_add_plan2): the Up block's skip-halves launch scatters the level's raw data gradient while it writes g_in
+            lv, gs, hv, _ = deferred
+            self.bwd_halves(lv.conv, gs, hv, lv.skip_act, 2 * lv.c, pool_grads=g_pooled)
         return True
 
     def down(self, lv, g_out, g_in, h, w):
@@ -427,6 +488,19 @@ class _Backward:
         second as the two halves of its input, the first with the scatter -- instead of four launches; the launcher declines a
         16-channel pooled map (down2)"""
         S, A = self.S, self.A
+        if self.deferred is not None and lv is DOWN1:
+            # pool-add order (pool_add_plan): the first layer's raw data gradient stays at the pooled resolution; the Up block's deferred
+            # skip launch scatters it into g_in while it writes that map -- once
+            up_lv, up_gs, g_skip, g_mid, g_pooled = self.deferred
+            self.deferred = None
+            assert all(g_skip[s] is g_in[s] for s in S)
+            hv = self.halves(g_out, lv.mid, g_mid)
+            if hv is None:
+                raise RuntimeError("pool-add backward: the fused backward declines the Down block it was planned for")
+            self.bwd_halves(lv.conv2, g_out, hv, lv.conv1, 16)
+            self.bwd8(lv.conv1, g_mid, lv.pooled, None, g_pooled, cin_total=lv.cin)
+            self.bwd8(up_lv.conv, up_gs, up_lv.skip, up_lv.skip_act, g_in, cin_total=2 * up_lv.c, pool_grads=g_pooled)
+            return
         pooled = all(A[s].get(lv.pooled) is not None for s in S)              # the forward pass saved the pooled map
         fulls = {s: A[s][lv.full] for s in S}
         g_mid = self.new(16, h, w)

@@ -141,6 +141,16 @@ def conv3x3_bwd_ok(g, x, out, pool_act=None):
     return bool(L.lib().pc_conv3x3_bwd_ok(C.byref(sg), C.byref(sx), C.byref(d), C.byref(spa) if spa is not None else None, B, H, W))
 
 
+def conv3x3_bwd_pool_add_ok(g, x, out, pool_grad):
+    """fp32 mode: does the one-launch backward take this problem with ``pool_grad`` (the pool-add form: whole strips, the split-operand
+    kernel, the pooled gradient planar with 8-byte rows)?"""
+    if g.dtype != torch.float32 or pool_grad is None:
+        return False
+    B, _, H, W = g.shape
+    sg, sx, d, spg = L.src(g), L.src(x), L.dst(out), L.src(pool_grad)
+    return bool(L.lib().pc_conv3x3_bwd_pool_add_ok(C.byref(sg), C.byref(sx), C.byref(d), C.byref(spg), B, H, W))
+
+
 def conv3x3_bn_relu(a, w, bias, gamma=None, beta=None, mean=None, var=None, eps=1e-5, relu=True, **kw):
     return conv3x3_raw(a, w, L.bn(bias, gamma, beta, mean, var, eps), relu=relu, **kw)
 
@@ -1635,7 +1645,9 @@ class WgradBatch:
         """bf16 mode: data gradient + weight-gradient partials of a conv layer (g: 8 / 16 channels, x: an 8- or 16-channel column
         block of the layer's input) in ONE launch.  problems: list of dicts {g, x, w, out, dw (the full [Cg][cin_total][3][3]
         gradient), db (or None), x_bn (opt: ReLU / BN factor of x's producer), x_offset (opt), c0_add (opt: this problem's column
-        block starts at c0 + c0_add -- the blocks of a concat layer in one launch)}; the partials cover the columns
+        block starts at c0 + c0_add -- the blocks of a concat layer in one launch), pool_act (opt: a Down block's first layer),
+        pool_grad (opt, fp32: the pool-add form -- out also receives the max-pool scatter of this pooled-resolution gradient,
+        popcorn_hip.h: pc_conv_bwd_desc)}; the partials cover the columns
         [c0 + c0_add, c0 + c0_add + x.shape[1]) of dw."""
         n = len(problems)
         g0 = problems[0]["g"]
@@ -1654,6 +1666,10 @@ class WgradBatch:
                 spa = L.src(pr["pool_act"])
                 keep.append(spa)
                 descs[i].pool_act = C.pointer(spa)
+            if pr.get("pool_grad") is not None:       # pool-add form: x also went through a MaxPool2d(2); its pooled copy's raw gradient
+                spg = L.src(pr["pool_grad"])
+                keep.append(spg)
+                descs[i].pool_grad = C.pointer(spg)
         nwg = C.c_int(0)
         L.check(L.lib().pc_conv3x3_bwd_group(n, descs, cin_total, c0, int(accumulate), B, H, W, C.byref(nwg), L.stream_ptr()),
                 "pc_conv3x3_bwd_group")
@@ -1696,7 +1712,8 @@ class WgradBatch:
     def level2_bwd_group(self, problems):
         """Backward of down2's DoubleConv (the 32 x 32 level) in ONE launch: problems = list of {g2 (dL/d conv2 output, masked),
         c1, x (pooled input), w1, w2, bn1 (BN of conv1: relu'(c1) factor), act (b2, full resolution), act_bn, out (G_b2, +=),
-        dw1, db1, dw2, db2}.  Queues the two layers' weight / bias gradient partials; the data gradients never leave the kernel."""
+        dw1, db1, dw2, db2, pool_grad_out (opt, fp32: the raw gradient of x goes there INSTEAD of the scatter into out)}.  Queues the
+        two layers' weight / bias gradient partials; the data gradients never leave the kernel (but for pool_grad_out)."""
         n = len(problems)
         B = problems[0]["g2"].shape[0]
         nbytes = int(L.lib().pc_level2_bwd_ws_bytes(B))
@@ -1711,6 +1728,10 @@ class WgradBatch:
             descs[i].w1, descs[i].w2 = pr["w1"].data_ptr(), pr["w2"].data_ptr()
             descs[i].bn1, descs[i].act_bn = C.pointer(pr["bn1"]), C.pointer(pr["act_bn"])
             descs[i].ws1, descs[i].ws2 = ws1, ws2
+            if pr.get("pool_grad_out") is not None:
+                dpg = L.dst(pr["pool_grad_out"])
+                keep.append(dpg)
+                descs[i].pool_grad_out = C.pointer(dpg)
         nwg = C.c_int(0)
         L.check(L.lib().pc_level2_bwd_group(n, descs, B, C.byref(nwg), L.stream_ptr()), "pc_level2_bwd_group")
         for (ws1, ws2), pr in zip(slices, problems):

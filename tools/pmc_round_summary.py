@@ -47,7 +47,8 @@ for prec, sfx, head_kernel, conv_kernel, esz in (("fp32", "", "head_bwd_pc_kerne
         r["note"] = ("traffic = 2*FETCH_SIZE + WRITE_SIZE (gfx950 FETCH_SIZE correction for 16-byte-per-lane streams; an upper estimate "
                      "where loads are narrower); separate rocprofv3 --pmc passes of bench.py --steps 2 --warmup 1 --no-graph, B=64 100x100")
         json.dump(r, open(f"{OUT}/{tag}_pmc_head_bwd{sfx}.json", "w"), indent=1)
-    cb = [r for r in rows if r["kernel"].startswith("conv3x3_bwd_s3_kernel<8, false>")]
+    # (the plain 8-channel form: `<8, false>` before the pool-add form existed, `<8, false, false>` since)
+    cb = [r for r in rows if r["kernel"].startswith(("conv3x3_bwd_s3_kernel<8, false>", "conv3x3_bwd_s3_kernel<8, false, false>"))]
     if cb and prec == "fp32":
         r = dict(cb[0])
         r["alg_bytes_mean_launch"] = (3 * 2 * 64 * 128 * 128 * 24 * 4 + 2 * 64 * 64 * 64 * 24 * 4 + 2 * 64 * 64 * 64 * 40 * 4) / 5
