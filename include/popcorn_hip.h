@@ -729,6 +729,37 @@ int pc_census_finalize(const int64_t* table, int M, int64_t T, double* totals, f
  * 16-byte loads and stores where aligned, scalar tail. */
 int pc_census_paint(const int32_t* boundary, int64_t n, int num_ids, int K, const float* const* tables, float* const* out, void* stream);
 
+/* ---- dasymetric adjustment across census levels on the census table, per member (csrc/census_adjust.hip) ----
+ * adjust_map_to_census (data/PopulationDataset.py:823-852) scales every pixel of a unit c of level a by one factor POP[c] / P[c], so the
+ * adjusted total of a unit f of another level l follows from the joint sums over (f, c) pairs; the pairs are one more id raster, filled
+ * by pc_census_accumulate as one more level (num_ids = NP), and ride in the table's exact int64 all-reduce.
+ *
+ * Pair plan of two id rasters of n pixels (any 4-byte aligned address).  A pixel belongs to f = b_l[p] when 0 <= f < num_l and to
+ * c = b_a[p] when 0 <= c < num_a; anything else is "no unit".  Two calls:
+ *   pair_plane == NULL   partners[num_l][PC_CENSUS_PAIR_SLOTS] (16-byte aligned): the distinct c that share a pixel with f, ascending,
+ *                        padded with -1; count[num_l]; flags[2] = {bit 0: a unit has more than PC_CENSUS_PAIR_SLOTS partners (its first
+ *                        four are kept), the smallest such unit (INT32_MAX: none)}; scratch: int32 [num_l].
+ *   pair_plane != NULL   pair_plane[p] = base[f] + k where partners[f][k] == c, -1 where f or c is no unit (or c is a fifth partner);
+ *                        base[num_l + 1]: the exclusive prefix sum of count (the caller's); count / flags / scratch may be NULL.
+ * The outputs are a function of the two rasters alone (integer minima; equal bits for every run). */
+#define PC_CENSUS_PAIR_SLOTS 4
+int pc_census_pair_plan(const int32_t* b_l, const int32_t* b_a, int64_t n, int num_l, int num_a, int32_t* partners, int32_t* count,
+                        int32_t* flags, int32_t* scratch, const int32_t* base, int32_t* pair_plane, void* stream);
+/* Adjusted totals of level l (columns [off_l, off_l + num_l) of table[M][T]) after the adjustment to level a (columns [off_a, off_a +
+ * num_a)), with the pair columns [off_p, off_p + num_p), base[num_l + 1] and pair_c[num_p] (the c of every pair) of the plan, pop[num_a]
+ * (float32, widened) and has[num_a] (uint8: the unit has a census row).  Per member m (every operation in double, rounded on its own):
+ *     P[m][c]      = table[m][off_a + c]
+ *     factor[m][c] = (double)pop[c] / ((double)P[m][c] * 2^-30)  when has[c] and P[m][c] > 0, else 1.0
+ *     rem[m][f]    = table[m][off_l + f] - sum_k pair_k,  pair_k = table[m][off_p + base[f] + k]           (exact integer difference)
+ *     adj[m][f]    = 2^-30 * ((double)rem + sum_k (double)pair_k * factor[m][c_k]),  k ascending
+ * adj[M][f]: the adjustment of the ensemble-mean map -- the same formulas on the exact integer sums over members of P, pair and rem, with
+ * factor[c] = ((double)pop[c] * M) / ((double)sum_m P * 2^-30), the result divided by M (the sums over members must stay below 2^63).
+ * adj: float64 [M + 1][num_l]; mean / stdv: float32 [num_l] over rows 0 .. M - 1 as pc_census_finalize.
+ * base == NULL: level a judged on itself (off_l == off_a, num_l == num_a): adj[m][c] = pop[c] where c is scaled, P[m][c] * 2^-30 where not. */
+int pc_census_adjust_finalize(const int64_t* table, int M, int64_t T, int64_t off_l, int64_t off_a, int64_t off_p, int num_l, int num_a,
+                              int64_t num_p, const int32_t* base, const int32_t* pair_c, const float* pop, const uint8_t* has,
+                              double* adj, float* mean, float* stdv, void* stream);
+
 /* ---- NaN fill of Sentinel inputs (data/PopulationDataset.py:526-551 interpolate_nan, scipy griddata "nearest") ----
  * x: contiguous fp32 (B, C, H, W), filled in place.  Per sample b, over its extent rows [0, h_b) x columns [0, w_b) (hw: DEVICE int32
  * [B][2] = {h_b, w_b}, NULL = the whole H x W; anchored top-left like the collate's zero padding; entries outside the extent are neither

@@ -109,6 +109,7 @@ PC_ADAM_MAX_SEG, PC_ADAM_GROUPS = 8, 4
 PC_EINVAL, PC_ENOGPU, PC_ENOMEM, PC_ENOTSUP = -1, -2, -3, -4
 PC_NAN_FILL_MAX_C, PC_NAN_FILL_MAX_HW, PC_NAN_FILL_COUNT_ONLY = 8, 16384, 1
 PC_CENSUS_MAX_LEVELS, PC_CENSUS_FIX_SHIFT, PC_CENSUS_MAX_PLANES = 4, 30, 8
+PC_CENSUS_PAIR_SLOTS = 4
 PC_UNIT_QUANTUM = 2.0 ** -PC_CENSUS_FIX_SHIFT          # grid of pc_unit_popcount's terms
 
 
@@ -221,6 +222,9 @@ def lib():
                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         _lib.pc_census_finalize.argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.pc_census_paint.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]
+        _lib.pc_census_pair_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 7
+        _lib.pc_census_adjust_finalize.argtypes = ([C.c_void_p, C.c_int] + [C.c_int64] * 4 + [C.c_int, C.c_int, C.c_int64] +
+                                                   [C.c_void_p] * 8)
         _lib.pc_unit_ws_bytes.restype = C.c_int64
         _lib.pc_unit_ws_bytes.argtypes = [C.c_int64]
         _lib.pc_unit_mask.argtypes = [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]

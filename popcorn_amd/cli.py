@@ -21,7 +21,7 @@ import torch
 from . import ops
 from .data import stats
 from .data.collate import Population_Dataset_collate_fn
-from .data.dataset import SyntheticTestRaster, SyntheticWeaksupDataset
+from .data.dataset import TEST_RASTER_REGIONS, SyntheticTestRaster, SyntheticWeaksupDataset
 from .data.feed import RegionFeed
 from .distributed import FlatReducer, init_from_env
 from .model import get_model_kwargs, model_dict
@@ -183,6 +183,11 @@ def eval_parser():
                    help="--census_table: torch.save {totals, mean, std, num_ids[, details]} here (rank 0)")
     p.add_argument("--census_details", action="store_true",
                    help="--census_table: also paint the reference's six per-unit detail maps (+ totals_std) into --census_out")
+    p.add_argument("--coarse_regions", type=int, default=0,
+                   help="a second, coarser census level of about N units (blocks of fine units; N >= 2, fewer than the fine units): the map "
+                        "is adjusted to the COARSE census and judged on both levels (AdjCensus_synthetic_fine is then the disaggregation "
+                        "result); with --census_table the adjusted fine totals come from the table as well, per member "
+                        "(TableAdjCensus_synthetic_fine + _members_mean / _members_std; --census_out gains adjusted / adjusted_std)")
     return p
 
 
@@ -306,6 +311,11 @@ def check_eval_args(args):
     if args.resident_windows and args.raw_input:
         raise SystemExit("--resident_windows and --raw_input name two paths for the same raw raster (windows planned once on the device / "
                          "filled one by one): give one of them")
+    if args.coarse_regions:
+        fine = TEST_RASTER_REGIONS
+        if args.coarse_regions < 2 or args.coarse_regions >= fine:
+            raise SystemExit(f"--coarse_regions groups the {fine} fine census units into N coarse ones: 2 <= N < {fine}, got "
+                             f"{args.coarse_regions}")
 
 
 class Trainer:
@@ -764,7 +774,9 @@ def run_eval(argv=None):
             m.load_state_dict(torch.load(args.resume[j], map_location="cpu", weights_only=False)["model"])   # run_eval.py:243-257
         models.append(m.eval().set_precision(args.precision))
     data = SyntheticTestRaster(args.raster_hw[0], args.raster_hw[1], seasons=4 if args.fourseasons else 1, device=dev,
-                               raw=args.raw_input or args.resident_windows, nan_clouds=args.nan_clouds, s1_gap=args.s1_gap)
+                               raw=args.raw_input or args.resident_windows, nan_clouds=args.nan_clouds, s1_gap=args.s1_gap,
+                               coarse_regions=args.coarse_regions)
+    coarse = args.coarse_regions > 0
     reducer = FlatReducer()
     raster = data.raster
     if args.resident_windows:
@@ -776,7 +788,14 @@ def run_eval(argv=None):
                   f"({raster.nbytes} bytes), built in {raster.build_ms:.1f} ms", flush=True)
     product = E.ProductGrid(args.raster_hw[0], args.raster_hw[1], args.product_cell, n, dev) if args.product_cell > 0 else None
     num_ids = int(data.census_idx.max()) + 1
-    census = E.CensusTable(args.raster_hw[0], args.raster_hw[1], [data.boundary], [num_ids], n, dev) if args.census_table else None
+    census = None
+    if args.census_table and coarse:
+        # both levels and the pair plane of (fine, coarse): the adjustment to the coarse census judged on the fine one, per member
+        census = E.CensusTable(args.raster_hw[0], args.raster_hw[1], [data.boundary, data.boundary_coarse],
+                               [num_ids, int(data.census_idx_coarse.max()) + 1], n, dev,
+                               adjust={"level": 1, "census_idx": data.census_idx_coarse, "census_pop": data.census_pop_coarse})
+    elif args.census_table:
+        census = E.CensusTable(args.raster_hw[0], args.raster_hw[1], [data.boundary], [num_ids], n, dev)
     t0 = time.time()
     out, out_std, scale, scale_std = E.evaluate_raster(models, raster, args.patchsize, args.overlap, args.fourseasons,
                                                        reducer, rank, raw=args.raw_input, ascfill=args.ascfill, product=product,
@@ -784,7 +803,15 @@ def run_eval(argv=None):
     res = {}
     cp, cg = E.convert_popmap_to_census(out, data.boundary, data.census_idx, data.census_pop)
     res.update({k: float(v) for k, v in get_test_metrics(cp, cg, tag="MainCensus_synthetic_fine").items()})
-    adj = E.adjust_map_to_census(out.clone(), data.boundary, data.census_idx, data.census_pop)
+    if coarse:
+        # the reference's evaluator: adjusted to the TRAINING (coarse) level, judged on every level (run_eval.py:168-200)
+        cp, cg = E.convert_popmap_to_census(out, data.boundary_coarse, data.census_idx_coarse, data.census_pop_coarse)
+        res.update({k: float(v) for k, v in get_test_metrics(cp, cg, tag="MainCensus_synthetic_coarse").items()})
+        adj = E.adjust_map_to_census(out.clone(), data.boundary_coarse, data.census_idx_coarse, data.census_pop_coarse)
+        cp, cg = E.convert_popmap_to_census(adj, data.boundary_coarse, data.census_idx_coarse, data.census_pop_coarse)
+        res.update({k: float(v) for k, v in get_test_metrics(cp, cg, tag="AdjCensus_synthetic_coarse").items()})
+    else:
+        adj = E.adjust_map_to_census(out.clone(), data.boundary, data.census_idx, data.census_pop)
     cp, cg = E.convert_popmap_to_census(adj, data.boundary, data.census_idx, data.census_pop)
     res.update({k: float(v) for k, v in get_test_metrics(cp, cg, tag="AdjCensus_synthetic_fine").items()})
     if product is not None:
@@ -797,11 +824,20 @@ def run_eval(argv=None):
                        args.product_out)
     if census is not None:
         res.update(census.metrics(0, data.census_idx, data.census_pop, tag="TableCensus_synthetic_fine"))
+        if coarse:
+            res.update(census.adjusted_metrics(0, data.census_idx, data.census_pop, tag="TableAdjCensus_synthetic_fine"))
         if args.census_out and rank == 0:
             saved = {"totals": census.totals.cpu(), "mean": census.mean.cpu(), "std": census.std.cpu(), "num_ids": census.num_ids}
+            if coarse:
+                _, ens, _, astd = census.adjusted(0)
+                saved["adjusted"], saved["adjusted_std"] = ens.cpu(), astd.cpu()
             if args.census_details:
-                maps = E.census_detail_maps(census.mean, data.boundary, data.census_idx, data.census_pop, pred_std=census.std)
+                mean0, std0 = (census.level(0)[1], census.level(0)[2]) if coarse else (census.mean, census.std)
+                maps = E.census_detail_maps(mean0, data.boundary, data.census_idx, data.census_pop, pred_std=std0)
                 saved["details"] = {k: v.cpu() for k, v in maps.items()}
+                if coarse:      # the reference's <region>_<level>_adj folder: the detail maps of the adjusted ensemble totals
+                    maps = E.census_detail_maps(ens.float(), data.boundary, data.census_idx, data.census_pop, pred_std=astd)
+                    saved["details_adj"] = {k: v.cpu() for k, v in maps.items()}
             torch.save(saved, args.census_out)
     torch.cuda.synchronize()
     if rank == 0:

@@ -101,15 +101,24 @@ class SyntheticWeaksupDataset(Dataset):
         return s2, s1
 
 
+TEST_RASTER_REGIONS = 400          # census units of a SyntheticTestRaster unless told otherwise
+
+
 class SyntheticTestRaster:
     """A normalised (seasons,6,H,W) raster with a blocky census map (ids 1..n, 0 = outside) and a census table.
 
     raw=True: the loader's un-normalised bands instead -- S2 (seasons, 4, H, W) digital numbers, S1 (seasons, 2, H, W) descending-orbit
     backscatter and its ascending companion ``s1_asc`` -- with seeded NaNs: cloud discs over about ``nan_clouds`` of S2 (all bands) and
     orbit-gap rows over ``s1_gap`` of the descending S1.  The object is then the raster callable of ``eval.evaluate_raster(raw=True)``:
-    ``self(x, y, season, ps)`` -> {"S2": (1,4,ps,ps), "S1": (1,2,ps,ps), "S1_asc": callable} (copies; ``self.raster`` is the object)."""
+    ``self(x, y, season, ps)`` -> {"S2": (1,4,ps,ps), "S1": (1,2,ps,ps), "S1_asc": callable} (copies; ``self.raster`` is the object).
 
-    def __init__(self, h=2304, w=2560, seasons=1, n_regions=400, seed=1610, device="cpu", raw=False, nan_clouds=0.0, s1_gap=0.0):
+    coarse_regions = N > 0: a second, coarser census level (the reference's training level next to the fine one it is judged on) --
+    ``boundary_coarse``: rectangular blocks of fine units grouped into about N coarse ones (ids 1 .. n_coarse, 0 outside; every fine unit
+    lies in exactly one), ``census_idx_coarse`` and ``census_pop_coarse``: the sums of the member fine counts.  Nothing is drawn from the
+    generator for it: every other attribute keeps its bits."""
+
+    def __init__(self, h=2304, w=2560, seasons=1, n_regions=TEST_RASTER_REGIONS, seed=1610, device="cpu", raw=False, nan_clouds=0.0, s1_gap=0.0,
+                 coarse_regions=0):
         g = torch.Generator().manual_seed(seed)
         self.raw = raw
         if raw:
@@ -135,6 +144,18 @@ class SyntheticTestRaster:
         self.census_idx = torch.arange(1, n_regions + 1)
         self.census_pop = torch.rand(n_regions, generator=g) * 2000
         self.shape = (h, w)
+        if coarse_regions > 0:
+            cy = max(1, min(gy, int(coarse_regions ** 0.5)))
+            cx = max(1, min(gx, (coarse_regions + cy - 1) // cy))
+            fid = torch.arange(n_regions)                                   # fine unit id - 1 -> its grid cell -> its coarse block
+            block = ((fid // gx) * cy // gy) * cx + (fid % gx) * cx // gx
+            _, member = torch.unique(block, return_inverse=True)            # compact ids in block order
+            coarse_of = torch.cat([torch.zeros(1, dtype=torch.int64), member + 1])
+            self.boundary_coarse = coarse_of[b.long()].to(torch.int32).to(device)
+            n_coarse = int(member.max()) + 1
+            self.census_idx_coarse = torch.arange(1, n_coarse + 1)
+            self.census_pop_coarse = torch.zeros(n_coarse, dtype=torch.float64).index_add_(0, member, self.census_pop.double()).float()
+            self.coarse_of_fine = coarse_of                                 # [fine id] -> coarse id (0 -> 0)
 
     def __call__(self, x, y, season, ps):
         """One raw window (raw=True): copies of the bands, so that the fill can work in place."""

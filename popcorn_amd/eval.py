@@ -248,9 +248,17 @@ class CensusTable:
     fractional bits, so it holds the same bits for any window order and rank sharding (a unit total must stay below 2^33 per member).
     ``visits`` (h, w) int16 is the visit count of one member over the whole window list; pass a ``ProductGrid``'s to share it.
 
-    Multi-GPU: every rank sets the complete window list and adds its own windows; ``all_reduce`` is an exact int64 sum."""
+    Multi-GPU: every rank sets the complete window list and adds its own windows; ``all_reduce`` is an exact int64 sum.
 
-    def __init__(self, h, w, boundaries, num_ids, members, device, visits=None):
+    ``adjust`` (opt-in) = {"level": a, "census_idx": ..., "census_pop": ...}: the dasymetric adjustment of every member's map to the census
+    of level a (``adjust_map_to_census``), judged on every level, without the maps (``csrc/census_adjust.hip``).  The adjustment scales
+    every pixel of a unit c of level a by one factor, so the adjusted total of a unit f of level l follows from the joint sums over the
+    (f, c) pairs that share a pixel: one pair plane per other level is planned once at construction (``ops.census_pair_plan``; boundaries
+    are fixed, every ``set_windows`` reuses it) and accumulated as one more level, its columns behind the levels' (``offsets``,
+    ``level(l)`` and ``metrics`` keep their meaning; ``T`` grows).  Levels plus pair planes must not exceed ``PC_CENSUS_MAX_LEVELS``.  Read
+    ``pairs(l)``, ``adjusted(l)``, ``adjusted_census(...)``, ``adjusted_metrics(...)``."""
+
+    def __init__(self, h, w, boundaries, num_ids, members, device, visits=None, adjust=None):
         if torch.device(device).type != "cuda":
             raise L.PopcornHipError("CensusTable accumulates on a HIP device only")
         boundaries, num_ids = list(boundaries), [int(n) for n in num_ids]
@@ -266,6 +274,10 @@ class CensusTable:
         self.boundaries = [b.to(device=device, dtype=torch.int32).contiguous() for b in boundaries]     # converted once
         self.offsets = [sum(num_ids[:l]) for l in range(len(num_ids))]
         self.T = sum(num_ids)
+        self.adjust_level, self._pairs, self._adjusted = None, {}, {}
+        planes, plane_ids = [], []
+        if adjust is not None:
+            planes, plane_ids = self._plan_adjust(adjust, device)
         self.table = torch.zeros(self.members, self.T, dtype=torch.int64, device=device)
         self.flags = torch.zeros(1, dtype=torch.int32, device=device)
         if visits is not None and (tuple(visits.shape) != (self.h, self.w) or visits.dtype != torch.int16 or not visits.is_cuda
@@ -273,10 +285,43 @@ class CensusTable:
             raise ValueError("CensusTable: visits must be a contiguous (h, w) int16 device map")
         self.shared_visits = visits is not None
         self.visits = visits if visits is not None else torch.zeros(self.h, self.w, dtype=torch.int16, device=device)
-        nl = len(num_ids)
-        self._bptr = (C.c_void_p * nl)(*[b.data_ptr() for b in self.boundaries])
-        self._nids, self._off = (C.c_int32 * nl)(*num_ids), (C.c_int32 * nl)(*self.offsets)
+        # what one accumulate launch takes: the levels, then the pair planes (ids of a plane: its pairs, at least 1)
+        self._planes = self.boundaries + planes
+        all_ids = num_ids + plane_ids
+        nl = len(all_ids)
+        self._bptr = (C.c_void_p * nl)(*[b.data_ptr() for b in self._planes])
+        self._nids, self._off = (C.c_int32 * nl)(*all_ids), (C.c_int32 * nl)(*[sum(all_ids[:l]) for l in range(nl)])
         self.totals = self.mean = self.std = None
+
+    def _plan_adjust(self, adjust, device):
+        """The pair plane of every level but ``adjust["level"]`` (one plan per region) and the census of that level as per-unit tables."""
+        from . import ops
+        a = int(adjust["level"])
+        nl = len(self.num_ids)
+        if not 0 <= a < nl:
+            raise ValueError(f"CensusTable: adjust level {a} of {nl} levels")
+        if 2 * nl - 1 > L.PC_CENSUS_MAX_LEVELS:
+            raise ValueError(f"CensusTable: {nl} census levels plus {nl - 1} pair planes (one per level judged after the adjustment to "
+                             f"level {a}) exceed the {L.PC_CENSUS_MAX_LEVELS} levels one accumulate pass takes")
+        idx = torch.as_tensor(adjust["census_idx"], dtype=torch.int64).reshape(-1)
+        pop = torch.as_tensor(adjust["census_pop"], dtype=torch.float32).reshape(-1)
+        if idx.numel() != pop.numel() or (idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.num_ids[a])):
+            raise ValueError(f"CensusTable: adjust needs one census_pop per census_idx, ids in [0, {self.num_ids[a]})")
+        self.adjust_level = a
+        self._pop = torch.zeros(self.num_ids[a], dtype=torch.float32, device=device)
+        self._has = torch.zeros(self.num_ids[a], dtype=torch.uint8, device=device)
+        self._pop[idx.to(device)] = pop.to(device)
+        self._has[idx.to(device)] = 1
+        planes, plane_ids = [], []
+        for l in range(nl):
+            if l == a:
+                continue
+            plane, pair_f, pair_c, base = ops.census_pair_plan(self.boundaries[l], self.boundaries[a], self.num_ids[l], self.num_ids[a])
+            self._pairs[l] = {"f": pair_f, "c": pair_c, "base": base, "np": int(pair_c.numel()), "off": self.T}
+            planes.append(plane)
+            plane_ids.append(max(1, int(pair_c.numel())))
+            self.T += plane_ids[-1]
+        return planes, plane_ids
 
     def set_windows(self, idx, patchsize=INFERENCE_PATCH_SIZE, overlap=OVERLAP):
         """The complete window list of the evaluation (as ``ProductGrid.set_windows``) -> the visit map.  Starts a new accumulation: the
@@ -284,6 +329,7 @@ class CensusTable:
         self.table.zero_()
         self.flags.zero_()
         self.totals = self.mean = self.std = None
+        self._adjusted = {}
         if not self.shared_visits:
             self.visits.zero_()
             count_windows(self.visits, [(r[0], r[1]) for r in idx], 1, patchsize, overlap)
@@ -296,7 +342,7 @@ class CensusTable:
             raise ValueError(f"CensusTable of {self.members} members got a window of {M}")
         popdense = popdense.contiguous().float()
         L.check(L.lib().pc_census_accumulate(L.ptr(popdense), M, psx, psy, int(overlap), int(xl), int(yl), L.ptr(self.visits), self.h,
-                                             self.w, len(self.num_ids), self._bptr, self._nids, self._off, L.ptr(self.table),
+                                             self.w, len(self._planes), self._bptr, self._nids, self._off, L.ptr(self.table),
                                              C.c_int64(self.T), L.ptr(self.flags), L.stream_ptr()), "pc_census_accumulate")
 
     def all_reduce(self, reducer: FlatReducer):
@@ -318,6 +364,7 @@ class CensusTable:
             self.mean, self.std = torch.empty(self.T, dtype=torch.float32, device=dev), torch.empty(self.T, dtype=torch.float32, device=dev)
         L.check(L.lib().pc_census_finalize(L.ptr(self.table), self.members, C.c_int64(self.T), L.ptr(self.totals), L.ptr(self.mean),
                                            L.ptr(self.std), L.stream_ptr()), "pc_census_finalize")
+        self._adjusted = {}
         return self.totals, self.mean, self.std
 
     def level(self, l):
@@ -338,15 +385,68 @@ class CensusTable:
     def metrics(self, l, census_idx, census_pop, tag=""):
         """``get_test_metrics`` of the ensemble mean under its usual keys, plus ``<key>_members_mean`` / ``<key>_members_std``: the mean
         and the n - 1 standard deviation (0 for one member) over members of the metric computed for each member's own totals."""
-        from .utils.metrics import get_test_metrics
         pm, _, members, gt = self.census(l, census_idx, census_pop)
-        res = {k: float(v) for k, v in get_test_metrics(pm, gt, tag=tag).items()}
+        return self._metrics_with_spread(pm, members, gt, tag)
+
+    def _metrics_with_spread(self, pred, members, gt, tag):
+        from .utils.metrics import get_test_metrics
+        res = {k: float(v) for k, v in get_test_metrics(pred, gt, tag=tag).items()}
         per = [get_test_metrics(members[m], gt, tag=tag) for m in range(self.members)]
         for k in list(res):
             v = torch.tensor([float(p[k]) for p in per], dtype=torch.float64)
             res[k + "_members_mean"] = v.mean().item()
             res[k + "_members_std"] = v.std(unbiased=True).item() if self.members > 1 else 0.0
         return res
+
+
+    # ---- the adjustment to the census of level ``adjust["level"]`` ------------------------------------------------------------------
+    def pairs(self, l):
+        """(pair_f (NP,), pair_c (NP,), totals (M, NP)) of level l: the (unit of l, unit of the adjust level) pairs that share a pixel,
+        ordered by (f, c), and every member's joint sums (views of the finalised table)."""
+        if self.adjust_level is None or l not in self._pairs:
+            raise ValueError(f"CensusTable: no pair plane for level {l} (adjust level: {self.adjust_level})")
+        if self.totals is None:
+            self.finalize()
+        p = self._pairs[l]
+        return p["f"], p["c"], self.totals[:, p["off"]:p["off"] + p["np"]]
+
+    def adjusted(self, l):
+        """(adj_members (M, n) float64, adj_ensemble (n,) float64, mean (n,), std (n,)) of level l after the adjustment: every member's
+        own map adjusted to the census of the adjust level, the adjustment of the ENSEMBLE-MEAN map (what the reference adjusts; it is
+        not the mean of the members' where their factors differ), and the mean / (n - 1) standard deviation over the members.  The
+        arithmetic: ``include/popcorn_hip.h``, pc_census_adjust_finalize."""
+        if self.adjust_level is None:
+            raise ValueError("CensusTable was built without adjust=")
+        if self.totals is None:
+            self.finalize()
+        if l not in self._adjusted:
+            a, n, dev = self.adjust_level, self.num_ids[l], self.table.device
+            adj = torch.empty(self.members + 1, n, dtype=torch.float64, device=dev)
+            mean, std = torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev)
+            p = self._pairs.get(l)
+            if l != a and p is None:
+                raise ValueError(f"CensusTable: level {l} of {len(self.num_ids)} levels")
+            L.check(L.lib().pc_census_adjust_finalize(
+                L.ptr(self.table), self.members, C.c_int64(self.T), C.c_int64(self.offsets[l]), C.c_int64(self.offsets[a]),
+                C.c_int64(p["off"] if p else 0), n, self.num_ids[a], C.c_int64(p["np"] if p else 0), L.ptr(p["base"] if p else None),
+                L.ptr(p["c"] if p else None), L.ptr(self._pop), L.ptr(self._has), L.ptr(adj), L.ptr(mean), L.ptr(std), L.stream_ptr()),
+                "pc_census_adjust_finalize")
+            self._adjusted[l] = (adj[:self.members], adj[self.members], mean, std)
+        return self._adjusted[l]
+
+    def adjusted_census(self, l, census_idx, census_pop):
+        """(pred_ensemble (n,), pred_std (n,), pred_members (M, n), gt (n,)) in fp32 for the census rows of level l, after the adjustment:
+        the counterpart of ``census``; pred_ensemble is the adjusted ensemble-mean map's total."""
+        members, ens, _, std = self.adjusted(l)
+        census_idx = torch.as_tensor(census_idx, dtype=torch.int64, device=ens.device)
+        gt = torch.as_tensor(census_pop, dtype=torch.float32, device=ens.device)
+        return ens[census_idx].to(torch.float32), std[census_idx], members[:, census_idx].to(torch.float32), gt
+
+    def adjusted_metrics(self, l, census_idx, census_pop, tag=""):
+        """``get_test_metrics`` of the adjusted ensemble-mean map under its usual keys, plus ``<key>_members_mean`` /
+        ``<key>_members_std`` over the members' own adjusted totals, as ``metrics``."""
+        ens, _, members, gt = self.adjusted_census(l, census_idx, census_pop)
+        return self._metrics_with_spread(ens, members, gt, tag)
 
 
 def census_detail_maps(pred_totals, boundary, census_idx, census_pop, pred_std=None):

@@ -989,6 +989,45 @@ def census_paint(boundary, tables, out=None):
     return out
 
 
+def census_pair_plan(b_l, b_a, num_l, num_a):
+    """The (unit of level l, unit of level a) pairs of two id rasters as one more id raster (csrc/census_adjust.hip,
+    pc_census_pair_plan): what ``eval.CensusTable(adjust=...)`` accumulates beside the levels.  b_l / b_a: int32 device maps of one shape,
+    rows stacked without gaps (a row band of a larger map is fine: any 4-byte aligned start); a pixel belongs to f = b_l[p] when
+    0 <= f < num_l and to c = b_a[p] when 0 <= c < num_a.  Returns (pair_plane (h, w) int32: the compact pair id, -1 where f or c is no
+    unit; pair_f (NP,), pair_c (NP,) int32: the pairs, ordered by (f, c); base (num_l + 1,) int32: pairs of unit f are base[f] ..
+    base[f + 1]).  A function of the two rasters alone.  Raises ValueError, naming the smallest such unit, when a unit of level l meets
+    more than PC_CENSUS_PAIR_SLOTS units of level a (one host synchronisation: NP sizes the table)."""
+    L.require_device(b_l, b_a)
+    for b in (b_l, b_a):
+        if b.dim() != 2 or b.dtype != torch.int32 or not b.is_contiguous() or b.shape != b_l.shape:
+            raise ValueError(f"census_pair_plan: two contiguous int32 (h, w) maps of one shape, got {b.dtype} {tuple(b.shape)}")
+    num_l, num_a = int(num_l), int(num_a)
+    if num_l < 1 or num_a < 1 or num_l * (L.PC_CENSUS_PAIR_SLOTS + 1) >= 1 << 31:
+        raise ValueError(f"census_pair_plan: num_l, num_a >= 1 and {L.PC_CENSUS_PAIR_SLOTS + 1} * num_l < 2^31, got {num_l}, {num_a}")
+    dev = b_l.device
+    partners = torch.empty(num_l, L.PC_CENSUS_PAIR_SLOTS, dtype=torch.int32, device=dev)
+    count = torch.empty(num_l, dtype=torch.int32, device=dev)
+    scratch = torch.empty(num_l, dtype=torch.int32, device=dev)
+    flags = torch.empty(2, dtype=torch.int32, device=dev)
+    n = C.c_int64(b_l.numel())
+    L.check(L.lib().pc_census_pair_plan(L.ptr(b_l), L.ptr(b_a), n, num_l, num_a, L.ptr(partners), L.ptr(count), L.ptr(flags),
+                                        L.ptr(scratch), None, None, L.stream_ptr()), "pc_census_pair_plan")
+    over, first = flags.tolist()
+    if over:
+        raise ValueError(f"census_pair_plan: unit {first} of the judged level shares pixels with more than {L.PC_CENSUS_PAIR_SLOTS} units "
+                         f"of the level adjusted to (it is the smallest such unit); the adjusted table holds at most "
+                         f"{L.PC_CENSUS_PAIR_SLOTS} partners per unit")
+    base = torch.zeros(num_l + 1, dtype=torch.int32, device=dev)
+    base[1:] = torch.cumsum(count, 0)
+    pair_plane = torch.empty(b_l.shape, dtype=torch.int32, device=dev)
+    L.check(L.lib().pc_census_pair_plan(L.ptr(b_l), L.ptr(b_a), n, num_l, num_a, L.ptr(partners), None, None, None, L.ptr(base),
+                                        L.ptr(pair_plane), L.stream_ptr()), "pc_census_pair_plan")
+    held = partners >= 0
+    pair_c = partners[held]                                             # row-major: ordered by (f, c)
+    pair_f = torch.arange(num_l, dtype=torch.int32, device=dev).repeat_interleave(count.long())
+    return pair_plane, pair_f, pair_c, base
+
+
 def region_units(boundary, num_ids, max_blocks=0):
     """The census bookkeeping of a boundary raster in one device pass (csrc/region.hip, pc_region_units; the reference: one Python pass per
     unit, utils/02_preprocess_rwa_shapefile.py:142-161).  boundary: contiguous int32 device map (h, w), h * w < 2^31.  Returns (table int32
