@@ -670,13 +670,16 @@ int pc_census_adjust(float* pred, const int32_t* boundary, int64_t n, int num_id
                      const uint8_t* has_entry, void* stream);
 /* One sliding window of an M-member ensemble into the (H,W) device accumulators (run_eval.py:108-135): interior pixels
  * only (border of `overlap` excluded, PopulationDataset.py:656-672), window origin (yl,xl) = img_coords.
- * popdense/scale: [M][ps_y][ps_x] (scale may be NULL). */
+ * popdense/scale: [M][ps_y][ps_x] (scale may be NULL).  The interior is clipped to [0, H) x [0, W) on all four sides, so (yl, xl) may
+ * be negative or lie beyond the raster; a window with ps <= 2 * overlap, or whose interior lies outside, adds nothing.  overlap < 0:
+ * PC_EINVAL. */
 int pc_stitch_accumulate(const float* popdense, const float* scale, int M, int ps_y, int ps_x, int overlap, int yl, int xl,
                          float* out_sum, float* out_sq, float* scale_sum, float* scale_sq, int16_t* count, int H, int W,
                          void* stream);
 /* The visit counts of nwin windows that OTHER ranks computed (sharded sliding-window inference: every rank needs the complete count map,
  * run_eval.py:140-154), in one pass: count[r][c] += M for every window whose interior rows [x0, x1) x columns [y0, y1) cover (r, c).
- * win: DEVICE array of nwin x {x0, x1, y0, y1} (already clipped to the raster); overlapping interiors (the catch-up windows at the bottom /
+ * win: DEVICE array of nwin x {x0, x1, y0, y1}; the kernel compares every (r, c) of the raster with them, so bounds below 0 or beyond the
+ * raster clip themselves and no store leaves the map; overlapping interiors (the catch-up windows at the bottom /
  * right edge) add up.  No scratch plane, no atomics on the map. */
 int pc_stitch_count_windows(const int32_t* win, int nwin, int M, int16_t* count, int H, int W, void* stream);
 /* run_eval.py:140-154: where count > 1: sum -> mean, sq -> unbiased std; pixels visited once keep their raw values. */

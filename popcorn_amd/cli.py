@@ -311,6 +311,9 @@ def check_eval_args(args):
     if args.resident_windows and args.raw_input:
         raise SystemExit("--resident_windows and --raw_input name two paths for the same raw raster (windows planned once on the device / "
                          "filled one by one): give one of them")
+    if min(args.raster_hw) < args.patchsize:
+        raise SystemExit(f"--raster_hw {args.raster_hw[0]} {args.raster_hw[1]} is smaller than --patchsize {args.patchsize}: the reference's "
+                         f"sliding windows are not defined for a raster with a side below the patch size (h, w >= patchsize)")
     if args.coarse_regions:
         fine = TEST_RASTER_REGIONS
         if args.coarse_regions < 2 or args.coarse_regions >= fine:

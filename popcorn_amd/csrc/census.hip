@@ -90,17 +90,17 @@ __global__ __launch_bounds__(256) void census_adjust_kernel(float* pred, const i
 struct StitchArgs {
     const float* pd; const float* sc;       // [M][ps_y][ps_x] (sc may be NULL)
     float* out_sum; float* out_sq; float* sc_sum; float* sc_sq; int16_t* count;
-    int M, psy, psx, overlap, yl, xl, H, W;
+    int M, psy, psx, yl, xl, W;
+    int y0, y1, x0, x1;                     // the interior clipped to the raster on all four sides (raster coordinates, not empty)
 };
 
 __global__ __launch_bounds__(256) void stitch_accumulate_kernel(const StitchArgs a) {
-    const int iy = a.psy - 2 * a.overlap, ix = a.psx - 2 * a.overlap;
-    const int n = iy * ix;
+    const int ix = a.x1 - a.x0;
+    const int n = (a.y1 - a.y0) * ix;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
         const int ry = i / ix, rx = i - ry * ix;
-        const int py = a.overlap + ry, px = a.overlap + rx;
-        const int gy = a.yl + py, gx = a.xl + px;
-        if (gy >= a.H || gx >= a.W) continue;
+        const int gy = a.y0 + ry, gx = a.x0 + rx;
+        const int py = gy - a.yl, px = gx - a.xl;   // the window's own element: origin (yl, xl) may lie above / left of the raster
         float s = 0.f, s2 = 0.f, t = 0.f, t2 = 0.f;
         for (int m = 0; m < a.M; ++m) {
             const float v = a.pd[((int64_t)m * a.psy + py) * a.psx + px];
@@ -216,13 +216,21 @@ extern "C" int pc_census_adjust(float* pred, const int32_t* boundary, int64_t n,
 extern "C" int pc_stitch_accumulate(const float* popdense, const float* scale, int M, int ps_y, int ps_x, int overlap,
                                     int yl, int xl, float* out_sum, float* out_sq, float* scale_sum, float* scale_sq,
                                     int16_t* count, int H, int W, void* stream) {
-    if (!popdense || !out_sum || !out_sq || !count || M < 1) return PC_EINVAL;
+    if (!popdense || !out_sum || !out_sq || !count || M < 1 || H < 1 || W < 1 || overlap < 0) return PC_EINVAL;
     if (scale && (!scale_sum || !scale_sq)) return PC_EINVAL;
     if (ps_y <= 2 * overlap || ps_x <= 2 * overlap) return 0;
     StitchArgs a{};
+    // the interior clipped to [0, H) x [0, W) on all four sides, as pc_product_accumulate and pc_census_accumulate clip it: a window
+    // whose origin is negative (it sticks out above / left of the raster) adds only the part of its interior that lies inside
+    a.y0 = yl + overlap > 0 ? yl + overlap : 0;
+    a.x0 = xl + overlap > 0 ? xl + overlap : 0;
+    a.y1 = yl + ps_y - overlap < H ? yl + ps_y - overlap : H;
+    a.x1 = xl + ps_x - overlap < W ? xl + ps_x - overlap : W;
+    if (a.y1 <= a.y0 || a.x1 <= a.x0) return 0;              // the interior lies outside the raster
     a.pd = popdense; a.sc = scale; a.out_sum = out_sum; a.out_sq = out_sq; a.sc_sum = scale_sum; a.sc_sq = scale_sq;
-    a.count = count; a.M = M; a.psy = ps_y; a.psx = ps_x; a.overlap = overlap; a.yl = yl; a.xl = xl; a.H = H; a.W = W;
-    const int64_t n = (int64_t)(ps_y - 2 * overlap) * (ps_x - 2 * overlap);
+    a.count = count; a.M = M; a.psy = ps_y; a.psx = ps_x; a.yl = yl; a.xl = xl; a.W = W;
+    const int64_t n = (int64_t)(a.y1 - a.y0) * (a.x1 - a.x0);
+    if (n > INT32_MAX) return PC_EINVAL;
     hipLaunchKernelGGL(stitch_accumulate_kernel, dim3(stream_grid(n, 2)), dim3(256), 0, (hipStream_t)stream, a);
     PC_CHECK_LAUNCH();
     return 0;

@@ -498,9 +498,10 @@ class ResidentWindows:
         h, w = self.shape
         ps = self.patchsize
         S = 4 if self.fourseasons else 1
-        if not 1 <= ps <= min(h, w) or not 0 <= self.overlap or 2 * self.overlap >= ps:
-            raise ValueError(f"ResidentWindows: 1 <= patchsize <= min(h, w) = {min(h, w)} and 0 <= 2 * overlap < patchsize, got patchsize "
-                             f"{patchsize}, overlap {overlap}")
+        E.require_raster_fits(h, w, ps, "ResidentWindows")
+        if not 1 <= ps or not 0 <= self.overlap or 2 * self.overlap >= ps:
+            raise ValueError(f"ResidentWindows: 1 <= patchsize and 0 <= 2 * overlap < patchsize, got patchsize {patchsize}, overlap "
+                             f"{overlap}")
         if region.seasons < S:
             raise ValueError(f"ResidentWindows: fourseasons evaluates seasons 0 .. 3, the region holds {region.seasons}")
         if not 0 <= self.rank < self.world:

@@ -38,6 +38,17 @@ def get_patch_indices(h, w, patchsize=INFERENCE_PATCH_SIZE, overlap=OVERLAP, fou
     return torch.cat([torch.cat([main, torch.full((main.shape[0], 1), s, dtype=int)], dim=1) for s in seasons], dim=0)
 
 
+def require_raster_fits(h, w, patchsize, who):
+    """A raster with a side below the patch size is not defined by the reference: its window list (``get_patch_indices``) needs
+    ``torch.arange(0, h - patchsize, stride)`` with a negative end -- a RuntimeError in current torch builds, a negative origin (which
+    tensor slices wrap silently) where arange tolerates it -- and its loader would read a window at a negative offset
+    (data/PopulationDataset.py:294-334, 624-653).  Every consumer of the window list refuses it here by name, before anything is
+    allocated or launched."""
+    if min(int(h), int(w)) < int(patchsize):
+        raise ValueError(f"{who}: a raster of h {int(h)} x w {int(w)} is smaller than patchsize {int(patchsize)}; the sliding windows of "
+                         f"the reference are not defined for it (evaluate with a patchsize <= min(h, w))")
+
+
 def create_mask(patchsize_x, patchsize_y, overlap):
     """Interior of a window (data/PopulationDataset.py:656-672)."""
     m = torch.zeros(patchsize_x, patchsize_y, dtype=torch.bool)
@@ -49,7 +60,9 @@ def count_windows(count, windows, M, ps, overlap=OVERLAP):
     """count[r][c] += M for every window of ``windows`` (iterable of (row origin, column origin)) whose interior covers (r, c), in ONE
     launch of ``census.hip`` (pc_stitch_count_windows).  count: (h, w) int16 device map, rows contiguous."""
     h, w = count.shape
-    # clipped interiors {x0, x1, y0, y1} of all windows as ONE small device array; census.hip counts them into the map in one launch
+    # interiors {x0, x1, y0, y1} of all windows as ONE small device array; census.hip counts them into the map in one launch.  Clipped at
+    # the bottom / right here; a negative origin needs no clamp: the kernel compares every pixel (r, c) of the raster with x0 <= r < x1,
+    # y0 <= c < y1, so the part of an interior above / left of the raster matches no pixel (all four sides clip through the comparisons)
     rows = []
     for x, y in windows:
         x, y = int(x), int(y)
@@ -88,8 +101,8 @@ class Stitcher:
         self.band = None                                   # (row0, row1) once the accumulators hold only this rank's band
 
     def add_window(self, xl, yl, popdense, scale=None, overlap=OVERLAP):
-        """popdense / scale: (M, ps, ps) member outputs of the window whose origin is row xl, column yl (the reference's
-        ``img_coords``)."""
+        """popdense / scale: (M, psx, psy) member outputs of the window whose origin is row xl, column yl (the reference's
+        ``img_coords``); psx rows, psy columns.  The interior is clipped to the raster on all four sides: the origin may be negative."""
         L.require_device(popdense)
         M, psx, psy = popdense.shape
         popdense = popdense.contiguous().float()
@@ -100,8 +113,8 @@ class Stitcher:
 
     def add_count_only(self, xl, yl, M, ps, overlap=OVERLAP):
         """A window another rank computed: only its visit count (interior += M), no data."""
-        x0, x1 = xl + overlap, min(xl + ps - overlap, self.h)
-        y0, y1 = yl + overlap, min(yl + ps - overlap, self.w)
+        x0, x1 = max(xl + overlap, 0), min(xl + ps - overlap, self.h)       # (a negative slice start would wrap)
+        y0, y1 = max(yl + overlap, 0), min(yl + ps - overlap, self.w)
         if x1 > x0 and y1 > y0:
             self.count[x0:x1, y0:y1] += M
 
@@ -206,6 +219,7 @@ class ProductGrid:
     def set_windows(self, idx, patchsize=INFERENCE_PATCH_SIZE, overlap=OVERLAP):
         """The complete window list of the evaluation (``get_patch_indices``: rows of (row origin, column origin[, season]); every
         season's windows count) -> the visit map.  Starts a new accumulation: the planes are zeroed."""
+        require_raster_fits(self.h, self.w, patchsize, "ProductGrid.set_windows")
         self.cells.zero_()
         self.visits.zero_()
         self.mean = self.std = None
@@ -326,6 +340,7 @@ class CensusTable:
     def set_windows(self, idx, patchsize=INFERENCE_PATCH_SIZE, overlap=OVERLAP):
         """The complete window list of the evaluation (as ``ProductGrid.set_windows``) -> the visit map.  Starts a new accumulation: the
         table and the flags are zeroed.  A shared visit map is left to its owner, whose ``set_windows`` must have run."""
+        require_raster_fits(self.h, self.w, patchsize, "CensusTable.set_windows")
         self.table.zero_()
         self.flags.zero_()
         self.totals = self.mean = self.std = None
@@ -588,6 +603,7 @@ def evaluate_raster(models, raster, patchsize=INFERENCE_PATCH_SIZE, overlap=OVER
         raster = lambda x, y, s, ps: tensor[s:s + 1, :, x:x + ps, y:y + ps]  # noqa: E731
     else:
         h, w = raster.shape
+    require_raster_fits(h, w, patchsize, "evaluate_raster")            # before anything is allocated or launched
     dev = next(models[0].parameters()).device
     st = Stitcher(h, w, dev, world=reducer.world)
     idx = get_patch_indices(h, w, patchsize, overlap, fourseasons)

@@ -18,6 +18,7 @@ import tests.test_gpu_census_table as t_census
 import tests.test_gpu_conv3x3 as t_conv
 import tests.test_gpu_conv_fwd_split as t_split
 import tests.test_gpu_convt_head as t_ch
+import tests.test_gpu_eval_kernels as t_ev
 import tests.test_gpu_feed as t_feed
 import tests.test_gpu_input_grad as t_ig
 import tests.test_gpu_level2 as t_l2
@@ -225,6 +226,9 @@ CASES = [
     ("census_paint-K1", t_census.test_paint_equals_gather, (1,), 3),
     ("census_paint-K3", t_census.test_paint_equals_gather, (3,), 3),
     ("augment_raw-rot1_rot3-non_square", t_feed.test_augment_raw_rotation_direction_known_answer, (), 14),
+    # ---- census.hip: stitcher (accumulate + finalize, windows that stick out on every side), segment sum (all 16 alignment phases)
+    ("stitcher-exact-M2-some_without_scale", t_ev.test_stitcher_exact_known_answer.body, (2, "some"), 20),
+    ("segment_sum-4097ids-n4099", t_ev.test_segment_sum_exact_at_every_alignment_phase.body, (4097, 4099), 50),
 ]
 
 
