@@ -1054,6 +1054,38 @@ int pc_region_item(const void* s2, int s2_u16, const float* s1, const float* s1_
                    const int32_t* idx, const float* val, int64_t cap, int64_t start, int64_t count, float* out, float* admin_out,
                    void* stream);
 
+/* ---- the building layer a dataset ships (data/PopulationDataset.py:606-612; popcorn.py:112-114) ----
+ * A building layer is an fp32 raster without a season axis: resident (h, w) for the region entry points, (B, 1, H, W) in a batch.  It
+ * follows the admin mask's geometry (crop, flips, quarter turns; utils/utils.py:182-209), its padding is the collate's 0.0
+ * (PopulationDataset.py:909-956), and it gets no value transform, no normalisation and no repair: payloads arrive bit for bit, NaN included.
+ * Each `_layer` entry point below IS the code of the entry point it is named after, which is its call with layer = layer_out = NULL:
+ *   pc_augment_raw_layer     layer (B, 1, H, W) -> layer_out (B, 1, Ho, Wo), the map of admin_out
+ *   pc_region_gather_layer   layer DEVICE (h, w) -> layer_out (B, 1, Hm, Wm), 0.0 outside the crop (pc_region_gather_orbit's other arguments)
+ *   pc_region_batch_layer    layer DEVICE (h, w) -> layer_out (B, 1, Ho, Wo) == the layer of
+ *                            pc_augment_raw_layer( pc_region_gather_layer(...) ), bit for bit (pc_region_batch_orbit's other arguments)
+ *   pc_region_window_layer   layer DEVICE (h, w) -> layer_out (ps, ps), the raster's slice: one more blockIdx.y plane of the same launch
+ *   pc_region_item_layer     layer DEVICE (h, w) -> layer_out (hc, wc), likewise
+ * PC_EINVAL before anything is enqueued, besides what the plain entry point refuses: layer without layer_out, layer_out without layer,
+ * either misaligned for fp32.  The 16-byte forms are taken only when layer_out is 16-byte aligned as well. */
+int pc_augment_raw_layer(const float* s2, const float* s1, const float* admin, const float* layer, float* raw, float* admin_out,
+                         float* layer_out, int B, int H, int W, int vflip, int hflip, int rot, int bright, float beta, int gam, float gamma,
+                         void* stream);
+int pc_region_gather_layer(const void* s2, int s2_u16, const float* s1, const float* s1_asc, const uint8_t* orbit, const int32_t* boundary,
+                           const float* layer, int S, int C2, int C1, int h, int w, const int32_t* band_sel, const int32_t* crops, int B,
+                           int Hm, int Wm, float* s2_out, float* s1_out, float* admin_out, float* layer_out, int32_t* data_hw, void* stream);
+int pc_region_batch_layer(const void* s2, int s2_u16, const float* s1, const float* s1_asc, const uint8_t* orbit, const int32_t* boundary,
+                          const float* layer, int S, int C2, int C1, int h, int w, const int32_t* band_sel, const int32_t* crops, int B,
+                          int Hm, int Wm, int vflip, int hflip, int rot, int bright, float beta, int gam, float gamma, float* raw,
+                          float* admin_out, float* layer_out, int Ho, int Wo, const pc_region_labels* labels, void* stream);
+int pc_region_window_layer(const void* s2, int s2_u16, const float* s1, const float* s1_asc, int orbit, const float* layer, int S, int C2,
+                           int C1, int h, int w, const int32_t* band_sel, int x, int y, int season, int ps, const float* mean6,
+                           const float* std6, const int32_t* idx, const float* val, int64_t cap, int64_t start, int64_t count, float* out,
+                           float* layer_out, void* stream);
+int pc_region_item_layer(const void* s2, int s2_u16, const float* s1, const float* s1_asc, int orbit, const int32_t* boundary,
+                         const float* layer, int S, int C2, int C1, int h, int w, const int32_t* band_sel, int x0, int x1, int y0, int y1,
+                         int season, const float* mean6, const float* std6, const int32_t* idx, const float* val, int64_t cap, int64_t start,
+                         int64_t count, float* out, float* admin_out, float* layer_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

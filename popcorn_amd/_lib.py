@@ -271,6 +271,24 @@ def lib():
                                         [C.POINTER(C.c_int32)] + [C.c_int] * 5 +
                                         [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p] + [C.c_int64] * 3 +
                                         [C.c_void_p] * 3)
+        # the building layer (the `_layer` forms): the plain entry point's arguments with `layer` after the last source pointer and
+        # `layer_out` after the last fp32 output
+        _lib.pc_augment_raw_layer.argtypes = ([C.c_void_p] * 7 + [C.c_int] * 7 + [C.c_float, C.c_int, C.c_float, C.c_void_p])
+        _lib.pc_region_gather_layer.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), C.c_void_p, C.c_void_p] +
+                                                [C.c_int] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_int] * 3 +
+                                                [C.c_void_p] * 6)
+        _lib.pc_region_batch_layer.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint8), C.c_void_p, C.c_void_p] +
+                                               [C.c_int] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_int] * 7 +
+                                               [C.c_float, C.c_int, C.c_float] +
+                                               [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(PcRegionLabels), C.c_void_p])
+        _lib.pc_region_window_layer.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 5 +
+                                                [C.POINTER(C.c_int32)] + [C.c_int] * 4 +
+                                                [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p] + [C.c_int64] * 3 +
+                                                [C.c_void_p] * 3)
+        _lib.pc_region_item_layer.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] +
+                                              [C.c_int] * 5 + [C.POINTER(C.c_int32)] + [C.c_int] * 5 +
+                                              [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p] + [C.c_int64] * 3 +
+                                              [C.c_void_p] * 4)
     return _lib
 
 

@@ -137,6 +137,11 @@ def train_parser():
                         "(random_state 1610), the run trains on the first 80 %% and validate_weak runs over the other 20 %% through "
                         "data/region.py: ResidentItems (season, orbit and NaN repair of every item planned once, one launch per item, no "
                         "per-item fill or synchronisation); needs -wvb 1; keeps the ascending S1 resident as --resident_repair does")
+    p.add_argument("--building_layer", action="store_true",
+                   help="the dataset ships a building layer (the reference's path whenever -senbuilds is absent: Google Open Buildings / "
+                        "swissTLM3D counts): the synthetic host datasets, the resident region and the test raster carry a seeded layer and "
+                        "every step, validation and target test multiplies the occupancy head by it instead of running the frozen "
+                        "extractor; refused together with -senbuilds (the reference's dataset loads no layer then)")
     return p
 
 
@@ -188,7 +193,19 @@ def eval_parser():
                         "is adjusted to the COARSE census and judged on both levels (AdjCensus_synthetic_fine is then the disaggregation "
                         "result); with --census_table the adjusted fine totals come from the table as well, per member "
                         "(TableAdjCensus_synthetic_fine + _members_mean / _members_std; --census_out gains adjusted / adjusted_std)")
+    p.add_argument("--building_layer", action="store_true",
+                   help="the test raster ships a building layer (the reference's path whenever -senbuilds is absent): every window's sample "
+                        "carries building_counts and no member runs its frozen extractor; with --resident_windows the layer stays resident "
+                        "and comes out of each window's own launch; refused together with -senbuilds")
     return p
+
+
+def check_building_layer(args):
+    """--building_layer -senbuilds: the reference's dataset loads no layer for a model that scores buildings itself
+    (PopulationDataset.py:606-612 under ``not sentinelbuildings``), and its model would ignore one (popcorn.py:112-114)."""
+    if args.building_layer and args.sentinelbuildings:
+        raise SystemExit("--building_layer ships a building layer for a model built WITHOUT -senbuilds; with -senbuilds the reference's "
+                         "dataset loads no layer and the model ignores one: drop --building_layer or -senbuilds")
 
 
 def seed_all(seed):
@@ -237,11 +254,20 @@ def normalize_sample(sample, device, transform=None, nan_fill=False):
     raw = torch.cat([s2, s1], 1).contiguous()
     x = ops.select_normalize(raw, (0, 1, 2, 3, 4, 5), stats.MEAN6, stats.STD6)
     admin = sample["admin_mask"].to(device).float()
+    # a shipped building layer is stacked with the admin mask and turned / flipped with it (utils/utils.py:182-209); no value transform
+    layer = sample.get("building_counts")
+    if layer is not None:
+        layer = layer.to(device).float()
     if transform is not None and "general" in transform:
-        x, m = transform["general"]((x, admin.unsqueeze(1)))
+        stack = admin.unsqueeze(1) if layer is None else torch.cat([admin.unsqueeze(1), layer], 1)
+        x, m = transform["general"]((x, stack))
         admin = m[:, 0]
+        if layer is not None:
+            layer = m[:, 1:2]
     out = {"input": x.contiguous(), "admin_mask": admin.contiguous(),
            "census_idx": sample["census_idx"].to(device).contiguous(), "y": sample["y"].to(device).float().contiguous()}
+    if layer is not None:
+        out["building_counts"] = layer.contiguous()
     return out
 
 
@@ -251,7 +277,8 @@ def prepare_sample_fused(sample, transform=None, nan_fill=False):
     (``ops.augment_raw``) applies them while it assembles the raw [S2 | S1] tile, and the normalisation happens inside the step's ingest
     (the executor's ``raw`` input form) -- no ``.float()`` / ``torch.cat`` / normalise / flip / rot90 launches, no synchronous copy.
     Returns None when ``transform`` is not the reference trainer's set (the caller then takes ``normalize_sample``).
-    nan_fill: ``fill_sample_`` on the staged tensors first."""
+    nan_fill: ``fill_sample_`` on the staged tensors first.  A shipped ``building_counts`` (B, 1, H, W) goes through the same launch under
+    the admin mask's map and is returned."""
     from .utils.transform import draw_fused_params
     s2, s1, admin = sample["S2"], sample["S1"], sample["admin_mask"]
     if not (s2.is_cuda and s2.dtype == torch.float32 and s1.dtype == torch.float32 and s2.shape[1] == 4 and s1.shape[1] == 2):
@@ -262,6 +289,13 @@ def prepare_sample_fused(sample, transform=None, nan_fill=False):
     if nan_fill:
         s2, s1 = s2.contiguous(), s1.contiguous()
         fill_sample_(s2, s1, sample)
+    layer = sample.get("building_counts")
+    if layer is not None:
+        if not (layer.is_cuda and layer.dtype == torch.float32):
+            return None
+        raw, adm, bc = ops.augment_raw(s2.contiguous(), s1.contiguous(), admin.float().contiguous(), params, buildings=layer.contiguous())
+        return {"raw": raw, "admin_mask": adm, "census_idx": sample["census_idx"].contiguous(), "y": sample["y"].float().contiguous(),
+                "building_counts": bc}
     raw, adm = ops.augment_raw(s2.contiguous(), s1.contiguous(), admin.float().contiguous(), params)
     return {"raw": raw, "admin_mask": adm, "census_idx": sample["census_idx"].contiguous(), "y": sample["y"].float().contiguous()}
 
@@ -324,6 +358,7 @@ def check_eval_args(args):
 class Trainer:
     def __init__(self, args):
         self.args = args
+        check_building_layer(args)
         check_repair_args(args)
         self.rank, self.local_rank, self.world = init_from_env()
         if not torch.cuda.is_available():
@@ -352,11 +387,13 @@ class Trainer:
                                  "parallelism); --device_units lifts the second restriction and the eager one")
             from .data.units import SyntheticMultiUnitDataset, collate_units
             ds = SyntheticMultiUnitDataset(args.synthetic_regions, units=args.units_per_crop, min_hw=args.synthetic_hw_range[0],
-                                           max_hw=args.synthetic_hw_range[1], seed=args.seed, fixed_hw=args.fixed_hw, ragged=True)
+                                           max_hw=args.synthetic_hw_range[1], seed=args.seed, fixed_hw=args.fixed_hw, ragged=True,
+                                           buildings=args.building_layer)
             collate = collate_units
         else:
             ds = SyntheticWeaksupDataset(args.synthetic_regions, min_hw=args.synthetic_hw_range[0], max_hw=args.synthetic_hw_range[1],
-                                         seed=args.seed, fixed_hw=args.fixed_hw, nan_clouds=args.nan_clouds, ascfill=args.ascfill)
+                                         seed=args.seed, fixed_hw=args.fixed_hw, nan_clouds=args.nan_clouds, ascfill=args.ascfill,
+                                         buildings=args.building_layer)
         self.sampler = None
         if self.world > 1:
             self.sampler = torch.utils.data.distributed.DistributedSampler(ds, num_replicas=self.world, rank=self.rank,
@@ -368,7 +405,8 @@ class Trainer:
         # weak validation set (run_train.py:410-414: a second Population_Dataset in weaksup mode, batch size -wvb)
         self.val_loader = torch.utils.data.DataLoader(
             SyntheticWeaksupDataset(args.synthetic_val_regions, min_hw=args.synthetic_hw_range[0], max_hw=args.synthetic_hw_range[1],
-                                    seed=args.seed + 77, fixed_hw=args.fixed_hw, nan_clouds=args.nan_clouds, ascfill=args.ascfill),
+                                    seed=args.seed + 77, fixed_hw=args.fixed_hw, nan_clouds=args.nan_clouds, ascfill=args.ascfill,
+                                    buildings=args.building_layer),
             batch_size=args.weak_val_batch_size, shuffle=False, collate_fn=Population_Dataset_collate_fn, drop_last=False)
         self._test_raster = None
         self._resident_windows = None                                    # --resident_test: planned at the first test, reused afterwards
@@ -427,7 +465,8 @@ class Trainer:
                                   plan_repair, split_census)
         S = a.resident_seasons
         data = SyntheticTestRaster(a.resident_region[0], a.resident_region[1], seasons=S, n_regions=a.resident_units, seed=a.seed + 20,
-                                   device=self.device, raw=True, nan_clouds=a.nan_clouds, s1_gap=a.resident_s1_gap)
+                                   device=self.device, raw=True, nan_clouds=a.nan_clouds, s1_gap=a.resident_s1_gap,
+                                   buildings=a.building_layer)
         self.region = ResidentRegion.from_synthetic(data, with_asc=a.resident_repair or a.resident_test or a.resident_val)
         self.region_data = data                                          # (the raster callable of evaluate_raster(raw=True) over the same data)
         kw = dict(max_pix=a.max_weak_pix, max_pix_box=a.max_pix_box)
@@ -533,7 +572,7 @@ class Trainer:
         s = None
         if self.fused is not None and torch.is_tensor(sample.get("raw")) and sample["raw"].is_cuda:
             # a batch assembled by ResidentBatchFeed: augmented raw tile and labels are there already, the coins drawn by the feed
-            s = {k: sample[k] for k in ("raw", "admin_mask", "census_idx", "y")}
+            s = {k: sample[k] for k in ("raw", "admin_mask", "census_idx", "y", "building_counts") if k in sample}
         elif self.fused is not None and torch.is_tensor(sample.get("S2")) and sample["S2"].is_cuda:
             # a batch staged by the feed: augmentation + assembly in one launch, normalisation inside the step (raw input form)
             s = prepare_sample_fused(sample, self.data_transform, nan_fill=self._step_nan_fill)
@@ -632,12 +671,13 @@ class Trainer:
             return self._test_resident(save)
         if self._test_raster is None:
             self._test_raster = SyntheticTestRaster(a.test_raster_hw[0], a.test_raster_hw[1], seasons=1, n_regions=64,
-                                                    seed=a.seed + 10, device=self.device)
+                                                    seed=a.seed + 10, device=self.device, buildings=a.building_layer)
         data = self._test_raster
         self.model.eval()
+        kw = {} if data.buildings is None else {"buildings": data.buildings}       # --building_layer: the test raster's own layer
         out, _, scale, _ = E.evaluate_raster([self.model], data.raster, a.test_patchsize, a.test_overlap, False,
-                                             FlatReducer(), 0) if self.world == 1 else \
-            E.evaluate_raster([self.model], data.raster, a.test_patchsize, a.test_overlap, False, self.reducer, self.rank)
+                                             FlatReducer(), 0, **kw) if self.world == 1 else \
+            E.evaluate_raster([self.model], data.raster, a.test_patchsize, a.test_overlap, False, self.reducer, self.rank, **kw)
         cp, cg = E.convert_popmap_to_census(out, data.boundary, data.census_idx, data.census_pop)
         stats = get_test_metrics(cp, cg, tag="MainCensus_synthetic_fine")
         self.target_test_stats = {k + "/targettest": float(v) for k, v in stats.items()}
@@ -764,6 +804,7 @@ def run_eval(argv=None):
     from . import eval as E
     from .utils.metrics import get_test_metrics
     args = eval_parser().parse_args(argv)
+    check_building_layer(args)
     check_eval_args(args)
     rank, local_rank, world = init_from_env()
     torch.cuda.set_device(local_rank)
@@ -778,7 +819,7 @@ def run_eval(argv=None):
         models.append(m.eval().set_precision(args.precision))
     data = SyntheticTestRaster(args.raster_hw[0], args.raster_hw[1], seasons=4 if args.fourseasons else 1, device=dev,
                                raw=args.raw_input or args.resident_windows, nan_clouds=args.nan_clouds, s1_gap=args.s1_gap,
-                               coarse_regions=args.coarse_regions)
+                               coarse_regions=args.coarse_regions, buildings=args.building_layer)
     coarse = args.coarse_regions > 0
     reducer = FlatReducer()
     raster = data.raster
@@ -802,7 +843,8 @@ def run_eval(argv=None):
     t0 = time.time()
     out, out_std, scale, scale_std = E.evaluate_raster(models, raster, args.patchsize, args.overlap, args.fourseasons,
                                                        reducer, rank, raw=args.raw_input, ascfill=args.ascfill, product=product,
-                                                       census=census)
+                                                       census=census,
+                                                       **({"buildings": data.buildings} if args.building_layer else {}))
     res = {}
     cp, cg = E.convert_popmap_to_census(out, data.boundary, data.census_idx, data.census_pop)
     res.update({k: float(v) for k, v in get_test_metrics(cp, cg, tag="MainCensus_synthetic_fine").items()})

@@ -29,6 +29,12 @@
 // validates every crop before anything is enqueued; the kernel never forms an address outside the sources.
 // pc_region_gather_orbit is the same kernel with the S1 source chosen per crop: a second raster (the ascending orbit) and a 128-bit mask per
 // launch in the kernel arguments; pc_region_gather is its call without either (region_repair.hip plans the mask once per region).
+// pc_region_gather_layer is the same kernel again with a building layer: a resident fp32 (h, w) raster without a season axis, copied as an
+// eighth plane building_counts (B, 1, Hm, Wm) under the admin mask's map, padded with the collate's 0.0 and otherwise bit for bit (no value
+// transform, no repair: a NaN keeps its payload).  pc_region_gather_orbit is its call without a layer.  The layer is a TEMPLATE PARAMETER
+// (BL) of the one kernel body, not a pointer test, here and in region_batch.hip / train_ops.hip: the transposed forms of those files size
+// their static LDS image by it (8 planes against 7), so the instantiation without a layer is the code it was, and one rule serves all
+// three files.
 #include "common.h"
 #include "region_args.h"
 #include "region_load.h"
@@ -163,12 +169,13 @@ struct RegionGatherArgs {
     RegionSources src;
     uint32_t orbit[PC_REGION_GATHER_MAX_B / 32];                // bit b: crop b reads its S1 from s1_asc (16 bytes; zero: every crop from s1)
     float* o2; float* o1; float* adm; int32_t* data_hw;          // already offset to the launch's first crop
+    const float* bld; float* obld;                               // the building layer (h, w) and its output, offset likewise (BL)
     int Hm, Wm;
     int32_t crop[PC_REGION_GATHER_MAX_B][5];                     // {x0, x1, y0, y1, season}, validated by the host: 2,560 bytes of arguments
 };
 
 // V = 4: Wm % 4 == 0 and 16-byte aligned outputs; V = 1: anything
-template <typename T2, int V>
+template <typename T2, int V, bool BL>
 __global__ __launch_bounds__(RG_THREADS) void region_gather_kernel(const RegionGatherArgs a) {
     const int t = threadIdx.x, b = blockIdx.y;
     const RegionSources& r = a.src;
@@ -180,6 +187,8 @@ __global__ __launch_bounds__(RG_THREADS) void region_gather_kernel(const RegionG
     float* o2 = a.o2 + (int64_t)b * 4 * oplane;
     float* o1 = a.o1 + (int64_t)b * 2 * oplane;
     float* adm = a.adm + (int64_t)b * oplane;
+    const float* bld = a.bld;
+    float* obld = BL ? a.obld + (int64_t)b * oplane : nullptr;
     const int wg = a.Wm / V, groups = a.Hm * wg;                   // (Hm * Wm < 2^31: host)
     for (int g = blockIdx.x * RG_THREADS + t; g < groups; g += gridDim.x * RG_THREADS) {
         const int y = g / wg, x = (g - y * wg) * V;
@@ -194,6 +203,7 @@ __global__ __launch_bounds__(RG_THREADS) void region_gather_kernel(const RegionG
                 for (int c = 0; c < 2; ++c) pc_st4(o1 + c * oplane + o, rg_ld4(s1 + r.band1[c] * plane + src + x));
                 const i32x4u id = *reinterpret_cast<const i32x4u*>(r.boundary + src + x);
                 pc_st4(adm + o, f32x4{(float)id[0], (float)id[1], (float)id[2], (float)id[3]});
+                if constexpr (BL) pc_st4(obld + o, rg_ld4(bld + src + x));
                 continue;
             }
             if (y >= hb || x >= wb) {
@@ -204,6 +214,7 @@ __global__ __launch_bounds__(RG_THREADS) void region_gather_kernel(const RegionG
 #pragma unroll
                 for (int c = 0; c < 2; ++c) pc_st4(o1 + c * oplane + o, zero);
                 pc_st4(adm + o, f32x4{-1.f, -1.f, -1.f, -1.f});
+                if constexpr (BL) pc_st4(obld + o, zero);
                 continue;
             }
         }
@@ -223,6 +234,10 @@ __global__ __launch_bounds__(RG_THREADS) void region_gather_kernel(const RegionG
                 o1[c * oplane + o + e] = in ? v : 0.f;
             }
             adm[o + e] = in ? (float)r.boundary[s] : -1.f;
+            if constexpr (BL) {
+                const float v = bld[s];
+                obld[o + e] = in ? v : 0.f;
+            }
         }
     }
 }
@@ -233,8 +248,14 @@ inline void rg_launch(const RegionGatherArgs& a, int Bc, bool vec, hipStream_t s
     int64_t gx = (groups + RG_THREADS - 1) / RG_THREADS;
     const int cap = RG_MAX_BLOCKS / Bc > 1 ? RG_MAX_BLOCKS / Bc : 1;
     if (gx > cap) gx = cap;
-    if (vec) hipLaunchKernelGGL((region_gather_kernel<T2, 4>), dim3((int)gx, Bc), dim3(RG_THREADS), 0, st, a);
-    else hipLaunchKernelGGL((region_gather_kernel<T2, 1>), dim3((int)gx, Bc), dim3(RG_THREADS), 0, st, a);
+    const dim3 grid((int)gx, Bc);
+    if (a.bld) {
+        if (vec) hipLaunchKernelGGL((region_gather_kernel<T2, 4, true>), grid, dim3(RG_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((region_gather_kernel<T2, 1, true>), grid, dim3(RG_THREADS), 0, st, a);
+    } else {
+        if (vec) hipLaunchKernelGGL((region_gather_kernel<T2, 4, false>), grid, dim3(RG_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((region_gather_kernel<T2, 1, false>), grid, dim3(RG_THREADS), 0, st, a);
+    }
 }
 
 }  // namespace
@@ -266,11 +287,13 @@ extern "C" int pc_region_units(const int32_t* boundary, int h, int w, int num_id
     return 0;
 }
 
-extern "C" int pc_region_gather_orbit(const void* s2, int s2_u16, const float* s1, const float* s1_asc, const uint8_t* orbit,
-                                      const int32_t* boundary, int S, int C2, int C1, int h, int w, const int32_t* band_sel,
-                                      const int32_t* crops, int B, int Hm, int Wm, float* s2_out, float* s1_out, float* admin_out,
-                                      int32_t* data_hw, void* stream) {
+extern "C" int pc_region_gather_layer(const void* s2, int s2_u16, const float* s1, const float* s1_asc, const uint8_t* orbit,
+                                      const int32_t* boundary, const float* layer, int S, int C2, int C1, int h, int w,
+                                      const int32_t* band_sel, const int32_t* crops, int B, int Hm, int Wm, float* s2_out, float* s1_out,
+                                      float* admin_out, float* layer_out, int32_t* data_hw, void* stream) {
     RegionGatherArgs a{};
+    bool bl;
+    if (rg_layer(layer, layer_out, bl)) return PC_EINVAL;
     if (rg_sources(a.src, s2, s2_u16, s1, s1_asc, boundary, true, S, C2, C1, h, w, band_sel)) return PC_EINVAL;
     if (!crops || !s2_out || !s1_out || !admin_out || !data_hw || B < 1 || Hm < 1 || Wm < 1) return PC_EINVAL;
     if ((int64_t)Hm * Wm >= ((int64_t)1 << 31)) return PC_EINVAL;
@@ -284,13 +307,14 @@ extern "C" int pc_region_gather_orbit(const void* s2, int s2_u16, const float* s
         if (rg_orbit_mask(a.orbit, orbit ? orbit + b0 : nullptr, B - b0 < PC_REGION_GATHER_MAX_B ? B - b0 : PC_REGION_GATHER_MAX_B, s1_asc))
             return PC_EINVAL;
     const bool vec = (Wm & 3) == 0 && ((reinterpret_cast<uintptr_t>(s2_out) | reinterpret_cast<uintptr_t>(s1_out) |
-                                        reinterpret_cast<uintptr_t>(admin_out)) & 15) == 0;
+                                        reinterpret_cast<uintptr_t>(admin_out) | reinterpret_cast<uintptr_t>(layer_out)) & 15) == 0;
     const int64_t oplane = (int64_t)Hm * Wm;
-    a.Hm = Hm; a.Wm = Wm;
+    a.Hm = Hm; a.Wm = Wm; a.bld = layer;
     for (int b0 = 0; b0 < B; b0 += PC_REGION_GATHER_MAX_B) {
         const int Bc = B - b0 < PC_REGION_GATHER_MAX_B ? B - b0 : PC_REGION_GATHER_MAX_B;
         a.o2 = s2_out + (int64_t)b0 * 4 * oplane; a.o1 = s1_out + (int64_t)b0 * 2 * oplane; a.adm = admin_out + (int64_t)b0 * oplane;
         a.data_hw = data_hw + 2 * (int64_t)b0;
+        a.obld = bl ? layer_out + (int64_t)b0 * oplane : nullptr;
         for (int b = 0; b < Bc; ++b)
             for (int k = 0; k < 5; ++k) a.crop[b][k] = crops[5 * (int64_t)(b0 + b) + k];
         rg_orbit_mask(a.orbit, orbit ? orbit + b0 : nullptr, Bc, s1_asc);
@@ -299,6 +323,15 @@ extern "C" int pc_region_gather_orbit(const void* s2, int s2_u16, const float* s
         PC_CHECK_LAUNCH();
     }
     return 0;
+}
+
+// the call of the same code without a layer
+extern "C" int pc_region_gather_orbit(const void* s2, int s2_u16, const float* s1, const float* s1_asc, const uint8_t* orbit,
+                                      const int32_t* boundary, int S, int C2, int C1, int h, int w, const int32_t* band_sel,
+                                      const int32_t* crops, int B, int Hm, int Wm, float* s2_out, float* s1_out, float* admin_out,
+                                      int32_t* data_hw, void* stream) {
+    return pc_region_gather_layer(s2, s2_u16, s1, s1_asc, orbit, boundary, nullptr, S, C2, C1, h, w, band_sel, crops, B, Hm, Wm, s2_out,
+                                  s1_out, admin_out, nullptr, data_hw, stream);
 }
 
 // the mask-zero call of the same code

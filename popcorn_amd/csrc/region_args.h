@@ -1,6 +1,7 @@
 // region_args.h -- what every entry point over the resident rasters (region.hip, region_batch.hip, region_repair.hip, region_crop.hip)
 // checks and computes, once: the sources and the band selection as they travel in the kernel arguments, the validity of a crop, the
-// orbit mask of a launch, and the device prologue that turns (sources, crop) into the crop's origin, extent and season planes.
+// orbit mask of a launch, the building layer of the `_layer` forms (both pointers or neither, aligned for fp32), and the device prologue
+// that turns (sources, crop) into the crop's origin, extent and season planes.
 // Every failure is PC_EINVAL and nothing is enqueued before the checks are through.
 #pragma once
 #include "common.h"
@@ -24,6 +25,15 @@ static inline int rg_sources(RegionSources& r, const void* s2, int s2_u16, const
     r.s2 = s2; r.s1 = s1; r.s1_asc = s1_asc; r.boundary = boundary; r.C2 = C2; r.C1 = C1; r.h = h; r.w = w;
     for (int c = 0; c < 4; ++c) r.band2[c] = band_sel[c];
     for (int c = 0; c < 2; ++c) r.band1[c] = band_sel[4 + c];
+    return 0;
+}
+
+// The building layer of an entry point that takes one (the `_layer` forms): a resident fp32 (h, w) raster without a season axis and the
+// output it is copied to.  Both or neither, and both aligned for fp32.  `given` tells the caller which launch to make.
+static inline int rg_layer(const float* layer, const float* layer_out, bool& given) {
+    given = layer != nullptr;
+    if ((layer != nullptr) != (layer_out != nullptr)) return PC_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(layer) | reinterpret_cast<uintptr_t>(layer_out)) & 3) return PC_EINVAL;
     return 0;
 }
 

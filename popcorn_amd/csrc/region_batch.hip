@@ -25,6 +25,11 @@
 // pc_region_batch_orbit is the same code with the S1 source chosen per crop (s1_asc and a 128-bit mask per launch in the kernel arguments);
 // pc_region_batch is its call without either.  The map between output and tile positions is region_index.h's, which the patch launch of
 // region_repair.hip uses in the other direction.
+// pc_region_batch_layer is the same code again with a building layer (region.hip: pc_region_gather_layer): building_counts (B, 1, Ho, Wo)
+// follows the admin mask's map, its padding is 0.0 and it gets no value transform -- by definition and bit for bit the layer of
+// pc_augment_raw_layer( pc_region_gather_layer(...) ).  pc_region_batch_orbit is its call without a layer.  The layer is the template
+// parameter BL of the one kernel body (why a template parameter and not a pointer test: region.hip's header): the odd-rot LDS image is
+// [8][32][33] with a layer and [7][32][33] without.
 #include "common.h"
 #include "aug_value.h"
 #include "region_args.h"
@@ -40,6 +45,7 @@ struct RegionBatchArgs {
     RegionSources src;
     uint32_t orbit[PC_REGION_GATHER_MAX_B / 32];                // bit b: crop b reads its S1 from s1_asc (16 bytes; zero: every crop from s1)
     float* raw; float* adm;                                     // already offset to the launch's first crop
+    const float* bld; float* obld;                              // the building layer (h, w) and its output, offset likewise (BL)
     int Hm, Wm, Ho, Wo;                                         // the gathered tile and the output: (Ho, Wo) = (Wm, Hm) for odd rot
     int vflip, hflip, rot;
     int bright, gam;
@@ -65,7 +71,7 @@ __device__ __forceinline__ void rb_labels(const RegionBatchArgs& a, int b, int t
 
 // even rot: the output row i is tile row i or Hm - 1 - i, its columns run along the tile row, ascending or descending.
 // V = 4: Wm % 4 == 0 and 16-byte aligned outputs; V = 1: anything
-template <typename T2, int V>
+template <typename T2, int V, bool BL>
 __global__ __launch_bounds__(RB_THREADS) void region_batch_kernel(const RegionBatchArgs a) {
     const int t = threadIdx.x, b = blockIdx.y;
     rb_labels(a, b, t);
@@ -76,6 +82,8 @@ __global__ __launch_bounds__(RB_THREADS) void region_batch_kernel(const RegionBa
     const int64_t plane = (int64_t)r.h * r.w, oplane = (int64_t)a.Hm * a.Wm;
     float* raw = a.raw + (int64_t)b * 6 * oplane;
     float* adm = a.adm + (int64_t)b * oplane;
+    const float* bld = a.bld;
+    float* obld = BL ? a.obld + (int64_t)b * oplane : nullptr;
     // out = rot90^k(hflip(vflip(T))), k in {0, 2}: a half turn mirrors both axes, a flip mirrors one
     const bool yrev = pc_region_yrev(a.vflip, a.rot), xrev = pc_region_xrev(a.hflip, a.rot);
     const bool value = a.bright || a.gam;
@@ -110,6 +118,11 @@ __global__ __launch_bounds__(RB_THREADS) void region_batch_kernel(const RegionBa
                 f32x4 m = f32x4{(float)id[0], (float)id[1], (float)id[2], (float)id[3]};
                 if (xrev) m = rb_rev(m);
                 pc_st4(adm + o, m);
+                if constexpr (BL) {
+                    f32x4 v = rg_ld4(bld + src + xl);
+                    if (xrev) v = rb_rev(v);
+                    pc_st4(obld + o, v);
+                }
                 continue;
             }
             if (y >= hb || xl >= wb) {
@@ -119,6 +132,7 @@ __global__ __launch_bounds__(RB_THREADS) void region_batch_kernel(const RegionBa
 #pragma unroll
                 for (int c = 0; c < 2; ++c) pc_st4(raw + (4 + c) * oplane + o, f32x4{0.f, 0.f, 0.f, 0.f});
                 pc_st4(adm + o, f32x4{-1.f, -1.f, -1.f, -1.f});
+                if constexpr (BL) pc_st4(obld + o, f32x4{0.f, 0.f, 0.f, 0.f});
                 continue;
             }
         }
@@ -139,15 +153,19 @@ __global__ __launch_bounds__(RB_THREADS) void region_batch_kernel(const RegionBa
                 raw[(4 + c) * oplane + o + e] = in ? v : 0.f;
             }
             adm[o + e] = in ? (float)r.boundary[s] : -1.f;
+            if constexpr (BL) {
+                const float v = bld[s];
+                obld[o + e] = in ? v : 0.f;
+            }
         }
     }
 }
 
 // odd rot: a 32 x 32 tile of the output is a 32 x 32 tile of the gathered tile read ACROSS its rows -- staged through LDS so that both the
 // reads (along raster rows) and the writes (along output rows) are coalesced
-template <typename T2>
+template <typename T2, bool BL>
 __global__ __launch_bounds__(RB_THREADS) void region_batch_transposed_kernel(const RegionBatchArgs a) {
-    __shared__ float tile[7][32][33];
+    __shared__ float tile[BL ? 8 : 7][32][33];
     const int t = threadIdx.x, b = blockIdx.y;
     rb_labels(a, b, t);
     const RegionSources& r = a.src;
@@ -157,6 +175,8 @@ __global__ __launch_bounds__(RB_THREADS) void region_batch_transposed_kernel(con
     const int64_t plane = (int64_t)r.h * r.w, oplane = (int64_t)a.Ho * a.Wo;
     float* raw = a.raw + (int64_t)b * 6 * oplane;
     float* adm = a.adm + (int64_t)b * oplane;
+    const float* bld = a.bld;
+    float* obld = BL ? a.obld + (int64_t)b * oplane : nullptr;
     const float pad2 = pc_aug_s2_value(0.f, a.bright, a.beta, a.gam, a.gamma);
     const int tiles_j = (a.Wo + 31) / 32, tiles = ((a.Ho + 31) / 32) * tiles_j;
     const int tx = t & 31, ty0 = t >> 5;                           // 32 x 8 threads, four rows each
@@ -185,6 +205,10 @@ __global__ __launch_bounds__(RB_THREADS) void region_batch_transposed_kernel(con
                     tile[4 + c][dj][di] = in ? v : 0.f;
                 }
                 tile[6][dj][di] = in ? (float)r.boundary[s] : -1.f;
+                if constexpr (BL) {
+                    const float v = bld[s];
+                    tile[7][dj][di] = in ? v : 0.f;
+                }
             }
         }
         __syncthreads();
@@ -197,6 +221,7 @@ __global__ __launch_bounds__(RB_THREADS) void region_batch_transposed_kernel(con
 #pragma unroll
                 for (int c = 0; c < 6; ++c) raw[c * oplane + o] = tile[c][dj][di];
                 adm[o] = tile[6][dj][di];
+                if constexpr (BL) obld[o] = tile[7][dj][di];
             }
         }
     }
@@ -208,24 +233,33 @@ inline void rb_launch(const RegionBatchArgs& a, int Bc, bool vec, hipStream_t st
     if (a.rot & 1) {
         int gx = ((a.Ho + 31) / 32) * ((a.Wo + 31) / 32);          // (< 2^31 / 1024 + Ho + Wo)
         if (gx > cap) gx = cap;
-        hipLaunchKernelGGL((region_batch_transposed_kernel<T2>), dim3(gx, Bc), dim3(RB_THREADS), 0, st, a);
+        if (a.bld) hipLaunchKernelGGL((region_batch_transposed_kernel<T2, true>), dim3(gx, Bc), dim3(RB_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((region_batch_transposed_kernel<T2, false>), dim3(gx, Bc), dim3(RB_THREADS), 0, st, a);
         return;
     }
     const int64_t groups = (int64_t)a.Hm * (vec ? a.Wm / 4 : a.Wm);
     int64_t gx = (groups + RB_THREADS - 1) / RB_THREADS;
     if (gx > cap) gx = cap;
-    if (vec) hipLaunchKernelGGL((region_batch_kernel<T2, 4>), dim3((int)gx, Bc), dim3(RB_THREADS), 0, st, a);
-    else hipLaunchKernelGGL((region_batch_kernel<T2, 1>), dim3((int)gx, Bc), dim3(RB_THREADS), 0, st, a);
+    const dim3 grid((int)gx, Bc);
+    if (a.bld) {
+        if (vec) hipLaunchKernelGGL((region_batch_kernel<T2, 4, true>), grid, dim3(RB_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((region_batch_kernel<T2, 1, true>), grid, dim3(RB_THREADS), 0, st, a);
+    } else {
+        if (vec) hipLaunchKernelGGL((region_batch_kernel<T2, 4, false>), grid, dim3(RB_THREADS), 0, st, a);
+        else hipLaunchKernelGGL((region_batch_kernel<T2, 1, false>), grid, dim3(RB_THREADS), 0, st, a);
+    }
 }
 
 }  // namespace
 
-extern "C" int pc_region_batch_orbit(const void* s2, int s2_u16, const float* s1, const float* s1_asc, const uint8_t* orbit,
-                                     const int32_t* boundary, int S, int C2, int C1, int h, int w, const int32_t* band_sel,
-                                     const int32_t* crops, int B, int Hm, int Wm, int vflip, int hflip, int rot, int bright, float beta,
-                                     int gam, float gamma, float* raw, float* admin_out, int Ho, int Wo, const pc_region_labels* labels,
-                                     void* stream) {
+extern "C" int pc_region_batch_layer(const void* s2, int s2_u16, const float* s1, const float* s1_asc, const uint8_t* orbit,
+                                     const int32_t* boundary, const float* layer, int S, int C2, int C1, int h, int w,
+                                     const int32_t* band_sel, const int32_t* crops, int B, int Hm, int Wm, int vflip, int hflip, int rot,
+                                     int bright, float beta, int gam, float gamma, float* raw, float* admin_out, float* layer_out, int Ho,
+                                     int Wo, const pc_region_labels* labels, void* stream) {
     RegionBatchArgs a{};
+    bool bl;
+    if (rg_layer(layer, layer_out, bl)) return PC_EINVAL;
     if (rg_sources(a.src, s2, s2_u16, s1, s1_asc, boundary, true, S, C2, C1, h, w, band_sel)) return PC_EINVAL;
     if (!crops || !raw || !admin_out || B < 1 || Hm < 1 || Wm < 1 || rot < 0 || rot > 3) return PC_EINVAL;
     if (Ho != ((rot & 1) ? Wm : Hm) || Wo != ((rot & 1) ? Hm : Wm)) return PC_EINVAL;
@@ -245,14 +279,17 @@ extern "C" int pc_region_batch_orbit(const void* s2, int s2_u16, const float* s1
         for (int b = 0; b < B; ++b)
             if (labels->items[b] < 0 || labels->items[b] >= labels->n) return PC_EINVAL;
     }
-    const bool vec = (Wm & 3) == 0 && ((reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(admin_out)) & 15) == 0;
+    const bool vec = (Wm & 3) == 0 && ((reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(admin_out) |
+                                        reinterpret_cast<uintptr_t>(layer_out)) & 15) == 0;
     const int64_t oplane = (int64_t)Hm * Wm;
+    a.bld = layer;
     a.Hm = Hm; a.Wm = Wm; a.Ho = Ho; a.Wo = Wo;
     a.vflip = vflip != 0; a.hflip = hflip != 0; a.rot = rot; a.bright = bright != 0; a.gam = gam != 0; a.beta = beta; a.gamma = gamma;
     if (labels) { a.plan_cidx = labels->plan_cidx; a.plan_y = labels->plan_y; a.Kp = labels->Kp; a.K = labels->K; }
     for (int b0 = 0; b0 < B; b0 += PC_REGION_GATHER_MAX_B) {
         const int Bc = B - b0 < PC_REGION_GATHER_MAX_B ? B - b0 : PC_REGION_GATHER_MAX_B;
         a.raw = raw + (int64_t)b0 * 6 * oplane; a.adm = admin_out + (int64_t)b0 * oplane;
+        a.obld = bl ? layer_out + (int64_t)b0 * oplane : nullptr;
         for (int b = 0; b < Bc; ++b)
             for (int k = 0; k < 5; ++k) a.crop[b][k] = crops[5 * (int64_t)(b0 + b) + k];
         rg_orbit_mask(a.orbit, orbit ? orbit + b0 : nullptr, Bc, s1_asc);
@@ -265,6 +302,16 @@ extern "C" int pc_region_batch_orbit(const void* s2, int s2_u16, const float* s1
         PC_CHECK_LAUNCH();
     }
     return 0;
+}
+
+// the call of the same code without a layer
+extern "C" int pc_region_batch_orbit(const void* s2, int s2_u16, const float* s1, const float* s1_asc, const uint8_t* orbit,
+                                     const int32_t* boundary, int S, int C2, int C1, int h, int w, const int32_t* band_sel,
+                                     const int32_t* crops, int B, int Hm, int Wm, int vflip, int hflip, int rot, int bright, float beta,
+                                     int gam, float gamma, float* raw, float* admin_out, int Ho, int Wo, const pc_region_labels* labels,
+                                     void* stream) {
+    return pc_region_batch_layer(s2, s2_u16, s1, s1_asc, orbit, boundary, nullptr, S, C2, C1, h, w, band_sel, crops, B, Hm, Wm, vflip, hflip,
+                                 rot, bright, beta, gam, gamma, raw, admin_out, nullptr, Ho, Wo, labels, stream);
 }
 
 // the mask-zero call of the same code

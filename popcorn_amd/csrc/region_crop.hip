@@ -33,6 +33,12 @@
 // range starts at a multiple of 4 (range % 4 == 0), so a group of 4 never leaves its row.  The division is the fp32 division of
 // pc_select_normalize (train_ops.hip), the same expression on the same operands.
 // No loop's trip count depends on another lane's, wave's or workgroup's progress; both barriers sit in code the whole workgroup takes.
+//
+// pc_region_window_layer / pc_region_item_layer: the same launch with a building layer, a resident fp32 (h, w) raster without a season
+// axis, copied over the crop to layer_out (hc, wc) bit for bit (no normalisation, no table: a NaN keeps its payload).  It is one more
+// blockIdx.y plane after the channels and the admin plane, a plain copy like the admin plane.  Here the layer is a POINTER TEST, not a
+// template parameter: a launch without one simply has no such plane in its grid, so the code every other workgroup runs is what it was.
+// pc_region_window / pc_region_item are the calls without a layer.
 #include "common.h"
 #include "region_args.h"
 #include "region_load.h"
@@ -56,6 +62,7 @@ struct RegionCropArgs {
     const int32_t* idx; const float* val;   // the crop's slice of the patch table (already offset by start)
     int count;
     float* out; float* admin;
+    const float* layer; float* layer_out;   // the building layer at the crop's origin and its output (a launch with the layer plane)
 };
 
 __device__ __forceinline__ float rc_norm(float v, float mean, float stdv) { return (v - mean) / stdv; }
@@ -150,6 +157,24 @@ __device__ __forceinline__ void rc_admin(const RegionCropArgs& a, int o0, int n)
     }
 }
 
+// the layer plane: the building layer over the same range, bit for bit
+template <int V>
+__device__ __forceinline__ void rc_layer(const RegionCropArgs& a, int o0, int n) {
+    const int t = threadIdx.x;
+    const float* src = pc_pin_ptr(a.layer);
+    int w = a.w;
+    pc_fastdiv div = a.div;
+    pc_pin(w); pc_pin(div);
+    const int groups = n / V, g0 = o0 / V;
+    float* out = pc_pin_ptr(a.layer_out + o0);
+    for (int g = t; g < groups; g += RC_THREADS) {
+        const int r = (int)pc_div((uint32_t)(g0 + g), div), j = (g0 + g - r * (int)div.d) * V;
+        const float* p = src + (int64_t)r * w + j;
+        if constexpr (V == 4) pc_st4(out + g * 4, rg_ld4(p));
+        else out[g] = *p;
+    }
+}
+
 // V = 4: wc % 4 == 0 and 16-byte aligned outputs; V = 1: anything
 template <typename T2, int V>
 __global__ __launch_bounds__(RC_THREADS) void region_crop_kernel(const RegionCropArgs a) {
@@ -162,8 +187,10 @@ __global__ __launch_bounds__(RC_THREADS) void region_crop_kernel(const RegionCro
     const int o0 = blockIdx.x * a.range;                                 // (o0 < plane: the grid)
     const int n = min(a.range, a.plane - o0);
     // blockIdx.y: the whole workgroup takes one branch
-    if (c == 6) {
-        rc_admin<V>(a, o0, n);
+    if (c >= 6) {
+        // the planes after the channels: the admin plane where the launch has one, then the layer plane (kernel arguments: uniform)
+        if (c == 6 && a.admin) rc_admin<V>(a, o0, n);
+        else rc_layer<V>(a, o0, n);
     } else if constexpr (sizeof(T2) == 4) {
         rc_channel<float, V>(a, c, o0, n, ends, tile);
     } else {
@@ -174,12 +201,14 @@ __global__ __launch_bounds__(RC_THREADS) void region_crop_kernel(const RegionCro
 
 // What both entry points share, for the crop of hc x wc at (x0, y0) of `season` that the caller found inside the raster with
 // 6 * hc * wc < 2^31: the remaining checks, the six channel pointers, the fastdiv, the vector / scalar choice and the type dispatch.
-// boundary / admin_out NULL: a launch without the admin plane.
-int rc_launch(const void* s2, int s2_u16, const float* s1, const float* s1_asc, int orbit, const int32_t* boundary, int S, int C2, int C1,
-              int h, int w, const int32_t* band_sel, int x0, int y0, int hc, int wc, int season, int range, const float* mean6,
+// boundary / admin_out NULL: a launch without the admin plane.  layer / layer_out NULL: a launch without the layer plane.
+int rc_launch(const void* s2, int s2_u16, const float* s1, const float* s1_asc, int orbit, const int32_t* boundary, const float* layer,
+              int S, int C2, int C1, int h, int w, const int32_t* band_sel, int x0, int y0, int hc, int wc, int season, int range, const float* mean6,
               const float* std6, const int32_t* idx, const float* val, int64_t cap, int64_t start, int64_t count, float* out,
-              float* admin_out, void* stream) {
+              float* admin_out, float* layer_out, void* stream) {
     RegionSources r{};
+    bool bl;
+    if (rg_layer(layer, layer_out, bl)) return PC_EINVAL;
     if (rg_sources(r, s2, s2_u16, s1, s1_asc, boundary, admin_out != nullptr, S, C2, C1, h, w, band_sel)) return PC_EINVAL;
     if (!mean6 || !std6 || !out || season < 0 || season >= S) return PC_EINVAL;
     if (orbit < 0 || orbit > 1 || (orbit == 1 && !s1_asc)) return PC_EINVAL;
@@ -189,7 +218,8 @@ int rc_launch(const void* s2, int s2_u16, const float* s1, const float* s1_asc, 
     if ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(admin_out) | reinterpret_cast<uintptr_t>(idx) |
          reinterpret_cast<uintptr_t>(val)) & 3)
         return PC_EINVAL;
-    const bool vec = (wc & 3) == 0 && ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(admin_out)) & 15) == 0;
+    const bool vec = (wc & 3) == 0 && ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(admin_out) |
+                                        reinterpret_cast<uintptr_t>(layer_out)) & 15) == 0;
     const int64_t rplane = (int64_t)h * w, origin = (int64_t)x0 * w + y0;
     RegionCropArgs a{};
     for (int c = 0; c < 4; ++c) {
@@ -203,7 +233,8 @@ int rc_launch(const void* s2, int s2_u16, const float* s1, const float* s1_asc, 
     for (int c = 0; c < 6; ++c) { a.mean[c] = mean6[c]; a.stdv[c] = std6[c]; }
     a.idx = count > 0 ? idx + start : nullptr; a.val = count > 0 ? val + start : nullptr; a.count = (int)count;
     a.out = out; a.admin = admin_out;
-    const dim3 grid((unsigned)((plane + range - 1) / range), admin_out ? 7 : 6);
+    a.layer = bl ? layer + origin : nullptr; a.layer_out = layer_out;
+    const dim3 grid((unsigned)((plane + range - 1) / range), 6 + (admin_out ? 1 : 0) + (bl ? 1 : 0));
     const size_t lds = RC_HEAD + (size_t)range * sizeof(float);          // the tile: <= 32 KB
     hipStream_t st = (hipStream_t)stream;
     if (s2_u16) {
@@ -227,23 +258,42 @@ extern "C" int pc_region_window_rows(int ps) {
     return R < 1 ? 1 : R;
 }
 
+extern "C" int pc_region_window_layer(const void* s2, int s2_u16, const float* s1, const float* s1_asc, int orbit, const float* layer, int S,
+                                      int C2, int C1, int h, int w, const int32_t* band_sel, int x, int y, int season, int ps,
+                                      const float* mean6, const float* std6, const int32_t* idx, const float* val, int64_t cap,
+                                      int64_t start, int64_t count, float* out, float* layer_out, void* stream) {
+    if (ps < 1 || ps > PC_REGION_WINDOW_MAX_PS) return PC_EINVAL;
+    if (x < 0 || y < 0 || ps > h || ps > w || x > h - ps || y > w - ps) return PC_EINVAL;         // the window stays inside the raster
+    return rc_launch(s2, s2_u16, s1, s1_asc, orbit, nullptr, layer, S, C2, C1, h, w, band_sel, x, y, ps, ps, season,
+                     pc_region_window_rows(ps) * ps, mean6, std6, idx, val, cap, start, count, out, nullptr, layer_out, stream);
+}
+
+// the call of the same code without a layer
 extern "C" int pc_region_window(const void* s2, int s2_u16, const float* s1, const float* s1_asc, int orbit, int S, int C2, int C1, int h,
                                 int w, const int32_t* band_sel, int x, int y, int season, int ps, const float* mean6, const float* std6,
                                 const int32_t* idx, const float* val, int64_t cap, int64_t start, int64_t count, float* out,
                                 void* stream) {
-    if (ps < 1 || ps > PC_REGION_WINDOW_MAX_PS) return PC_EINVAL;
-    if (x < 0 || y < 0 || ps > h || ps > w || x > h - ps || y > w - ps) return PC_EINVAL;         // the window stays inside the raster
-    return rc_launch(s2, s2_u16, s1, s1_asc, orbit, nullptr, S, C2, C1, h, w, band_sel, x, y, ps, ps, season, pc_region_window_rows(ps) * ps,
-                     mean6, std6, idx, val, cap, start, count, out, nullptr, stream);
+    return pc_region_window_layer(s2, s2_u16, s1, s1_asc, orbit, nullptr, S, C2, C1, h, w, band_sel, x, y, season, ps, mean6, std6, idx, val,
+                                  cap, start, count, out, nullptr, stream);
 }
 
+extern "C" int pc_region_item_layer(const void* s2, int s2_u16, const float* s1, const float* s1_asc, int orbit, const int32_t* boundary,
+                                    const float* layer, int S, int C2, int C1, int h, int w, const int32_t* band_sel, int x0, int x1, int y0,
+                                    int y1, int season, const float* mean6, const float* std6, const int32_t* idx, const float* val,
+                                    int64_t cap, int64_t start, int64_t count, float* out, float* admin_out, float* layer_out,
+                                    void* stream) {
+    if (!boundary || !admin_out) return PC_EINVAL;
+    if (x0 < 0 || y0 < 0 || x1 <= x0 || y1 <= y0 || x1 > h || y1 > w) return PC_EINVAL;          // non-empty, inside the raster
+    if (6 * (int64_t)(x1 - x0) * (y1 - y0) >= ((int64_t)1 << 31)) return PC_EINVAL;             // idx is int32 in the item's own space
+    return rc_launch(s2, s2_u16, s1, s1_asc, orbit, boundary, layer, S, C2, C1, h, w, band_sel, x0, y0, x1 - x0, y1 - y0, season,
+                     PC_REGION_ITEM_TILE, mean6, std6, idx, val, cap, start, count, out, admin_out, layer_out, stream);
+}
+
+// the call of the same code without a layer
 extern "C" int pc_region_item(const void* s2, int s2_u16, const float* s1, const float* s1_asc, int orbit, const int32_t* boundary, int S,
                               int C2, int C1, int h, int w, const int32_t* band_sel, int x0, int x1, int y0, int y1, int season,
                               const float* mean6, const float* std6, const int32_t* idx, const float* val, int64_t cap, int64_t start,
                               int64_t count, float* out, float* admin_out, void* stream) {
-    if (!boundary || !admin_out) return PC_EINVAL;
-    if (x0 < 0 || y0 < 0 || x1 <= x0 || y1 <= y0 || x1 > h || y1 > w) return PC_EINVAL;          // non-empty, inside the raster
-    if (6 * (int64_t)(x1 - x0) * (y1 - y0) >= ((int64_t)1 << 31)) return PC_EINVAL;             // idx is int32 in the item's own space
-    return rc_launch(s2, s2_u16, s1, s1_asc, orbit, boundary, S, C2, C1, h, w, band_sel, x0, y0, x1 - x0, y1 - y0, season, PC_REGION_ITEM_TILE,
-                     mean6, std6, idx, val, cap, start, count, out, admin_out, stream);
+    return pc_region_item_layer(s2, s2_u16, s1, s1_asc, orbit, boundary, nullptr, S, C2, C1, h, w, band_sel, x0, x1, y0, y1, season, mean6,
+                                std6, idx, val, cap, start, count, out, admin_out, nullptr, stream);
 }

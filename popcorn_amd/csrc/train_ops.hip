@@ -249,15 +249,21 @@ extern "C" int pc_select_normalize(const float* raw, int Craw, const int* band6,
 // (popcorn_amd/utils/transform.py: draw_fused_params); this kernel applies them while it assembles the 6-channel raw tile the step's ingest
 // normalises -- one launch instead of ~35 elementwise / flip / rot90 / cat launches per step.  Per element the S2 arithmetic is the
 // reference's, operation by operation in fp32: x / 10000 * beta clamped to [0, 1] * 10000; max(x, 0) / 10000 to the power gamma clamped * 10000.
+// pc_augment_raw_layer is the same code with a building layer (B, 1, H, W) -> (B, 1, Ho, Wo) moved under the admin mask's map, bit for bit
+// (utils/utils.py:182-209 turns and flips it jointly with the mask; no value transform); pc_augment_raw is its call without one.  The
+// layer is the template parameter BL of both kernel bodies (region.hip's header says why): the eighth plane of the transposed form's LDS
+// image exists only with a layer.
 namespace {
 struct AugArgs {
     const float* s2; const float* s1; const float* admin;
     float* raw; float* admin_out;
+    const float* bld; float* bld_out;  // the building layer and its output (BL)
     int B, H, W, Ho, Wo;
     int vflip, hflip, rot;             // rot = number of counter-clockwise quarter turns (torch.rot90 k)
     int bright, gam;
     float beta, gamma;
 };
+template <bool BL>
 __global__ __launch_bounds__(256) void augment_raw_kernel(const AugArgs a) {
     const int64_t npx = (int64_t)a.Ho * a.Wo;
     const int64_t n = (int64_t)a.B * npx;
@@ -285,12 +291,14 @@ __global__ __launch_bounds__(256) void augment_raw_kernel(const AugArgs a) {
 #pragma unroll
         for (int c = 0; c < 2; ++c) a.raw[((int64_t)b * 6 + 4 + c) * npx + r] = a.s1[((int64_t)b * 2 + c) * hw + src];
         a.admin_out[(int64_t)b * npx + r] = a.admin[(int64_t)b * hw + src];
+        if constexpr (BL) a.bld_out[(int64_t)b * npx + r] = a.bld[(int64_t)b * hw + src];
     }
 }
 // odd rotations: a 32 x 32 tile of the output is a 32 x 32 tile of the source read ACROSS its rows -- staged through LDS so that both the
 // reads (along source rows) and the writes (along output rows) are coalesced (the direct form above touches one cache line per thread)
+template <bool BL>
 __global__ __launch_bounds__(256) void augment_raw_transposed_kernel(const AugArgs a) {
-    __shared__ float tile[7][32][33];
+    __shared__ float tile[BL ? 8 : 7][32][33];
     const int tiles_j = (a.Wo + 31) / 32, tiles_i = (a.Ho + 31) / 32;
     const int64_t hw = (int64_t)a.H * a.W, npx = (int64_t)a.Ho * a.Wo;
     const int tx = threadIdx.x & 31, ty0 = threadIdx.x >> 5;            // 32 x 8 threads, four rows each
@@ -318,6 +326,7 @@ __global__ __launch_bounds__(256) void augment_raw_transposed_kernel(const AugAr
 #pragma unroll
                 for (int c = 0; c < 2; ++c) tile[4 + c][dj][di] = a.s1[((int64_t)b * 2 + c) * hw + src];
                 tile[6][dj][di] = a.admin[(int64_t)b * hw + src];
+                if constexpr (BL) tile[7][dj][di] = a.bld[(int64_t)b * hw + src];
             }
         }
         __syncthreads();
@@ -330,17 +339,23 @@ __global__ __launch_bounds__(256) void augment_raw_transposed_kernel(const AugAr
 #pragma unroll
                 for (int c = 0; c < 6; ++c) a.raw[((int64_t)b * 6 + c) * npx + o] = tile[c][dj][di];
                 a.admin_out[(int64_t)b * npx + o] = tile[6][dj][di];
+                if constexpr (BL) a.bld_out[(int64_t)b * npx + o] = tile[7][dj][di];
             }
         }
     }
 }
 }  // namespace
 
-extern "C" int pc_augment_raw(const float* s2, const float* s1, const float* admin, float* raw, float* admin_out, int B, int H, int W,
-                              int vflip, int hflip, int rot, int bright, float beta, int gam, float gamma, void* stream) {
+extern "C" int pc_augment_raw_layer(const float* s2, const float* s1, const float* admin, const float* layer, float* raw, float* admin_out,
+                                    float* layer_out, int B, int H, int W, int vflip, int hflip, int rot, int bright, float beta, int gam,
+                                    float gamma, void* stream) {
+    // the layer and its output: both or neither, aligned for fp32 (region_args.h's rule)
+    if ((layer != nullptr) != (layer_out != nullptr)) return PC_EINVAL;
+    if ((reinterpret_cast<uintptr_t>(layer) | reinterpret_cast<uintptr_t>(layer_out)) & 3) return PC_EINVAL;
     if (!s2 || !s1 || !admin || !raw || !admin_out || B < 1 || H < 1 || W < 1 || rot < 0 || rot > 3) return PC_EINVAL;
     AugArgs a{};
     a.s2 = s2; a.s1 = s1; a.admin = admin; a.raw = raw; a.admin_out = admin_out;
+    a.bld = layer; a.bld_out = layer_out;
     a.B = B; a.H = H; a.W = W;
     a.Ho = (rot & 1) ? W : H; a.Wo = (rot & 1) ? H : W;
     a.vflip = vflip; a.hflip = hflip; a.rot = rot; a.bright = bright; a.gam = gam; a.beta = beta; a.gamma = gamma;
@@ -350,10 +365,18 @@ extern "C" int pc_augment_raw(const float* s2, const float* s1, const float* adm
     if (rot & 1) {
         int tiles = B * ((a.Ho + 31) / 32) * ((a.Wo + 31) / 32);
         if (tiles > 8192) tiles = 8192;
-        hipLaunchKernelGGL(augment_raw_transposed_kernel, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
+        if (layer) hipLaunchKernelGGL(augment_raw_transposed_kernel<true>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL(augment_raw_transposed_kernel<false>, dim3(tiles), dim3(256), 0, (hipStream_t)stream, a);
     } else {
-        hipLaunchKernelGGL(augment_raw_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+        if (layer) hipLaunchKernelGGL(augment_raw_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL(augment_raw_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, a);
     }
     PC_CHECK_LAUNCH();
     return 0;
+}
+
+// the call of the same code without a layer
+extern "C" int pc_augment_raw(const float* s2, const float* s1, const float* admin, float* raw, float* admin_out, int B, int H, int W,
+                              int vflip, int hflip, int rot, int bright, float beta, int gam, float gamma, void* stream) {
+    return pc_augment_raw_layer(s2, s1, admin, nullptr, raw, admin_out, nullptr, B, H, W, vflip, hflip, rot, bright, beta, gam, gamma, stream);
 }

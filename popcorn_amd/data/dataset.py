@@ -44,13 +44,24 @@ def gap_rows(h, fraction, g):
     return m
 
 
+def building_layer(h, w, g):
+    """A synthetic building layer as a dataset ships it (Google Open Buildings / swissTLM3D counts; data/PopulationDataset.py:606-612): fp32
+    (h, w), whole-numbered counts 0 .. 12, exactly 0.0 on about 70 % of the pixels so that the occupancy model's ``building_counts > 0``
+    mask matters.  Drawn from ``g`` alone."""
+    counts = torch.randint(1, 13, (h, w), generator=g).float()
+    built = torch.rand(h, w, generator=g) < 0.3
+    return torch.where(built, counts, torch.zeros(()))
+
+
 class SyntheticWeaksupDataset(Dataset):
-    def __init__(self, n_regions=256, min_hw=64, max_hw=144, seed=1600, fixed_hw=None, nan_clouds=0.0, ascfill=False):
+    def __init__(self, n_regions=256, min_hw=64, max_hw=144, seed=1600, fixed_hw=None, nan_clouds=0.0, ascfill=False, buildings=False):
         """nan_clouds > 0 (opt-in): real-raster NaNs -- cloud discs over about that fraction of every item's S2 (all bands), orbit-gap rows in
         its descending S1 (every third item over 5 % of the rows) and a NaN-free ascending S1; the item carries the S1 of the orbit the
         reference's rule picks (data.nanfill.select_s1_host; ``ascfill``: always the ascending one where the descending has a gap).  The
-        NaN-free data underneath is the same as with nan_clouds = 0.  The fill runs on the device (Trainer ``--nan_fill``)."""
-        self.nan_clouds, self.ascfill = float(nan_clouds), bool(ascfill)
+        NaN-free data underneath is the same as with nan_clouds = 0.  The fill runs on the device (Trainer ``--nan_fill``).
+        buildings (opt-in): every item carries ``building_counts`` (1, h, w), a ``building_layer`` from a generator of its own -- every
+        other tensor of the item keeps its bits."""
+        self.nan_clouds, self.ascfill, self.buildings = float(nan_clouds), bool(ascfill), bool(buildings)
         self.n = n_regions
         g = torch.Generator().manual_seed(seed)
         if fixed_hw is not None:
@@ -84,8 +95,11 @@ class SyntheticWeaksupDataset(Dataset):
         y = torch.rand(1, generator=g).item() * 500.0
         if self.nan_clouds > 0:
             s2, s1 = self._holes(i, s2, s1)
-        return {"S2": s2, "S1": s1, "admin_mask": admin, "y": torch.tensor(y), "census_idx": torch.tensor([cid]),
+        item = {"S2": s2, "S1": s1, "admin_mask": admin, "y": torch.tensor(y), "census_idx": torch.tensor([cid]),
                 "img_coords": (0, 0), "valid_coords": (0, 0), "season": i % 4}
+        if self.buildings:
+            item["building_counts"] = building_layer(h, w, torch.Generator().manual_seed(self.seed * 15485863 + i)).unsqueeze(0)
+        return item
 
 
     def _holes(self, i, s2, s1):
@@ -115,12 +129,16 @@ class SyntheticTestRaster:
     coarse_regions = N > 0: a second, coarser census level (the reference's training level next to the fine one it is judged on) --
     ``boundary_coarse``: rectangular blocks of fine units grouped into about N coarse ones (ids 1 .. n_coarse, 0 outside; every fine unit
     lies in exactly one), ``census_idx_coarse`` and ``census_pop_coarse``: the sums of the member fine counts.  Nothing is drawn from the
-    generator for it: every other attribute keeps its bits."""
+    generator for it: every other attribute keeps its bits.
+
+    buildings=True: ``.buildings`` (h, w), a ``building_layer`` without a season axis from a generator of its own (every other attribute
+    keeps its bits); None otherwise.  ``eval.evaluate_raster`` picks it up from the raster object."""
 
     def __init__(self, h=2304, w=2560, seasons=1, n_regions=TEST_RASTER_REGIONS, seed=1610, device="cpu", raw=False, nan_clouds=0.0, s1_gap=0.0,
-                 coarse_regions=0):
+                 coarse_regions=0, buildings=False):
         g = torch.Generator().manual_seed(seed)
         self.raw = raw
+        self.buildings = building_layer(h, w, torch.Generator().manual_seed(seed + 2)).to(device) if buildings else None
         if raw:
             self.s2 = torch.randint(0, 10000, (seasons, 4, h, w), generator=g).float()
             sd, mu = torch.tensor(stats.S1_STD).view(1, 2, 1, 1), torch.tensor(stats.S1_MEAN).view(1, 2, 1, 1)

@@ -48,9 +48,14 @@ class ResidentRegion:
     (h, w) of census-unit ids, optionally s1_asc (the ascending-orbit S1, shaped and checked like s1), and the census table (census_idx (n,) ids, census_pop (n,) counts; host).  ``table`` (host int32
     (num_ids, 5) = {xmin, xmax, ymin, ymax, count}, the reference's convention) is computed once on the device.  Raises when the boundary
     holds ids outside [0, num_ids) (num_ids defaults to the largest census id + 1) and when the tensors that still have to move do not
-    fit the device's free memory."""
+    fit the device's free memory.
+    buildings: the building layer a dataset ships (PopulationDataset.py:606-612), an (h, w) raster without a season axis, kept resident as
+    fp32, shape-checked against the boundary and counted in the free-memory check.  Every feed / plan over the region then emits
+    ``building_counts`` from the launch that produces the rest (``plan_repair`` / ``RegionRepair`` never touch it: the reference repairs
+    S2 / S1 only)."""
 
-    def __init__(self, s2, s1, boundary, census_idx, census_pop, band_sel=REFERENCE_BANDS, device=None, num_ids=None, s1_asc=None):
+    def __init__(self, s2, s1, boundary, census_idx, census_pop, band_sel=REFERENCE_BANDS, device=None, num_ids=None, s1_asc=None,
+                 buildings=None):
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if dev.type != "cuda":
             raise ValueError(f"ResidentRegion: the region lives on a HIP device, got {dev}")
@@ -58,7 +63,12 @@ class ResidentRegion:
             dev = torch.device("cuda", torch.cuda.current_device())
         if s1_asc is not None and tuple(s1_asc.shape) != tuple(s1.shape):
             raise ValueError(f"ResidentRegion: s1_asc is shaped like s1 {tuple(s1.shape)}, got {tuple(s1_asc.shape)}")
+        if buildings is not None and tuple(buildings.shape) != tuple(boundary.shape):
+            raise ValueError(f"ResidentRegion: buildings is an (h, w) raster shaped like the boundary {tuple(boundary.shape)}, got "
+                             f"{tuple(buildings.shape)}")
         need = sum(t.numel() * t.element_size() for t in (s2, s1, boundary, s1_asc) if t is not None and t.device != dev)
+        if buildings is not None and (buildings.device != dev or buildings.dtype != torch.float32):
+            need += buildings.numel() * 4                              # resident as fp32 whatever it arrives as
         if need:
             free, total = torch.cuda.mem_get_info(dev)
             if need > free:
@@ -68,6 +78,7 @@ class ResidentRegion:
         self.s1 = s1.to(dev).float().contiguous()
         self.s1_asc = None if s1_asc is None else s1_asc.to(dev).float().contiguous()
         self.boundary = boundary.to(dev).to(torch.int32).contiguous()
+        self.buildings = None if buildings is None else buildings.to(dev).float().contiguous()
         if self.s2.dtype not in (torch.float32, torch.uint16):
             raise ValueError(f"ResidentRegion: S2 as fp32 or uint16, got {self.s2.dtype}")
         self.device = dev
@@ -89,18 +100,21 @@ class ResidentRegion:
     @classmethod
     def from_synthetic(cls, data, device=None, with_asc=False):
         """From a ``SyntheticTestRaster(raw=True, ...)``: its S2 / S1 / boundary / census table, bands in the model's order.  with_asc: its
-        ascending-orbit S1 stays resident as well (a third more S1 memory; off by default)."""
+        ascending-orbit S1 stays resident as well (a third more S1 memory; off by default).  Its building layer (``buildings=True``) is
+        taken over."""
         if not getattr(data, "raw", False):
             raise ValueError("ResidentRegion.from_synthetic: a SyntheticTestRaster(raw=True)")
         return cls(data.s2, data.s1, data.boundary, data.census_idx, data.census_pop, band_sel=MODEL_ORDER_BANDS,
-                   device=data.s2.device if data.s2.is_cuda and device is None else device, s1_asc=data.s1_asc if with_asc else None)
+                   device=data.s2.device if data.s2.is_cuda and device is None else device, s1_asc=data.s1_asc if with_asc else None,
+                   buildings=getattr(data, "buildings", None))
 
     def gather(self, crops, out=None, orbit=None):
         """``ops.region_gather`` of host crops (B, 5) = {x0, x1, y0, y1, season} on this region; orbit: per crop 0 = descending S1,
-        1 = ascending (None: the plain gather)."""
+        1 = ascending (None: the plain gather).  A region with a building layer gathers it in the same launch ("building_counts")."""
+        kw = {} if self.buildings is None else {"buildings": self.buildings}
         if orbit is None:
-            return ops.region_gather(self.s2, self.s1, self.boundary, self.band_sel, crops, out=out)
-        return ops.region_gather(self.s2, self.s1, self.boundary, self.band_sel, crops, out=out, s1_asc=self.s1_asc, orbit=orbit)
+            return ops.region_gather(self.s2, self.s1, self.boundary, self.band_sel, crops, out=out, **kw)
+        return ops.region_gather(self.s2, self.s1, self.boundary, self.band_sel, crops, out=out, s1_asc=self.s1_asc, orbit=orbit, **kw)
 
 
 class RegionPlan:
@@ -540,6 +554,7 @@ class ResidentWindows:
         self._mine = set(self.mine)
         _finish_plan(self, {slot[key]: pc for key, pc in pieces.items()}, n, "ResidentWindows",
                      "evaluate fewer seasons or shard over more ranks")
+        self.window_buildings = None                                     # building_counts (1, 1, ps, ps) of the last window (a region with a layer)
         self.build_ms = (time.perf_counter() - t0) * 1e3
 
     def __call__(self, x, y, season, ps):
@@ -552,8 +567,14 @@ class ResidentWindows:
                              f"for rank {self.rank} of {self.world} and holds no patches for it")
         r = self.region
         start = self._off[k]
-        return ops.region_window(r.s2, r.s1, r.band_sel, (x, y, season), self.patchsize, self.mean6, self.std6, s1_asc=r.s1_asc,
-                                 orbit=self._orbit[k], table=(self.table_idx, self.table_val, start, self._off[k + 1] - start))
+        kw = {} if r.buildings is None else {"buildings": r.buildings}
+        got = ops.region_window(r.s2, r.s1, r.band_sel, (x, y, season), self.patchsize, self.mean6, self.std6, s1_asc=r.s1_asc,
+                                orbit=self._orbit[k], table=(self.table_idx, self.table_val, start, self._off[k + 1] - start), **kw)
+        if r.buildings is None:
+            return got
+        # the plane of the window just produced, from the same launch: ``evaluate_raster`` reads it through ``window_buildings``
+        self.window_buildings = got[1]
+        return got[0]
 
 
 class ResidentItems:
@@ -617,12 +638,16 @@ class ResidentItems:
         """Item k: one ``ops.region_item`` launch."""
         r, plan = self.region, self.plan
         start = self._off[k]
-        x, admin = ops.region_item(r.s2, r.s1, r.boundary, r.band_sel, self._crops[k], self.mean6, self.std6, s1_asc=r.s1_asc,
-                                   orbit=self._orbit[k], table=(self.table_idx, self.table_val, start, self._off[k + 1] - start))
+        kw = {} if r.buildings is None else {"buildings": r.buildings}
+        got = ops.region_item(r.s2, r.s1, r.boundary, r.band_sel, self._crops[k], self.mean6, self.std6, s1_asc=r.s1_asc,
+                              orbit=self._orbit[k], table=(self.table_idx, self.table_val, start, self._off[k + 1] - start), **kw)
+        x, admin = got[0], got[1]
+        layer = {} if r.buildings is None else {"building_counts": got[2]}     # (1, 1, hc, wc), from the same launch
         if plan.multi:
             K = plan.census_n[k]
-            return {"input": x, "admin_mask": admin, "census_idx": self._cidx[k:k + 1, :K], "y": self._y[k:k + 1, :K], "census_n": [K]}
-        return {"input": x, "admin_mask": admin, "census_idx": self._cidx[k, :1], "y": self._y[k, :1]}
+            return {"input": x, "admin_mask": admin, "census_idx": self._cidx[k:k + 1, :K], "y": self._y[k:k + 1, :K], "census_n": [K],
+                    **layer}
+        return {"input": x, "admin_mask": admin, "census_idx": self._cidx[k, :1], "y": self._y[k, :1], **layer}
 
     def __iter__(self):
         for k in range(len(self.plan)):
@@ -826,14 +851,15 @@ class ResidentBatchFeed:
             cn = [plan.census_n[i] for i in idx] if plan.multi else None
             params = self._draw(self.transform)                        # the coins, immediately before the batch goes out
             labels = (self._cidx, self._y, idx, max(cn) if plan.multi else 1)
+            kw = {} if self.region.buildings is None else {"buildings": self.region.buildings}     # "building_counts", same launch
             if self.repair is None:
                 out = ops.region_batch(self.region.s2, self.region.s1, self.region.boundary, self.region.band_sel, crops, params,
-                                       labels=labels)
+                                       labels=labels, **kw)
             else:
                 # the plan's orbit column, then the batch's patches through the same coins: one small launch behind the assembly
                 orbit = self.repair.orbit_of(idx, sea)
                 out = ops.region_batch(self.region.s2, self.region.s1, self.region.boundary, self.region.band_sel, crops, params,
-                                       labels=labels, s1_asc=self.region.s1_asc, orbit=orbit)
+                                       labels=labels, s1_asc=self.region.s1_asc, orbit=orbit, **kw)
                 tile = (max(self._hw[i][0] for i in idx), max(self._hw[i][1] for i in idx))
                 self.repair.apply(idx, sea, out["raw"][:, :4], out["raw"][:, 4:], tile, params)
                 out["orbit"] = orbit.tolist()

@@ -19,9 +19,12 @@ class SyntheticMultiUnitDataset(Dataset):
     """Crops tiled by K irregular census units (listed, each with its own count ``y``) plus unlisted neighbours: the nearest-seed
     tiling of K + ``neighbours`` jittered seed points, the neighbours' seeds near the crop's border.  Item keys as
     ``SyntheticWeaksupDataset`` except ``census_idx`` (K_i,) int64 and ``y`` (K_i,).  ragged: every third item lists one unit fewer and
-    every fifth two fewer (at least one), so that batches are ragged; the dropped units stay in ``admin_mask`` as neighbours."""
+    every fifth two fewer (at least one), so that batches are ragged; the dropped units stay in ``admin_mask`` as neighbours.
+    buildings (opt-in): every item carries ``building_counts`` (1, h, w), ``dataset.building_layer`` from a generator of its own -- every
+    other tensor of the item keeps its bits; ``collate_units`` pads it with zeros as the plain collate does."""
 
-    def __init__(self, n_regions=64, units=4, neighbours=3, min_hw=64, max_hw=144, seed=1600, fixed_hw=None, ragged=False):
+    def __init__(self, n_regions=64, units=4, neighbours=3, min_hw=64, max_hw=144, seed=1600, fixed_hw=None, ragged=False, buildings=False):
+        self.buildings = bool(buildings)
         if units < 1:
             raise ValueError("units >= 1")
         self.n, self.units, self.neighbours, self.ragged = n_regions, int(units), int(neighbours), bool(ragged)
@@ -63,8 +66,12 @@ class SyntheticMultiUnitDataset(Dataset):
         if self.ragged:
             k_i = max(1, K - (1 if i % 3 == 0 else 0) - (2 if i % 5 == 0 else 0))
         y = torch.rand(K, generator=g) * 500.0
-        return {"S2": s2, "S1": s1, "admin_mask": admin, "y": y[:k_i].clone(), "census_idx": ids[:k_i].to(torch.int64).clone(),
+        item = {"S2": s2, "S1": s1, "admin_mask": admin, "y": y[:k_i].clone(), "census_idx": ids[:k_i].to(torch.int64).clone(),
                 "img_coords": (0, 0), "valid_coords": (0, 0), "season": i % 4}
+        if self.buildings:
+            from .dataset import building_layer
+            item["building_counts"] = building_layer(h, w, torch.Generator().manual_seed(self.seed * 15485863 + i)).unsqueeze(0)
+        return item
 
 
 def collate_units(batch):

@@ -578,7 +578,7 @@ def raw_window_input(win, ascfill=False):
 
 def evaluate_raster(models, raster, patchsize=INFERENCE_PATCH_SIZE, overlap=OVERLAP, fourseasons=False,
                     reducer: FlatReducer | None = None, rank=0, band_reduce=True, gather=True, return_stitcher=False, raw=False,
-                    ascfill=False, product: ProductGrid | None = None, census: CensusTable | None = None):
+                    ascfill=False, product: ProductGrid | None = None, census: CensusTable | None = None, buildings=None):
     """Ensemble sliding-window inference over ``raster`` = callable (x, y, season, ps) -> normalised model input
     (1,6,ps,ps) on the device (the reference's Population_Dataset(mode="test") item, PopulationDataset.py:336-420), or a
     (S,6,h,w) device tensor of pre-normalised seasons.  Returns the finalised (mean map, std map, scale mean, scale std).
@@ -595,14 +595,29 @@ def evaluate_raster(models, raster, patchsize=INFERENCE_PATCH_SIZE, overlap=OVER
     ``product``: a ``ProductGrid`` of this raster and ensemble; it is given the window list, fed every window this rank computes,
     all-reduced and finalised on every rank (read ``product.mean`` / ``.std`` / ``.cells``); what is returned does not change.
     ``census``: a ``CensusTable`` of this raster and ensemble, handled exactly like ``product`` (read ``census.totals`` / ``.mean`` /
-    ``.std``, ``census.level(l)``, ``census.metrics(...)``)."""
+    ``.std``, ``census.level(l)``, ``census.metrics(...)``).
+    ``buildings``: the building layer the dataset ships for test windows as well (PopulationDataset.py:475,520-523) -- an (h, w) device
+    tensor without a season axis; None takes what the raster object provides (``raster.buildings``, e.g. a ``SyntheticTestRaster(
+    buildings=True)``).  A ``raw=True`` callable may instead add "building_counts" (1, 1, ps, ps) to its dict, and a ``ResidentWindows``
+    over a region with a layer hands over the plane of the window it just produced (``window_buildings``); both take precedence over the
+    tensor.  Every window's sample of a member built WITHOUT ``sentinelbuildings`` then carries ``building_counts`` (1, 1, ps, ps) and the
+    member never runs its extractor; members built with it ignore the layer, as the reference's model does (popcorn.py:112-114).  Stitcher,
+    product grid, census table and the rank sharding are unchanged."""
     reducer = reducer or FlatReducer()
+    source = raster
     if torch.is_tensor(raster):
         h, w = raster.shape[-2:]
         tensor = raster
         raster = lambda x, y, s, ps: tensor[s:s + 1, :, x:x + ps, y:y + ps]  # noqa: E731
     else:
         h, w = raster.shape
+        if buildings is None:
+            buildings = getattr(raster, "buildings", None)
+    if buildings is not None:
+        L.require_device(buildings)
+        if tuple(buildings.shape) != (h, w):
+            raise ValueError(f"evaluate_raster: buildings is an (h, w) = ({h}, {w}) layer without a season axis, got {tuple(buildings.shape)}")
+        buildings = buildings.float()
     require_raster_fits(h, w, patchsize, "evaluate_raster")            # before anything is allocated or launched
     dev = next(models[0].parameters()).device
     st = Stitcher(h, w, dev, world=reducer.world)
@@ -625,16 +640,29 @@ def evaluate_raster(models, raster, patchsize=INFERENCE_PATCH_SIZE, overlap=OVER
         x, y, season = (int(v) for v in idx[i])
         if i not in mine:
             continue
+        layer = None
         if raw:
-            inp, _ = raw_window_input(raster(x, y, season, patchsize), ascfill)
+            win = raster(x, y, season, patchsize)
+            inp, _ = raw_window_input(win, ascfill)
+            layer = win.get("building_counts")
         else:
             inp = raster(x, y, season, patchsize).contiguous()
+        if layer is None:
+            layer = getattr(source, "window_buildings", None)           # ResidentWindows: the plane of the window it just produced
+        if layer is None and buildings is not None:
+            layer = buildings[x:x + patchsize, y:y + patchsize]
+        if layer is not None:
+            layer = layer.reshape(1, 1, patchsize, patchsize).contiguous()
         sample = {"input": inp}
         pds, scs = [], []
         with torch.no_grad(), L.padded_rows():      # (16-byte aligned rows for the levels whose width is not a multiple of 4)
             for j, m in enumerate(models):
                 m.eval()
-                if j > 0 and m.sentinelbuildings and "building_counts" in sample:
+                if layer is not None and not m.sentinelbuildings:
+                    # a shipped layer: the member multiplies its occupancy head by it and never runs the extractor (a dict of its own,
+                    # so that no member's extractor score stands in for the layer)
+                    o = m({"input": inp, "building_counts": layer}, padding=False)
+                elif j > 0 and m.sentinelbuildings and "building_counts" in sample:
                     # identical frozen extractor in every member: reuse the score of member 0
                     keep = m.sentinelbuildings
                     m.sentinelbuildings = False

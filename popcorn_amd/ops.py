@@ -1156,7 +1156,28 @@ def _region_table(what, table, sites, device):
     return idx, val, cap, start, count
 
 
-def region_gather(s2, s1, boundary, band_sel, crops, out=None, s1_asc=None, orbit=None):
+def _region_layer(what, buildings, h, w, device):
+    """The building layer of a ``region_*`` wrapper: a contiguous fp32 (h, w) raster on the rasters' device (no season axis), or None."""
+    if buildings is None:
+        return None
+    L.require_device(buildings)
+    if (buildings.dtype != torch.float32 or tuple(buildings.shape) != (h, w) or not buildings.is_contiguous() or
+            buildings.device != device):
+        raise ValueError(f"{what}: buildings must be a contiguous fp32 ({h}, {w}) raster on the rasters' device, got {buildings.dtype} "
+                         f"{tuple(buildings.shape)}")
+    return buildings
+
+
+def _layer_out(what, t, shapes, device):
+    """An ``out=`` slot for the building layer: a contiguous fp32 device tensor of one of ``shapes``."""
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) not in shapes or not t.is_contiguous() or \
+            t.device != device:
+        raise ValueError(f"{what}: the building_counts output must be a contiguous fp32 {shapes[0]} tensor on the rasters' device, got "
+                         f"{None if not torch.is_tensor(t) else (t.dtype, tuple(t.shape))}")
+    return t
+
+
+def region_gather(s2, s1, boundary, band_sel, crops, out=None, s1_asc=None, orbit=None, buildings=None):
     """One batch of crops of resident rasters in ONE launch (csrc/region.hip, pc_region_gather): what the reference's weaksup items
     (data/PopulationDataset.py:403-458,566-568,624-649) and ``Population_Dataset_collate_fn`` (:885-958) assemble on the host.
     s2: device (S, C2, h, w) fp32 or uint16; s1: device fp32 (S, C1, h, w); boundary: device int32 (h, w); band_sel: six 0-based source
@@ -1166,19 +1187,26 @@ def region_gather(s2, s1, boundary, band_sel, crops, out=None, s1_asc=None, orbi
     and fp32 sources are copied bit for bit.  out: such a dict to write into (its (Hm, Wm) may exceed the batch maximum).  An empty crop, one
     that leaves the raster and a season >= S raise before anything is enqueued.
     s1_asc / orbit (pc_region_gather_orbit): the ascending-orbit S1, shaped like s1, and B host values in {0, 1}: crop b takes its S1 from
-    s1_asc where orbit[b] == 1.  Without them the same entry point is called with NULL for both, which IS pc_region_gather."""
+    s1_asc where orbit[b] == 1.  Without them the same entry point is called with NULL for both, which IS pc_region_gather.
+    buildings (pc_region_gather_layer): a resident fp32 (h, w) building layer; the result then carries "building_counts" (B, 1, Hm, Wm),
+    the layer over each crop bit for bit, 0.0 outside it -- from the same launch.  An ``out`` dict must then hold that key as well."""
     S, C2, C1, h, w, band, cr32, Hm, Wm = _region_inputs("region_gather", s2, s1, boundary, band_sel, crops)
     B = cr32.shape[0]
     orb = _region_orbit("region_gather", s1, s1_asc, orbit, B)
     dev = s1.device
+    buildings = _region_layer("region_gather", buildings, h, w, dev)
     if out is None:
         out = {"S2": torch.empty(B, 4, Hm, Wm, dtype=torch.float32, device=dev),
                "S1": torch.empty(B, 2, Hm, Wm, dtype=torch.float32, device=dev),
                "admin_mask": torch.empty(B, Hm, Wm, dtype=torch.float32, device=dev),
                "data_hw": torch.empty(B, 2, dtype=torch.int32, device=dev)}
+        if buildings is not None:
+            out["building_counts"] = torch.empty(B, 1, Hm, Wm, dtype=torch.float32, device=dev)
     else:
         L.require_device(out["S2"], out["S1"], out["admin_mask"], out["data_hw"])
         Ho, Wo = out["admin_mask"].shape[-2:]
+        if buildings is not None:
+            _layer_out("region_gather", out.get("building_counts"), ((B, 1, int(Ho), int(Wo)),), dev)
         if (tuple(out["S2"].shape) != (B, 4, Ho, Wo) or tuple(out["S1"].shape) != (B, 2, Ho, Wo) or
                 tuple(out["admin_mask"].shape) != (B, Ho, Wo) or tuple(out["data_hw"].shape) != (B, 2) or Ho < Hm or Wo < Wm or
                 any(out[k].dtype != torch.float32 or not out[k].is_contiguous() for k in ("S2", "S1", "admin_mask")) or
@@ -1188,14 +1216,18 @@ def region_gather(s2, s1, boundary, band_sel, crops, out=None, s1_asc=None, orbi
         Hm, Wm = int(Ho), int(Wo)
     if Hm * Wm >= 1 << 31:
         raise ValueError(f"region_gather: Hm * Wm < 2^31, got {Hm} x {Wm}")
-    tail = (S, C2, C1, h, w, (C.c_int32 * 6)(*band), cr32.ctypes.data_as(C.POINTER(C.c_int32)), B, Hm, Wm, L.ptr(out["S2"]),
-            L.ptr(out["S1"]), L.ptr(out["admin_mask"]), L.ptr(out["data_hw"]), L.stream_ptr())
-    L.check(L.lib().pc_region_gather_orbit(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orb, L.ptr(boundary),
-                                           *tail), "pc_region_gather_orbit")
+    head = (L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orb, L.ptr(boundary))
+    mid = (S, C2, C1, h, w, (C.c_int32 * 6)(*band), cr32.ctypes.data_as(C.POINTER(C.c_int32)), B, Hm, Wm, L.ptr(out["S2"]),
+           L.ptr(out["S1"]), L.ptr(out["admin_mask"]))
+    if buildings is None:
+        L.check(L.lib().pc_region_gather_orbit(*head, *mid, L.ptr(out["data_hw"]), L.stream_ptr()), "pc_region_gather_orbit")
+    else:
+        L.check(L.lib().pc_region_gather_layer(*head, L.ptr(buildings), *mid, L.ptr(out["building_counts"]), L.ptr(out["data_hw"]),
+                                               L.stream_ptr()), "pc_region_gather_layer")
     return out
 
 
-def region_batch(s2, s1, boundary, band_sel, crops, params=None, hw=None, labels=None, out=None, s1_asc=None, orbit=None):
+def region_batch(s2, s1, boundary, band_sel, crops, params=None, hw=None, labels=None, out=None, s1_asc=None, orbit=None, buildings=None):
     """The batch a fused step takes, assembled from resident rasters in ONE launch (csrc/region_batch.hip, pc_region_batch).  By definition,
     bit for bit: ``augment_raw(*region_gather(...; tile (Hm, Wm)), params)`` -- without the intermediate S2 / S1 / admin_mask.
     s2, s1, boundary, band_sel, crops: as ``region_gather``.  params: ``draw_fused_params``' dict (None = no augmentation).  hw: the gathered
@@ -1204,7 +1236,9 @@ def region_batch(s2, s1, boundary, band_sel, crops, params=None, hw=None, labels
     Returns {"raw" (B, 6, Ho, Wo), "admin_mask" (B, Ho, Wo), ["census_idx" int64 (B, K), "y" fp32 (B, K)]} with (Ho, Wo) = (Wm, Hm) for an odd
     rotation; out: such a dict to write into.  Everything ``region_gather`` refuses, a rotation outside 0 .. 3, an item outside [0, n), a K
     outside [1, Kp] and an ``out`` of another shape raise ValueError before anything is enqueued.
-    s1_asc / orbit: as ``region_gather`` takes them (pc_region_batch_orbit; NULL for both IS pc_region_batch)."""
+    s1_asc / orbit: as ``region_gather`` takes them (pc_region_batch_orbit; NULL for both IS pc_region_batch).
+    buildings (pc_region_batch_layer): a resident fp32 (h, w) building layer; the result then carries "building_counts" (B, 1, Ho, Wo) --
+    by definition and bit for bit the layer of ``augment_raw(region_gather(..., buildings=), buildings=)``, from the same launch."""
     S, C2, C1, h, w, band, cr32, Hm, Wm = _region_inputs("region_batch", s2, s1, boundary, band_sel, crops)
     B = cr32.shape[0]
     orb = _region_orbit("region_batch", s1, s1_asc, orbit, B)
@@ -1221,6 +1255,7 @@ def region_batch(s2, s1, boundary, band_sel, crops, params=None, hw=None, labels
         raise ValueError(f"region_batch: rot is a number of quarter turns in 0 .. 3, got {k}")
     Ho, Wo = (Wm, Hm) if k & 1 else (Hm, Wm)
     dev = s1.device
+    buildings = _region_layer("region_batch", buildings, h, w, dev)
     lab = None
     if labels is not None:
         plan_cidx, plan_y, items, K = labels
@@ -1242,8 +1277,12 @@ def region_batch(s2, s1, boundary, band_sel, crops, params=None, hw=None, labels
         if labels is not None:
             out["census_idx"] = torch.empty(B, K, dtype=torch.int64, device=dev)
             out["y"] = torch.empty(B, K, dtype=torch.float32, device=dev)
+        if buildings is not None:
+            out["building_counts"] = torch.empty(B, 1, Ho, Wo, dtype=torch.float32, device=dev)
     else:
         want = {"raw": ((B, 6, Ho, Wo), torch.float32), "admin_mask": ((B, Ho, Wo), torch.float32)}
+        if buildings is not None:
+            want["building_counts"] = ((B, 1, Ho, Wo), torch.float32)
         if labels is not None:
             want.update({"census_idx": ((B, K), torch.int64), "y": ((B, K), torch.float32)})
         for key, (shape, dt) in want.items():
@@ -1255,13 +1294,17 @@ def region_batch(s2, s1, boundary, band_sel, crops, params=None, hw=None, labels
         lab = L.PcRegionLabels(plan_cidx.data_ptr(), plan_y.data_ptr(), it32.ctypes.data_as(C.POINTER(C.c_int32)),
                                out["census_idx"].data_ptr(), out["y"].data_ptr(), n, Kp, K, 0)
     beta, gamma = pr.get("beta"), pr.get("gamma")
-    tail = (S, C2, C1, h, w, (C.c_int32 * 6)(*band), cr32.ctypes.data_as(C.POINTER(C.c_int32)), B, Hm, Wm,
-            int(bool(pr.get("vflip"))), int(bool(pr.get("hflip"))), k, int(beta is not None),
-            C.c_float(beta if beta is not None else 1.0), int(gamma is not None),
-            C.c_float(gamma if gamma is not None else 1.0), L.ptr(out["raw"]), L.ptr(out["admin_mask"]), Ho, Wo,
-            C.byref(lab) if lab is not None else None, L.stream_ptr())
-    L.check(L.lib().pc_region_batch_orbit(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orb, L.ptr(boundary),
-                                          *tail), "pc_region_batch_orbit")
+    head = (L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orb, L.ptr(boundary))
+    mid = (S, C2, C1, h, w, (C.c_int32 * 6)(*band), cr32.ctypes.data_as(C.POINTER(C.c_int32)), B, Hm, Wm,
+           int(bool(pr.get("vflip"))), int(bool(pr.get("hflip"))), k, int(beta is not None),
+           C.c_float(beta if beta is not None else 1.0), int(gamma is not None),
+           C.c_float(gamma if gamma is not None else 1.0), L.ptr(out["raw"]), L.ptr(out["admin_mask"]))
+    tail = (Ho, Wo, C.byref(lab) if lab is not None else None, L.stream_ptr())
+    if buildings is None:
+        L.check(L.lib().pc_region_batch_orbit(*head, *mid, *tail), "pc_region_batch_orbit")
+    else:
+        L.check(L.lib().pc_region_batch_layer(*head, L.ptr(buildings), *mid, L.ptr(out["building_counts"]), *tail),
+                "pc_region_batch_layer")
     return out
 
 
@@ -1377,7 +1420,8 @@ def region_window_rows(ps):
     return int(L.lib().pc_region_window_rows(int(ps)))
 
 
-def region_window(s2, s1, band_sel, window, ps, mean6, std6, out=None, s1_asc=None, orbit=0, table=None):
+def region_window(s2, s1, band_sel, window, ps, mean6, std6, out=None, s1_asc=None, orbit=0, table=None, buildings=None,
+                  buildings_out=None):
     """The normalised model input (1, 6, ps, ps) of ONE evaluation window of resident rasters in ONE launch (csrc/region_crop.hip,
     pc_region_window), channels [S2 R G B NIR | S1 VV VH]: out = (v - mean6[c]) / std6[c] with ``select_normalize``'s fp32 division.
     s2, s1, band_sel: as ``region_gather``; window: HOST integers (x, y, season) = row origin, column origin, season; orbit: 0 = s1,
@@ -1386,9 +1430,15 @@ def region_window(s2, s1, band_sel, window, ps, mean6, std6, out=None, s1_asc=No
     value, which replaces the raster's value BEFORE the normalisation.  Every element of out is stored exactly once; no synchronisation.
     out: a contiguous fp32 device (1, 6, ps, ps) or (6, ps, ps) tensor to write into.  A window that leaves the raster, a season >= S, a ps
     outside [1, PC_REGION_WINDOW_MAX_PS], a band outside its source, an orbit outside {0, 1} or 1 without s1_asc and a slice outside the
-    tables raise ValueError before anything is enqueued."""
+    tables raise ValueError before anything is enqueued.
+    buildings (pc_region_window_layer): a resident fp32 (h, w) building layer; the same launch then also copies its slice over the window,
+    bit for bit, and the result is the tuple (out, building_counts (1, 1, ps, ps)).  buildings_out: such a tensor (or (ps, ps)) to write
+    into."""
     what = "region_window"
     S, C2, C1, h, w, band = _region_sources(what, s2, s1, None, band_sel)
+    buildings = _region_layer(what, buildings, h, w, s1.device)
+    if buildings is None and buildings_out is not None:
+        raise ValueError(f"{what}: buildings_out without buildings")
     orbit = _region_crop_orbit(what, s1, s1_asc, orbit)
     ps = int(ps)
     if not 1 <= ps <= L.PC_REGION_WINDOW_MAX_PS:
@@ -1409,13 +1459,22 @@ def region_window(s2, s1, band_sel, window, ps, mean6, std6, out=None, s1_asc=No
                 out.device != s1.device):
             raise ValueError(f"{what}: out must be a contiguous fp32 (1, 6, {ps}, {ps}) tensor on the rasters' device, got {out.dtype} "
                              f"{tuple(out.shape)}")
-    L.check(L.lib().pc_region_window(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orbit, S, C2, C1, h, w,
-                                     (C.c_int32 * 6)(*band), x, y, season, ps, mean, std, L.ptr(idx), L.ptr(val), C.c_int64(cap),
-                                     C.c_int64(start), C.c_int64(count), L.ptr(out), L.stream_ptr()), "pc_region_window")
-    return out
+    head = (L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orbit)
+    mid = (S, C2, C1, h, w, (C.c_int32 * 6)(*band), x, y, season, ps, mean, std, L.ptr(idx), L.ptr(val), C.c_int64(cap), C.c_int64(start),
+           C.c_int64(count), L.ptr(out))
+    if buildings is None:
+        L.check(L.lib().pc_region_window(*head, *mid, L.stream_ptr()), "pc_region_window")
+        return out
+    if buildings_out is None:
+        buildings_out = torch.empty(1, 1, ps, ps, dtype=torch.float32, device=s1.device)
+    else:
+        _layer_out(what, buildings_out, ((1, 1, ps, ps), (ps, ps)), s1.device)
+    L.check(L.lib().pc_region_window_layer(*head, L.ptr(buildings), *mid, L.ptr(buildings_out), L.stream_ptr()), "pc_region_window_layer")
+    return out, buildings_out.view(1, 1, ps, ps)
 
 
-def region_item(s2, s1, boundary, band_sel, crop, mean6, std6, out=None, admin_out=None, s1_asc=None, orbit=0, table=None):
+def region_item(s2, s1, boundary, band_sel, crop, mean6, std6, out=None, admin_out=None, s1_asc=None, orbit=0, table=None, buildings=None,
+                buildings_out=None):
     """The normalised model input (1, 6, hc, wc) AND the admin mask (1, hc, wc) of ONE rectangular crop of resident rasters in ONE launch
     (csrc/region_crop.hip, pc_region_item) -- a validation item: input = (v - mean6[c]) / std6[c] with ``select_normalize``'s fp32
     division, channels [S2 R G B NIR | S1 VV VH]; admin_mask = (float)boundary over the crop.
@@ -1426,7 +1485,10 @@ def region_item(s2, s1, boundary, band_sel, crop, mean6, std6, out=None, admin_o
     no synchronisation; no cap on a side (6 * hc * wc < 2^31).  out / admin_out: contiguous fp32 device tensors (1, 6, hc, wc) or
     (6, hc, wc) / (1, hc, wc) or (hc, wc) to write into.  Returns (input, admin_mask).  An empty crop, one that leaves the raster, a season
     >= S, a band outside its source, an orbit outside {0, 1} or 1 without s1_asc and a slice outside the tables raise ValueError before
-    anything is enqueued."""
+    anything is enqueued.
+    buildings (pc_region_item_layer): a resident fp32 (h, w) building layer; the same launch then also copies its slice over the crop, bit
+    for bit, and the result is (input, admin_mask, building_counts (1, 1, hc, wc)).  buildings_out: such a tensor (or (hc, wc)) to write
+    into."""
     what = "region_item"
     cr = [int(v) for v in (crop.tolist() if torch.is_tensor(crop) or isinstance(crop, np.ndarray) else crop)]
     if len(cr) != 5:
@@ -1438,6 +1500,9 @@ def region_item(s2, s1, boundary, band_sel, crop, mean6, std6, out=None, admin_o
     mean, std = _region_norm(what, mean6, std6)
     idx, val, cap, start, count = _region_table(what, table, 6 * hc * wc, s1.device)
     dev = s1.device
+    buildings = _region_layer(what, buildings, h, w, dev)
+    if buildings is None and buildings_out is not None:
+        raise ValueError(f"{what}: buildings_out without buildings")
     if out is None:
         out = torch.empty(1, 6, hc, wc, dtype=torch.float32, device=dev)
     if admin_out is None:
@@ -1447,11 +1512,19 @@ def region_item(s2, s1, boundary, band_sel, crop, mean6, std6, out=None, admin_o
         if t.dtype != torch.float32 or tuple(t.shape) not in shapes or not t.is_contiguous() or t.device != dev:
             raise ValueError(f"{what}: {name} must be a contiguous fp32 {shapes[0]} tensor on the rasters' device, got {t.dtype} "
                              f"{tuple(t.shape)}")
-    L.check(L.lib().pc_region_item(L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orbit, L.ptr(boundary), S, C2, C1,
-                                   h, w, (C.c_int32 * 6)(*band), cr[0], cr[1], cr[2], cr[3], cr[4], mean, std, L.ptr(idx), L.ptr(val),
-                                   C.c_int64(cap), C.c_int64(start), C.c_int64(count), L.ptr(out), L.ptr(admin_out), L.stream_ptr()),
-            "pc_region_item")
-    return out if out.dim() == 4 else out.view(1, 6, hc, wc), admin_out if admin_out.dim() == 3 else admin_out.view(1, hc, wc)
+    head = (L.ptr(s2), int(s2.dtype == torch.uint16), L.ptr(s1), L.ptr(s1_asc), orbit, L.ptr(boundary))
+    mid = (S, C2, C1, h, w, (C.c_int32 * 6)(*band), cr[0], cr[1], cr[2], cr[3], cr[4], mean, std, L.ptr(idx), L.ptr(val), C.c_int64(cap),
+           C.c_int64(start), C.c_int64(count), L.ptr(out), L.ptr(admin_out))
+    res = (out if out.dim() == 4 else out.view(1, 6, hc, wc), admin_out if admin_out.dim() == 3 else admin_out.view(1, hc, wc))
+    if buildings is None:
+        L.check(L.lib().pc_region_item(*head, *mid, L.stream_ptr()), "pc_region_item")
+        return res
+    if buildings_out is None:
+        buildings_out = torch.empty(1, 1, hc, wc, dtype=torch.float32, device=dev)
+    else:
+        _layer_out(what, buildings_out, ((1, 1, hc, wc), (hc, wc)), dev)
+    L.check(L.lib().pc_region_item_layer(*head, L.ptr(buildings), *mid, L.ptr(buildings_out), L.stream_ptr()), "pc_region_item_layer")
+    return res + (buildings_out.view(1, 1, hc, wc),)
 
 
 def nan_fill_(x, hw=None, count_only=False):
@@ -1523,12 +1596,21 @@ def input_grad(problems, out, pads):
     return out
 
 
-def augment_raw(s2, s1, admin_mask, params, out=None, admin_out=None):
+def augment_raw(s2, s1, admin_mask, params, out=None, admin_out=None, buildings=None, buildings_out=None):
     """The trainer's augmentations (run_train.py:386-402) with parameters drawn on the host (utils/transform.py: draw_fused_params), applied
     while the raw 6-channel tile [S2 | S1] is assembled -- ONE launch (pc_augment_raw).  s2 (B, 4, H, W) digital numbers, s1 (B, 2, H, W),
-    admin_mask (B, H, W), fp32 device tensors; returns (raw (B, 6, Ho, Wo), admin (B, Ho, Wo)); params None = no augmentation."""
+    admin_mask (B, H, W), fp32 device tensors; returns (raw (B, 6, Ho, Wo), admin (B, Ho, Wo)); params None = no augmentation.
+    buildings (pc_augment_raw_layer): a building layer (B, 1, H, W) fp32, moved under the admin mask's map in the same launch, bit for bit;
+    the result is then (raw, admin, building_counts (B, 1, Ho, Wo)).  buildings_out: such a tensor to write into."""
     L.require_device(s2, s1, admin_mask)
     B, c2, H, W = s2.shape
+    if buildings is not None:
+        L.require_device(buildings)
+        if buildings.dtype != torch.float32 or tuple(buildings.shape) != (B, 1, H, W) or not buildings.is_contiguous():
+            raise ValueError(f"augment_raw: buildings must be a contiguous fp32 ({B}, 1, {H}, {W}) tensor, got {buildings.dtype} "
+                             f"{tuple(buildings.shape)}")
+    elif buildings_out is not None:
+        raise ValueError("augment_raw: buildings_out without buildings")
     if c2 != 4 or tuple(s1.shape) != (B, 2, H, W) or tuple(admin_mask.shape) != (B, H, W):
         raise ValueError(f"augment_raw: S2 (B, 4, H, W), S1 (B, 2, H, W), admin_mask (B, H, W); got {tuple(s2.shape)}, {tuple(s1.shape)}, "
                          f"{tuple(admin_mask.shape)}")
@@ -1543,11 +1625,19 @@ def augment_raw(s2, s1, admin_mask, params, out=None, admin_out=None):
     if admin_out is None:
         admin_out = torch.empty(B, Ho, Wo, device=s2.device, dtype=torch.float32)
     beta, gamma = pr.get("beta"), pr.get("gamma")
-    L.check(L.lib().pc_augment_raw(L.ptr(s2), L.ptr(s1), L.ptr(admin_mask), L.ptr(out), L.ptr(admin_out), B, H, W,
-                                   int(bool(pr.get("vflip"))), int(bool(pr.get("hflip"))), k, int(beta is not None),
-                                   C.c_float(beta if beta is not None else 1.0), int(gamma is not None),
-                                   C.c_float(gamma if gamma is not None else 1.0), L.stream_ptr()), "pc_augment_raw")
-    return out, admin_out
+    tail = (B, H, W, int(bool(pr.get("vflip"))), int(bool(pr.get("hflip"))), k, int(beta is not None),
+            C.c_float(beta if beta is not None else 1.0), int(gamma is not None), C.c_float(gamma if gamma is not None else 1.0),
+            L.stream_ptr())
+    if buildings is None:
+        L.check(L.lib().pc_augment_raw(L.ptr(s2), L.ptr(s1), L.ptr(admin_mask), L.ptr(out), L.ptr(admin_out), *tail), "pc_augment_raw")
+        return out, admin_out
+    if buildings_out is None:
+        buildings_out = torch.empty(B, 1, Ho, Wo, device=s2.device, dtype=torch.float32)
+    else:
+        _layer_out("augment_raw", buildings_out, ((B, 1, Ho, Wo),), s2.device)
+    L.check(L.lib().pc_augment_raw_layer(L.ptr(s2), L.ptr(s1), L.ptr(admin_mask), L.ptr(buildings), L.ptr(out), L.ptr(admin_out),
+                                         L.ptr(buildings_out), *tail), "pc_augment_raw_layer")
+    return out, admin_out, buildings_out
 
 
 def loss_fwd_bwd(popcount, y, stats, lam4, scale_regularization, lam_weak, inv_B, loss_out, g_popcount, g_scale_const):

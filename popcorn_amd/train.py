@@ -640,7 +640,9 @@ class FusedTrainStep:
                                                      census_idx=s["census_idx"] if one else None, stats=self.stats,
                                                      nsel_counts=c.counts, pack_both=True,
                                                      defer_reduce=one and not self.reducer.active)
-        self.last = {"popcount": popcount, "popdensemap": popdense, "scale_map": scale_map, "mask": c.mask}
+        # (building_counts: the layer the step multiplied by -- the extractor's score or the sample's own --, as the native step's outputs name it)
+        self.last = {"popcount": popcount, "popdensemap": popdense, "scale_map": scale_map, "mask": c.mask,
+                     "building_counts": s["building_counts"]}
         if not one and "n_dev" in c.lay:
             # device-N: the sums belong to the loss launch pair of ``_backward`` (after the stats all-reduce); their outputs exist from here
             # on, so that ``last`` names the tensors a replayed graph writes
