@@ -586,8 +586,10 @@ int pc_augment_raw(const float* s2, const float* s1, const float* admin, float* 
  * activation / gradient / workspace out of ONE caller-provided arena (bump allocation, rows padded to 16 bytes so that every conv
  * launch takes the aligned staged loaders whatever the region's width), fills the descriptors and issues all launches from C++.
  * The plan (parameter pointers, BN descriptors, optimiser constants) is built once per trainer (pc_step_create); a step passes only
- * its batch.  PC_PREC_FP32, dual-stream (S1 + S2) models whose building score comes from the frozen extractor; anything else
- * returns PC_ENOTSUP and the caller keeps the per-launch path (same kernels, launched through the entry points above).
+ * its batch.  PC_PREC_FP32, dual-stream (S1 + S2) models, with or without the occupancy product (plan.occupancymodel = 0: the mask is
+ * the region only and the head multiplies by a plane of ones the step fills in the arena, popcorn.py:179-181), whose building score
+ * comes from the frozen extractor or from the layer the batch ships (pc_train_step_layer, below); anything else (bf16, single-modality
+ * models) returns PC_ENOTSUP and the caller keeps the per-launch path (same kernels, launched through the entry points above).
  * Small regions fork the frozen extractor's chain and the weight-gradient launches onto an internal side stream; WHICH stream is
  * measured at the first call on a caller's stream (HIP multiplexes streams onto a few hardware queues, and a side stream on the
  * caller's queue serialises with it): that first call launches a few microsecond-long probe kernels and synchronises once, so
@@ -638,12 +640,23 @@ typedef struct pc_step_io {
     int64_t arena_needed;                   /* bytes this geometry takes (always set; PC_ENOMEM when arena_bytes is smaller) */
     int64_t off_popcount, off_popdense, off_scale, off_mask, off_building;   /* byte offsets of the step's outputs inside the arena:
                                                popcount f32[B], popdensemap f32[B][H][W], scale map f32[B][H][W], mask u8[B][H][W],
-                                               building score f32[B][1][H][W] -- valid until the next call */
+                                               building score f32[B][1][H][W] -- valid until the next call.  With a given layer
+                                               (pc_train_step_layer) no plane is allocated and off_building = -1: the caller's tensor is
+                                               the output */
     int32_t launches, _pad2;                /* kernels enqueued by the call */
 } pc_step_io;
 void* pc_step_create(const pc_step_plan* plan);
 void pc_step_destroy(void* handle);
 int pc_train_step(void* handle, pc_step_io* io, int phases, void* stream);
+/* pc_train_step on a building layer the batch ships (a dataset's building counts; popcorn.py:113-114 with sentinelbuildings = False):
+ * layer = the batch's building_counts, fp32 (B, 1, H, W), dense, on the device, 4-byte aligned (else PC_EINVAL); read, never written,
+ * its payloads used bit for bit (NaN included).  The frozen extractor does not run at all -- no ingest of its domain, no forward, no
+ * side-stream fork, on the shared 128 x 128 domain either: pc_sparsity_mask on the layer, the trainable U-Net alone, and the head
+ * forward / backward multiply by the layer.  No building plane is allocated (io->off_building = -1, io->arena_needed shrinks).
+ * layer == NULL is pc_train_step: the same bits, arena and launches.  Phases (io->dp): the pointer passed with PC_STEP_FWD is the one
+ * PC_STEP_BWD reads, so the layer must stay unchanged until BWD has been enqueued; a BWD or UPD call passes the same pointer or NULL
+ * (anything else: PC_EINVAL).  Refusals as pc_train_step, all before anything is enqueued.  No gradient with respect to the layer. */
+int pc_train_step_layer(void* handle, pc_step_io* io, const float* layer, int phases, void* stream);
 /* debug: host nanoseconds the LAST pc_train_step call spent in its sizing pass (out[0]) and in its launching pass (out[1])
  * (tools/host_time_eager.py) */
 void pc_debug_step_host_ns(double* out);
@@ -909,6 +922,9 @@ typedef struct pc_step_units {
     int64_t off_popcount;                           /* popcount f32 [N] in the caller's (b, k) order */
 } pc_step_units;
 int pc_train_step_units(void* handle, pc_step_io* io, pc_step_units* u, int phases, void* stream);
+/* ... on a given building layer (as pc_train_step_layer): pc_unit_layout -> pc_unit_mask on the layer -> the trainable U-Net alone ->
+ * the multi-unit tail.  layer == NULL is pc_train_step_units. */
+int pc_train_step_units_layer(void* handle, pc_step_io* io, pc_step_units* u, const float* layer, int phases, void* stream);
 
 /* ---- region-resident training data (csrc/region.hip) ----
  * The reference's weaksup items are crops of a country's rasters around one census unit (data/PopulationDataset.py:403-458,624-649) and its

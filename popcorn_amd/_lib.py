@@ -237,6 +237,10 @@ def lib():
         _lib.pc_unit_popcount_loss_dev.argtypes = ([C.c_void_p] * 10 + [C.POINTER(C.c_float), C.c_float, C.c_float] + [C.c_int] * 4 +
                                                    [C.c_void_p] * 4)
         _lib.pc_train_step_units.argtypes = [C.c_void_p, C.POINTER(PcStepIo), C.POINTER(PcStepUnits), C.c_int, C.c_void_p]
+        # ... on a given building layer (a device fp32 (B, 1, H, W) pointer in front of the phases)
+        _lib.pc_train_step_layer.argtypes = [C.c_void_p, C.POINTER(PcStepIo), C.c_void_p, C.c_int, C.c_void_p]
+        _lib.pc_train_step_units_layer.argtypes = [C.c_void_p, C.POINTER(PcStepIo), C.POINTER(PcStepUnits), C.c_void_p, C.c_int,
+                                                   C.c_void_p]
         _lib.pc_region_units.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib.pc_region_gather.argtypes = ([C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
                                           [C.POINTER(C.c_int32), C.POINTER(C.c_int32)] + [C.c_int] * 3 + [C.c_void_p] * 5)

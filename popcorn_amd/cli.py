@@ -95,6 +95,10 @@ def train_parser():
     p.add_argument("--native_units", action="store_true",
                    help="--units_per_crop steps through the native step executor (pc_train_step_units: one call per step, the same "
                         "bits as the per-launch engine); experimental, off by default")
+    p.add_argument("--native_layer", action="store_true",
+                   help="--building_layer steps (and steps of a model without -occmodel) through the native step executor "
+                        "(pc_train_step_layer: one call per step, the same bits as the per-launch engine); experimental, off by default; "
+                        "no effect on steps the executor takes anyway")
     p.add_argument("--device_units", action="store_true",
                    help="--units_per_crop steps in the device-N form (counts, N and 1 / N read from device memory): allowed with --fixed_hw "
                         "(replayed HIP graph) and under data parallelism; implies nothing without --units_per_crop")
@@ -441,7 +445,8 @@ class Trainer:
                                         reducer=self.reducer,
                                         use_graph=args.fixed_hw is not None and (args.units_per_crop == 0 or args.device_units),
                                         raw_norm=(tuple(range(6)), stats.MEAN6, stats.STD6), native_units=args.native_units,
-                                        device_units=args.device_units and args.units_per_crop > 0)
+                                        device_units=args.device_units and args.units_per_crop > 0,
+                                        native_layer=getattr(args, "native_layer", False))
         if args.resume:
             self.resume(args.resume)
 

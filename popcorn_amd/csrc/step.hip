@@ -124,6 +124,9 @@ struct Step {
     bool have_fwd = false;
     int B = 0, H = 0, W = 0, pt = 0, pl = 0, Hp = 0, Wp = 0;
     Ten feats, building, Xp_u;
+    const float* layer = nullptr;               // the batch's building layer of this call (pc_train_step_layer; null: the extractor's score)
+    const float* fwd_layer = nullptr;           // ... of the forward pass in the arena
+    const float* bld = nullptr;                 // the plane the head multiplies by: the score, the layer, or ones (no occupancy product)
     uint8_t* mask = nullptr;
     const uint8_t* sel = nullptr;               // device selection flags of this step (io.sel, or unpacked from io.sel_host)
     int32_t* counts = nullptr;
@@ -166,6 +169,11 @@ inline void pad_geometry(int H, int W, int& pt, int& pb, int& pl, int& pr) {    
 struct SelBits { uint32_t w[PC_STEP_SEL_MAX / 32]; };
 __global__ __launch_bounds__(256) void sel_unpack_kernel(const SelBits b, uint8_t* out, int n) {
     for (int i = threadIdx.x; i < n; i += 256) out[i] = (b.w[i >> 5] >> (i & 31)) & 1u;
+}
+
+// the plane of ones the head multiplies by in a model without the occupancy product (train.py: torch.ones_like(building))
+__global__ __launch_bounds__(256) void ones_fill_kernel(float* p, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = 1.f;
 }
 
 struct Net {                   // one DualStreamUNet taking part in a forward pass
@@ -451,8 +459,16 @@ void forward(Step& X, pc_step_io& io) {
     io.off_scale = reinterpret_cast<char*>(X.scale_map) - A.base;
     X.mask = reinterpret_cast<uint8_t*>(A.raw((int64_t)B * H * W));
     io.off_mask = reinterpret_cast<char*>(X.mask) - A.base;
-    X.building = A.act(B, 1, H, W, /*dense=*/true);
-    io.off_building = reinterpret_cast<char*>(X.building.p) - A.base;
+    const bool given = X.layer != nullptr;
+    X.fwd_layer = X.layer;
+    if (given) {
+        // the caller's tensor IS the output: no plane, no offset
+        X.building = Ten{};
+        io.off_building = -1;
+    } else {
+        X.building = A.act(B, 1, H, W, /*dense=*/true);
+        io.off_building = reinterpret_cast<char*>(X.building.p) - A.base;
+    }
     X.counts = reinterpret_cast<int32_t*>(A.raw(16));
     X.sel = io.sel;
     uint8_t* sel_dev = io.sel_host ? reinterpret_cast<uint8_t*>(A.raw(H + W)) : nullptr;
@@ -514,7 +530,26 @@ void forward(Step& X, pc_step_io& io) {
             X.rc(pc_building_score_mask(&fs, X.ones2, P.extractor.fusion_b, &db, am, io.census_idx, X.sel, X.sel + H, P.occupancymodel, X.mask,
                                         X.counts, B, H, W, oy, ox, X.st));
     };
-    if (same_domain) {
+    if (given) {
+        // a shipped building layer (train.py: _forward, `given`): no extractor on either domain -- the mask on the layer, then the
+        // trainable U-Net alone (forward_multi([eng_u]))
+        unpack_sel();
+        unit_layout();
+        if (X.un) {
+            if (X.go())
+                X.rc(pc_unit_mask(X.layer, am, X.U.units, X.U.unit_off, X.sel, X.sel + H, P.occupancymodel, X.U.slot, X.mask, X.counts,
+                                  nullptr, B, H, W, X.U.N, X.st));
+        } else if (X.go()) {
+            X.rc(pc_sparsity_mask(X.layer, am, io.census_idx, X.sel, X.sel + H, P.occupancymodel, X.mask, X.counts, B, H, W, X.st));
+        }
+        const Ten Xp = ingest(X, io, pt, pb, pl, pr);
+        X.Xp_u = Xp;
+        const Net nu[1] = {Net{&P.unet, !X.unet_ng, false}};
+        sv = svbuf;
+        forward_nets(X, nu, 1, Xp, Hp, Wp, feats, sv);
+        X.feats = feats[0];
+        X.sv[0] = svbuf[0][0]; X.sv[1] = svbuf[0][1];
+    } else if (same_domain) {
         unpack_sel();
         unit_layout();
         const Ten Xp = ingest(X, io, pt, pb, pl, pr);
@@ -560,11 +595,20 @@ void forward(Step& X, pc_step_io& io) {
         if (two && X.go()) X.rc((int)hipStreamWaitEvent(main_st, X.ev_join, 0));      // join: the head needs the building score and the mask
     }
     // sparse head + occupancy product + census sums (popcorn.py:161-190,195-228)
-    const float* bld = X.building.p;
+    X.bld = given ? X.layer : X.building.p;
     if (!P.occupancymodel) {
-        // popcorn.py:179-181: popdensemap = relu(out), no building product
-        return X.rc(PC_ENOTSUP);
+        // popcorn.py:179-181: popdensemap = relu(out), no building product -- the head multiplies by a plane of ones
+        // (train.py: _forward, torch.ones_like(building)); the score / the layer stays the step's building output
+        const int64_t n = (int64_t)B * H * W;
+        float* ones = reinterpret_cast<float*>(A.raw(n * 4));
+        X.bld = ones;
+        if (X.go()) {
+            const int64_t blocks = (n + 255) / 256;
+            hipLaunchKernelGGL(ones_fill_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, X.st, ones, n);
+            X.rc((int)hipGetLastError());
+        }
     }
+    const float* bld = X.bld;
     const pc_src sf = S(X.feats);
     if (X.un) {
         // the union mask, no region: popdensemap is written at every pixel (0 * building outside the mask -- what the unit sums of
@@ -994,7 +1038,7 @@ void backward(Step& X, pc_step_io& io) {
         const pc_dst dg = D(G);
         const bool defer = !X.unet_ng;
         if (X.go())
-            X.rc(pc_head_bwd(&sf, X.pt, X.pl, P.head_w, X.mask, X.building.p, g_pd ? nullptr : io.admin_mask, g_pd ? nullptr : io.census_idx,
+            X.rc(pc_head_bwd(&sf, X.pt, X.pl, P.head_w, X.mask, X.bld, g_pd ? nullptr : io.admin_mask, g_pd ? nullptr : io.census_idx,
                              g_pd ? nullptr : X.g_pc, g_pd, nullptr,
                              P.g_scale_const_dev, P.head_dw, 0, &dg, X.unet_ng ? nullptr : &X.bn_nobias[0][L_UP1B],
                              X.unet_ng ? nullptr : &X.bn_nobias[1][L_UP1B], Hp, Wp, X.head_ws, B, H, W,
@@ -1213,9 +1257,12 @@ extern "C" void pc_step_destroy(void* handle) {
 }
 
 // un: the unit lists of pc_train_step_units (checked by it), or null: one unit per sample, io->census_idx / io->y
-static int train_step(void* handle, pc_step_io* io, pc_step_units* un, int phases, void* stream) {
+// layer: the batch's building layer (pc_train_step_layer), or null: the frozen extractor's score
+static int train_step(void* handle, pc_step_io* io, pc_step_units* un, const float* layer, int phases, void* stream) {
     Step* X = reinterpret_cast<Step*>(handle);
     if (!X || !io || io->B < 1 || io->H < 1 || io->W < 1 || !(phases & 7)) return PC_EINVAL;
+    // a backward / update phase continues the forward pass in the arena: its layer, named again or left out
+    if (!(phases & PC_STEP_FWD) && layer && layer != X->fwd_layer) return PC_EINVAL;
     if (g_pc_precision != PC_PREC_FP32) return PC_ENOTSUP;
     if ((phases & PC_STEP_FWD) && (!io->data || !io->admin_mask || (!un && !io->census_idx) || (!io->sel && !io->sel_host) ||
                                    (io->sel_host && io->H + io->W > PC_STEP_SEL_MAX) || (io->data_kind == PC_DATA_SPLIT && !io->data2)))
@@ -1224,6 +1271,7 @@ static int train_step(void* handle, pc_step_io* io, pc_step_units* un, int phase
     // a backward phase continues the forward pass that is in the arena: of the same kind
     if ((phases & PC_STEP_BWD) && !(phases & PC_STEP_FWD) && X->have_fwd && X->fwd_units != (un != nullptr)) return PC_EINVAL;
     X->un = un;
+    X->layer = layer;
     if (phases & PC_STEP_FWD) {
         int pt, pb, pl, pr;
         pad_geometry(io->H, io->W, pt, pb, pl, pr);
@@ -1258,10 +1306,18 @@ static int train_step(void* handle, pc_step_io* io, pc_step_units* un, int phase
     return rc;
 }
 
-extern "C" int pc_train_step(void* handle, pc_step_io* io, int phases, void* stream) { return train_step(handle, io, nullptr, phases, stream); }
+extern "C" int pc_train_step_layer(void* handle, pc_step_io* io, const float* layer, int phases, void* stream) {
+    if (!handle || !io || (reinterpret_cast<uintptr_t>(layer) & 3)) return PC_EINVAL;      // (before the handle is looked at)
+    const int rc = train_step(handle, io, nullptr, layer, phases, stream);
+    reinterpret_cast<Step*>(handle)->layer = nullptr;       // (the layer is the caller's: only fwd_layer, compared and never read, outlives the call)
+    return rc;
+}
 
-extern "C" int pc_train_step_units(void* handle, pc_step_io* io, pc_step_units* u, int phases, void* stream) {
+extern "C" int pc_train_step(void* handle, pc_step_io* io, int phases, void* stream) { return pc_train_step_layer(handle, io, nullptr, phases, stream); }
+
+extern "C" int pc_train_step_units_layer(void* handle, pc_step_io* io, pc_step_units* u, const float* layer, int phases, void* stream) {
     // every check of the lists comes before the handle is looked at: nothing here touches a device
+    if (reinterpret_cast<uintptr_t>(layer) & 3) return PC_EINVAL;
     if (!handle || !io || !u || !u->census_idx || !u->y || !u->census_n || u->K < 1 || u->N < 1 || io->B < 1) return PC_EINVAL;
     if (u->K > PC_UNIT_LAYOUT_MAX_K || io->B > PC_UNIT_LAYOUT_MAX_B || io->dp != 0) return PC_ENOTSUP;
     int64_t n = 0;
@@ -1272,7 +1328,12 @@ extern "C" int pc_train_step_units(void* handle, pc_step_io* io, pc_step_units* 
     if (n != u->N) return PC_EINVAL;
     // (the unit sums' range, pc_unit_popcount: a unit's integer sums cannot wrap below 2^27 pixels per sample)
     if ((int64_t)io->H * io->W >= ((int64_t)1 << 27) || (int64_t)io->B * io->H * io->W >= ((int64_t)1 << 31)) return PC_ENOTSUP;
-    const int rc = train_step(handle, io, u, phases, stream);
+    const int rc = train_step(handle, io, u, layer, phases, stream);
     reinterpret_cast<Step*>(handle)->un = nullptr;          // (the lists are the caller's: no pointer to them outlives the call)
+    reinterpret_cast<Step*>(handle)->layer = nullptr;
     return rc;
+}
+
+extern "C" int pc_train_step_units(void* handle, pc_step_io* io, pc_step_units* u, int phases, void* stream) {
+    return pc_train_step_units_layer(handle, io, u, nullptr, phases, stream);
 }

@@ -50,9 +50,10 @@ class _ArenaOutputs:
     """The outputs of a native step -- views into the step's arena, built on first access (``popcount``, ``popdensemap``, ``scale_map``,
     ``mask``, ``building_counts``).  Valid until the trainer's next step (the arena is reused), like the static outputs of a replayed graph."""
 
-    def __init__(self, arena, io, units=None):
+    def __init__(self, arena, io, units=None, layer=None):
         B, H, W = io.B, io.H, io.W
         self._arena = arena
+        self._layer = layer             # a step on a given building layer: the sample's own tensor is the output (io.off_building = -1)
         self._spec = {"popcount": (io.off_popcount, torch.float32, (B,)), "popdensemap": (io.off_popdense, torch.float32, (B, H, W)),
                       "scale_map": (io.off_scale, torch.float32, (B, H, W)), "mask": (io.off_mask, torch.uint8, (B, H, W)),
                       "building_counts": (io.off_building, torch.float32, (B, 1, H, W))}
@@ -64,6 +65,8 @@ class _ArenaOutputs:
         v = self._views.get(k)
         if v is None:
             off, dt, shape = self._spec[k]
+            if off < 0:
+                return self._layer
             n = 1
             for d in shape:
                 n *= d
@@ -162,7 +165,7 @@ class FusedTrainStep:
     def __init__(self, model, lr=1e-4, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, gradient_clip=0.01,
                  loss=("log_l1_loss",), lam=(1.0,), scale_regularization=0.01, lam_weak=100.0,
                  reducer: FlatReducer | None = None, use_graph=False, raw_norm=None, graph_cache_max=None, native_units=False,
-                 device_units=False):
+                 device_units=False, native_layer=False):
         """raw_norm = (band6, mean6, std6): how a RAW tile (sample key "raw" instead of "input": (B, Craw, H, W) reflectances /
         backscatter) becomes the model input -- band selection (data/PopulationDataset.py:566-568) + apply_normalize
         (utils/utils.py:105-127); default: the reference's dataset statistics (popcorn_amd.data.stats).  With a raw sample the
@@ -173,7 +176,10 @@ class FusedTrainStep:
         native_units: multi-unit samples (2-D census_idx) go through the native executor (pc_train_step_units) where it takes them --
         opt-in, experimental; off: the per-launch engine, as before.  The two compute the same bits.
         device_units: multi-unit samples take the device-N step (``step``): eager, captured (``use_graph=True``) and with an active
-        data-parallel reducer; the native executor is not asked.  Off: as before, refusals included.  One-unit samples are unaffected."""
+        data-parallel reducer; the native executor is not asked.  Off: as before, refusals included.  One-unit samples are unaffected.
+        native_layer: eager steps on a given building layer (``sentinelbuildings=False`` models fed ``building_counts``) and of models without
+        the occupancy product go through the native executor too (pc_train_step_layer / pc_train_step_units_layer) -- opt-in; off: the
+        per-launch engine, as before.  The two compute the same bits.  Multi-unit samples on a layer need ``native_units`` as well."""
         from .data import stats as _stats
         self.raw_norm = raw_norm or (_stats.BAND6, _stats.MEAN6, _stats.STD6)
         self.model = model
@@ -247,6 +253,7 @@ class FusedTrainStep:
         self.native_units = bool(native_units)
         self.native_unit_steps = 0      # multi-unit steps that went through pc_train_step_units (native_steps counts one-unit steps only)
         self.device_units = bool(device_units)
+        self.native_layer = bool(native_layer)
         self.device_unit_steps = 0      # multi-unit steps that took the device-N form (eager or replayed)
         self.captures = 0               # graph captures so far (tests / tools read it)
         self._cn_ring, self._cn_next = [], 0            # pinned host slots for census_n (as the selection's ring)
@@ -366,16 +373,17 @@ class FusedTrainStep:
     # ---- native executor (one C-ABI call per eager step) ------------------------------------------------------------
     def _native_ok(self, sample):
         """Which steps pc_train_step covers (include/popcorn_hip.h): fp32, dual-stream models whose building score comes from the frozen
-        extractor, with the occupancy product.  Everything else keeps the per-launch engine (same kernels)."""
+        extractor, with the occupancy product -- and, with ``native_layer``, a given building layer and models without the product.
+        Everything else keeps the per-launch engine (same kernels)."""
         m = self.model
-        if not NATIVE_STEP or m.precision != "fp32" or not (m.S1 and m.S2) or not m.occupancymodel:
+        if not NATIVE_STEP or m.precision != "fp32" or not (m.S1 and m.S2) or not (m.occupancymodel or self.native_layer):
             return False
         if _is_multi_unit(sample) and (self.device_units or not self.native_units):
             return False               # opt-in (pc_train_step_units); pc_train_step supervises one unit per sample.  device_units: not asked
         if not (E.PADDED_INPUT and E.COMPOSED_UP and E.FUSED_LEVEL2 and E.FUSED_CONV_BWD and DEFER_HEAD_REDUCE):
             return False               # an A/B switch of the per-launch engine is off its default: that engine is what is being asked for
-        if (not m.sentinelbuildings) and sample.get("building_counts") is not None:
-            return False
+        if (not m.sentinelbuildings) and sample.get("building_counts") is not None and not self.native_layer:
+            return False               # opt-in (pc_train_step_layer)
         return True
 
     def _native_handle(self):
@@ -476,6 +484,13 @@ class FusedTrainStep:
             io.data_kind, io.data = L.PC_DATA_INPUT, s["input"].data_ptr()
         want("admin_mask", torch.float32, (B, H, W))
         io.admin_mask = s["admin_mask"].data_ptr()
+        io._layer = None
+        if (not self.model.sentinelbuildings) and s.get("building_counts") is not None:
+            # the given building layer (pc_train_step_layer reads it where it read the extractor's score)
+            if not s["building_counts"].is_cuda:
+                raise ValueError(f"building_counts: expected a tensor on {self.device}, got one on {s['building_counts'].device}")
+            want("building_counts", torch.float32, (B, 1, H, W))
+            io._layer = s["building_counts"]            # (kept alive with the struct)
         if _is_multi_unit(s):
             # the unit lists travel in their own struct (pc_step_units); census_n is host data, default K per row
             K = s["census_idx"].shape[1]
@@ -500,16 +515,18 @@ class FusedTrainStep:
         return io if units is None else (io, units)
 
     def _native_call(self, h, io, phases, stream, units=None):
-        """pc_train_step (``units``: pc_train_step_units) with the arena grown to what the geometry takes.  With ``units`` a PC_ENOTSUP is
-        returned instead of raised: nothing was enqueued, the caller takes the per-launch engine."""
+        """pc_train_step_layer (``units``: pc_train_step_units_layer; without a layer they are pc_train_step / pc_train_step_units) with the
+        arena grown to what the geometry takes.  With ``units`` a PC_ENOTSUP is returned instead of raised: nothing was enqueued, the caller
+        takes the per-launch engine."""
         lib = L.lib()
         for _ in range(2):
             if self._arena is not None:
                 io.arena, io.arena_bytes = self._arena.data_ptr(), self._arena.numel()
+            layer = io._layer.data_ptr() if getattr(io, "_layer", None) is not None else None      # (every phase names the same layer)
             if units is None:
-                rc = lib.pc_train_step(h, C.byref(io), phases, stream)
+                rc = lib.pc_train_step_layer(h, C.byref(io), layer, phases, stream)
             else:
-                rc = lib.pc_train_step_units(h, C.byref(io), C.byref(units), phases, stream)
+                rc = lib.pc_train_step_units_layer(h, C.byref(io), C.byref(units), layer, phases, stream)
             if rc != L.PC_ENOMEM or not (phases & L.PC_STEP_FWD):
                 break               # (a backward / update phase never grows the arena: the forward's activations live in it)
             # the arena grows to what this geometry takes (+ 1/8: the next region is a little larger more often than not); the old one is
@@ -530,7 +547,7 @@ class FusedTrainStep:
             io, units = io
             if self._native_call(h, io, L.PC_STEP_FWD | L.PC_STEP_BWD | L.PC_STEP_UPD, stream, units) == L.PC_ENOTSUP:
                 return False
-            self.last = _ArenaOutputs(self._arena, io, units)
+            self.last = _ArenaOutputs(self._arena, io, units, layer=io._layer)
             self.native_unit_steps += 1
             return True
         if not self.reducer.active:
@@ -541,7 +558,7 @@ class FusedTrainStep:
             self._native_call(h, io, L.PC_STEP_BWD, stream)
             self.reducer.reduce_grads(self.flat_g)
             self._native_call(h, io, L.PC_STEP_UPD, stream)
-        self.last = _ArenaOutputs(self._arena, io)
+        self.last = _ArenaOutputs(self._arena, io, layer=io._layer)
         self.native_steps += 1
         return True
 
