@@ -11,7 +11,8 @@
  *     never synchronises, and returns 0 or a hipError_t / negative PC_E* code -- with ONE exception: pc_train_step, the eager
  *     whole-step executor, measures on its FIRST call per caller stream which of its side streams runs beside that stream (one host
  *     synchronisation, ~3 ms, cached per stream) and forks / joins through events of its own; it cannot be called while `stream` is
- *     being captured (PC_ENOTSUP) -- captured steps are built from the per-launch entry points;
+ *     being captured (PC_ENOTSUP) -- captured steps are built from the per-launch entry points; pc_forward, the whole-forward
+ *     executor on the same handle type, shares the side stream and the rule;
  *   - tensors are NCHW, described by pc_src / pc_dst (strides in ELEMENTS; element type = `dtype`: fp32, or bf16 for the
  *     activation / activation-gradient tensors of PC_PREC_BF16); parameters, weight gradients and scalars are always fp32;
  *   - pointers are borrowed for the duration of the enqueued work only.
@@ -658,8 +659,51 @@ int pc_train_step(void* handle, pc_step_io* io, int phases, void* stream);
  * (anything else: PC_EINVAL).  Refusals as pc_train_step, all before anything is enqueued.  No gradient with respect to the layer. */
 int pc_train_step_layer(void* handle, pc_step_io* io, const float* layer, int phases, void* stream);
 /* debug: host nanoseconds the LAST pc_train_step call spent in its sizing pass (out[0]) and in its launching pass (out[1])
- * (tools/host_time_eager.py) */
+ * (tools/host_time_eager.py); pc_forward records its two passes there as well */
 void pc_debug_step_host_ns(double* out);
+
+/* ---- native executor of ONE forward pass: inference and validation in one call -----------------------------------------------------
+ *   model(sample, padding=False) in eval mode under no_grad with the dense head (popcorn.py:100-193):
+ *   ingest -> building score from the frozen extractor on its 14-pixel reflect domain (on the shared domain, e.g. 100 x 100 tiles, the
+ *   score and the features come from the grouped launches of both networks) -> the trainable U-Net on the add_padding(force=False)
+ *   domain with nothing saved -> pc_head_fwd with mask = NULL: scale map, popdensemap, popcount.
+ * The launches are those of pc_train_step's forward under unet_no_grad without everything a step adds: no selection flags, no sparsity
+ * mask, no counts, no loss, no statistics (pc_head_fwd's stats = NULL).  popcount[b] sums the pixels with admin_mask == census_idx[b],
+ * or every pixel when both are NULL (popcorn.py:189-190); one without the other is PC_EINVAL.  A model without the occupancy product
+ * (plan.occupancymodel = 0) multiplies by a plane of ones the call fills in the arena, as the step does.  The building score is an
+ * output (off_building).  layer != NULL replaces the extractor exactly as in pc_train_step_layer: fp32 (B, 1, H, W), dense, 4-byte
+ * aligned (else PC_EINVAL), only read, its payloads used bit for bit; no plane is allocated and off_building = -1.
+ * handle: from pc_step_create.  A plan whose gradient, optimiser, loss and statistics pointers (dw / db / dwt / dbt, head_dw, flat_p,
+ * flat_g, adam_m, adam_v, hyper_dev, step_dev, norm_dev, stats_dev, loss_dev, g_scale_const_dev) are NULL is a valid INFERENCE plan:
+ * pc_forward reads none of them.  A plan with ANY of flat_p, flat_g, adam_m, adam_v, loss_dev, stats_dev NULL is not a training plan:
+ * pc_train_step* on such a handle returns PC_EINVAL before anything is enqueued (the others are not examined).  pc_forward works
+ * on a copy of the handle's state: the context a training step keeps between its phases is not touched, so a FWD / BWD pair of a
+ * data-parallel step survives a pc_forward call in between (on a handle of its own or on the same one, given an arena of its own).
+ * An EAGER entry point like pc_train_step: small regions fork the extractor's chain onto the handle's side stream (measured per
+ * caller's stream), so a capturing stream gets PC_ENOTSUP.  The arena is sized by a dry pass (arena_needed is always set; the
+ * extractor's activations are released before the U-Net's are carved where the chain is not forked); outputs are valid until the next
+ * call on that arena.  Refusals, all before anything is enqueued: bf16 mode, a single-modality plan, B * H * W >= 2^31: PC_ENOTSUP;
+ * the reflect rule of pc_train_step (a pad of either domain >= the side), NULL data, PC_DATA_SPLIT without data2, one of admin_mask /
+ * census_idx alone, a misaligned layer: PC_EINVAL; an arena that is too small (or not 256-byte aligned): PC_ENOMEM. */
+typedef struct pc_fwd_io {
+    int32_t B, H, W, data_kind;                 /* enum pc_step_data */
+    const void* data; const void* data2; int32_t craw, flags;      /* flags: 0, or PC_FWD_DENSE_ROW_RULE */
+    const float* admin_mask; const int64_t* census_idx;   /* both NULL: popcount = plain sum (popcorn.py:189-190); both or neither */
+    void* arena; int64_t arena_bytes;           /* as pc_step_io */
+    /* results */
+    int64_t arena_needed;
+    int64_t off_popcount, off_popdense, off_scale, off_building;   /* off_building = -1 with a layer */
+    int32_t launches, _pad2;
+} pc_fwd_io;
+/* PC_FWD_DENSE_ROW_RULE: the arena pads every row to 16 bytes, so the composed form of an Up block (pc_conv3x3_up_fwd_ok) is open at
+ * every even width; a caller whose own tensors have dense rows composes only where the width is a multiple of 4 as well.  The two forms
+ * round differently (the composed weights are products), so a binding that must return the bits of such a caller -- the per-launch
+ * engine outside padded_rows() -- sets this flag and the decision is taken on dense rows; the arena's layout stays what it is.  It
+ * matters on the extractor's (H + 28) x (W + 28) domain only: the U-Net's sides are multiples of 32. */
+#define PC_FWD_DENSE_ROW_RULE 1
+int pc_forward(void* handle, pc_fwd_io* io, const float* layer, void* stream);
+/* sizeof(pc_fwd_io) as compiled (pc_sizeof's nine indices stay as they are) */
+int pc_sizeof_fwd_io(void);
 
 /* pc_reflect_pad_select / pc_select_normalize_pad / pc_ingest_split (planar form) for rows of any width and an output whose rows are
  * out_rstride >= Wp floats apart (planes of Hp * out_rstride): kind as enum pc_step_data; mean == NULL: no normalisation. */

@@ -161,6 +161,16 @@ class PcStepUnits(C.Structure):
                 ("off_slot", C.c_int64), ("off_popcount", C.c_int64)]
 
 
+class PcFwdIo(C.Structure):
+    """pc_fwd_io: one native forward pass (pc_forward); its size is checked at load against pc_sizeof_fwd_io()."""
+    _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("data_kind", C.c_int32), ("data", C.c_void_p), ("data2", C.c_void_p),
+                ("craw", C.c_int32), ("flags", C.c_int32), ("admin_mask", C.c_void_p), ("census_idx", C.c_void_p),
+                ("arena", C.c_void_p), ("arena_bytes", C.c_int64), ("arena_needed", C.c_int64), ("off_popcount", C.c_int64),
+                ("off_popdense", C.c_int64), ("off_scale", C.c_int64), ("off_building", C.c_int64),
+                ("launches", C.c_int32), ("_pad2", C.c_int32)]
+
+
+PC_FWD_DENSE_ROW_RULE = 1
 PC_UNIT_LAYOUT_MAX_K, PC_UNIT_LAYOUT_MAX_B = 1024, 256
 PC_REGION_GATHER_MAX_B = 128          # crops per pc_region_gather launch (the crop list travels in the kernel arguments)
 PC_REGION_PATCH_CHUNK = 4096          # entries of an item's index space per workgroup of pc_region_patch_count / _write
@@ -194,6 +204,10 @@ def lib():
         ver = cand.pc_abi_version() if hasattr(cand, "pc_abi_version") else -1
         sizes = [cand.pc_sizeof(i) for i in range(9)] if hasattr(cand, "pc_sizeof") else []
         want = [C.sizeof(t) for t in (PcSrc, PcDst, PcBn, PcConvFwdDesc, PcAdamGroups, PcLevel2FwdDesc, PcStepPlan, PcStepIo, PcStepUnits)]
+        # (structs added without an ABI bump export their size through a function of their own: pc_sizeof's nine indices stay)
+        if hasattr(cand, "pc_sizeof_fwd_io"):
+            sizes.append(cand.pc_sizeof_fwd_io())
+        want.append(C.sizeof(PcFwdIo))
         if ver != PC_ABI_VERSION or sizes != want:
             raise PopcornHipError(f"{LIB_PATH} is stale: ABI version {ver} (binding: {PC_ABI_VERSION}), struct sizes {sizes} "
                                   f"(binding: {want}); rebuild it with `make -C popcorn_amd/csrc`")
@@ -204,6 +218,7 @@ def lib():
         _lib.pc_step_destroy.restype = None
         _lib.pc_step_destroy.argtypes = [C.c_void_p]
         _lib.pc_train_step.argtypes = [C.c_void_p, C.POINTER(PcStepIo), C.c_int, C.c_void_p]
+        _lib.pc_forward.argtypes = [C.c_void_p, C.POINTER(PcFwdIo), C.c_void_p, C.c_void_p]
         for name in ("pc_conv3x3_wgrad_ws_bytes", "pc_convt2x2_wgrad_ws_bytes", "pc_head_ws_bytes",
                      "pc_compact_ws_bytes", "pc_unet_ws_bytes", "pc_level2_bwd_ws_bytes", "pc_conv3x3_up_ws_bytes", "pc_conv3x3_up_bwd_ws_bytes",
                      "pc_nan_fill_ws_bytes"):

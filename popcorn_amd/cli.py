@@ -99,6 +99,11 @@ def train_parser():
                    help="--building_layer steps (and steps of a model without -occmodel) through the native step executor "
                         "(pc_train_step_layer: one call per step, the same bits as the per-launch engine); experimental, off by default; "
                         "no effect on steps the executor takes anyway")
+    p.add_argument("--native_forward", action="store_true",
+                   help="validate_weak and the target test (--resident_val / --resident_test included) run model(sample, padding=False) "
+                        "through the native forward executor (pc_forward: one call per forward, the same bits as the per-launch engine); "
+                        "off by default.  Still declined, as by the training executor: --precision bf16, -S1 alone, -S2 alone (and "
+                        "multi-unit validation items) keep the per-launch engine -- the count printed at the end is then 0")
     p.add_argument("--device_units", action="store_true",
                    help="--units_per_crop steps in the device-N form (counts, N and 1 / N read from device memory): allowed with --fixed_hw "
                         "(replayed HIP graph) and under data parallelism; implies nothing without --units_per_crop")
@@ -170,6 +175,10 @@ def eval_parser():
     p.add_argument("--overlap", type=int, default=128)
     p.add_argument("--ensemble", type=int, default=1, help="members to instantiate when no --resume checkpoints are given")
     p.add_argument("--precision", choices=["fp32", "bf16"], default="fp32", help="arithmetic mode of the kernels (DESIGN.md 7)")
+    p.add_argument("--native_forward", action="store_true",
+                   help="every member's window forward through the native forward executor (pc_forward: one call per window and member, "
+                        "the same bits as the per-launch engine); off by default.  Still declined, as by the training executor: "
+                        "--precision bf16, -S1 alone, -S2 alone keep the per-launch engine -- the count printed at the end is then 0")
     p.add_argument("--raw_input", action="store_true",
                    help="un-normalised S2 / S1 windows, NaN-filled on the device per window before normalisation (real rasters)")
     p.add_argument("--nan_clouds", type=float, default=0.0, help="--raw_input: NaN cloud discs over about this fraction of S2")
@@ -416,6 +425,7 @@ class Trainer:
         self._resident_windows = None                                    # --resident_test: planned at the first test, reused afterwards
         self.model = model_dict[args.model](**get_model_kwargs(args, args.model)).to(self.device)   # same seed: same init on every rank
         self.model.set_precision(args.precision)
+        self.model.native_forward = bool(getattr(args, "native_forward", False))     # (validate_weak / test_target; infer.py: route_ok)
         # from here on the CPU generators feed per-rank randomness (augmentation coins, the 60x60 sparsity grid of
         # get_sparsity_mask): every rank gets its own stream, rank 0 keeps the single-process one
         seed_all(args.seed + 2 + 1000 * self.rank)
@@ -647,18 +657,19 @@ class Trainer:
         from .utils.metrics import get_test_metrics
         self.model.eval()
         pred, gt = [], []
+        native = bool(self.model.native_forward)         # a native forward's outputs live in the model's arena (infer.py): keep copies
         with torch.no_grad():
             if self.args.resident_val:
                 from .data.units import flat_valid
                 for s in self.val_items:
                     out = self.model(s, padding=False)
-                    pred.append(out["popcount"])
+                    pred.append(out["popcount"].clone() if native else out["popcount"])
                     gt.append(flat_valid(s["y"], s["census_n"]) if s.get("census_n") is not None else s["y"])
             else:
                 for sample in self.val_loader:
                     s = normalize_sample(sample, self.device, None, nan_fill=self.args.nan_fill)
                     out = self.model(s, padding=False)
-                    pred.append(out["popcount"])
+                    pred.append(out["popcount"].clone() if native else out["popcount"])
                     gt.append(s["y"])
         stats = get_test_metrics(torch.cat(pred), torch.cat(gt).float(), tag="MainCensus_synthetic_fine")
         self.valweak_stats = {k + "/val": float(v) for k, v in stats.items()}
@@ -795,6 +806,8 @@ class Trainer:
                 break
         if self.rank == 0:
             print(f"Training finished in {time.time() - t0:.1f} s, {self.info['iter']} iterations; logs in {self.exp}")
+            if getattr(a, "native_forward", False):
+                print(f"native forwards: {self.model.native_forwards}", flush=True)
         return losses
 
 
@@ -821,6 +834,7 @@ def run_eval(argv=None):
         m = model_dict[args.model](**get_model_kwargs(args, args.model)).to(dev)
         if j < len(args.resume):
             m.load_state_dict(torch.load(args.resume[j], map_location="cpu", weights_only=False)["model"])   # run_eval.py:243-257
+        m.native_forward = bool(args.native_forward)
         models.append(m.eval().set_precision(args.precision))
     data = SyntheticTestRaster(args.raster_hw[0], args.raster_hw[1], seasons=4 if args.fourseasons else 1, device=dev,
                                raw=args.raw_input or args.resident_windows, nan_clouds=args.nan_clouds, s1_gap=args.s1_gap,
@@ -892,5 +906,8 @@ def run_eval(argv=None):
     torch.cuda.synchronize()
     if rank == 0:
         res["seconds"] = time.time() - t0
+        if args.native_forward:
+            res["native_forwards"] = sum(m.native_forwards for m in models)
+            print(f"native forwards: {res['native_forwards']}", flush=True)
         print(json.dumps(res))
     return res

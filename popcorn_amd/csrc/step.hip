@@ -151,6 +151,8 @@ struct Step {
     hipStream_t st = nullptr;
     int launches = 0;
     int err = 0;
+    bool infer = false;                         // pc_forward: the dense no-grad forward -- no mask, no selection, no loss context
+    bool dense_rule = false;                    // pc_forward(PC_FWD_DENSE_ROW_RULE): compose the Up blocks only where dense rows would be aligned
 
     bool go() const { return !ar.dry && err == 0; }
     void rc(int code) {
@@ -273,7 +275,9 @@ void forward_nets(Step& X, const Net* nets, int nE, const Ten& Xp, int Hp, int W
     auto fake = [&](int C, int h, int w) {          // a tensor of the arena's layout at an aligned address (for the *_ok predicates)
         Ten t;
         t.p = reinterpret_cast<float*>(A.base); t.B = B; t.C = C; t.H = h; t.W = w;
-        t.sr = (w + 3) & ~3; t.sc = (int64_t)h * t.sr; t.sb = C * t.sc;
+        // (dense_rule: the question is asked of dense rows, as the per-launch engine asks it of its tensors outside padded_rows() --
+        // composed and plain Up blocks round differently, so the executor must take the form that engine takes)
+        t.sr = X.dense_rule ? w : (w + 3) & ~3; t.sc = (int64_t)h * t.sr; t.sb = C * t.sc;
         return t;
     };
     auto can_compose = [&](int h, int w, int hz, int wz, int Cz) {
@@ -439,6 +443,9 @@ Ten ingest(Step& X, const pc_step_io& io, int top, int bottom, int left, int rig
     return out;
 }
 
+// One forward pass in the arena.  X.infer (pc_forward): model(sample, padding=False) in eval mode under no_grad with the dense head --
+// the same ingest, networks and head launches without the sparsity mask, its counts and selection flags, the loss's popcount gradient
+// and the statistics; nothing is saved (io.unet_no_grad is set by the caller) and nothing of it outlives the call.
 void forward(Step& X, pc_step_io& io) {
     const pc_step_plan& P = X.plan;
     Arena& A = X.ar;
@@ -457,8 +464,9 @@ void forward(Step& X, pc_step_io& io) {
     io.off_popdense = reinterpret_cast<char*>(X.popdense) - A.base;
     X.scale_map = reinterpret_cast<float*>(A.raw((int64_t)B * H * W * 4));
     io.off_scale = reinterpret_cast<char*>(X.scale_map) - A.base;
-    X.mask = reinterpret_cast<uint8_t*>(A.raw((int64_t)B * H * W));
-    io.off_mask = reinterpret_cast<char*>(X.mask) - A.base;
+    const bool infer = X.infer;
+    X.mask = infer ? nullptr : reinterpret_cast<uint8_t*>(A.raw((int64_t)B * H * W));
+    io.off_mask = infer ? -1 : reinterpret_cast<char*>(X.mask) - A.base;
     const bool given = X.layer != nullptr;
     X.fwd_layer = X.layer;
     if (given) {
@@ -469,9 +477,9 @@ void forward(Step& X, pc_step_io& io) {
         X.building = A.act(B, 1, H, W, /*dense=*/true);
         io.off_building = reinterpret_cast<char*>(X.building.p) - A.base;
     }
-    X.counts = reinterpret_cast<int32_t*>(A.raw(16));
+    X.counts = infer ? nullptr : reinterpret_cast<int32_t*>(A.raw(16));
     X.sel = io.sel;
-    uint8_t* sel_dev = io.sel_host ? reinterpret_cast<uint8_t*>(A.raw(H + W)) : nullptr;
+    uint8_t* sel_dev = io.sel_host && !infer ? reinterpret_cast<uint8_t*>(A.raw(H + W)) : nullptr;
     auto unpack_sel = [&]() {          // (on the stream whose chain ends in the mask kernel)
         if (!sel_dev) return;
         X.sel = sel_dev;
@@ -483,7 +491,7 @@ void forward(Step& X, pc_step_io& io) {
         hipLaunchKernelGGL(sel_unpack_kernel, dim3(1), dim3(256), 0, X.st, bits, sel_dev, H + W);
         X.rc((int)hipGetLastError());
     };
-    X.g_pc = reinterpret_cast<float*>(A.raw((int64_t)B * 4));
+    X.g_pc = infer ? nullptr : reinterpret_cast<float*>(A.raw((int64_t)B * 4));
     X.head_ws = A.raw(pc_head_ws_bytes(B, H, W));
     X.fwd_units = X.un != nullptr;
     if (X.un) {
@@ -518,6 +526,11 @@ void forward(Step& X, pc_step_io& io) {
     auto score_mask = [&](const Ten& logits, int oy, int ox) {
         const pc_src fs = S(logits);
         const pc_dst db = D(X.building);
+        if (infer) {
+            // the score alone (engine.py: building_score / score_from_features): the dense head has no mask
+            if (X.go()) X.rc(pc_outconv_sigmoid_crop(&fs, X.ones2, P.extractor.fusion_b, &db, B, H, W, oy, ox, X.st));
+            return;
+        }
         if (X.un) {
             // multi-unit: the score as a map, then the unit lookup + union mask (train.py: score_from_features + ops.unit_mask)
             if (X.go()) X.rc(pc_outconv_sigmoid_crop(&fs, X.ones2, P.extractor.fusion_b, &db, B, H, W, oy, ox, X.st));
@@ -535,7 +548,9 @@ void forward(Step& X, pc_step_io& io) {
         // trainable U-Net alone (forward_multi([eng_u]))
         unpack_sel();
         unit_layout();
-        if (X.un) {
+        if (infer) {
+            // (the layer is only read: by the head)
+        } else if (X.un) {
             if (X.go())
                 X.rc(pc_unit_mask(X.layer, am, X.U.units, X.U.unit_off, X.sel, X.sel + H, P.occupancymodel, X.U.slot, X.mask, X.counts,
                                   nullptr, B, H, W, X.U.N, X.st));
@@ -610,6 +625,14 @@ void forward(Step& X, pc_step_io& io) {
     }
     const float* bld = X.bld;
     const pc_src sf = S(X.feats);
+    if (infer) {
+        // dense head (mask == NULL), popcount over the region or the plain sum (admin_mask == NULL), no statistics
+        if (X.go())
+            X.rc(pc_head_fwd(&sf, pt, pl, P.head_w, nullptr, bld, am, io.census_idx, X.scale_map, X.popdense, X.popcount, nullptr, nullptr,
+                             X.head_ws, B, H, W, 0, X.st));
+        X.launches += 2;           // (X.rc counted one; flags = 0 is three launches: head_pack_kernel + the head kernel + head_popcount_reduce_kernel)
+        return;
+    }
     if (X.un) {
         // the union mask, no region: popdensemap is written at every pixel (0 * building outside the mask -- what the unit sums of
         // backward() rely on), {Nsel, sum scale} finished by the call, popcount[B] = the plain sums (unused)
@@ -1256,11 +1279,17 @@ extern "C" void pc_step_destroy(void* handle) {
     delete X;
 }
 
+// any of these NULL: not a training plan (popcorn_hip.h).  pc_forward reads none of the gradient / optimiser / loss / statistics pointers
+static bool inference_plan(const pc_step_plan& P) {
+    return !P.flat_p || !P.flat_g || !P.adam_m || !P.adam_v || !P.loss_dev || !P.stats_dev;
+}
+
 // un: the unit lists of pc_train_step_units (checked by it), or null: one unit per sample, io->census_idx / io->y
 // layer: the batch's building layer (pc_train_step_layer), or null: the frozen extractor's score
 static int train_step(void* handle, pc_step_io* io, pc_step_units* un, const float* layer, int phases, void* stream) {
     Step* X = reinterpret_cast<Step*>(handle);
     if (!X || !io || io->B < 1 || io->H < 1 || io->W < 1 || !(phases & 7)) return PC_EINVAL;
+    if (inference_plan(X->plan)) return PC_EINVAL;          // (a plan without gradient / optimiser / loss targets serves pc_forward only)
     // a backward / update phase continues the forward pass in the arena: its layer, named again or left out
     if (!(phases & PC_STEP_FWD) && layer && layer != X->fwd_layer) return PC_EINVAL;
     if (g_pc_precision != PC_PREC_FP32) return PC_ENOTSUP;
@@ -1336,4 +1365,66 @@ extern "C" int pc_train_step_units_layer(void* handle, pc_step_io* io, pc_step_u
 
 extern "C" int pc_train_step_units(void* handle, pc_step_io* io, pc_step_units* u, int phases, void* stream) {
     return pc_train_step_units_layer(handle, io, u, nullptr, phases, stream);
+}
+
+// ---- pc_forward: inference and validation in one call (popcorn_hip.h) ------------------------------------------------------------------
+extern "C" int pc_sizeof_fwd_io(void) { return (int)sizeof(pc_fwd_io); }
+
+extern "C" int pc_forward(void* handle, pc_fwd_io* fio, const float* layer, void* stream) {
+    Step* X = reinterpret_cast<Step*>(handle);
+    if (!X || !fio || (reinterpret_cast<uintptr_t>(layer) & 3)) return PC_EINVAL;
+    if (fio->B < 1 || fio->H < 1 || fio->W < 1) return PC_EINVAL;
+    if (g_pc_precision != PC_PREC_FP32) return PC_ENOTSUP;
+    const pc_step_plan& P = X->plan;
+    for (int s = 0; s < 2; ++s)               // single-modality plan: one stream's table is empty
+        if (P.unet.s[s].cin < 1 || !P.unet.s[s].w[0] || !P.extractor.s[s].w[0]) return PC_ENOTSUP;
+    if ((int64_t)fio->B * fio->H * fio->W >= ((int64_t)1 << 31)) return PC_ENOTSUP;
+    if (!fio->data || (fio->data_kind == PC_DATA_SPLIT && !fio->data2) || (fio->admin_mask == nullptr) != (fio->census_idx == nullptr))
+        return PC_EINVAL;
+    if (fio->data_kind != PC_DATA_INPUT && fio->data_kind != PC_DATA_RAW && fio->data_kind != PC_DATA_SPLIT) return PC_EINVAL;
+    {
+        int pt, pb, pl, pr;
+        pad_geometry(fio->H, fio->W, pt, pb, pl, pr);
+        const int p = P.extractor_pad;
+        // the reflect rule of train_step (the extractor's pad is checked with a layer too: one rule per geometry)
+        if (pt >= fio->H || pb >= fio->H || pl >= fio->W || pr >= fio->W || p >= fio->H || p >= fio->W) return PC_EINVAL;
+    }
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    {
+        // an eager entry point, as pc_train_step: the fork's events and the side-stream probe are illegal under capture
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return PC_EINVAL; }
+        if (cs != hipStreamCaptureStatusNone) return PC_ENOTSUP;
+    }
+    pc_step_io io;
+    memset(&io, 0, sizeof(io));
+    io.B = fio->B; io.H = fio->H; io.W = fio->W; io.data_kind = fio->data_kind;
+    io.data = fio->data; io.data2 = fio->data2; io.craw = fio->craw;
+    io.admin_mask = fio->admin_mask; io.census_idx = fio->census_idx;
+    io.encoder_no_grad = 1; io.unet_no_grad = 1;
+    io.arena = fio->arena; io.arena_bytes = fio->arena_bytes;
+    // the pass runs on a copy of the handle: the context a training step keeps between its phases stays as it is
+    const auto t_a = std::chrono::steady_clock::now();
+    Step work = *X;
+    work.infer = true;
+    work.dense_rule = (fio->flags & PC_FWD_DENSE_ROW_RULE) != 0;
+    work.un = nullptr;
+    work.layer = layer;
+    work.st = st;
+    int rc = run(work, io, PC_STEP_FWD, true);
+    if (rc) return rc;
+    fio->arena_needed = work.ar.peak + 256;
+    if (!fio->arena || fio->arena_bytes < fio->arena_needed || (reinterpret_cast<uintptr_t>(fio->arena) & 255)) return PC_ENOMEM;
+    if (X->side && (!X->side_picked || X->side_for != st)) {
+        pick_side_stream(*X, st);          // (which stream runs beside the caller's: the handle's, not a step's context)
+        work.side = X->side;
+    }
+    const auto t_b = std::chrono::steady_clock::now();
+    rc = run(work, io, PC_STEP_FWD, false);
+    fio->off_popcount = io.off_popcount; fio->off_popdense = io.off_popdense; fio->off_scale = io.off_scale;
+    fio->off_building = io.off_building;
+    fio->launches = work.launches;
+    g_step_host_ns[0] = std::chrono::duration<double, std::nano>(t_b - t_a).count();
+    g_step_host_ns[1] = std::chrono::duration<double, std::nano>(std::chrono::steady_clock::now() - t_b).count();
+    return rc;
 }

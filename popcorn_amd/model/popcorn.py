@@ -134,6 +134,11 @@ class POPCORN(nn.Module):
         self._engines = None
         self._w0_pad = None
         self.precision = "fp32"          # "bf16": PC_PREC_BF16 mixed precision (include/popcorn_hip.h; BASELINE config 4)
+        # opt-in (build-specific): dense no-grad forwards with padding=False as ONE C-ABI call (pc_forward; popcorn_amd/infer.py says what
+        # it covers and how long its outputs -- views into the model's arena -- stay valid); native_forwards counts the calls that took it
+        self.native_forward = False
+        self.native_forwards = 0
+        self._native_fwd = None
 
     def set_precision(self, mode):
         """Arithmetic mode of every kernel this module enqueues: "fp32" (the reference's arithmetic) or "bf16" (bf16 MFMA
@@ -284,10 +289,22 @@ class POPCORN(nn.Module):
         slot, mask, _ = ops.unit_mask(building.float(), admin, lay["units"], lay["unit_off"], rows, cols, self.occupancymodel)
         return lay, slot, (mask if sparse else None)
 
+    def _need_grad(self, inputs, unet_no_grad):
+        """Does this forward build an autograd graph?  A differentiable input makes one as well, frozen parameters or not (unet_no_grad
+        cuts it off, as in the reference)."""
+        if not torch.is_grad_enabled():
+            return False
+        _, params = self.trainable()
+        return any(p.requires_grad for p in params) or (inputs["input"].requires_grad and not unet_no_grad)
+
     # ------------------------------------------------------------------------------------------------ forward
     def forward(self, inputs, train=False, padding=True, return_features=True, encoder_no_grad=False,
                 unet_no_grad=False, sparse=False):
         X = inputs["input"]
+        if self.native_forward and not sparse and not padding:
+            from .. import infer
+            if infer.route_ok(self, inputs, self._need_grad(inputs, unet_no_grad), sparse, padding):
+                return infer.native_forward(self, inputs)
         L.require_device(X)
         if X.dim() != 4:
             raise ValueError("Input tensor must have shape (batch_size, channels, height, width)")
@@ -316,10 +333,8 @@ class POPCORN(nn.Module):
             # popcorn.py:179-181: popdensemap = relu(out), no building product
             building = torch.ones_like(building)
 
-        names, params = self.trainable()
-        # a differentiable input makes a graph as well, frozen parameters or not (unet_no_grad cuts it off, as in the reference)
-        need_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or
-                                                 (inputs["input"].requires_grad and not unet_no_grad))
+        _, params = self.trainable()
+        need_grad = self._need_grad(inputs, unet_no_grad)
         if unet_no_grad:
             self.unetmodel.eval()
         with L.precision(self.precision):
