@@ -1146,6 +1146,43 @@ int pc_region_item_layer(const void* s2, int s2_u16, const float* s1, const floa
                          int season, const float* mean6, const float* std6, const int32_t* idx, const float* val, int64_t cap, int64_t start,
                          int64_t count, float* out, float* admin_out, float* layer_out, void* stream);
 
+/* ---- the resident atlas: several resident regions, one launch per batch (csrc/region_atlas.hip; run_train.py:423-431) ----
+ * An atlas is R resident regions, 1 <= R <= PC_ATLAS_MAX_REGIONS, each with its own rasters, extent, season count, band counts and band
+ * selection; a batch whose crops come from different regions is still one launch per PC_REGION_GATHER_MAX_B crops.
+ * pc_atlas_create: regions HOST [R]; s2_u16 is one flag for the whole atlas (mixed S2 types are not part of it).  Per region everything
+ * pc_region_gather_layer validates of its sources (s1_asc and layer may be NULL); a layer on all regions or on none.  The handle keeps a
+ * host copy of the descriptors and uploads a device copy once, on the current device: the only copy and the only synchronisation.
+ * pc_atlas_gather: crop b = crops[b] = {x0, x1, y0, y1, season} of region region_of[b] (HOST uint8 [B]); orbit HOST uint8 [B] or NULL.
+ * Outputs, padding (0 / 0 / -1 / 0.0) and the rule of the 16-byte forms are pc_region_gather_layer's.  By definition, bit for bit (fp32
+ * compared as integers, NaN payloads kept):
+ *   row b of pc_atlas_gather == row 0 of pc_region_gather_layer on region region_of[b] alone with crop b, orbit[b] and the tile (Hm, Wm)
+ * pc_atlas_batch: the one-launch assembly of pc_region_batch_layer with a region per crop:
+ *   raw, admin_out, layer_out == pc_augment_raw_layer( pc_atlas_gather(...; Hm, Wm), coins )
+ * plus the label rows as pc_region_batch writes them; labels->items index ONE plan table, the regions' tables concatenated.
+ * With R = 1 both equal the single-region entry points on every output.
+ * PC_EINVAL before anything is enqueued: everything the single-region entry points refuse; region_of[b] >= R; a crop or season that is
+ * invalid in its OWN region's (h, w, S), even if another region of the atlas would hold it; orbit[b] == 1 for a region without s1_asc;
+ * layer_out when the atlas has no layer, and no layer_out when it has one. */
+#define PC_ATLAS_MAX_REGIONS 16
+typedef struct pc_atlas_region {
+    const void* s2;                                 /* DEVICE (S, C2, h, w) fp32 or uint16 */
+    const float* s1;                                /* DEVICE fp32 (S, C1, h, w) */
+    const float* s1_asc;                            /* DEVICE fp32 (S, C1, h, w) or NULL */
+    const int32_t* boundary;                        /* DEVICE int32 (h, w) */
+    const float* layer;                             /* DEVICE fp32 (h, w) or NULL: on all regions of an atlas or on none */
+    int32_t S, C2, C1, h, w;
+    int32_t band_sel[6];
+    int32_t _pad;
+} pc_atlas_region;
+int pc_sizeof_atlas_region(void);
+int pc_atlas_create(const pc_atlas_region* regions, int R, int s2_u16, void** handle);
+void pc_atlas_destroy(void* handle);
+int pc_atlas_gather(void* handle, const uint8_t* region_of, const int32_t* crops, const uint8_t* orbit, int B, int Hm, int Wm,
+                    float* s2_out, float* s1_out, float* admin_out, float* layer_out, int32_t* data_hw, void* stream);
+int pc_atlas_batch(void* handle, const uint8_t* region_of, const int32_t* crops, const uint8_t* orbit, int B, int Hm, int Wm, int vflip,
+                   int hflip, int rot, int bright, float beta, int gam, float gamma, float* raw, float* admin_out, float* layer_out, int Ho,
+                   int Wo, const pc_region_labels* labels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

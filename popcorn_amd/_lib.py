@@ -184,6 +184,16 @@ class PcRegionLabels(C.Structure):
                 ("y_out", C.c_void_p), ("n", C.c_int32), ("Kp", C.c_int32), ("K", C.c_int32), ("_pad", C.c_int32)]
 
 
+PC_ATLAS_MAX_REGIONS = 16             # regions of one atlas (popcorn_hip.h)
+
+
+class PcAtlasRegion(C.Structure):
+    """pc_atlas_region: one region of a resident atlas (pc_atlas_create); its size is checked at load against pc_sizeof_atlas_region()."""
+    _fields_ = [("s2", C.c_void_p), ("s1", C.c_void_p), ("s1_asc", C.c_void_p), ("boundary", C.c_void_p), ("layer", C.c_void_p),
+                ("S", C.c_int32), ("C2", C.c_int32), ("C1", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("band_sel", C.c_int32 * 6),
+                ("_pad", C.c_int32)]
+
+
 class PopcornHipError(RuntimeError):
     pass
 
@@ -208,6 +218,9 @@ def lib():
         if hasattr(cand, "pc_sizeof_fwd_io"):
             sizes.append(cand.pc_sizeof_fwd_io())
         want.append(C.sizeof(PcFwdIo))
+        if hasattr(cand, "pc_sizeof_atlas_region"):
+            sizes.append(cand.pc_sizeof_atlas_region())
+        want.append(C.sizeof(PcAtlasRegion))
         if ver != PC_ABI_VERSION or sizes != want:
             raise PopcornHipError(f"{LIB_PATH} is stale: ABI version {ver} (binding: {PC_ABI_VERSION}), struct sizes {sizes} "
                                   f"(binding: {want}); rebuild it with `make -C popcorn_amd/csrc`")
@@ -308,6 +321,15 @@ def lib():
                                               [C.c_int] * 5 + [C.POINTER(C.c_int32)] + [C.c_int] * 5 +
                                               [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p] + [C.c_int64] * 3 +
                                               [C.c_void_p] * 4)
+        # the resident atlas (csrc/region_atlas.hip): handle, region_of, crops, orbit, B, Hm, Wm, ... as the `_layer` forms continue
+        _lib.pc_atlas_create.argtypes = [C.POINTER(PcAtlasRegion), C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        _lib.pc_atlas_destroy.restype = None
+        _lib.pc_atlas_destroy.argtypes = [C.c_void_p]
+        _lib.pc_atlas_gather.argtypes = ([C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)] + [C.c_int] * 3 +
+                                         [C.c_void_p] * 6)
+        _lib.pc_atlas_batch.argtypes = ([C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)] + [C.c_int] * 7 +
+                                        [C.c_float, C.c_int, C.c_float] +
+                                        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(PcRegionLabels), C.c_void_p])
     return _lib
 
 

@@ -28,6 +28,13 @@ from .model import get_model_kwargs, model_dict
 from .utils.transform import default_train_transform
 
 
+class _OneOrMany(argparse.Action):
+    """nargs="+" whose single value stays the scalar it always was (--resident_units 24 -> 24, --resident_units 24 30 -> [24, 30])"""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values[0] if len(values) == 1 else list(values))
+
+
 def train_parser():
     p = argparse.ArgumentParser(description="Training Population Estimation (MI355X)")
     p.add_argument("-r", "--resume", type=str)
@@ -107,10 +114,17 @@ def train_parser():
     p.add_argument("--device_units", action="store_true",
                    help="--units_per_crop steps in the device-N form (counts, N and 1 / N read from device memory): allowed with --fixed_hw "
                         "(replayed HIP graph) and under data parallelism; implies nothing without --units_per_crop")
-    p.add_argument("--resident_region", type=int, nargs=2, default=None, metavar=("H", "W"),
+    p.add_argument("--resident_region", type=int, nargs="+", default=None, metavar=("H", "W"),
                    help="region-resident training: a synthetic H x W raw raster stays on the device and every batch of census-unit crops "
-                        "is one gather launch (data/region.py); one unit per crop, or --units_per_crop K complete units per crop")
-    p.add_argument("--resident_units", type=int, default=400, help="--resident_region: census units of the synthetic raster")
+                        "is one gather launch (data/region.py); one unit per crop, or --units_per_crop K complete units per crop.  "
+                        "2 * R integers: R rasters (region k seeded --seed + 20 + k) form a resident atlas (data/atlas.py) -- the "
+                        "reference's multi-country -tregtrain -- and a batch is still one launch whichever regions its crops come from")
+    p.add_argument("--resident_units", type=int, nargs="+", default=400, action=_OneOrMany,
+                   help="--resident_region: census units of the synthetic raster; one value, or one per region")
+    p.add_argument("--resident_ascfill", type=int, nargs="+", default=None, metavar="K",
+                   help="--resident_region: the regions (0-based) whose repair, validation and test plans take the ascending S1 wherever "
+                        "the descending one holds NaN -- the reference's need_asc; --ascfill keeps meaning all regions; needs "
+                        "--resident_repair, --resident_val or --resident_test (a plan that takes it)")
     p.add_argument("--max_weak_pix", type=int, default=10_000_000,
                    help="--resident_region: census units with at least this many pixels are dropped (the reference's max_pix)")
     p.add_argument("--max_pix_box", type=int, default=12_000_000,
@@ -327,8 +341,37 @@ def limit_regime(num_pix, limit1, limit2, limit3):
     return enc_ng, unet_ng, skip
 
 
+def resident_shapes(args):
+    """--resident_region as [(H, W)] * R, --resident_units as R values: SystemExit for an odd count or a list of another length."""
+    v = list(args.resident_region)
+    if len(v) < 2 or len(v) % 2:
+        raise SystemExit(f"--resident_region takes H W per region (2 * R integers), got {len(v)}: {v}")
+    shapes = [(int(v[2 * k]), int(v[2 * k + 1])) for k in range(len(v) // 2)]
+    u = args.resident_units
+    units = [int(x) for x in u] if isinstance(u, (list, tuple)) else [int(u)]
+    if len(units) == 1:
+        units = units * len(shapes)
+    if len(units) != len(shapes):
+        raise SystemExit(f"--resident_units takes one value or one per region ({len(shapes)}), got {len(units)}")
+    return shapes, units
+
+
 def check_repair_args(args):
     """The refusals of --resident_repair and its companions that need no device: raised before anything else is set up."""
+    if args.resident_region is not None:
+        shapes, _ = resident_shapes(args)
+        from ._lib import PC_ATLAS_MAX_REGIONS
+        if len(shapes) > PC_ATLAS_MAX_REGIONS:
+            raise SystemExit(f"--resident_region: an atlas holds at most {PC_ATLAS_MAX_REGIONS} regions, got {len(shapes)}")
+    if getattr(args, "resident_ascfill", None) is not None:
+        if args.resident_region is None:
+            raise SystemExit("--resident_ascfill names regions of a resident atlas: it needs --resident_region")
+        if not (args.resident_repair or args.resident_val or args.resident_test):
+            raise SystemExit("--resident_ascfill chooses the S1 orbit in a region's repair, validation and test plans: without "
+                             "--resident_repair, --resident_val or --resident_test no plan takes it")
+        bad = [k for k in args.resident_ascfill if not 0 <= k < len(shapes)]
+        if bad:
+            raise SystemExit(f"--resident_ascfill names regions in [0, {len(shapes)}), got {bad}")
     if args.resident_repair and args.resident_region is None:
         raise SystemExit("--resident_repair plans the NaN repair of a resident crop plan (orbit column and patch table on the device): it "
                          "needs --resident_region")
@@ -462,7 +505,9 @@ class Trainer:
 
     def _init_resident_region(self):
         """--resident_region: the training data is a synthetic raw raster kept on the device, planned into census-unit crops and fed by one
-        gather launch per batch (data/region.py) in place of loader -> collate -> pinned staging -> copy stream."""
+        gather launch per batch (data/region.py) in place of loader -> collate -> pinned staging -> copy stream.  2 * R integers: R
+        rasters as one resident atlas (data/atlas.py) -- concatenated plans, one launch per batch, validation and test per region.  Two
+        integers are the single-region run as it was: same raster, plan, feeds, launches and metric keys."""
         a = self.args
         if a.torch_optimizer:
             raise SystemExit("--resident_region feeds device batches to the fused step: the --torch_optimizer recipe keeps the host loader")
@@ -476,60 +521,84 @@ class Trainer:
                              "gather and the augmentation, which the one-launch assembly fuses; the unfused --resident_region feed takes it")
         if a.resident_pixel_budget < 0 or a.resident_max_batch < 1 or not 0.0 <= a.resident_min_fill <= 1.0:
             raise SystemExit("--resident_pixel_budget >= 0, --resident_max_batch >= 1 and --resident_min_fill in [0, 1]")
+        from .data.atlas import AtlasBatchFeed, AtlasPlan, AtlasRegionFeed, ResidentAtlas, plan_repair_atlas
         from .data.region import (ResidentBatchFeed, ResidentItems, ResidentRegion, ResidentRegionFeed, plan_multi_unit, plan_one_unit,
                                   plan_repair, split_census)
         S = a.resident_seasons
-        data = SyntheticTestRaster(a.resident_region[0], a.resident_region[1], seasons=S, n_regions=a.resident_units, seed=a.seed + 20,
-                                   device=self.device, raw=True, nan_clouds=a.nan_clouds, s1_gap=a.resident_s1_gap,
-                                   buildings=a.building_layer)
-        self.region = ResidentRegion.from_synthetic(data, with_asc=a.resident_repair or a.resident_test or a.resident_val)
-        self.region_data = data                                          # (the raster callable of evaluate_raster(raw=True) over the same data)
+        # R rasters: region 0 is the single-region run's (seed + 20), region k is seeded seed + 20 + k
+        shapes, units = resident_shapes(a)
+        R = len(shapes)
+        with_asc = a.resident_repair or a.resident_test or a.resident_val
+        self.region_datas = [SyntheticTestRaster(hw[0], hw[1], seasons=S, n_regions=units[k], seed=a.seed + 20 + k, device=self.device,
+                                                 raw=True, nan_clouds=a.nan_clouds, s1_gap=a.resident_s1_gap, buildings=a.building_layer)
+                             for k, hw in enumerate(shapes)]
+        self.regions = [ResidentRegion.from_synthetic(d, with_asc=with_asc) for d in self.region_datas]
+        self.region, self.region_data = self.regions[0], self.region_datas[0]     # (R = 1: the raster of evaluate_raster(raw=True) too)
+        self.atlas = ResidentAtlas(self.regions) if R > 1 else None
+        # the reference's need_asc: --ascfill means every region, --resident_ascfill the listed ones
+        self.region_ascfill = [a.ascfill or k in (getattr(a, "resident_ascfill", None) or ()) for k in range(R)]
         kw = dict(max_pix=a.max_weak_pix, max_pix_box=a.max_pix_box)
 
-        def plan_of(split):
+        def plan_of(split, region):
             # the reference's order: the split, then the two size filters (inside the planner)
-            n = self.region.census_idx.numel()
-            ids, pop = split_census(self.region.census_idx, self.region.census_pop, split)
+            n = region.census_idx.numel()
+            ids, pop = split_census(region.census_idx, region.census_pop, split)
             if ids.numel() < 1:
                 raise SystemExit(f"--resident_val: the {split} split of {n} census rows is empty (int({n} * 0.8) = {int(n * 0.8)} rows train)")
             if a.units_per_crop > 0:
-                return plan_multi_unit(self.region.table, ids, pop, self.region.shape, units_per_crop=a.units_per_crop, **kw)
-            return plan_one_unit(self.region.table, ids, pop, self.region.shape, **kw)
+                return plan_multi_unit(region.table, ids, pop, region.shape, units_per_crop=a.units_per_crop, **kw)
+            return plan_one_unit(region.table, ids, pop, region.shape, **kw)
 
-        self.region_plan = plan_of("train" if a.resident_val else "all")
-        self.val_items = None
+        plans = [plan_of("train" if a.resident_val else "all", r) for r in self.regions]
+        self.region_plan = plans[0] if R == 1 else AtlasPlan.concat(plans)
+        self.val_sets, self.val_items = None, None
         if a.resident_val:
-            # the held-out 20 %: season, orbit and repaired sites of every item planned once; its own generator, seeded from --seed
-            val_plan = plan_of("val")
-            if len(val_plan) < 1:
-                raise SystemExit("--resident_val: no unit of the validation split survives the size filters")
-            v = self.val_items = ResidentItems(self.region, val_plan, seasons=S, generator=torch.Generator().manual_seed(a.seed),
-                                               ascfill=a.ascfill)
-            if self.rank == 0:
-                print(f"resident validation: {len(val_plan)} items, {len(v.dropped)} dropped, {v.ascending} ascending, {v.entries} table "
-                      f"entries ({v.nbytes} bytes), built in {v.build_ms:.1f} ms", flush=True)
+            # the held-out 20 % of every region: season, orbit and repaired sites of every item planned once; a generator of its own per
+            # region, seeded from --seed
+            self.val_sets = []
+            for k, r in enumerate(self.regions):
+                val_plan = plan_of("val", r)
+                if len(val_plan) < 1:
+                    raise SystemExit("--resident_val: no unit of the validation split survives the size filters")
+                v = ResidentItems(r, val_plan, seasons=S, generator=torch.Generator().manual_seed(a.seed), ascfill=self.region_ascfill[k])
+                self.val_sets.append(v)
+                if self.rank == 0:
+                    print(f"resident validation{'' if R == 1 else f' (region {k})'}: {len(val_plan)} items, {len(v.dropped)} dropped, "
+                          f"{v.ascending} ascending, {v.entries} table entries ({v.nbytes} bytes), built in {v.build_ms:.1f} ms", flush=True)
+            self.val_items = self.val_sets[0]
         self.region_repair = None
         if a.resident_repair:
             n0 = len(self.region_plan)
-            self.region_plan, self.region_repair = plan_repair(self.region, self.region_plan, seasons=S, ascfill=a.ascfill)
+            if R == 1:
+                self.region_plan, self.region_repair = plan_repair(self.region, self.region_plan, seasons=S, ascfill=self.region_ascfill[0])
+            else:
+                self.region_plan, self.region_repair = plan_repair_atlas(self.atlas, self.region_plan, seasons=S,
+                                                                         ascfill=[k for k in range(R) if self.region_ascfill[k]])
             self._step_nan_fill = False
             r = self.region_repair
             if self.rank == 0:
-                print(f"resident repair: {n0} items, {len(r.dropped)} dropped, {r.ascending} ascending, {r.entries} table entries "
+                per = "" if R == 1 else " (per region: " + ", ".join(f"{k}: {len(v)}" for k, v in sorted(r.dropped_by_region.items())) + ")"
+                print(f"resident repair: {n0} items, {len(r.dropped)} dropped{per}, {r.ascending} ascending, {r.entries} table entries "
                       f"({r.nbytes} bytes), built in {r.build_ms:.1f} ms", flush=True)
         if len(self.region_plan) < a.weak_batch_size:
             raise SystemExit(f"--resident_region: the plan holds {len(self.region_plan)} crops, fewer than one batch of {a.weak_batch_size}")
         gen = torch.Generator().manual_seed(a.seed)
+        source = self.region if R == 1 else self.atlas
         if assemble:
             # the coins are the feed's to draw (once per batch, right before the step).  The feed validates its transform at construction;
             # Trainer.__init__ hands it the trainer's own data_transform, the same set, once that exists
-            self._resident_feed = ResidentBatchFeed(self.region, self.region_plan, a.weak_batch_size, transform=default_train_transform(),
-                                                    generator=gen, drop_last=True, pixel_budget=a.resident_pixel_budget,
-                                                    max_batch=a.resident_max_batch, min_fill=a.resident_min_fill, repair=self.region_repair,
-                                                    seasons=S)
+            feed = ResidentBatchFeed if R == 1 else AtlasBatchFeed
+            self._resident_feed = feed(source, self.region_plan, a.weak_batch_size, transform=default_train_transform(),
+                                       generator=gen, drop_last=True, pixel_budget=a.resident_pixel_budget,
+                                       max_batch=a.resident_max_batch, min_fill=a.resident_min_fill, repair=self.region_repair, seasons=S)
         else:
-            self._resident_feed = ResidentRegionFeed(self.region, self.region_plan, a.weak_batch_size, generator=gen, drop_last=True,
-                                                     repair=self.region_repair, seasons=S)
+            feed = ResidentRegionFeed if R == 1 else AtlasRegionFeed
+            self._resident_feed = feed(source, self.region_plan, a.weak_batch_size, generator=gen, drop_last=True,
+                                       repair=self.region_repair, seasons=S)
+
+    def _region_tag(self, k):
+        """The metric tag of resident region k: today's for a single region, numbered for an atlas (the reference keys them per region)."""
+        return "MainCensus_synthetic_fine" if len(self.regions) == 1 else f"MainCensus_synthetic{k}_fine"
 
     # ---- checkpoint (run_train.py:445-476) --------------------------------------------------------------------------
     def save_model(self, prefix="last"):
@@ -660,11 +729,19 @@ class Trainer:
         native = bool(self.model.native_forward)         # a native forward's outputs live in the model's arena (infer.py): keep copies
         with torch.no_grad():
             if self.args.resident_val:
+                # one ResidentItems per region, metrics per region (run_train.py:295-310)
                 from .data.units import flat_valid
-                for s in self.val_items:
-                    out = self.model(s, padding=False)
-                    pred.append(out["popcount"].clone() if native else out["popcount"])
-                    gt.append(flat_valid(s["y"], s["census_n"]) if s.get("census_n") is not None else s["y"])
+                self.valweak_stats = {}
+                for k, items in enumerate(self.val_sets):
+                    pred, gt = [], []
+                    for s in items:
+                        out = self.model(s, padding=False)
+                        pred.append(out["popcount"].clone() if native else out["popcount"])
+                        gt.append(flat_valid(s["y"], s["census_n"]) if s.get("census_n") is not None else s["y"])
+                    stats = get_test_metrics(torch.cat(pred), torch.cat(gt).float(), tag=self._region_tag(k))
+                    self.valweak_stats.update({key + "/val": float(v) for key, v in stats.items()})
+                self._log(self.valweak_stats)
+                return self.valweak_stats
             else:
                 for sample in self.val_loader:
                     s = normalize_sample(sample, self.device, None, nan_fill=self.args.nan_fill)
@@ -709,20 +786,27 @@ class Trainer:
         from . import eval as E
         from .data.region import ResidentWindows
         from .utils.metrics import get_test_metrics
-        a, region = self.args, self.region
+        a, R = self.args, len(self.regions)
         if self._resident_windows is None:
-            f = self._resident_windows = ResidentWindows(region, a.test_patchsize, a.test_overlap, fourseasons=False, ascfill=a.ascfill)
-            if self.rank == 0:
-                print(f"resident windows: {len(f.idx)} windows, {f.ascending} ascending, {f.entries} table entries ({f.nbytes} bytes), "
-                      f"built in {f.build_ms:.1f} ms", flush=True)
+            # one plan per region, each made once (run_train.py:322-366 tests region by region)
+            self._resident_window_sets = []
+            for k, region in enumerate(self.regions):
+                f = ResidentWindows(region, a.test_patchsize, a.test_overlap, fourseasons=False, ascfill=self.region_ascfill[k])
+                self._resident_window_sets.append(f)
+                if self.rank == 0:
+                    print(f"resident windows{'' if R == 1 else f' (region {k})'}: {len(f.idx)} windows, {f.ascending} ascending, "
+                          f"{f.entries} table entries ({f.nbytes} bytes), built in {f.build_ms:.1f} ms", flush=True)
+            self._resident_windows = self._resident_window_sets[0]
         self.model.eval()
-        out, _, scale, _ = E.evaluate_raster([self.model], self._resident_windows, a.test_patchsize, a.test_overlap, False, FlatReducer(), 0)
-        cp, cg = E.convert_popmap_to_census(out, region.boundary, region.census_idx, region.census_pop)
-        stats = get_test_metrics(cp, cg, tag="MainCensus_synthetic_fine")
-        self.target_test_stats = {k + "/targettest": float(v) for k, v in stats.items()}
-        if save and self.rank == 0:
-            torch.save({"popdensemap": out.cpu(), "scale": None if scale is None else scale.cpu()},
-                       os.path.join(self.exp, "synthetic_predictions.pt"))
+        self.target_test_stats = {}
+        for k, (region, windows) in enumerate(zip(self.regions, self._resident_window_sets)):
+            out, _, scale, _ = E.evaluate_raster([self.model], windows, a.test_patchsize, a.test_overlap, False, FlatReducer(), 0)
+            cp, cg = E.convert_popmap_to_census(out, region.boundary, region.census_idx, region.census_pop)
+            stats = get_test_metrics(cp, cg, tag=self._region_tag(k))
+            self.target_test_stats.update({key + "/targettest": float(v) for key, v in stats.items()})
+            if save and self.rank == 0:
+                torch.save({"popdensemap": out.cpu(), "scale": None if scale is None else scale.cpu()},
+                           os.path.join(self.exp, "synthetic_predictions.pt" if R == 1 else f"synthetic{k}_predictions.pt"))
         self._log(self.target_test_stats)
         return self.target_test_stats
 

@@ -23,6 +23,7 @@ and pixel counts are made at preprocessing time with one pass per unit (utils/02
   ``ResidentItems``       the same region VALIDATED: the items of a (validation) plan with season, orbit and repaired sites planned once,
                           each item's normalised input and admin mask then ONE ``ops.region_item`` launch
 
+Several regions at once (the reference's multi-country -tregtrain): data/atlas.py, whose feeds are these with the launch replaced.
 Host glue, plain torch; the kernels are csrc/region.hip, csrc/region_batch.hip, csrc/region_repair.hip and csrc/region_crop.hip.
 Deviations from the reference, all named where they happen: units without pixels are dropped (``plan_one_unit``); the per-epoch order and the season per item come from a torch generator, not Python's ``random`` stream
 (``ResidentRegionFeed``); without ``plan_repair`` the resident S1 is the orbit already chosen per season (``--nan_fill`` fills what is
@@ -693,6 +694,10 @@ class ResidentRegionFeed:
         n, B = len(self.plan), self.batch_size
         return n // B if self.drop_last else -(-n // B)
 
+    def _gather(self, idx, crops, orbit=None):
+        """The gather launch of plan rows ``idx`` (what a feed over several regions, data/atlas.py, replaces)."""
+        return self.region.gather(crops) if orbit is None else self.region.gather(crops, orbit=orbit)
+
     def __iter__(self):
         plan, B, n = self.plan, self.batch_size, len(self.plan)
         order = torch.randperm(n, generator=self.generator)
@@ -708,11 +713,11 @@ class ResidentRegionFeed:
             crops[:, :4] = self._crops[idx]
             crops[:, 4] = season_np[k * B:(k + 1) * B]
             if self.repair is None:
-                out = self.region.gather(crops)
+                out = self._gather(idx, crops)
             else:
                 # the plan's orbit column, then the batch's patches: one small launch behind the gather, none for a batch without entries
                 orbit = self.repair.orbit_of(idx, crops[:, 4])
-                out = self.region.gather(crops, orbit=orbit)
+                out = self._gather(idx, crops, orbit)
                 self.repair.apply(idx, crops[:, 4], out["S2"], out["S1"], tuple(out["admin_mask"].shape[1:]))
                 out["orbit"] = orbit.tolist()
             if plan.multi:
@@ -825,6 +830,14 @@ class ResidentBatchFeed:
         n, B = len(self.plan), self.batch_size
         return n // B if self.drop_last else -(-n // B)
 
+    def _assemble(self, idx, crops, params, labels, orbit=None):
+        """The assembly launch of plan rows ``idx`` (what a feed over several regions, data/atlas.py, replaces)."""
+        r = self.region
+        kw = {} if r.buildings is None else {"buildings": r.buildings}     # "building_counts", same launch
+        if orbit is None:
+            return ops.region_batch(r.s2, r.s1, r.boundary, r.band_sel, crops, params, labels=labels, **kw)
+        return ops.region_batch(r.s2, r.s1, r.boundary, r.band_sel, crops, params, labels=labels, s1_asc=r.s1_asc, orbit=orbit, **kw)
+
     def __iter__(self):
         plan, B, n = self.plan, self.batch_size, len(self.plan)
         order = torch.randperm(n, generator=self.generator)
@@ -851,15 +864,12 @@ class ResidentBatchFeed:
             cn = [plan.census_n[i] for i in idx] if plan.multi else None
             params = self._draw(self.transform)                        # the coins, immediately before the batch goes out
             labels = (self._cidx, self._y, idx, max(cn) if plan.multi else 1)
-            kw = {} if self.region.buildings is None else {"buildings": self.region.buildings}     # "building_counts", same launch
             if self.repair is None:
-                out = ops.region_batch(self.region.s2, self.region.s1, self.region.boundary, self.region.band_sel, crops, params,
-                                       labels=labels, **kw)
+                out = self._assemble(idx, crops, params, labels)
             else:
                 # the plan's orbit column, then the batch's patches through the same coins: one small launch behind the assembly
                 orbit = self.repair.orbit_of(idx, sea)
-                out = ops.region_batch(self.region.s2, self.region.s1, self.region.boundary, self.region.band_sel, crops, params,
-                                       labels=labels, s1_asc=self.region.s1_asc, orbit=orbit, **kw)
+                out = self._assemble(idx, crops, params, labels, orbit)
                 tile = (max(self._hw[i][0] for i in idx), max(self._hw[i][1] for i in idx))
                 self.repair.apply(idx, sea, out["raw"][:, :4], out["raw"][:, 4:], tile, params)
                 out["orbit"] = orbit.tolist()

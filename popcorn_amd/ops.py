@@ -1308,6 +1308,190 @@ def region_batch(s2, s1, boundary, band_sel, crops, params=None, hw=None, labels
     return out
 
 
+class AtlasHandle:
+    """The C handle of a resident atlas (csrc/region_atlas.hip, pc_atlas_create): R regions = dicts of the device tensors s2, s1, boundary,
+    optionally s1_asc and buildings, and band_sel.  One device, one S2 type, a building layer on all regions or on none: ValueError
+    otherwise, before the library is called.  The descriptors are uploaded once, here: the only copy and the only synchronisation.  The
+    handle keeps the tensors alive and frees the device table when it is collected."""
+
+    def __init__(self, regions):
+        regions = list(regions)
+        if not 1 <= len(regions) <= L.PC_ATLAS_MAX_REGIONS:
+            raise ValueError(f"atlas: 1 .. {L.PC_ATLAS_MAX_REGIONS} regions, got {len(regions)}")
+        self.meta, keep = [], []
+        desc = (L.PcAtlasRegion * len(regions))()
+        dev, dt = regions[0]["s1"].device, regions[0]["s2"].dtype
+        layered = regions[0].get("buildings") is not None
+        for k, r in enumerate(regions):
+            what = f"atlas region {k}"
+            S, C2, C1, h, w, band = _region_sources(what, r["s2"], r["s1"], r["boundary"], r["band_sel"])
+            asc, bld = r.get("s1_asc"), r.get("buildings")
+            _region_orbit(what, r["s1"], asc, None, 1)
+            _region_layer(what, bld, h, w, r["s1"].device)
+            if r["s1"].device != dev or r["s2"].device != dev or r["boundary"].device != dev:
+                raise ValueError(f"{what}: every region of an atlas lives on one device ({dev}), got {r['s1'].device}")
+            if r["s2"].dtype != dt:
+                raise ValueError(f"{what}: one S2 type per atlas ({dt}), got {r['s2'].dtype}: mixed S2 types are not part of it")
+            if (bld is not None) != layered:
+                raise ValueError(f"{what}: a building layer on all regions of an atlas or on none")
+            d = desc[k]
+            d.s2, d.s1, d.boundary = r["s2"].data_ptr(), r["s1"].data_ptr(), r["boundary"].data_ptr()
+            d.s1_asc = 0 if asc is None else asc.data_ptr()
+            d.layer = 0 if bld is None else bld.data_ptr()
+            d.S, d.C2, d.C1, d.h, d.w = S, C2, C1, h, w
+            d.band_sel[:] = band
+            self.meta.append((S, h, w, asc is not None))
+            keep.append((r["s2"], r["s1"], r["boundary"], asc, bld))
+        self._keep = keep
+        self.device, self.layered, self.R = dev, layered, len(regions)
+        self._h = C.c_void_p()
+        self._destroy = L.lib().pc_atlas_destroy
+        with torch.cuda.device(dev):
+            L.check(L.lib().pc_atlas_create(desc, self.R, int(dt == torch.uint16), C.byref(self._h)), "pc_atlas_create")
+
+    def __del__(self):
+        import sys
+        h = getattr(self, "_h", None)
+        if h is not None and h.value and not sys.is_finalizing():       # (at interpreter exit the runtime frees the table itself)
+            self._destroy(h)
+            self._h = None
+
+
+def _atlas_inputs(what, atlas, region_of, crops, orbit):
+    """The host lists of an ``atlas_*`` wrapper: region_of = B region indices, crops (B, 5) each checked in its OWN region, orbit = B values
+    in {0, 1} with 1 only for a region that holds s1_asc.  Returns (region list, uint8 array, crops int32 (B, 5), (Hm, Wm), orbit pointer)."""
+    if not isinstance(atlas, AtlasHandle):
+        raise ValueError(f"{what}: an ops.AtlasHandle, got {type(atlas).__name__}")
+    ro = np.ascontiguousarray(np.asarray(region_of.cpu() if torch.is_tensor(region_of) else region_of, dtype=np.int64).reshape(-1))
+    if torch.is_tensor(crops):
+        if crops.is_cuda:
+            raise ValueError(f"{what}: crops is host data (it travels in the kernel arguments)")
+        crops = crops.numpy()
+    cr = np.ascontiguousarray(np.asarray(crops, dtype=np.int64).reshape(-1, 5))
+    B = cr.shape[0]
+    if B < 1 or ro.size != B or (ro < 0).any() or (ro >= atlas.R).any():
+        raise ValueError(f"{what}: region_of names one region in [0, {atlas.R}) per crop ({B}), got {ro.tolist()}")
+    ob = None
+    if orbit is not None:
+        ob = np.ascontiguousarray(np.asarray(orbit.cpu() if torch.is_tensor(orbit) else orbit, dtype=np.int64).reshape(-1))
+        if ob.size != B or ((ob != 0) & (ob != 1)).any():
+            raise ValueError(f"{what}: orbit holds one value in {{0, 1}} per crop ({B}), got {ob.tolist()}")
+    for k in np.unique(ro).tolist():
+        S, h, w, has_asc = atlas.meta[k]
+        rows = np.flatnonzero(ro == k)
+        try:
+            _region_crops(what, cr[rows], S, h, w)
+        except ValueError as e:
+            raise ValueError(f"{e} (region {k} of the atlas; batch rows {rows.tolist()})") from None
+        if ob is not None and ob[rows].any() and not has_asc:
+            raise ValueError(f"{what}: orbit 1 (ascending) for a crop of region {k}, which holds no s1_asc")
+    orb = None
+    if ob is not None:
+        ob8 = ob.astype(np.uint8)
+        orb = ob8.ctypes.data_as(C.POINTER(C.c_uint8))
+        orb._keep = ob8
+    ro8 = ro.astype(np.uint8)
+    return ro.tolist(), ro8, cr.astype(np.int32), (int((cr[:, 1] - cr[:, 0]).max()), int((cr[:, 3] - cr[:, 2]).max())), orb
+
+
+def atlas_gather(atlas, region_of, crops, out=None, orbit=None):
+    """``region_gather`` over a resident atlas in ONE launch (csrc/region_atlas.hip, pc_atlas_gather): crop b is crops[b] = {x0, x1, y0, y1,
+    season} of region region_of[b].  By definition, bit for bit: row b equals row 0 of ``region_gather`` on that region alone with crop b,
+    orbit[b] and the tile (Hm, Wm).  Returns ``region_gather``'s dict ("building_counts" when the atlas has layers) plus "region", the host
+    list of region indices.  A crop or season invalid in its own region, a region outside [0, R) and orbit 1 for a region without s1_asc
+    raise ValueError before anything is enqueued."""
+    regions, ro8, cr32, (Hm, Wm), orb = _atlas_inputs("atlas_gather", atlas, region_of, crops, orbit)
+    B, dev = cr32.shape[0], atlas.device
+    if out is None:
+        out = {"S2": torch.empty(B, 4, Hm, Wm, dtype=torch.float32, device=dev),
+               "S1": torch.empty(B, 2, Hm, Wm, dtype=torch.float32, device=dev),
+               "admin_mask": torch.empty(B, Hm, Wm, dtype=torch.float32, device=dev),
+               "data_hw": torch.empty(B, 2, dtype=torch.int32, device=dev)}
+        if atlas.layered:
+            out["building_counts"] = torch.empty(B, 1, Hm, Wm, dtype=torch.float32, device=dev)
+    else:
+        L.require_device(out["S2"], out["S1"], out["admin_mask"], out["data_hw"])
+        Ho, Wo = out["admin_mask"].shape[-2:]
+        if atlas.layered:
+            _layer_out("atlas_gather", out.get("building_counts"), ((B, 1, int(Ho), int(Wo)),), dev)
+        if (tuple(out["S2"].shape) != (B, 4, Ho, Wo) or tuple(out["S1"].shape) != (B, 2, Ho, Wo) or
+                tuple(out["admin_mask"].shape) != (B, Ho, Wo) or tuple(out["data_hw"].shape) != (B, 2) or Ho < Hm or Wo < Wm or
+                any(out[k].dtype != torch.float32 or not out[k].is_contiguous() for k in ("S2", "S1", "admin_mask")) or
+                out["data_hw"].dtype != torch.int32 or not out["data_hw"].is_contiguous()):
+            raise ValueError(f"atlas_gather: out must hold contiguous fp32 S2 ({B}, 4, H, W), S1 ({B}, 2, H, W), admin_mask ({B}, H, W) with "
+                             f"(H, W) >= ({Hm}, {Wm}) and int32 data_hw ({B}, 2)")
+        Hm, Wm = int(Ho), int(Wo)
+    if Hm * Wm >= 1 << 31:
+        raise ValueError(f"atlas_gather: Hm * Wm < 2^31, got {Hm} x {Wm}")
+    L.check(L.lib().pc_atlas_gather(atlas._h, ro8.ctypes.data_as(C.POINTER(C.c_uint8)), cr32.ctypes.data_as(C.POINTER(C.c_int32)), orb, B,
+                                    Hm, Wm, L.ptr(out["S2"]), L.ptr(out["S1"]), L.ptr(out["admin_mask"]),
+                                    L.ptr(out["building_counts"]) if atlas.layered else None, L.ptr(out["data_hw"]), L.stream_ptr()),
+            "pc_atlas_gather")
+    out["region"] = regions
+    return out
+
+
+def atlas_batch(atlas, region_of, crops, params=None, hw=None, labels=None, out=None, orbit=None):
+    """``region_batch`` over a resident atlas in ONE launch (csrc/region_atlas.hip, pc_atlas_batch).  By definition, bit for bit:
+    ``augment_raw(*atlas_gather(...; tile (Hm, Wm)), params)``.  params, hw, labels and out as ``region_batch`` takes them; the items of
+    labels index ONE plan table, the regions' tables concatenated.  Returns ``region_batch``'s dict plus "region".  Everything
+    ``atlas_gather`` and ``region_batch`` refuse raises ValueError before anything is enqueued."""
+    regions, ro8, cr32, (Hm, Wm), orb = _atlas_inputs("atlas_batch", atlas, region_of, crops, orbit)
+    B, dev = cr32.shape[0], atlas.device
+    if hw is not None:
+        th, tw = int(hw[0]), int(hw[1])
+        if th < Hm or tw < Wm:
+            raise ValueError(f"atlas_batch: the tile hw = ({th}, {tw}) is smaller than the batch maximum ({Hm}, {Wm})")
+        Hm, Wm = th, tw
+    if Hm * Wm >= 1 << 31:
+        raise ValueError(f"atlas_batch: Hm * Wm < 2^31, got {Hm} x {Wm}")
+    pr = params or {}
+    k = int(pr.get("rot", 0))
+    if not 0 <= k <= 3:
+        raise ValueError(f"atlas_batch: rot is a number of quarter turns in 0 .. 3, got {k}")
+    Ho, Wo = (Wm, Hm) if k & 1 else (Hm, Wm)
+    lab = None
+    if labels is not None:
+        plan_cidx, plan_y, items, K = labels
+        L.require_device(plan_cidx, plan_y)
+        K = int(K)
+        if (plan_cidx.dim() != 2 or plan_cidx.dtype != torch.int64 or plan_y.dtype != torch.float32 or plan_y.shape != plan_cidx.shape or
+                not plan_cidx.is_contiguous() or not plan_y.is_contiguous() or plan_cidx.shape[0] < 1):
+            raise ValueError("atlas_batch: labels are contiguous device tables plan_cidx int64 (n, Kp) and plan_y fp32 (n, Kp)")
+        n, Kp = plan_cidx.shape
+        it = np.ascontiguousarray(np.asarray(items, dtype=np.int64).reshape(-1))
+        if it.size != B or (it < 0).any() or (it >= n).any():
+            raise ValueError(f"atlas_batch: items names one plan row in [0, {n}) per crop ({B}), got {it.tolist()}")
+        if not 1 <= K <= Kp:
+            raise ValueError(f"atlas_batch: K in [1, {Kp}], got {K}")
+        it32 = it.astype(np.int32)
+    want = {"raw": ((B, 6, Ho, Wo), torch.float32), "admin_mask": ((B, Ho, Wo), torch.float32)}
+    if atlas.layered:
+        want["building_counts"] = ((B, 1, Ho, Wo), torch.float32)
+    if labels is not None:
+        want.update({"census_idx": ((B, K), torch.int64), "y": ((B, K), torch.float32)})
+    if out is None:
+        out = {key: torch.empty(*shape, dtype=dt, device=dev) for key, (shape, dt) in want.items()}
+    else:
+        for key, (shape, dt) in want.items():
+            t = out.get(key)
+            if t is None or not t.is_cuda or tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+                raise ValueError(f"atlas_batch: out[{key!r}] must be a contiguous device {dt} tensor of shape {shape}, got "
+                                 f"{None if t is None else (t.dtype, tuple(t.shape))}")
+    if labels is not None:
+        lab = L.PcRegionLabels(plan_cidx.data_ptr(), plan_y.data_ptr(), it32.ctypes.data_as(C.POINTER(C.c_int32)),
+                               out["census_idx"].data_ptr(), out["y"].data_ptr(), n, Kp, K, 0)
+    beta, gamma = pr.get("beta"), pr.get("gamma")
+    L.check(L.lib().pc_atlas_batch(atlas._h, ro8.ctypes.data_as(C.POINTER(C.c_uint8)), cr32.ctypes.data_as(C.POINTER(C.c_int32)), orb, B,
+                                   Hm, Wm, int(bool(pr.get("vflip"))), int(bool(pr.get("hflip"))), k, int(beta is not None),
+                                   C.c_float(beta if beta is not None else 1.0), int(gamma is not None),
+                                   C.c_float(gamma if gamma is not None else 1.0), L.ptr(out["raw"]), L.ptr(out["admin_mask"]),
+                                   L.ptr(out["building_counts"]) if atlas.layered else None, Ho, Wo,
+                                   C.byref(lab) if lab is not None else None, L.stream_ptr()), "pc_atlas_batch")
+    out["region"] = regions
+    return out
+
+
 def region_nan_census(s2, s1, boundary, band_sel, boxes, s1_asc=None, max_blocks=0):
     """The NaN entries of many boxes of the resident rasters in ONE pass (csrc/region_repair.hip, pc_region_nan_census): what decides an
     item's S1 orbit (data/PopulationDataset.py:419-441), for a whole plan at once.  Sources and band_sel as ``region_gather``; boxes: HOST
