@@ -587,10 +587,25 @@ int pc_augment_raw(const float* s2, const float* s1, const float* admin, float* 
  * activation / gradient / workspace out of ONE caller-provided arena (bump allocation, rows padded to 16 bytes so that every conv
  * launch takes the aligned staged loaders whatever the region's width), fills the descriptors and issues all launches from C++.
  * The plan (parameter pointers, BN descriptors, optimiser constants) is built once per trainer (pc_step_create); a step passes only
- * its batch.  PC_PREC_FP32, dual-stream (S1 + S2) models, with or without the occupancy product (plan.occupancymodel = 0: the mask is
- * the region only and the head multiplies by a plane of ones the step fills in the arena, popcorn.py:179-181), whose building score
- * comes from the frozen extractor or from the layer the batch ships (pc_train_step_layer, below); anything else (bf16, single-modality
- * models) returns PC_ENOTSUP and the caller keeps the per-launch path (same kernels, launched through the entry points above).
+ * its batch.  PC_PREC_FP32, dual-stream (S1 + S2) and one-stream models, with or without the occupancy product (plan.occupancymodel = 0:
+ * the mask is the region only and the head multiplies by a plane of ones the step fills in the arena, popcorn.py:179-181), whose building
+ * score comes from the frozen extractor or from the layer the batch ships (pc_train_step_layer, below); bf16 returns PC_ENOTSUP and the
+ * caller keeps the per-launch path (same kernels, launched through the entry points above).
+ * A ONE-STREAM PLAN (the reference's -S1 alone / -S2 -NIR alone models, popcorn.py:48-54,135-145,302-314) is the same pc_step_plan with
+ *   - the table of the absent stream (pc_step_stream: s[0] sar, s[1] optical -- a stream keeps its slot) ALL ZERO in both unet and extractor;
+ *   - fusion_w / fusion_b of each net pointing at the present stream's own out conv (sar_out_conv / optical_out_conv, networks.py:217-228:
+ *     8 weights, 1 bias): the building score is sigmoid(out conv over the stream's 8 feature channels) on both domains;
+ *   - head_w[0] / head_dw[0] pointing at the 64 x 8 first head layer and its gradient inside flat_g (the other seven as ever);
+ *   - feat_c0 of the present stream 0 or 8, the same in both nets.
+ * pc_train_step, pc_train_step_layer, pc_train_step_units and pc_train_step_units_layer take it and compute the bits of the per-launch
+ * step.  The feature map stays 16 channels: inside the call the absent stream's 8 are zero-filled, w0 is embedded at feat_c0 of a zeroed
+ * 64 x 16 image in the arena in front of the head forward, and the live half of the head's 64 x 16 first-layer gradient image is copied
+ * into head_dw[0] behind the reduction that finishes it, in front of the gradient norm.  Data: PC_DATA_INPUT is (B, cin, H, W) -- the
+ * stream's own channels, picked by chan[] --, or (B, io->craw, H, W) when io->craw > 0 (a wider tile of which chan[] picks);
+ * PC_DATA_RAW / PC_DATA_SPLIT as for two streams.  Side stream, phases (io->dp), arena_needed, the output offsets and launches behave as
+ * for a dual-stream plan.  Refused before anything is enqueued: a stream present in one net and absent in the other, or in neither
+ * (present: cin >= 1 and w[0] != NULL), a chan[] beyond the PC_DATA_INPUT tensor: PC_EINVAL.  pc_forward keeps refusing a one-stream
+ * plan (PC_ENOTSUP).
  * Small regions fork the frozen extractor's chain and the weight-gradient launches onto an internal side stream; WHICH stream is
  * measured at the first call on a caller's stream (HIP multiplexes streams onto a few hardware queues, and a side stream on the
  * caller's queue serialises with it): that first call launches a few microsecond-long probe kernels and synchronises once, so
@@ -606,10 +621,10 @@ typedef struct pc_step_stream {
     int32_t chan[4];                    /* model-input channel of conv channel c ([R,G,B,NIR,VV,VH]: SAR 4,5; optical 2,1,0,3) */
     int32_t cin, feat_c0;               /* 2 / 4 input channels; first channel of this stream in the 16-channel feature map */
 } pc_step_stream;
-typedef struct pc_step_net { pc_step_stream s[2]; const float* fusion_w; const float* fusion_b; } pc_step_net;
+typedef struct pc_step_net { pc_step_stream s[2]; const float* fusion_w; const float* fusion_b; } pc_step_net;   /* one-stream plan: the stream's out conv */
 typedef struct pc_step_plan {
     pc_step_net unet, extractor;        /* model.unetmodel (trainable), model.building_extractor (frozen) */
-    const float* head_w[8]; float* head_dw[8];     /* {w0,b0,w2,b2,w4,b4,w6,b6} and their gradients */
+    const float* head_w[8]; float* head_dw[8];     /* {w0,b0,w2,b2,w4,b4,w6,b6} and their gradients (w0: 64 x 16; one-stream plan: 64 x 8) */
     float* flat_p; float* flat_g; float* adam_m; float* adam_v;     /* flat parameter / gradient / moment buffers (n floats) */
     int32_t n, n_decay, n_head, occupancymodel;
     const float* hyper_dev; int32_t* step_dev; float* norm_dev; double* stats_dev; float* loss_dev; float* g_scale_const_dev;
@@ -682,7 +697,8 @@ void pc_debug_step_host_ns(double* out);
  * An EAGER entry point like pc_train_step: small regions fork the extractor's chain onto the handle's side stream (measured per
  * caller's stream), so a capturing stream gets PC_ENOTSUP.  The arena is sized by a dry pass (arena_needed is always set; the
  * extractor's activations are released before the U-Net's are carved where the chain is not forked); outputs are valid until the next
- * call on that arena.  Refusals, all before anything is enqueued: bf16 mode, a single-modality plan, B * H * W >= 2^31: PC_ENOTSUP;
+ * call on that arena.  Refusals, all before anything is enqueued: bf16 mode, a one-stream (single-modality) plan -- which the training
+ * entries take, this one does not --, B * H * W >= 2^31: PC_ENOTSUP;
  * the reflect rule of pc_train_step (a pad of either domain >= the side), NULL data, PC_DATA_SPLIT without data2, one of admin_mask /
  * census_idx alone, a misaligned layer: PC_EINVAL; an arena that is too small (or not 256-byte aligned): PC_ENOMEM. */
 typedef struct pc_fwd_io {

@@ -106,11 +106,16 @@ def train_parser():
                    help="--building_layer steps (and steps of a model without -occmodel) through the native step executor "
                         "(pc_train_step_layer: one call per step, the same bits as the per-launch engine); experimental, off by default; "
                         "no effect on steps the executor takes anyway")
+    p.add_argument("--native_single", action="store_true",
+                   help="steps of a single-modality model (-S1 alone, or -S2 alone) through the native step executor (a one-stream plan: "
+                        "one call per step, the same bits as the per-launch engine); off by default.  Needs exactly one of -S1 / -S2, "
+                        "--precision fp32 and the fused step (no --torch_optimizer)")
     p.add_argument("--native_forward", action="store_true",
                    help="validate_weak and the target test (--resident_val / --resident_test included) run model(sample, padding=False) "
                         "through the native forward executor (pc_forward: one call per forward, the same bits as the per-launch engine); "
-                        "off by default.  Still declined, as by the training executor: --precision bf16, -S1 alone, -S2 alone (and "
-                        "multi-unit validation items) keep the per-launch engine -- the count printed at the end is then 0")
+                        "off by default.  Still declined: --precision bf16, -S1 alone, -S2 alone (--native_single is the training "
+                        "executor's switch, not this one's) and multi-unit validation items keep the per-launch engine -- the count "
+                        "printed at the end is then 0")
     p.add_argument("--device_units", action="store_true",
                    help="--units_per_crop steps in the device-N form (counts, N and 1 / N read from device memory): allowed with --fixed_hw "
                         "(replayed HIP graph) and under data parallelism; implies nothing without --units_per_crop")
@@ -233,6 +238,19 @@ def check_building_layer(args):
     if args.building_layer and args.sentinelbuildings:
         raise SystemExit("--building_layer ships a building layer for a model built WITHOUT -senbuilds; with -senbuilds the reference's "
                          "dataset loads no layer and the model ignores one: drop --building_layer or -senbuilds")
+
+
+def check_native_single(args):
+    """--native_single: the refusals that need no device, raised before anything else is set up."""
+    if not getattr(args, "native_single", False):
+        return
+    if bool(args.Sentinel1) == bool(args.Sentinel2):
+        raise SystemExit("--native_single sends the steps of a single-modality model through the native executor: it needs exactly one of "
+                         "-S1 / -S2 (a model with both takes the executor without it)")
+    if args.precision == "bf16":
+        raise SystemExit("--native_single: the native executor is fp32 only; --precision bf16 keeps the per-launch engine (drop one of the two)")
+    if args.torch_optimizer:
+        raise SystemExit("--native_single belongs to the fused step: the --torch_optimizer recipe never reaches the native executor")
 
 
 def seed_all(seed):
@@ -416,6 +434,7 @@ class Trainer:
         self.args = args
         check_building_layer(args)
         check_repair_args(args)
+        check_native_single(args)
         self.rank, self.local_rank, self.world = init_from_env()
         if not torch.cuda.is_available():
             raise SystemExit("popcorn_amd training needs a HIP device (no CPU path)")
@@ -499,7 +518,8 @@ class Trainer:
                                         use_graph=args.fixed_hw is not None and (args.units_per_crop == 0 or args.device_units),
                                         raw_norm=(tuple(range(6)), stats.MEAN6, stats.STD6), native_units=args.native_units,
                                         device_units=args.device_units and args.units_per_crop > 0,
-                                        native_layer=getattr(args, "native_layer", False))
+                                        native_layer=getattr(args, "native_layer", False),
+                                        native_single=getattr(args, "native_single", False))
         if args.resume:
             self.resume(args.resume)
 

@@ -17,6 +17,11 @@
 // tail around the head: unit lists -> score -> unit mask -> head without a region -> unit sums + loss -> paint -> head backward on
 // g_popdense; everything between ingest and the U-Net update is shared, and a one-unit call (un == nullptr) issues what it always did.
 //
+// A one-stream plan (popcorn_hip.h: an S1-only / S2-only model; Step::ns / ps / cs) takes the same path over the present streams: every
+// per-stream loop and grouped launch runs over Step::ns of them, the feature map keeps its 16 channels with the absent stream's 8 zeroed
+// (zero_chans_kernel), the building score is the stream's own out conv over its 8 channels, and the head's 64 x 8 first layer travels
+// through 64 x 16 images in the arena (head_w0_embed_kernel, head_dw0_extract_kernel).  A dual-stream plan issues what it always did.
+//
 // The backward pass (struct Backward) is the network in reverse, one function per U-Net block, to be read next to engine.py: _Backward.
 // It has the COMPOSED form of the two Up blocks only: the trainable U-Net works on the add_padding domain, whose sides are multiples of
 // 32 (pad_geometry), so both levels have exact 2x geometry, widths that are multiples of 16 and 16-byte rows -- everything the composed
@@ -108,6 +113,17 @@ struct Step {
     pc_bn bn_half[2][2];                        // d1b's factor for the two 8-channel halves of its output (pointers into the same BN tensors)
     pc_bn bn_half_d1a[2][2];                    // ... and d1a's (the fused backward of d1b runs per 8-channel half of its input)
     float* ones2 = nullptr;                     // device {1, 1}: weights of the partial-logit sum
+    // the streams that are present (popcorn_hip.h: a one-stream plan has the table of the absent stream all zero in both networks).
+    // Everything per stream below -- cs, bn_nobias, bn_half, bn_half_d1a, sv -- is indexed by the position in ps, not by the stream
+    int ns = 2;
+    int ps[2] = {0, 1};
+    pc_step_stream cs[2];                       // the trainable network's tables of the present streams
+    pc_bn feat_bn[2];                           // ReLU / BN factor of the two halves of the feature map (absent stream: plain, its half is zero)
+    // one-stream plan: the 64 x 16 images of the head's first layer in the arena (head_w[0] / head_dw[0] of the plan are 64 x 8)
+    float* w0_img = nullptr;
+    float* dw0_img = nullptr;
+    const float* hw[8];                         // the head's tensors and gradient targets as its kernels get them (set by forward())
+    float* hdw[8];
     // small regions: the frozen extractor's forward chain runs on a side stream next to the trainable U-Net's (two chains of ~13 small,
     // latency-bound launches each; at B = 64 tiles -- a full chip per launch -- every multi-stream attempt lost)
     hipStream_t side = nullptr;
@@ -155,11 +171,36 @@ struct Step {
     bool dense_rule = false;                    // pc_forward(PC_FWD_DENSE_ROW_RULE): compose the Up blocks only where dense rows would be aligned
 
     bool go() const { return !ar.dry && err == 0; }
+    bool one() const { return ns == 1; }
     void rc(int code) {
         if (code != 0 && err == 0) err = code;
         ++launches;
     }
 };
+
+// a stream's table is either filled or all zero (popcorn_hip.h: one-stream plan)
+inline bool stream_present(const pc_step_stream& t) { return t.cin >= 1 && t.w[0] != nullptr; }
+
+// the streams of a training plan: the same ones in both networks, at least one; a one-stream plan needs its feature half named (0 / 8)
+// and room for its channels in the 4-entry chan[]
+inline int plan_streams_ok(const pc_step_plan& P) {
+    int n = 0;
+    for (int s = 0; s < 2; ++s) {
+        const bool u = stream_present(P.unet.s[s]), e = stream_present(P.extractor.s[s]);
+        if (u != e) return PC_EINVAL;
+        if (!u) continue;
+        ++n;
+        if (P.unet.s[s].cin > 4 || P.unet.s[s].cin != P.extractor.s[s].cin) return PC_EINVAL;
+    }
+    if (n == 0) return PC_EINVAL;
+    if (n == 1)
+        for (int s = 0; s < 2; ++s) {
+            if (!stream_present(P.unet.s[s])) continue;
+            const int f0 = P.unet.s[s].feat_c0;
+            if ((f0 != 0 && f0 != 8) || P.extractor.s[s].feat_c0 != f0) return PC_EINVAL;
+        }
+    return 0;
+}
 
 inline void pad_geometry(int H, int W, int& pt, int& pb, int& pl, int& pr) {          // add_padding(force=False), popcorn.py:231-258
     pt = pb = pl = pr = 0;
@@ -178,15 +219,38 @@ __global__ __launch_bounds__(256) void ones_fill_kernel(float* p, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) p[i] = 1.f;
 }
 
+// ---- one-stream plan (S1-only / S2-only model): the head kernels keep their 16-channel form, the absent stream's half is zero ----------
+// the dead 8 channels of the dense (B, 16, Hp, Wp) feature map (the arena's contents are undefined)
+__global__ __launch_bounds__(256) void zero_chans_kernel(float* p, int64_t bstride, int64_t per_b, int B) {
+    const int64_t n = per_b * B;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t b = i / per_b;
+        p[b * bstride + (i - b * per_b)] = 0.f;
+    }
+}
+
+// the head's first layer w0 (64 x 8) at columns [c0, c0 + 8) of a zeroed 64 x 16 image (model.head_tensors of the per-launch step)
+__global__ __launch_bounds__(256) void head_w0_embed_kernel(const float* __restrict__ w0, float* __restrict__ img, int c0) {
+    for (int i = threadIdx.x; i < 64 * 16; i += 256) {
+        const int r = i >> 4, c = (i & 15) - c0;
+        img[i] = (c >= 0 && c < 8) ? w0[r * 8 + c] : 0.f;
+    }
+}
+
+// ... and back: the live half of the first layer's 64 x 16 gradient image -> the parameter's gradient (model.head_grad_targets: fix)
+__global__ __launch_bounds__(256) void head_dw0_extract_kernel(const float* __restrict__ img, float* __restrict__ dw0, int c0) {
+    for (int i = threadIdx.x; i < 64 * 8; i += 256) dw0[i] = img[(i >> 3) * 16 + c0 + (i & 7)];
+}
+
 struct Net {                   // one DualStreamUNet taking part in a forward pass
     const pc_step_net* n;
     bool save;                 // keep the activations for the backward pass
     bool logit_only;           // write the two partial fusion_out_conv logits instead of the feature map
 };
 
-struct Key { int e, s; };
+struct Key { int e, s, c; };          // network, stream, position of the stream among the present ones
 
-// Forward of `nE` networks on the same padded input Xp (B, 6 stream-ordered channels, Hp, Wp), one grouped launch per layer for all
+// Forward of `nE` networks on the same padded input Xp (B, the present streams' channels in stream order, Hp, Wp), one grouped launch per layer for all
 // (network, stream) pairs -- engine.py: forward_multi.  feats[e]: (B, 16, Hp, Wp) or, for logit_only networks, (B, 2, Hp, Wp).
 void forward_nets(Step& X, const Net* nets, int nE, const Ten& Xp, int Hp, int Wp, Ten* feats, Saved (*saved)[2]) {
     const int B = Xp.B;
@@ -195,7 +259,7 @@ void forward_nets(Step& X, const Net* nets, int nE, const Ten& Xp, int Hp, int W
     Key keys[MAXK];
     int K = 0;
     for (int e = 0; e < nE; ++e)
-        for (int s = 0; s < 2; ++s) keys[K++] = Key{e, s};
+        for (int c = 0; c < X.ns; ++c) keys[K++] = Key{e, X.ps[c], c};
     auto lay = [&](const Key& k) -> const pc_step_stream& { return nets[k.e].n->s[k.s]; };
     bool any_save = false;
     for (int e = 0; e < nE; ++e) any_save = any_save || nets[e].save;
@@ -245,7 +309,8 @@ void forward_nets(Step& X, const Net* nets, int nE, const Ten& Xp, int Hp, int W
     // first layer: Cin differs per stream -> one launch per stream over the networks (aligned DIRECT loader on the padded input)
     {
         int c0 = 0;
-        for (int s = 0; s < 2; ++s) {
+        for (int c = 0; c < X.ns; ++c) {
+            const int s = X.ps[c];
             const int cin = nets[0].n->s[s].cin;
             pc_src sa[MAXK];
             pc_dst dout[MAXK];
@@ -412,19 +477,37 @@ void forward_nets(Step& X, const Net* nets, int nE, const Ten& Xp, int Hp, int W
             }
         }
         if (X.go()) X.rc(pc_conv3x3_bn_relu_fwd_group(K, d, 1, B, Hp, Wp, 8, 8, X.st));
+        // one stream: the head reads all 16 channels of the trainable network's map -- the absent stream's 8 are zero (engine.py:
+        // forward_multi allocates that map zeroed).  The extractor's map is read through its live half only (forward: score_mask)
+        for (int e = 0; e < nE && X.one(); ++e) {
+            if (nets[e].n != &X.plan.unet) continue;
+            const Ten dead = chans(feats[e], 8 - nets[e].n->s[X.ps[0]].feat_c0, 8);
+            if (X.go()) {
+                const int64_t per_b = 8 * dead.sc, blocks = (per_b * B + 255) / 256;
+                hipLaunchKernelGGL(zero_chans_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, X.st, dead.p, dead.sb, per_b, B);
+                X.rc((int)hipGetLastError());
+            }
+        }
     }
     for (int i = 0; i < K; ++i) {
         if (!saved || !nets[keys[i].e].save) continue;
-        Saved& sv = saved[keys[i].e][keys[i].s];
+        Saved& sv = saved[keys[i].e][keys[i].c];
         sv.a1 = a1[i]; sv.a2 = a2[i]; sv.b1 = b1[i]; sv.b2 = b2[i]; sv.c1 = c1[i]; sv.c2 = c2[i]; sv.e1 = e1[i];
         sv.e2 = e2[i]; sv.f1 = f1[i]; sv.pa2 = pa2[i]; sv.pb2 = pb2[i]; sv.ws_up1 = ws1[i]; sv.ws_up2 = ws2[i];
     }
 }
 
-// the padded, normalised, stream-ordered input of a domain: (B, 6, H + top + bottom, W + left + right), rows padded to 16 bytes
+// channels of a PC_DATA_INPUT tensor: 6, or for a one-stream plan the stream's own (2 / 4: the model's input_channels) unless io.craw
+// names another count (a 6-channel tile fed to a one-stream model: the stream's chan[] picks from it, as the per-launch step does)
+inline int input_channels(const Step& X, const pc_step_io& io) {
+    if (!X.one()) return 6;
+    return io.craw > 0 ? io.craw : X.cs[0].cin;
+}
+
+// the padded, normalised, stream-ordered input of a domain: (B, 6 -- one stream: 2 / 4 --, H + top + bottom, W + left + right), rows padded to 16 bytes
 Ten ingest(Step& X, const pc_step_io& io, int top, int bottom, int left, int right) {
     const pc_step_plan& P = X.plan;
-    const Ten out = X.ar.act(io.B, 6, io.H + top + bottom, io.W + left + right);
+    const Ten out = X.ar.act(io.B, P.unet.s[0].cin + P.unet.s[1].cin, io.H + top + bottom, io.W + left + right);
     int sel[8];
     float mean[8], stdv[8];
     int n = 0;
@@ -436,7 +519,7 @@ Ten ingest(Step& X, const pc_step_io& io, int top, int bottom, int left, int rig
             ++n;
         }
     const bool norm = io.data_kind != PC_DATA_INPUT;
-    const int Cin = io.data_kind == PC_DATA_RAW ? io.craw : (io.data_kind == PC_DATA_SPLIT ? 4 : 6);
+    const int Cin = io.data_kind == PC_DATA_RAW ? io.craw : (io.data_kind == PC_DATA_SPLIT ? 4 : input_channels(X, io));
     if (X.go())
         X.rc(pc_ingest_pad_strided(io.data_kind, io.data, io.data2, Cin, out.p, out.sr, io.B, n, sel, norm ? mean : nullptr, norm ? stdv : nullptr,
                                    io.H, io.W, top, bottom, left, right, X.st));
@@ -464,7 +547,7 @@ void forward(Step& X, pc_step_io& io) {
     io.off_popdense = reinterpret_cast<char*>(X.popdense) - A.base;
     X.scale_map = reinterpret_cast<float*>(A.raw((int64_t)B * H * W * 4));
     io.off_scale = reinterpret_cast<char*>(X.scale_map) - A.base;
-    const bool infer = X.infer;
+    const bool infer = X.infer, one = X.one();
     X.mask = infer ? nullptr : reinterpret_cast<uint8_t*>(A.raw((int64_t)B * H * W));
     io.off_mask = infer ? -1 : reinterpret_cast<char*>(X.mask) - A.base;
     const bool given = X.layer != nullptr;
@@ -493,6 +576,14 @@ void forward(Step& X, pc_step_io& io) {
     };
     X.g_pc = infer ? nullptr : reinterpret_cast<float*>(A.raw((int64_t)B * 4));
     X.head_ws = A.raw(pc_head_ws_bytes(B, H, W));
+    for (int t = 0; t < 8; ++t) { X.hw[t] = P.head_w[t]; X.hdw[t] = P.head_dw[t]; }
+    if (one) {
+        // the head kernels take a 64 x 16 first layer: the parameter embedded in a zeroed image, and an image for its gradient
+        X.w0_img = reinterpret_cast<float*>(A.raw(64 * 16 * 4));
+        X.dw0_img = reinterpret_cast<float*>(A.raw(64 * 16 * 4));
+        X.hw[0] = X.w0_img;
+        X.hdw[0] = X.dw0_img;
+    }
     X.fwd_units = X.un != nullptr;
     if (X.un) {
         // multi-unit batch: the flattened lists, the slot map and the N popcounts (sorted order for the loss, caller's order as the result)
@@ -523,24 +614,27 @@ void forward(Step& X, pc_step_io& io) {
     Saved svbuf[2][2];
     const float* am = io.admin_mask;
     // building score + mask + census counts from the extractor's partial logits, which start (oy, ox) inside its domain
+    // (one stream -- engine.py: _logit_operands: the extractor's 16-channel map read through its live half with the stream's own out conv,
+    // which is what the plan's fusion_w / fusion_b point at; no partial-logit epilogue there, as dot_ok has it)
     auto score_mask = [&](const Ten& logits, int oy, int ox) {
-        const pc_src fs = S(logits);
+        const pc_src fs = one ? S(chans(logits, P.extractor.s[X.ps[0]].feat_c0, 8)) : S(logits);
+        const float* lw = one ? P.extractor.fusion_w : X.ones2;
         const pc_dst db = D(X.building);
         if (infer) {
             // the score alone (engine.py: building_score / score_from_features): the dense head has no mask
-            if (X.go()) X.rc(pc_outconv_sigmoid_crop(&fs, X.ones2, P.extractor.fusion_b, &db, B, H, W, oy, ox, X.st));
+            if (X.go()) X.rc(pc_outconv_sigmoid_crop(&fs, lw, P.extractor.fusion_b, &db, B, H, W, oy, ox, X.st));
             return;
         }
         if (X.un) {
             // multi-unit: the score as a map, then the unit lookup + union mask (train.py: score_from_features + ops.unit_mask)
-            if (X.go()) X.rc(pc_outconv_sigmoid_crop(&fs, X.ones2, P.extractor.fusion_b, &db, B, H, W, oy, ox, X.st));
+            if (X.go()) X.rc(pc_outconv_sigmoid_crop(&fs, lw, P.extractor.fusion_b, &db, B, H, W, oy, ox, X.st));
             if (X.go())
                 X.rc(pc_unit_mask(X.building.p, am, X.U.units, X.U.unit_off, X.sel, X.sel + H, P.occupancymodel, X.U.slot, X.mask, X.counts,
                                   nullptr, B, H, W, X.U.N, X.st));
             return;
         }
         if (X.go())
-            X.rc(pc_building_score_mask(&fs, X.ones2, P.extractor.fusion_b, &db, am, io.census_idx, X.sel, X.sel + H, P.occupancymodel, X.mask,
+            X.rc(pc_building_score_mask(&fs, lw, P.extractor.fusion_b, &db, am, io.census_idx, X.sel, X.sel + H, P.occupancymodel, X.mask,
                                         X.counts, B, H, W, oy, ox, X.st));
     };
     if (given) {
@@ -569,7 +663,7 @@ void forward(Step& X, pc_step_io& io) {
         unit_layout();
         const Ten Xp = ingest(X, io, pt, pb, pl, pr);
         X.Xp_u = Xp;
-        const Net nets[2] = {Net{&P.extractor, false, true}, Net{&P.unet, !X.unet_ng, false}};
+        const Net nets[2] = {Net{&P.extractor, false, !one}, Net{&P.unet, !X.unet_ng, false}};
         sv = svbuf;
         forward_nets(X, nets, 2, Xp, Hp, Wp, feats, sv);
         X.feats = feats[1];
@@ -590,7 +684,7 @@ void forward(Step& X, pc_step_io& io) {
             unpack_sel();
             unit_layout();
             const Ten Xb = ingest(X, io, p, p, p, p);
-            const Net nb[1] = {Net{&P.extractor, false, true}};
+            const Net nb[1] = {Net{&P.extractor, false, !one}};
             forward_nets(X, nb, 1, Xb, H + 2 * p, W + 2 * p, feats, nullptr);
             score_mask(feats[0], p, p);
         }
@@ -623,12 +717,16 @@ void forward(Step& X, pc_step_io& io) {
             X.rc((int)hipGetLastError());
         }
     }
+    if (one && X.go()) {
+        hipLaunchKernelGGL(head_w0_embed_kernel, dim3(1), dim3(256), 0, X.st, P.head_w[0], X.w0_img, X.cs[0].feat_c0);
+        X.rc((int)hipGetLastError());
+    }
     const float* bld = X.bld;
     const pc_src sf = S(X.feats);
     if (infer) {
         // dense head (mask == NULL), popcount over the region or the plain sum (admin_mask == NULL), no statistics
         if (X.go())
-            X.rc(pc_head_fwd(&sf, pt, pl, P.head_w, nullptr, bld, am, io.census_idx, X.scale_map, X.popdense, X.popcount, nullptr, nullptr,
+            X.rc(pc_head_fwd(&sf, pt, pl, X.hw, nullptr, bld, am, io.census_idx, X.scale_map, X.popdense, X.popcount, nullptr, nullptr,
                              X.head_ws, B, H, W, 0, X.st));
         X.launches += 2;           // (X.rc counted one; flags = 0 is three launches: head_pack_kernel + the head kernel + head_popcount_reduce_kernel)
         return;
@@ -638,7 +736,7 @@ void forward(Step& X, pc_step_io& io) {
         // backward() rely on), {Nsel, sum scale} finished by the call, popcount[B] = the plain sums (unused)
         X.deferred_popcount = false;
         if (X.go())
-            X.rc(pc_head_fwd(&sf, pt, pl, P.head_w, X.mask, bld, nullptr, nullptr, X.scale_map, X.popdense, X.popcount, P.stats_dev, X.counts,
+            X.rc(pc_head_fwd(&sf, pt, pl, X.hw, X.mask, bld, nullptr, nullptr, X.scale_map, X.popdense, X.popcount, P.stats_dev, X.counts,
                              X.head_ws, B, H, W, PC_HEAD_FWD_PACK_BOTH, X.st));
         X.launches += 2;           // (pack + kernel + reduction)
         X.fwd_end = A.off;
@@ -647,7 +745,7 @@ void forward(Step& X, pc_step_io& io) {
     }
     X.deferred_popcount = io.dp == 0;
     if (X.go())
-        X.rc(pc_head_fwd(&sf, pt, pl, P.head_w, X.mask, bld, am, io.census_idx, X.scale_map, X.popdense, X.popcount, P.stats_dev, X.counts,
+        X.rc(pc_head_fwd(&sf, pt, pl, X.hw, X.mask, bld, am, io.census_idx, X.scale_map, X.popdense, X.popcount, P.stats_dev, X.counts,
                          X.head_ws, B, H, W, PC_HEAD_FWD_PACK_BOTH | (X.deferred_popcount ? PC_HEAD_FWD_DEFER_REDUCE : 0), X.st));
     X.launches += 1;           // (pack + kernel)
     X.fwd_end = A.off;
@@ -699,6 +797,7 @@ struct Backward {
     const pc_step_stream* ST;
     const Saved* sv;
     const int B;
+    const int NS;               // present streams: every per-stream loop and grouped launch below runs over them
     const bool enc_ng;
     Reduce R;
     // The weight-gradient-only launches (16-channel encoder layers, first layers) run on the side stream next to the data-gradient chain:
@@ -713,13 +812,13 @@ struct Backward {
     const int64_t slot_bytes = pc_conv3x3_wgrad_ws_bytes(32, 8);      // partials of one weight-gradient problem
 
     explicit Backward(Step& x)
-        : X(x), ST(x.plan.unet.s), sv(x.sv), B(x.B), enc_ng(x.enc_ng), main_st(x.st),
+        : X(x), ST(x.cs), sv(x.sv), B(x.B), NS(x.ns), enc_ng(x.enc_ng), main_st(x.st),
           two(x.side != nullptr && (int64_t)x.B * x.Hp * x.Wp <= x.side_bwd_px) {}
 
     void* slot(int64_t bytes = 0) { return X.ar.raw(bytes > slot_bytes ? bytes : slot_bytes); }
     T2 fresh(int C, int h, int w) {
         T2 t;
-        for (int s = 0; s < 2; ++s) t[s] = X.ar.act(B, C, h, w);
+        for (int s = 0; s < NS; ++s) t[s] = X.ar.act(B, C, h, w);
         return t;
     }
     T2 saved(Ten Saved::*m) const { return T2{{sv[0].*m, sv[1].*m}}; }
@@ -771,7 +870,7 @@ struct Backward {
     void bwd_halves(int L, const T2& g, const T2& x, const pc_bn (*half_bn)[2], T2& out, int cin_total, int h, int w, const T2* pool_grad = nullptr) {
         Blk b[4];
         Ten xh[2][2], oh[2][2], ph[2][2];
-        for (int s = 0; s < 2; ++s)
+        for (int s = 0; s < NS; ++s)
             for (int i = 0; i < 2; ++i) {
                 xh[s][i] = chans(x[s], 8 * i, 8);
                 oh[s][i] = chans(out[s], 8 * i, 8);
@@ -781,7 +880,7 @@ struct Backward {
                     b[2 * s + i].pool_grad = &ph[s][i];
                 }
             }
-        bwd8(b, 4, cin_total, h, w);
+        bwd8(b, 2 * NS, cin_total, h, w);
     }
     // does the fused launch take this (gradient, input block, output, pooled-from) combination?  (split-operand form, aligned fp32 tensors)
     bool bwd_ok(const Ten& g, const Ten& x, const Ten& out, const Ten* pool_act, int h, int w) const {
@@ -800,7 +899,7 @@ struct Backward {
         const T2 g_out = fresh(16, h / 2, w / 2), g_mid = fresh(16, h / 2, w / 2), g_pooled = fresh(DOWN1.cin, h / 2, w / 2);
         const T2 mid = saved(DOWN1.mid), pooled = saved(DOWN1.pooled), full = saved(DOWN1.full);
         bool ok = true;
-        for (int s = 0; s < 2 && ok; ++s) {
+        for (int s = 0; s < NS && ok; ++s) {
             const pc_src sg = S(g[s]), sx = S(skip[s]), spg = S(g_pooled[s]);
             const pc_dst dout = D(g_skip[s]);
             ok = pooled[s].ok() && bwd_ok(g_mid[s], pooled[s], g_skip[s], &full[s], h / 2, w / 2) &&
@@ -818,7 +917,7 @@ struct Backward {
         const int64_t mark = X.ar.off;
         const T2 gz = fresh(16, 32, 32), g_pooled = fresh(16, 32, 32);
         bool ok = true;
-        for (int s = 0; s < 2 && ok; ++s) {
+        for (int s = 0; s < NS && ok; ++s) {
             const pc_src sg2 = S(gz[s]), sc = S(sv[s].c1), sx = S(sv[s].pb2), sa = S(sv[s].b2);
             const pc_dst dz = D(g_skip[s]);
             ok = pc_level2_bwd_ok(&sg2, &sc, &sx, &sa, &dz) != 0;
@@ -838,7 +937,7 @@ struct Backward {
         pc_conv_wgrad_desc d[2];
         void* ws[2];
         int Cin = 0;
-        for (int s = 0; s < 2; ++s) {
+        for (int s = 0; s < NS; ++s) {
             Ten src = a[s];
             if (mode == PC_SRC_POOL2) src = crop(src, 2 * h, 2 * w);
             sa[s] = S(src, mode); sg[s] = S(g[s]);
@@ -847,8 +946,8 @@ struct Backward {
             Cin = src.C;
         }
         int nwg = 0;
-        if (X.go()) X.rc(pc_conv3x3_wgrad_partial_group(2, d, B, h, w, Cin, g[0].C, &nwg, X.st));
-        for (int s = 0; s < 2; ++s) R.add(ws[s], ST[s].dw[L], ST[s].db[L], nwg, Cin, g[0].C, 0, cin_total * 9);
+        if (X.go()) X.rc(pc_conv3x3_wgrad_partial_group(NS, d, B, h, w, Cin, g[0].C, &nwg, X.st));
+        for (int s = 0; s < NS; ++s) R.add(ws[s], ST[s].dw[L], ST[s].db[L], nwg, Cin, g[0].C, 0, cin_total * 9);
         side_off();
     }
     // data gradient of layer L w.r.t. all its cin input channels, masked by the producer actL of act; pool: scattered (+=) through the
@@ -857,18 +956,18 @@ struct Backward {
         pc_src sg[2], sa[2];
         pc_dst dout[2];
         pc_conv_dgrad_desc d[2];
-        for (int s = 0; s < 2; ++s) {
+        for (int s = 0; s < NS; ++s) {
             sg[s] = S(g[s]); sa[s] = S(act[s]); dout[s] = D(out[s]);
             d[s] = pc_conv_dgrad_desc{&sg[s], ST[s].w[L], &sa[s], &X.bn_nobias[s][actL], &dout[s]};
         }
-        if (X.go()) X.rc(pc_conv3x3_dgrad_group(2, d, cin, 0, cin, pool ? 1 : 0, pool ? 1 : 0, B, h, w, g[0].C, X.st));
+        if (X.go()) X.rc(pc_conv3x3_dgrad_group(NS, d, cin, 0, cin, pool ? 1 : 0, pool ? 1 : 0, B, h, w, g[0].C, X.st));
     }
     // composed Up block: dz, the composed weight gradient and the border sums from one pass over g (up_bwd.hip)
     void up_bwd(const UpLv& lv, const T2& g, const T2* gz, int h, int w) {
         pc_conv_up_bwd_desc* d = lv.c == 8 ? R.ch8 : R.ch16;
         const int k = lv.c == 8 ? 0 : 1;
         void* ws[2];
-        for (int s = 0; s < 2; ++s) {
+        for (int s = 0; s < NS; ++s) {
             R.ch_g[k][s] = S(g[s]); R.ch_z[k][s] = S(sv[s].*lv.z);
             if (gz) R.ch_gz[k][s] = D((*gz)[s]);
             ws[s] = slot(pc_conv3x3_up_bwd_ws_bytes(B, h, lv.c));
@@ -878,10 +977,10 @@ struct Backward {
             d[s].dw = ST[s].dw[lv.conv]; d[s].dwt = ST[s].dwt[lv.convt]; d[s].dbt = ST[s].dbt[lv.convt];
         }
         int nwg = 0, part = 0;
-        if (X.go()) X.rc(pc_conv3x3_up_bwd_partial_group(2, d, B, h, w, lv.c, lv.c, &nwg, &part, X.st));
+        if (X.go()) X.rc(pc_conv3x3_up_bwd_partial_group(NS, d, B, h, w, lv.c, lv.c, &nwg, &part, X.st));
         else { nwg = 1; part = 1; }
-        for (int s = 0; s < 2; ++s) R.add(ws[s], reinterpret_cast<float*>(ws[s]) + (int64_t)nwg * part, nullptr, nwg, part, 0, 2);
-        if (lv.c == 8) { R.n8 = 2; R.nwg8 = nwg; } else { R.n16 = 2; R.nwg16 = nwg; }
+        for (int s = 0; s < NS; ++s) R.add(ws[s], reinterpret_cast<float*>(ws[s]) + (int64_t)nwg * part, nullptr, nwg, part, 0, 2);
+        if (lv.c == 8) { R.n8 = NS; R.nwg8 = nwg; } else { R.n16 = NS; R.nwg16 = nwg; }
     }
 
     // ---- the blocks
@@ -890,8 +989,8 @@ struct Backward {
     T2 conv8(int L, const T2& g, Ten Saved::*x, int actL, int h, int w) {
         T2 out = fresh(8, h, w);
         Blk b[2];
-        for (int s = 0; s < 2; ++s) b[s] = Blk{&g[s], &(sv[s].*x), &X.bn_nobias[s][actL], &out[s], L, s, 0, true};
-        bwd8(b, 2, 8, h, w);
+        for (int s = 0; s < NS; ++s) b[s] = Blk{&g[s], &(sv[s].*x), &X.bn_nobias[s][actL], &out[s], L, s, 0, true};
+        bwd8(b, NS, 8, h, w);
         return out;
     }
     // An Up block from the gradient g of its first conv's output at (h, w): the skip column block of that conv (weight gradient into the
@@ -907,8 +1006,8 @@ struct Backward {
                 deferred_g = g;
             } else {
                 Blk b[2];
-                for (int s = 0; s < 2; ++s) b[s] = Blk{&g[s], &skip[s], &X.bn_nobias[s][lv.skip_act], &g_skip[s], lv.conv, s, 0, true};
-                bwd8(b, 2, 16, h, w);
+                for (int s = 0; s < NS; ++s) b[s] = Blk{&g[s], &skip[s], &X.bn_nobias[s][lv.skip_act], &g_skip[s], lv.conv, s, 0, true};
+                bwd8(b, NS, 16, h, w);
             }
         } else if (!enc_ng) {       // the two 8-channel halves of the 16-channel skip tensor
             g_skip = fresh(16, h, w);
@@ -933,7 +1032,7 @@ struct Backward {
         void* w1[2];
         void* w2[2];
         const int64_t mark = X.ar.off;
-        for (int s = 0; s < 2; ++s) {
+        for (int s = 0; s < NS; ++s) {
             sg[s] = S(g_out[s]); sc[s] = S(sv[s].c1); sx[s] = S(sv[s].pb2); sa[s] = S(sv[s].b2); dout[s] = D(g_in[s]);
             w1[s] = slot(pc_level2_bwd_ws_bytes(B)); w2[s] = slot(pc_level2_bwd_ws_bytes(B));
             d[s] = pc_level2_bwd_desc{&sg[s], &sc[s], &sx[s], ST[s].w[L_D2A], ST[s].w[L_D2B], &X.bn_nobias[s][L_D2A], &sa[s],
@@ -946,8 +1045,8 @@ struct Backward {
             if (deferred2) { dpg[s] = D(g_pooled[s]); d[s].pool_grad_out = &dpg[s]; }
         }
         int nwg = 0;
-        if (X.go()) X.rc(pc_level2_bwd_group(2, d, B, &nwg, X.st));
-        for (int s = 0; s < 2; ++s) {
+        if (X.go()) X.rc(pc_level2_bwd_group(NS, d, B, &nwg, X.st));
+        for (int s = 0; s < NS; ++s) {
             R.add(w1[s], ST[s].dw[L_D2A], ST[s].db[L_D2A], nwg, 16, 16, 0);
             R.add(w2[s], ST[s].dw[L_D2B], ST[s].db[L_D2B], nwg, 16, 16, 0);
         }
@@ -970,11 +1069,11 @@ struct Backward {
             T2 g_pooled = fresh(lv.cin, h, w);
             bwd_halves(lv.conv2, g_out, mid, X.bn_half_d1a, g_mid, 16, h, w);
             Blk a[2], b[2];
-            for (int s = 0; s < 2; ++s) a[s] = Blk{&g_mid[s], &pooled[s], nullptr, &g_pooled[s], lv.conv1, s, 0, true};
-            bwd8(a, 2, lv.cin, h, w);
-            for (int s = 0; s < 2; ++s)
+            for (int s = 0; s < NS; ++s) a[s] = Blk{&g_mid[s], &pooled[s], nullptr, &g_pooled[s], lv.conv1, s, 0, true};
+            bwd8(a, NS, lv.cin, h, w);
+            for (int s = 0; s < NS; ++s)
                 b[s] = Blk{&deferred_g[s], &full[s], &X.bn_nobias[s][lv.full_act], &g_in[s], UP1.conv, s, 0, true, nullptr, &g_pooled[s]};
-            bwd8(b, 2, 16, 2 * h, 2 * w);
+            bwd8(b, NS, 16, 2 * h, 2 * w);
             return;
         }
         // down1, round 6: data + weight gradient of each layer in ONE launch of the split-operand kernel -- the second conv as the two
@@ -982,13 +1081,13 @@ struct Backward {
         // into inc2's gradient -- instead of four launches (weight gradient 16 -> 16, data gradient 16 -> 16, weight gradient 8 -> 16,
         // pooled data gradient 16 -> 8).  Both layers take it, or neither; the launcher declines a 16-channel pooled map (down2).
         bool fused = lv.cin == 8;
-        for (int s = 0; s < 2 && fused; ++s)
+        for (int s = 0; s < NS && fused; ++s)
             fused = bwd_ok(g_out[s], chans(mid[s], 8, 8), chans(g_mid[s], 8, 8), nullptr, h, w) && bwd_ok(g_mid[s], pooled[s], g_in[s], &full[s], h, w);
         if (fused) {
             bwd_halves(lv.conv2, g_out, mid, X.bn_half_d1a, g_mid, 16, h, w);
             Blk a[2];
-            for (int s = 0; s < 2; ++s) a[s] = Blk{&g_mid[s], &pooled[s], &X.bn_nobias[s][lv.full_act], &g_in[s], lv.conv1, s, 0, true, &full[s]};
-            bwd8(a, 2, lv.cin, h, w);
+            for (int s = 0; s < NS; ++s) a[s] = Blk{&g_mid[s], &pooled[s], &X.bn_nobias[s][lv.full_act], &g_in[s], lv.conv1, s, 0, true, &full[s]};
+            bwd8(a, NS, lv.cin, h, w);
             return;
         }
         wgrad(lv.conv2, mid, PC_SRC_DIRECT, g_out, h, w);
@@ -1002,7 +1101,7 @@ struct Backward {
     void first_layer(const T2& G_a1) {
         int c0 = 0;
         side_on();
-        for (int s = 0; s < 2; ++s) {
+        for (int s = 0; s < NS; ++s) {
             const Ten xin = chans(X.Xp_u, c0, ST[s].cin);
             const pc_src sa = S(xin), sg = S(G_a1[s]);
             void* ws = slot();
@@ -1061,10 +1160,10 @@ void backward(Step& X, pc_step_io& io) {
         const pc_dst dg = D(G);
         const bool defer = !X.unet_ng;
         if (X.go())
-            X.rc(pc_head_bwd(&sf, X.pt, X.pl, P.head_w, X.mask, X.bld, g_pd ? nullptr : io.admin_mask, g_pd ? nullptr : io.census_idx,
+            X.rc(pc_head_bwd(&sf, X.pt, X.pl, X.hw, X.mask, X.bld, g_pd ? nullptr : io.admin_mask, g_pd ? nullptr : io.census_idx,
                              g_pd ? nullptr : X.g_pc, g_pd, nullptr,
-                             P.g_scale_const_dev, P.head_dw, 0, &dg, X.unet_ng ? nullptr : &X.bn_nobias[0][L_UP1B],
-                             X.unet_ng ? nullptr : &X.bn_nobias[1][L_UP1B], Hp, Wp, X.head_ws, B, H, W,
+                             P.g_scale_const_dev, X.hdw, 0, &dg, X.unet_ng ? nullptr : &X.feat_bn[0],
+                             X.unet_ng ? nullptr : &X.feat_bn[1], Hp, Wp, X.head_ws, B, H, W,
                              PC_HEAD_BWD_PACKED | (defer ? PC_HEAD_BWD_DEFER_REDUCE : 0), X.st));
         if (!defer) X.launches += 1;
     }
@@ -1072,7 +1171,14 @@ void backward(Step& X, pc_step_io& io) {
         // parameters without a gradient in this regime keep exact zeros in the flat buffer (the clip norm runs over all of it)
         if (X.go()) X.rc(pc_zero_fill(P.flat_g, P.n - P.n_head, X.st));
     }
-    if (X.unet_ng) return;
+    // one stream: the live half of the first layer's 64 x 16 gradient image -> the parameter's gradient, behind the reduction that
+    // finishes the image (the head's own here, the batched one of finish() below) and in front of the gradient norm of update()
+    auto extract_dw0 = [&]() {
+        if (!X.one() || !X.go()) return;
+        hipLaunchKernelGGL(head_dw0_extract_kernel, dim3(1), dim3(256), 0, X.st, X.dw0_img, P.head_dw[0], X.cs[0].feat_c0);
+        X.rc((int)hipGetLastError());
+    };
+    if (X.unet_ng) return extract_dw0();
 
     Backward p(X);
     {
@@ -1080,12 +1186,12 @@ void backward(Step& X, pc_step_io& io) {
         const float* pp = nullptr;
         int nwg = 0;
         pc_head_bwd_partials(X.head_ws, B, H, W, &pp, &nwg);
-        for (int t = 0; t < 8; ++t) p.R.head_ptrs[t] = P.head_dw[t];
+        for (int t = 0; t < 8; ++t) p.R.head_ptrs[t] = X.hdw[t];
         p.R.add(pp, reinterpret_cast<float*>(p.R.head_ptrs), nullptr, nwg, 0, 0, 3);
     }
     // the network in reverse, one call per block (engine.py: UNetEngine.backward)
     T2 G_f2, G_a2, G_e2, G_b2, G_c2;
-    for (int s = 0; s < 2; ++s) G_f2[s] = chans(G, p.ST[s].feat_c0, 8);
+    for (int s = 0; s < X.ns; ++s) G_f2[s] = chans(G, p.ST[s].feat_c0, 8);
     const T2 G_f1 = p.conv8(L_UP1B, G_f2, &Saved::f1, L_UP1A, Hp, Wp);
     p.up(UP1, G_f1, Hp, Wp, G_a2, &G_e2);
     const T2 G_e1 = p.conv8(L_UP2B, G_e2, &Saved::e1, L_UP2A, H1, W1);
@@ -1097,6 +1203,7 @@ void backward(Step& X, pc_step_io& io) {
         p.first_layer(G_a1);
     }
     p.finish();
+    extract_dw0();
 }
 
 void update(Step& X) {
@@ -1224,11 +1331,28 @@ extern "C" void* pc_step_create(const pc_step_plan* plan) {
     Step* X = new (std::nothrow) Step();
     if (!X) return nullptr;
     X->plan = *plan;
+    // the present streams.  A plan whose two networks disagree, or without a stream, still makes a handle: every entry point refuses it
+    // (plan_streams_ok) before anything is enqueued
+    X->ns = 0;
+    for (int s = 0; s < 2; ++s)
+        if (stream_present(plan->unet.s[s])) X->ps[X->ns++] = s;
+    memset(X->cs, 0, sizeof(X->cs));
+    memset(X->feat_bn, 0, sizeof(X->feat_bn));
+    X->feat_bn[0].eps = X->feat_bn[1].eps = 1e-5f;          // (plain: engine.py: feat_bn of a missing stream)
     for (int s = 0; s < 2; ++s) {
+        if (s >= X->ns) {
+            memset(X->bn_nobias[s], 0, sizeof(X->bn_nobias[s]));
+            memset(X->bn_half[s], 0, sizeof(X->bn_half[s]));
+            memset(X->bn_half_d1a[s], 0, sizeof(X->bn_half_d1a[s]));
+            continue;
+        }
+        const pc_step_stream& T = plan->unet.s[X->ps[s]];
+        X->cs[s] = T;
         for (int L = 0; L < PC_STEP_CONVS; ++L) {
-            X->bn_nobias[s][L] = plan->unet.s[s].bn[L];
+            X->bn_nobias[s][L] = T.bn[L];
             X->bn_nobias[s][L].conv_bias = nullptr;
         }
+        X->feat_bn[T.feat_c0 == 8 ? 1 : 0] = X->bn_nobias[s][L_UP1B];
         for (int i = 0; i < 2; ++i) {         // d1b's ReLU / BN factor for channels [8 i, 8 i + 8)
             pc_bn b = X->bn_nobias[s][L_D1B];
             if (b.gamma) { b.gamma += 8 * i; b.beta += 8 * i; b.mean += 8 * i; b.var += 8 * i; }
@@ -1290,6 +1414,7 @@ static int train_step(void* handle, pc_step_io* io, pc_step_units* un, const flo
     Step* X = reinterpret_cast<Step*>(handle);
     if (!X || !io || io->B < 1 || io->H < 1 || io->W < 1 || !(phases & 7)) return PC_EINVAL;
     if (inference_plan(X->plan)) return PC_EINVAL;          // (a plan without gradient / optimiser / loss targets serves pc_forward only)
+    if (int bad = plan_streams_ok(X->plan)) return bad;     // (a stream in one network only, or none)
     // a backward / update phase continues the forward pass in the arena: its layer, named again or left out
     if (!(phases & PC_STEP_FWD) && layer && layer != X->fwd_layer) return PC_EINVAL;
     if (g_pc_precision != PC_PREC_FP32) return PC_ENOTSUP;
@@ -1307,6 +1432,10 @@ static int train_step(void* handle, pc_step_io* io, pc_step_units* un, const flo
         const int p = X->plan.extractor_pad;
         // reflect padding must be smaller than the input (F.pad's rule); two 2 x 2 poolings need a 4 x 4 domain
         if (pt >= io->H || pb >= io->H || pl >= io->W || pr >= io->W || p >= io->H || p >= io->W) return PC_EINVAL;
+        // one-stream plan, PC_DATA_INPUT: the stream's channels must lie inside the tensor (the ingest would refuse after the first launches)
+        if (X->one() && io->data_kind == PC_DATA_INPUT)
+            for (int c = 0; c < X->cs[0].cin; ++c)
+                if (X->cs[0].chan[c] < 0 || X->cs[0].chan[c] >= input_channels(*X, *io)) return PC_EINVAL;
     }
     X->st = reinterpret_cast<hipStream_t>(stream);
     // An EAGER entry point: it forks onto a side stream through events of its own, and the first call on a caller's stream measures

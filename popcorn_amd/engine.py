@@ -160,14 +160,22 @@ class UNetEngine:
             self._ones2 = torch.ones(2, device=f.device, dtype=torch.float32)
         return self._ones2
 
+    def _logit_operands(self, f):
+        """(source, weights, bias) of the building logit over the feature map ``f``.  Two streams: ``fusion_out_conv`` over the 16
+        channels (or ones over the partial logits).  One stream: that stream's OWN out conv over its 8 channels (networks.py:217-228;
+        fixture g13) -- the matching half of ``fusion_out_conv`` is another set of weights and another bias."""
+        if self.single_out is None:
+            return f, self._logit_weights(f), self.fusion_b
+        f0 = self.streams[0][3]
+        return f[:, f0:f0 + 8], self.single_out[0], self.single_out[1]
+
     def score_from_features(self, f, H, W, py, px):
-        """fusion_out_conv + sigmoid + crop from either the 16-channel feature map or the partial logits."""
-        return ops.outconv_sigmoid_crop(f, self._logit_weights(f), self.fusion_b, H, W, py, px)
+        """out conv + sigmoid + crop from either the 16-channel feature map or the partial logits."""
+        return ops.outconv_sigmoid_crop(*self._logit_operands(f), H, W, py, px)
 
     def score_and_mask(self, f, H, W, py, px, admin_mask, census_idx, rowsel, colsel, occupancymodel=True):
         """score_from_features + get_sparsity_mask (popcorn.py:361-377) in one launch: (building, mask, counts)."""
-        return ops.building_score_mask(f, self._logit_weights(f), self.fusion_b, H, W, py, px, admin_mask, census_idx, rowsel, colsel,
-                                       occupancymodel)
+        return ops.building_score_mask(*self._logit_operands(f), H, W, py, px, admin_mask, census_idx, rowsel, colsel, occupancymodel)
 
     def feat_bn(self):
         """BN descriptors of the two layers that produce the feature map (for the head-backward epilogue)."""

@@ -6,7 +6,9 @@ head -- as ONE C-ABI call (``pc_forward``, include/popcorn_hip.h) instead of one
 ``POPCORN.forward`` routes a call here only when ``route_ok`` holds; every other call takes the per-launch engine unchanged (same
 kernels) and leaves the counter alone.  Still declined: bf16 precision, single-modality (S1-only / S2-only) models, ``sparse=True``,
 ``padding=True``, a 2-D ``census_idx``, calls that build an autograd graph, an ``input`` that is not a contiguous fp32 (B, 6, H, W)
-tensor, and an engine whose A/B switches are off their defaults.
+tensor, and an engine whose A/B switches are off their defaults.  (The TRAINING executor takes a single-modality model as a one-stream
+plan -- ``FusedTrainStep(native_single=True)`` --; ``pc_forward`` keeps refusing such a plan with PC_ENOTSUP and this module keeps
+declining the model: tests/test_gpu_native_forward.py pins both.)
 
 The outputs (``popcount``, ``popdensemap``, ``scale`` and the extractor's ``building_counts``) are VIEWS into the model's own arena:
 valid until that model's next native forward.  ``evaluate_raster`` and ``validate_weak`` copy what they keep.  Every model has an arena

@@ -46,6 +46,37 @@ _LAYER_TAGS = ("inc1", "inc2", "d1a", "d1b", "d2a", "d2b", "up2a", "up2b", "up1a
 _CONVT_TAGS = ("up2t", "up1t")
 
 
+def fill_step_net(net, eng, grads, prefix, keep):
+    """One network of a pc_step_plan (``net``: a PcStepNet) from its engine.  A stream keeps its slot -- 0: sar, 1: optical -- whichever
+    streams the model has: the table of an absent one stays all zero (a one-stream plan, include/popcorn_hip.h).  ``fusion_w`` /
+    ``fusion_b``: fusion_out_conv (16 + 1), or the only stream's own out conv (8 + 1).  ``grads`` / ``prefix``: the gradient targets of
+    the trainable network (None: the frozen extractor).  ``keep`` collects what the raw pointers refer to."""
+    slots = [n for n, _, _, _ in E.STREAMS]
+    for sname, chmap, cin, f0 in eng.streams:
+        st = net.s[slots.index(sname)]
+        for li, tag in enumerate(_LAYER_TAGS):
+            lay = eng.layers[(sname, tag)]
+            st.w[li] = lay.w.data_ptr()
+            st.bn[li] = lay.bn
+            if prefix is not None:
+                st.dw[li] = grads[prefix + lay.wname].data_ptr()
+                st.db[li] = grads[prefix + lay.bname].data_ptr()
+            keep.append(lay)
+        for ti, tag in enumerate(_CONVT_TAGS):
+            lay = eng.layers[(sname, tag)]
+            st.wt[ti], st.bt[ti] = lay.w.data_ptr(), lay.b.data_ptr()
+            if prefix is not None:
+                st.dwt[ti] = grads[prefix + lay.wname].data_ptr()
+                st.dbt[ti] = grads[prefix + lay.bname].data_ptr()
+            keep.append(lay)
+        for c in range(4):
+            st.chan[c] = chmap[c]
+        st.cin, st.feat_c0 = cin, f0
+    ow, ob = (eng.fusion_w, eng.fusion_b) if eng.single_out is None else eng.single_out
+    net.fusion_w, net.fusion_b = ow.data_ptr(), ob.data_ptr()
+    keep.append((ow, ob))
+
+
 class _ArenaOutputs:
     """The outputs of a native step -- views into the step's arena, built on first access (``popcount``, ``popdensemap``, ``scale_map``,
     ``mask``, ``building_counts``).  Valid until the trainer's next step (the arena is reused), like the static outputs of a replayed graph."""
@@ -165,7 +196,7 @@ class FusedTrainStep:
     def __init__(self, model, lr=1e-4, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, gradient_clip=0.01,
                  loss=("log_l1_loss",), lam=(1.0,), scale_regularization=0.01, lam_weak=100.0,
                  reducer: FlatReducer | None = None, use_graph=False, raw_norm=None, graph_cache_max=None, native_units=False,
-                 device_units=False, native_layer=False):
+                 device_units=False, native_layer=False, native_single=False):
         """raw_norm = (band6, mean6, std6): how a RAW tile (sample key "raw" instead of "input": (B, Craw, H, W) reflectances /
         backscatter) becomes the model input -- band selection (data/PopulationDataset.py:566-568) + apply_normalize
         (utils/utils.py:105-127); default: the reference's dataset statistics (popcorn_amd.data.stats).  With a raw sample the
@@ -179,7 +210,11 @@ class FusedTrainStep:
         data-parallel reducer; the native executor is not asked.  Off: as before, refusals included.  One-unit samples are unaffected.
         native_layer: eager steps on a given building layer (``sentinelbuildings=False`` models fed ``building_counts``) and of models without
         the occupancy product go through the native executor too (pc_train_step_layer / pc_train_step_units_layer) -- opt-in; off: the
-        per-launch engine, as before.  The two compute the same bits.  Multi-unit samples on a layer need ``native_units`` as well."""
+        per-launch engine, as before.  The two compute the same bits.  Multi-unit samples on a layer need ``native_units`` as well.
+        native_single: eager fp32 steps of a single-modality model (S1-only / S2-only: ``input_channels`` 2 / 4) go through the native
+        executor too, as a one-stream plan (include/popcorn_hip.h) -- opt-in; off: the per-launch engine, as before.  The two compute the
+        same bits; no torch op stays on that path (the 64 x 16 images of the head's first layer are made inside the call).  Multi-unit
+        samples and shipped layers of such a model need ``native_units`` / ``native_layer`` as well."""
         from .data import stats as _stats
         self.raw_norm = raw_norm or (_stats.BAND6, _stats.MEAN6, _stats.STD6)
         self.model = model
@@ -254,6 +289,7 @@ class FusedTrainStep:
         self.native_unit_steps = 0      # multi-unit steps that went through pc_train_step_units (native_steps counts one-unit steps only)
         self.device_units = bool(device_units)
         self.native_layer = bool(native_layer)
+        self.native_single = bool(native_single)
         self.device_unit_steps = 0      # multi-unit steps that took the device-N form (eager or replayed)
         self.captures = 0               # graph captures so far (tests / tools read it)
         self._cn_ring, self._cn_next = [], 0            # pinned host slots for census_n (as the selection's ring)
@@ -373,11 +409,13 @@ class FusedTrainStep:
     # ---- native executor (one C-ABI call per eager step) ------------------------------------------------------------
     def _native_ok(self, sample):
         """Which steps pc_train_step covers (include/popcorn_hip.h): fp32, dual-stream models whose building score comes from the frozen
-        extractor, with the occupancy product -- and, with ``native_layer``, a given building layer and models without the product.
-        Everything else keeps the per-launch engine (same kernels)."""
+        extractor, with the occupancy product -- and, with ``native_layer``, a given building layer and models without the product; with
+        ``native_single``, single-modality models (a one-stream plan).  Everything else keeps the per-launch engine (same kernels)."""
         m = self.model
-        if not NATIVE_STEP or m.precision != "fp32" or not (m.S1 and m.S2) or not (m.occupancymodel or self.native_layer):
+        if not NATIVE_STEP or m.precision != "fp32" or not (m.occupancymodel or self.native_layer):
             return False
+        if not (m.S1 and m.S2) and not self.native_single:
+            return False               # opt-in (one-stream plan)
         if _is_multi_unit(sample) and (self.device_units or not self.native_units):
             return False               # opt-in (pc_train_step_units); pc_train_step supervises one unit per sample.  device_units: not asked
         if not (E.PADDED_INPUT and E.COMPOSED_UP and E.FUSED_LEVEL2 and E.FUSED_CONV_BWD and DEFER_HEAD_REDUCE):
@@ -394,7 +432,7 @@ class FusedTrainStep:
         band, mean, std = self.raw_norm
         baked = (tuple(int(b) for b in band[:6]), tuple(float(v) for v in mean[:6]), tuple(float(v) for v in std[:6]),
                  tuple(float(v) for v in self.lam4), float(self.lam_weak), float(self.sreg), float(self.clip or 0.0), float(self.wd),
-                 tuple(float(b) for b in self.betas), float(self.eps), int(m.p), int(bool(m.occupancymodel)))
+                 tuple(float(b) for b in self.betas), float(self.eps), int(m.p), int(bool(m.occupancymodel)), bool(self.native_single))
         if self._native is not None and self._native[2] is engs and self._native[6] == baked:
             return self._native[0]
         if self._native is not None:
@@ -403,34 +441,10 @@ class FusedTrainStep:
         eng_u, eng_b = engs
         plan = L.PcStepPlan()
         keep = []
-
-        def fill(net, eng, prefix):
-            for si, (sname, chmap, cin, f0) in enumerate(eng.streams):
-                st = net.s[si]
-                for li, tag in enumerate(_LAYER_TAGS):
-                    lay = eng.layers[(sname, tag)]
-                    st.w[li] = lay.w.data_ptr()
-                    st.bn[li] = lay.bn
-                    if prefix is not None:
-                        st.dw[li] = self.grads[prefix + lay.wname].data_ptr()
-                        st.db[li] = self.grads[prefix + lay.bname].data_ptr()
-                    keep.append(lay)
-                for ti, tag in enumerate(_CONVT_TAGS):
-                    lay = eng.layers[(sname, tag)]
-                    st.wt[ti], st.bt[ti] = lay.w.data_ptr(), lay.b.data_ptr()
-                    if prefix is not None:
-                        st.dwt[ti] = self.grads[prefix + lay.wname].data_ptr()
-                        st.dbt[ti] = self.grads[prefix + lay.bname].data_ptr()
-                    keep.append(lay)
-                for c in range(4):
-                    st.chan[c] = chmap[c]
-                st.cin, st.feat_c0 = cin, f0
-            net.fusion_w = eng.fusion_w.data_ptr()
-            net.fusion_b = eng.fusion_b.data_ptr()
-
-        fill(plan.unet, eng_u, "unetmodel.")
-        fill(plan.extractor, eng_b, None)
-        ht = m.head_tensors()
+        fill_step_net(plan.unet, eng_u, self.grads, "unetmodel.", keep)
+        fill_step_net(plan.extractor, eng_b, None, None, keep)
+        # (one-stream plan: head_w[0] is the 64 x 8 parameter itself, not the padded image of head_tensors(): the executor embeds it)
+        ht = m.head_tensors() if (m.S1 and m.S2) else [getattr(m.head[i], n_) for i in (0, 2, 4, 6) for n_ in ("weight", "bias")]
         hg = [self.grads[n_] for n_ in self.names[-8:]]
         for i in range(8):
             plan.head_w[i], plan.head_dw[i] = ht[i].data_ptr(), hg[i].data_ptr()
@@ -477,11 +491,20 @@ class FusedTrainStep:
         elif form == "raw":
             want("raw", torch.float32)
             io.data_kind, io.data, io.craw = L.PC_DATA_RAW, s["raw"].data_ptr(), s["raw"].shape[1]
-        else:
+        elif self.model.S1 and self.model.S2:
             if s["input"].shape[1] != 6 or s["input"].dtype != torch.float32:
                 raise ValueError("input must be a (B, 6, H, W) fp32 tensor")
             want("input", torch.float32, (B, 6, H, W))
             io.data_kind, io.data = L.PC_DATA_INPUT, s["input"].data_ptr()
+        else:
+            # one-stream plan: the model's own input (B, input_channels, H, W) -- or any tensor that holds the channels the stream picks
+            # (a 6-channel tile: what the per-launch step reads of it); io.craw carries its channel count
+            Cx = s["input"].shape[1]
+            stream = self.model.engines()[0].streams[0]
+            if Cx <= max(stream[1][:stream[2]]):
+                raise ValueError(f"input: {Cx} channels, the model's stream reads channels {stream[1][:stream[2]]}")
+            want("input", torch.float32, (B, Cx, H, W))
+            io.data_kind, io.data, io.craw = L.PC_DATA_INPUT, s["input"].data_ptr(), Cx
         want("admin_mask", torch.float32, (B, H, W))
         io.admin_mask = s["admin_mask"].data_ptr()
         io._layer = None
